@@ -28,6 +28,9 @@ seconds, LM iterations, evaluations, mean deviation against the reference's 2e-4
 bytes of ALL program launches of the real calibration / their summed device time) and its own cpu_baseline.  The
 calibration runs in the native driver bin/lmm_hip (C++ over the C-ABI), started as a child process BEFORE this process
 touches the GPU.  `--workload stream` / `--workload lmm` run one half only.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (dump_stream_outputs, lmm_leg): every
+input is generated from fixed seeds, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -249,6 +252,9 @@ def lmm_leg(args, world, rank, nonce, cpu_base=True, store=None):
                     raise RuntimeError(f"rank {k} calibrated other parameters than rank 0: the ranks did not see the same expectations")
     if rank != 0:
         return None
+    if args.dump_outputs:
+        # --dump-outputs, LMM half: the volatility parameters the timed calibration (run 1) ended on, float64
+        dump_array(args.dump_outputs, "lmm_parameters", np.asarray(r["parameters"], dtype=np.float64))
     kernel_s = rp["kernel_ms_total"] / 1e3
     # Where the host's own time goes (the engine's FMHIP_HOST_PROFILE table of a third run, N = 1 only): the slots that do not contain
     # each other, largest first.  host_idle_s = wall time of the profiled run the device spent without a kernel.
@@ -424,6 +430,29 @@ def lmm_leg(args, world, rank, nonce, cpu_base=True, store=None):
     return lmm
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # of --dump-outputs (well under the 64 MB a dump may take)
+
+
+def dump_array(directory, name, values):
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), values)
+
+
+def dump_stream_outputs(directory, out_rows, moments):
+    """--dump-outputs, stream half: what a caller of the timed launch holds after the last timed step.
+      w.npy        float32 [B, k]: the escaping output w of every triple.  All N paths if they fit the budget, otherwise the same k paths
+                   of every triple, drawn once from a fixed seed (ascending path index) - the same paths in every run and every build;
+      moments.npy  float64 [B, 4]: {sum, sum of squares, min, max} of w per triple, as the launch left them on the device."""
+    B, n = len(out_rows), out_rows[0][0].n
+    k = min(n, DUMP_BUDGET_BYTES // (4 * B))
+    paths = slice(None) if k == n else np.sort(np.random.default_rng(31415).choice(n, size=k, replace=False))
+    w = np.empty((B, k), dtype=np.float32)
+    for b, row in enumerate(out_rows):
+        w[b] = row[0].to_float32()[paths]
+    dump_array(directory, "w", w)
+    dump_array(directory, "moments", np.ascontiguousarray(moments, dtype=np.float64))
+
+
 def brownian_block(fm, launches=8):
     """BASELINE.json configs[2]: BrownianMotionHip 1 M paths x 200 steps x 5 factors (seed 31415 + k) = 4.0 GB of N(0, dt) increments per
     generation, one launch of fm_bm_kernel into a slab the pool hands back from the previous generation (the first one allocates it
@@ -580,8 +609,12 @@ def main():
     ap.add_argument("--batch", type=int, default=64, help="independent (x,y,z) triples per launch")
     ap.add_argument("--paths", type=int, default=N_PATHS)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                                                          "(rank 0; dump_stream_outputs and lmm_leg say which arrays)")
     ap.add_argument("--cpu-worker", type=float, default=0.0, help=argparse.SUPPRESS)      # internal: one process of the all-cores CPU baseline
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
     if args.cpu_worker > 0:
         print(json.dumps(cpu_baseline(args.cpu_worker, -1.0)), flush=True)
         return
@@ -731,6 +764,7 @@ def main():
     # back-to-back launches, gaps included — the live figure behind roofline.achieved
     ev_begin, ev_end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     timing_rccl[0] = use_dist
+    first_timed = step_no[0]
     t0 = time.perf_counter()
     ev_begin.record(ext_stream)
     for _ in range(args.steps):
@@ -741,6 +775,10 @@ def main():
     elapsed = time.perf_counter() - t0
     timing_rccl[0] = False
     region_kernel_s = ev_begin.elapsed_time(ev_end) / 1e3 / args.steps
+    if args.dump_outputs and rank == 0:
+        # here, before the passes below launch into the same output vectors; the bank and slot the last timed step wrote its moments to
+        last = first_timed + args.steps - 1
+        dump_stream_outputs(args.dump_outputs, out_rows, partials[(last // G) & 1].view(G, B, 4)[last % G].cpu().numpy())
     per_gpu_kernel_s = [region_kernel_s]
     rccl = None
     if use_dist:
