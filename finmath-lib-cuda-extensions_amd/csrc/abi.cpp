@@ -4,11 +4,14 @@
 // directions).  A JNI layer maps 1:1 onto the entry points.
 #include "runtime.hpp"
 #include "sharded.hpp"
+#include "order_stats.hpp"
 #include <cmath>
 
 #include <chrono>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -566,6 +569,106 @@ int fmhip_expectation_combine(const fmhip_moments* gathered, int world, int coun
         need(gathered, "gathered"); need(out, "out");
         if (world < 1 || count < 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "bad world or count");
         combine_moments(gathered, world, count, out);
+    });
+}
+
+// ---------------------------------------------------------------- order statistics (order_stats.hpp / order_stats_engine.hpp)
+// One pass on THIS thread's engine (a shard's worker calls these: sharded.cpp), and the calls themselves: the host loop of
+// order_stats.hpp over passes that are the engine's, with the communicator's ranks added in.
+extern "C++" {
+namespace fm {
+int os_local_hist(const fmhip_vec* v, int count, int S, const uint32_t* slots, uint32_t shift, uint64_t* hist) { return guarded([&] { Engine::get().os_hist_pass(v, count, S, slots, shift, hist); }); }
+int os_local_sum(const fmhip_vec* v, int count, const uint32_t* keys, double* sums) { return guarded([&] { Engine::get().os_sum_pass(v, count, keys, sums); }); }
+int os_local_count(fmhip_vec v, const double* ascending, int m, uint64_t* counts) { return guarded([&] { Engine::get().os_count_pass(v, ascending, m, counts); }); }
+// bounds in any order, NaN among them → counts per bound, from passes over at most FM_OS_MAX_BOUNDS ascending bounds each
+void os_counts_from_passes(const double* bounds, int n_bounds, int64_t* counts_out, const std::function<void(const double*, int, uint64_t*)>& pass) {
+    std::vector<int> order;
+    for (int j = 0; j < n_bounds; ++j) { if (bounds[j] == bounds[j]) order.push_back(j); else counts_out[j] = 0; }
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return bounds[a] < bounds[b]; });
+    constexpr size_t CHUNK = 4096;
+    for (size_t c0 = 0; c0 < order.size(); c0 += CHUNK) {
+        const size_t m = std::min(CHUNK, order.size() - c0);
+        std::vector<double> asc(m);
+        for (size_t i = 0; i < m; ++i) asc[i] = bounds[order[c0 + i]];
+        std::vector<uint64_t> per(m + 1, 0);
+        pass(asc.data(), (int)m, per.data());
+        uint64_t cum = 0;
+        for (size_t i = 0; i < m; ++i) { cum += per[i]; counts_out[order[c0 + i]] = (int64_t)cum; }
+    }
+}
+}
+}
+// counts of every rank added (as doubles: exact below 2^53)
+static void comm_add_counts(Engine& e, uint64_t* counts, size_t m) {
+    if (e.comm_world <= 1 || !e.comm_gather) return;
+    if (m > (size_t)0x7fffffff) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "too many counts for one gather");
+    std::vector<double> mine(m), all((size_t)e.comm_world * m);
+    for (size_t i = 0; i < m; ++i) mine[i] = (double)counts[i];
+    const int st = e.comm_gather(e.comm_context, mine.data(), (int)m, all.data());
+    if (st != 0) throw Error(FMHIP_ERR_HIP, "the expectation communicator's gather failed with status " + std::to_string(st));
+    for (size_t i = 0; i < m; ++i) { double s = 0.0; for (int r = 0; r < e.comm_world; ++r) s += all[(size_t)r * m + i]; counts[i] = (uint64_t)s; }
+}
+static void comm_add_sums(Engine& e, double* sums, size_t m) {
+    if (e.comm_world <= 1 || !e.comm_gather) return;
+    std::vector<double> all((size_t)e.comm_world * m);
+    const int st = e.comm_gather(e.comm_context, sums, (int)m, all.data());
+    if (st != 0) throw Error(FMHIP_ERR_HIP, "the expectation communicator's gather failed with status " + std::to_string(st));
+    for (size_t i = 0; i < m; ++i) { double s = all[i]; for (int r = 1; r < e.comm_world; ++r) s += all[(size_t)r * m + i]; sums[i] = s; }      // rank order
+}
+static void check_ranks(const int64_t* ranks, int n_ranks, int64_t n_total) {
+    for (int j = 0; j < n_ranks; ++j)
+        if (ranks[j] < 0 || ranks[j] >= n_total) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "rank " + std::to_string(ranks[j]) + " outside a sample of " + std::to_string(n_total));
+}
+int fmhip_select_ranks_batch(const fmhip_vec* vectors, int count, const int64_t* ranks, int n_ranks, double* values_out) {
+    FRONT(select_ranks_batch(vectors, count, ranks, n_ranks, values_out));
+    TE_LOCAL(vectors, count, L, fmhip_select_ranks_batch(L, count, ranks, n_ranks, values_out));
+    return guarded([&] {
+        need(vectors, "vectors"); need(ranks, "ranks"); need(values_out, "values_out");
+        if (n_ranks < 1) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "n_ranks must be positive");
+        Engine& e = Engine::get();
+        check_ranks(ranks, n_ranks, e.os_size(vectors, count) * e.comm_world);
+        std::vector<fm::os::Selected> sel((size_t)count * n_ranks);
+        fm::os::select([&](int S, const uint32_t* slots, uint32_t shift, uint64_t* hist) {
+            e.os_hist_pass(vectors, count, S, slots, shift, hist);
+            comm_add_counts(e, hist, (size_t)count * S * fm::os::BINS);
+        }, count, ranks, n_ranks, sel.data());
+        for (size_t i = 0; i < sel.size(); ++i) values_out[i] = fm::os::value_of_key(sel[i].key);
+    });
+}
+int fmhip_rank_sums_batch(const fmhip_vec* vectors, int count, int64_t rank_from, int64_t rank_to, double* sums_out) {
+    FRONT(rank_sums_batch(vectors, count, rank_from, rank_to, sums_out));
+    TE_LOCAL(vectors, count, L, fmhip_rank_sums_batch(L, count, rank_from, rank_to, sums_out));
+    return guarded([&] {
+        need(vectors, "vectors"); need(sums_out, "sums_out");
+        Engine& e = Engine::get();
+        const int64_t ranks[2] = { rank_from, rank_to };
+        check_ranks(ranks, 2, e.os_size(vectors, count) * e.comm_world);
+        if (rank_from > rank_to) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "rank_from above rank_to");
+        std::vector<fm::os::Selected> sel((size_t)count * 2);
+        fm::os::select([&](int S, const uint32_t* slots, uint32_t shift, uint64_t* hist) {
+            e.os_hist_pass(vectors, count, S, slots, shift, hist);
+            comm_add_counts(e, hist, (size_t)count * S * fm::os::BINS);
+        }, count, ranks, 2, sel.data());
+        std::vector<uint32_t> keys((size_t)count * 2);
+        std::vector<double> inner((size_t)count, 0.0);
+        bool any = false;
+        for (int k = 0; k < count; ++k) { keys[2 * (size_t)k] = sel[2 * (size_t)k].key; keys[2 * (size_t)k + 1] = sel[2 * (size_t)k + 1].key; any |= keys[2 * (size_t)k] != keys[2 * (size_t)k + 1]; }
+        if (any) { e.os_sum_pass(vectors, count, keys.data(), inner.data()); comm_add_sums(e, inner.data(), (size_t)count); }      // (the keys are the global sample's: the same decision on every rank)
+        for (int k = 0; k < count; ++k) sums_out[k] = fm::os::rank_sum(sel[2 * (size_t)k], sel[2 * (size_t)k + 1], rank_from, rank_to, inner[(size_t)k]);
+    });
+}
+int fmhip_count_not_above(fmhip_vec v, const double* bounds, int n_bounds, int64_t* counts_out) {
+    FRONT(count_not_above(v, bounds, n_bounds, counts_out));
+    TE_OWNER(v, fmhip_count_not_above(v, bounds, n_bounds, counts_out));
+    return guarded([&] {
+        need(bounds, "bounds"); need(counts_out, "counts_out");
+        if (n_bounds < 1) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "n_bounds must be positive");
+        Engine& e = Engine::get();
+        e.os_size(&v, 1);
+        fm::os_counts_from_passes(bounds, n_bounds, counts_out, [&](const double* asc, int m, uint64_t* per) {
+            e.os_count_pass(v, asc, m, per);
+            comm_add_counts(e, per, (size_t)m + 1);
+        });
     });
 }
 

@@ -371,6 +371,190 @@ __global__ void __launch_bounds__(64) fm_combine_moments_kernel(const double* __
 }
 
 // ---------------------------------------------------------------------------------------------
+// Order statistics: quantiles, quantile expectations and histograms without a sort and without the vector leaving the
+// device.  Three kernels, one launch per pass for a whole batch (blockIdx.y = vector), each vector read once per pass with 16-byte loads.
+// All counts are integers (LDS atomics per workgroup, one agent-scope integer add per NON-EMPTY bin per workgroup); the one fp64 sum is
+// added in an order that depends on n alone.  No float atomics: results are the same from run to run by construction.
+// ---------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ uint32_t os_key(float x)
+{
+    const uint32_t u = __float_as_uint(x);
+    const uint32_t k = (u >> 31) ? ~u : (u | 0x80000000u);
+    return ((u & 0x7fffffffu) > 0x7f800000u) ? 0xffffffffu : k;     // NaNs of either sign and any payload: one key, the last
+}
+
+// h[bin] += 1 for every lane with `valid`.  Monte-Carlo data is clustered — the leading digit of values in [0.5, 2) is ONE bin, a floored
+// payoff is half exact zeros in every pass — and same-address LDS atomics serialise: the most frequent digits of the wave are peeled off
+// first, one add of a population count each (at most three rounds, given up as soon as a round finds fewer than eight equal lanes: digits
+// that are spread out gain nothing from it); what is left adds lane by lane.
+__device__ __forceinline__ void os_lds_add(uint32_t* h, const uint32_t bin, bool valid)
+{
+    uint64_t pending = __ballot(valid);
+#pragma unroll 1
+    for (int round = 0; round < 3 && pending != 0ull; ++round) {
+        const int leader = __ffsll((long long)pending) - 1;
+        const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)bin, leader);
+        const uint64_t same = __ballot(valid && bin == b0);
+        const uint32_t c = (uint32_t)__popcll(same);
+        if ((int)(threadIdx.x & 63u) == leader) atomicAdd(h + b0, c);
+        valid = valid && bin != b0;
+        pending &= ~same;
+        if (c < 8u) break;
+    }
+    if (valid) atomicAdd(h + bin, 1u);
+}
+
+// Arrival counting at `counter` (zero before the launch, zero again after the last arrival): true, for the whole workgroup, in the LAST of
+// `members` workgroups.  Whatever the others wrote before they arrived is visible to it: every thread's writes are released at agent scope
+// before the barrier, the count is an agent-scope acquire-release add, and the last arriver's threads fence again behind the barrier.
+__device__ __forceinline__ bool os_arrive_last(uint32_t* counter, const uint32_t members)
+{
+    __shared__ uint32_t last;
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        const uint32_t arrived = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        last = (arrived == members - 1u) ? 1u : 0u;
+        if (last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    const bool r = last != 0u;
+    if (r) __threadfence();
+    return r;
+}
+
+// Integers counted in LDS → the device array (adds of the non-empty bins) → by the last workgroup of the vector into pinned host memory
+// (the device array is zero again behind it) → the last vector's last workgroup raises the flag.
+__device__ __forceinline__ void os_publish_counts(const uint32_t* lds, const uint32_t count, uint32_t* dev, uint32_t* host, const DevOsCommon& C)
+{
+    for (uint32_t i = threadIdx.x; i < count; i += FM_BLOCK) {
+        const uint32_t c = lds[i];
+        if (c) __hip_atomic_fetch_add(dev + i, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (!os_arrive_last(C.counters + blockIdx.y, gridDim.x)) return;
+    for (uint32_t i = threadIdx.x; i < count; i += FM_BLOCK) {
+        host[i] = __hip_atomic_load(dev + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(dev + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __threadfence_system();
+    if (!os_arrive_last(C.counters + gridDim.y, gridDim.y)) return;
+    if (threadIdx.x == 0u) __hip_atomic_store(C.done_flag, C.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// The elements a lane holds in one iteration: FM_OS_TILE / FM_BLOCK = 16, as four 16-byte loads issued together.  Lanes past the end read
+// float4 0 and are masked by n (a partially valid float4 is in bounds: vectors are padded to 256 B).
+#define FM_OS_FOR_EACH_ELEMENT(P, TILE, N, BODY)                                                                    \
+    {                                                                                                               \
+        f32x4 os_v[4]; uint32_t os_i[4];                                                                            \
+        _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                                             \
+            os_i[u] = ((TILE) * 4u + (uint32_t)u) * FM_BLOCK + threadIdx.x;                                         \
+            os_v[u] = (P)[(int64_t)os_i[u] * 4 < (N) ? os_i[u] : 0u];                                               \
+        }                                                                                                           \
+        _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                                             \
+            const float os_x[4] = { os_v[u].x, os_v[u].y, os_v[u].z, os_v[u].w };                                   \
+            _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                         \
+                const bool in_range = (int64_t)os_i[u] * 4 + j < (N);                                               \
+                const float x = os_x[j];                                                                            \
+                BODY                                                                                                \
+            }                                                                                                       \
+        }                                                                                                           \
+    }
+
+__global__ void __launch_bounds__(FM_BLOCK) fm_os_hist_kernel(const DevSelectArgs A, const uint64_t* __restrict__ vecs, const uint32_t* __restrict__ slots)
+{
+    __shared__ uint32_t h[FM_OS_MAX_SLOTS * FM_OS_BINS];
+    __shared__ uint32_t prefix[FM_OS_MAX_SLOTS];
+    const uint32_t k = blockIdx.y;
+    const uint32_t* sl = A.c.use_inline ? A.slots0 : slots + (size_t)k * (1u + A.S);
+    const uint32_t ns = sl[0] < A.S ? sl[0] : A.S;
+    const f32x4* __restrict__ p = reinterpret_cast<const f32x4*>(A.c.use_inline ? A.c.vec0 : vecs[k]);
+    for (uint32_t i = threadIdx.x; i < ns * FM_OS_BINS; i += FM_BLOCK) h[i] = 0u;
+    if (threadIdx.x < ns) prefix[threadIdx.x] = sl[1u + threadIdx.x];
+    __syncthreads();
+    const uint32_t shift = A.shift, above = A.shift + 8u;
+    const int64_t n = A.c.n;
+    for (uint32_t tile = blockIdx.x; tile < A.c.tiles; tile += gridDim.x) {
+        FM_OS_FOR_EACH_ELEMENT(p, tile, n, {
+            const uint32_t key = os_key(x);
+            const uint32_t digit = (key >> shift) & 255u;
+            for (uint32_t s = 0; s < ns; ++s)
+                os_lds_add(h + s * FM_OS_BINS, digit, in_range && ((uint64_t)(key ^ prefix[s]) >> above) == 0ull);
+        })
+    }
+    __syncthreads();
+    const size_t base = (size_t)k * A.S * FM_OS_BINS;
+    os_publish_counts(h, ns * FM_OS_BINS, A.hist_dev + base, A.hist_host + base, A.c);
+}
+
+// Σ (double)x over the elements with key_lo < key < key_hi.  Order of the additions: a lane adds its elements tile by tile, the lanes of a
+// wave and the waves of a workgroup are added in a fixed tree, the last workgroup of the vector adds the workgroups' partials — lane-strided,
+// then the same tree.  The grid is a function of n alone (os_sum_blocks), so the bits depend on the data and on nothing else.
+__device__ __forceinline__ double os_wave_sum(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__global__ void __launch_bounds__(FM_BLOCK) fm_os_sum_kernel(const DevRankSumArgs A, const uint64_t* __restrict__ vecs, const uint32_t* __restrict__ keys)
+{
+    __shared__ double wave_part[FM_BLOCK / 64];
+    const uint32_t k = blockIdx.y;
+    const uint32_t lo = A.c.use_inline ? A.lo0 : keys[2u * k], hi = A.c.use_inline ? A.hi0 : keys[2u * k + 1u];
+    const f32x4* __restrict__ p = reinterpret_cast<const f32x4*>(A.c.use_inline ? A.c.vec0 : vecs[k]);
+    const int64_t n = A.c.n;
+    double acc = 0.0;
+    for (uint32_t tile = blockIdx.x; tile < A.c.tiles; tile += gridDim.x) {
+        FM_OS_FOR_EACH_ELEMENT(p, tile, n, {
+            const uint32_t key = os_key(x);
+            if (in_range && key > lo && key < hi) acc += (double)x;
+        })
+    }
+    acc = os_wave_sum(acc);
+    if ((threadIdx.x & 63u) == 0u) wave_part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    double* part = A.partials + (size_t)k * gridDim.x;
+    if (threadIdx.x == 0u) part[blockIdx.x] = ((wave_part[0] + wave_part[1]) + wave_part[2]) + wave_part[3];
+    if (!os_arrive_last(A.c.counters + k, gridDim.x)) return;
+    if (threadIdx.x < 64u) {
+        double s = 0.0;
+        for (uint32_t b = threadIdx.x; b < gridDim.x; b += 64u) s += part[b];
+        s = os_wave_sum(s);
+        if (threadIdx.x == 0u) A.out_host[k] = s;
+    }
+    __threadfence_system();
+    if (!os_arrive_last(A.c.counters + gridDim.y, gridDim.y)) return;
+    if (threadIdx.x == 0u) __hip_atomic_store(A.c.done_flag, A.c.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// counts[i] = number of elements x, not NaN, with exactly i of the m ascending bounds strictly below (double)x — i.e. x lies in
+// (bounds[i-1], bounds[i]]: the comparison of the reference's histogram loop (float promoted to double, `<=`).  Bounds and counts in LDS.
+__global__ void __launch_bounds__(FM_BLOCK) fm_os_count_kernel(const DevCountArgs A, const double* __restrict__ bounds)
+{
+    __shared__ double b[FM_OS_MAX_BOUNDS];
+    __shared__ uint32_t c[FM_OS_MAX_BOUNDS + 1];
+    const uint32_t m = A.m < (uint32_t)FM_OS_MAX_BOUNDS ? A.m : (uint32_t)FM_OS_MAX_BOUNDS;
+    for (uint32_t i = threadIdx.x; i < m; i += FM_BLOCK) b[i] = bounds[i];
+    for (uint32_t i = threadIdx.x; i <= m; i += FM_BLOCK) c[i] = 0u;
+    __syncthreads();
+    const f32x4* __restrict__ p = reinterpret_cast<const f32x4*>(A.c.vec0);
+    const int64_t n = A.c.n;
+    for (uint32_t tile = blockIdx.x; tile < A.c.tiles; tile += gridDim.x) {
+        FM_OS_FOR_EACH_ELEMENT(p, tile, n, {
+            const double xd = (double)x;
+            uint32_t pos = 0u;                                      // bounds below xd: branch-free lower bound
+            for (uint32_t half = A.pow2; half != 0u; half >>= 1) {
+                const uint32_t t = pos + half;
+                if (t <= m && b[t - 1u] < xd) pos = t;
+            }
+            os_lds_add(c, pos, in_range && x == x);
+        })
+    }
+    __syncthreads();
+    os_publish_counts(c, m + 1u, A.counts_dev, A.counts_host, A.c);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Host-side launchers (the only functions the runtime calls)
 // ---------------------------------------------------------------------------------------------
 
@@ -447,6 +631,9 @@ hipError_t preload_kernels()
     if (e == hipSuccess) e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&fm_fill_kernel));
     if (e == hipSuccess) e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&fm_gather_moments_kernel));
     if (e == hipSuccess) e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&fm_combine_moments_kernel));
+    if (e == hipSuccess) e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&fm_os_hist_kernel));
+    if (e == hipSuccess) e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&fm_os_sum_kernel));
+    if (e == hipSuccess) e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&fm_os_count_kernel));
     return e;
 }
 
@@ -461,6 +648,25 @@ hipError_t launch_gather_moments(const DevGatherArgs& a, double* out, hipStream_
 {
     if (a.count == 0) return hipSuccess;
     hipLaunchKernelGGL(fm_gather_moments_kernel, dim3((a.count + 63u) / 64u), dim3(64), 0, st, a, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_os_hist(const DevSelectArgs& a, const uint64_t* vecs, const uint32_t* slots, uint32_t batch, hipStream_t st)
+{
+    if (batch == 0 || batch > 65535u || a.c.n <= 0 || a.S == 0 || a.S > (uint32_t)FM_OS_MAX_SLOTS || a.shift > 24u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fm_os_hist_kernel, dim3(os_blocks_per_vector(a.c.n, batch), batch, 1), dim3(FM_BLOCK), 0, st, a, vecs, slots);
+    return hipGetLastError();
+}
+hipError_t launch_os_sum(const DevRankSumArgs& a, const uint64_t* vecs, const uint32_t* keys, uint32_t batch, hipStream_t st)
+{
+    if (batch == 0 || batch > 65535u || a.c.n <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fm_os_sum_kernel, dim3(os_sum_blocks(a.c.n), batch, 1), dim3(FM_BLOCK), 0, st, a, vecs, keys);
+    return hipGetLastError();
+}
+hipError_t launch_os_count(const DevCountArgs& a, const double* bounds, hipStream_t st)
+{
+    if (a.c.n <= 0 || a.m == 0 || a.m > (uint32_t)FM_OS_MAX_BOUNDS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fm_os_count_kernel, dim3(os_blocks_per_vector(a.c.n, 1u), 1, 1), dim3(FM_BLOCK), 0, st, a, bounds);
     return hipGetLastError();
 }
 

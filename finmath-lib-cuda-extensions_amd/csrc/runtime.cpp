@@ -304,6 +304,7 @@ void Engine::shutdown() {
     schedule_cache_.clear(); schedule_cache_bytes_ = 0; dag_policies_.clear(); policy_reset();
     for (auto& kv : program_cache_) if (--kv.second->refs == 0) delete kv.second;
     program_cache_.clear();
+    os_release();
     pool_.purge();
     pool_ = Pool();
     if (stage_) (void)hipHostFree(stage_);
@@ -4216,3 +4217,5 @@ void Engine::profile_read(double* ms_total, int64_t* n) {
 }
 
 } // namespace fm
+
+#include "order_stats_engine.hpp"      // Engine::os_*: the order-statistics passes

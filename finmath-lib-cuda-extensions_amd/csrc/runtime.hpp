@@ -365,6 +365,15 @@ public:
     MomentsTicket ticket_take(int64_t id);                   // removes it from the table (under the lock)
     void ticket_retire(MomentsTicket& t);                    // block and event back to their free lists (under the lock)
 
+    // order statistics (order_stats_engine.hpp): ONE pass over a batch each — the digit histograms of a radix-select pass, the fp64
+    // sums of the elements strictly between two keys, the counts per interval of ascending bounds.  Every call computes what is pending
+    // below its vectors in one flush, launches once, waits for the integers in pinned memory (under the lock, as read() does) and holds
+    // the vectors' storage — not their nodes — across the wait.  The loop over the passes is the caller's (order_stats.hpp).
+    int64_t os_size(const fmhip_vec* hs, int count);                                       // the common size; SIZE_MISMATCH / INVALID_ARGUMENT (empty)
+    void os_hist_pass(const fmhip_vec* hs, int count, int S, const uint32_t* slots, uint32_t shift, uint64_t* hist_out);
+    void os_sum_pass(const fmhip_vec* hs, int count, const uint32_t* keys, double* sums_out);
+    void os_count_pass(fmhip_vec h, const double* ascending_bounds, int m, uint64_t* counts_out);      // counts_out[m + 1]
+
     // programs
     fmhip_program program_create(const fmhip_prog_op* ops, int n_ops, int n_in, const int32_t* outs, int n_out,
                                  const int32_t* reds, int n_red);
@@ -444,6 +453,16 @@ private:
     void*  dump_dev_ = nullptr;             // FM_DUMP_BYTES nobody reads: target of the stores of lanes past the end of a vector (rolled kernels)
     void*  ensure_stage(size_t bytes);
     size_t ring_reserve(size_t bytes);
+
+    // order statistics: device scratch that is ZERO between launches (arrival counters, histograms; the kernels leave it so), scratch that
+    // need not be (tables, partial sums), the sequence number the completion flag receives
+    struct OsHold;
+    void os_prepare(const fmhip_vec* hs, int count, OsHold& hold);
+    void os_scratch(size_t zero_bytes, size_t other_bytes);
+    void os_wait(volatile uint64_t* flag, uint64_t value);
+    void os_release();
+    void* os_zero_ = nullptr; size_t os_zero_cap_ = 0; void* os_other_ = nullptr; size_t os_other_cap_ = 0;
+    uint64_t os_seq_ = 0; bool os_dirty_ = false;
 
     Node* new_node(int64_t n);
     void collect_pending(const fmhip_vec* roots, int n_roots, std::vector<Node*>& graph);      // pending nodes below the roots, in recording order

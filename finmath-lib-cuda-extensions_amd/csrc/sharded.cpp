@@ -2,6 +2,7 @@
 #include "sharded.hpp"
 #include "runtime.hpp"
 #include "kernels.h"
+#include "order_stats.hpp"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -666,6 +667,81 @@ int expectation_collective(int* kind, char* why, int why_len) {
     return fronted([&](Shards& s) {
         if (kind) *kind = s.collective;
         if (why && why_len > 0) { std::strncpy(why, s.collective_why.c_str(), (size_t)why_len - 1); why[why_len - 1] = 0; }
+    });
+}
+
+// Order statistics (order_stats.hpp): every shard runs the pass on its block, the front adds the shards' integers — histograms and
+// counts exactly, the fp64 sums of a rank sum in shard order (like combine()).  The host loop over the passes is the one a single
+// engine runs; a shard that holds no path of a short vector is left out.
+static int64_t os_front_size(Shards& s, const fmhip_vec* vectors, int count) {
+    need(vectors, "vectors");
+    if (count <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "count must be positive");
+    const int64_t n = s.vec(vectors[0]).n;
+    for (int i = 1; i < count; ++i) if (s.vec(vectors[i]).n != n) throw Error(FMHIP_ERR_SIZE_MISMATCH, "order statistics over vectors of different size");
+    if (n <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "order statistics of an empty vector");
+    return n;
+}
+static bool os_shard_has_paths(const Worker& w, int64_t n) { int64_t off, cnt; shard_range(n, w.shards, w.shard, &off, &cnt); return cnt > 0; }
+static void os_front_select(Shards& s, const fmhip_vec* vectors, int count, int64_t n, const int64_t* ranks, int n_ranks, os::Selected* sel) {
+    os::select([&](int S, const uint32_t* slots, uint32_t shift, uint64_t* hist) {
+        const size_t m = (size_t)count * S * os::BINS;
+        std::vector<std::vector<uint64_t>> per((size_t)s.D(), std::vector<uint64_t>(m, 0));
+        s.post([&](Worker& w) {
+            if (!os_shard_has_paths(w, n)) return;
+            std::vector<fmhip_vec> l; for (int i = 0; i < count; ++i) l.push_back(w.at(vectors[i]));
+            w.ok(os_local_hist(l.data(), count, S, slots, shift, per[(size_t)w.shard].data()));
+        });
+        s.wait();
+        for (size_t i = 0; i < m; ++i) { uint64_t c = 0; for (const auto& p : per) c += p[i]; hist[i] = c; }
+    }, count, ranks, n_ranks, sel);
+}
+int select_ranks_batch(const fmhip_vec* vectors, int count, const int64_t* ranks, int n_ranks, double* values_out) {
+    return fronted([&](Shards& s) {
+        need(ranks, "ranks"); need(values_out, "values_out");
+        const int64_t n = os_front_size(s, vectors, count);
+        if (n_ranks < 1) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "n_ranks must be positive");
+        for (int j = 0; j < n_ranks; ++j) if (ranks[j] < 0 || ranks[j] >= n) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "rank " + std::to_string(ranks[j]) + " outside a sample of " + std::to_string(n));
+        std::vector<os::Selected> sel((size_t)count * n_ranks);
+        os_front_select(s, vectors, count, n, ranks, n_ranks, sel.data());
+        for (size_t i = 0; i < sel.size(); ++i) values_out[i] = os::value_of_key(sel[i].key);
+    });
+}
+int rank_sums_batch(const fmhip_vec* vectors, int count, int64_t rank_from, int64_t rank_to, double* sums_out) {
+    return fronted([&](Shards& s) {
+        need(sums_out, "sums_out");
+        const int64_t n = os_front_size(s, vectors, count);
+        if (rank_from < 0 || rank_to >= n || rank_from > rank_to) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "bad rank range for a sample of " + std::to_string(n));
+        const int64_t ranks[2] = { rank_from, rank_to };
+        std::vector<os::Selected> sel((size_t)count * 2);
+        os_front_select(s, vectors, count, n, ranks, 2, sel.data());
+        std::vector<uint32_t> keys((size_t)count * 2);
+        bool any = false;
+        for (int k = 0; k < count; ++k) { keys[2 * (size_t)k] = sel[2 * (size_t)k].key; keys[2 * (size_t)k + 1] = sel[2 * (size_t)k + 1].key; any |= keys[2 * (size_t)k] != keys[2 * (size_t)k + 1]; }
+        std::vector<double> inner((size_t)count, 0.0);
+        if (any) {
+            std::vector<std::vector<double>> per((size_t)s.D(), std::vector<double>((size_t)count, 0.0));
+            s.post([&](Worker& w) {
+                if (!os_shard_has_paths(w, n)) return;
+                std::vector<fmhip_vec> l; for (int i = 0; i < count; ++i) l.push_back(w.at(vectors[i]));
+                w.ok(os_local_sum(l.data(), count, keys.data(), per[(size_t)w.shard].data()));
+            });
+            s.wait();
+            for (int k = 0; k < count; ++k) { double t = per[0][(size_t)k]; for (size_t d = 1; d < per.size(); ++d) t += per[d][(size_t)k]; inner[(size_t)k] = t; }      // shard order
+        }
+        for (int k = 0; k < count; ++k) sums_out[k] = os::rank_sum(sel[2 * (size_t)k], sel[2 * (size_t)k + 1], rank_from, rank_to, inner[(size_t)k]);
+    });
+}
+int count_not_above(fmhip_vec v, const double* bounds, int n_bounds, int64_t* counts_out) {
+    return fronted([&](Shards& s) {
+        need(bounds, "bounds"); need(counts_out, "counts_out");
+        if (n_bounds < 1) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "n_bounds must be positive");
+        const int64_t n = os_front_size(s, &v, 1);
+        os_counts_from_passes(bounds, n_bounds, counts_out, [&](const double* asc, int m, uint64_t* out) {
+            std::vector<std::vector<uint64_t>> per((size_t)s.D(), std::vector<uint64_t>((size_t)m + 1, 0));
+            s.post([&](Worker& w) { if (os_shard_has_paths(w, n)) w.ok(os_local_count(w.at(v), asc, m, per[(size_t)w.shard].data())); });
+            s.wait();
+            for (int i = 0; i <= m; ++i) { uint64_t c = 0; for (const auto& p : per) c += p[(size_t)i]; out[i] = c; }
+        });
     });
 }
 

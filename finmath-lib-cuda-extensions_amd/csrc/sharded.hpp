@@ -20,6 +20,7 @@
 // built on have one; tests use the device lists {0, 0} and {0, 0, 0} — shards on separate streams of one device.
 #pragma once
 #include <cstdint>
+#include <functional>
 #include "../../include/fmhip.h"
 
 namespace fm {
@@ -27,6 +28,11 @@ namespace fm {
 // over to the functions below (same signatures and statuses as their fmhip_* namesakes)
 bool front_active();
 void shard_range(int64_t n, int shards, int shard, int64_t* offset, int64_t* count);
+// one order-statistics pass on the calling thread's engine (abi.cpp; a shard's worker calls them), and the bounds bookkeeping both callers share
+int os_local_hist(const fmhip_vec* v, int count, int S, const uint32_t* slots, uint32_t shift, uint64_t* hist);
+int os_local_sum(const fmhip_vec* v, int count, const uint32_t* keys, double* sums);
+int os_local_count(fmhip_vec v, const double* ascending, int m, uint64_t* counts);
+void os_counts_from_passes(const double* bounds, int n_bounds, int64_t* counts_out, const std::function<void(const double*, int, uint64_t*)>& pass);
 namespace front {
 int init_devices(const int* devices, int count);
 int shutdown();
@@ -51,6 +57,9 @@ int reduce_moments_batch_devices(const fmhip_vec* vectors, int count, const doub
 int get_stream_of(int shard, void** stream_out);
 int expectation_collective(int* kind, char* why, int why_len);
 int vec_give_up_values(const fmhip_vec* vectors, int count);
+int select_ranks_batch(const fmhip_vec* vectors, int count, const int64_t* ranks, int n_ranks, double* values_out);
+int rank_sums_batch(const fmhip_vec* vectors, int count, int64_t rank_from, int64_t rank_to, double* sums_out);
+int count_not_above(fmhip_vec v, const double* bounds, int n_bounds, int64_t* counts_out);
 int program_create(const fmhip_prog_op* ops, int n_ops, int n_inputs, const int32_t* out_values, int n_outputs, const int32_t* reduce_values, int n_reduce, fmhip_program* out);
 int program_release(fmhip_program p);
 int program_shape(fmhip_program p, int* n_inputs, int* n_outputs, int* n_reduce);

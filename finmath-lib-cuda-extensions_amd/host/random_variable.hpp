@@ -21,6 +21,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <functional>
 #include <limits>
 #include <memory>
@@ -81,8 +82,12 @@ public:
     virtual RV isNaN() const = 0;
     virtual RV sin() const = 0;                                     // GPU class throws (:1373-1384); semantics from the twin (:927-954)
     virtual RV cos() const = 0;
-    // host-side cold paths: the reference sorts / maps on the host as well (:970-1091; twin :473-602, :667-748)
+    // apply maps on the host, as the reference does; the order statistics below are selected and counted on the DEVICE when the object
+    // has a device vector (orderStatisticsHandle) — fmhip_select_ranks_batch, fmhip_rank_sums_batch, fmhip_count_not_above — and sort
+    // on the host as the reference does (:970-1091; twin :473-602, :667-748) otherwise, or with FMHIP_DEVICE_ORDER_STATS=0
     virtual RV apply(const std::function<double(double)>& f) const = 0;
+    virtual fmhip_vec orderStatisticsHandle() const { return 0; }
+    static bool deviceOrderStatistics() { const char* e = std::getenv("FMHIP_DEVICE_ORDER_STATS"); return !(e && e[0] == '0' && e[1] == 0); }
     double getQuantile(double quantile) const;                      // index convention of the GPU class (:983: 1 - quantile)
     double getQuantileExpectation(double quantileStart, double quantileEnd) const;
     std::vector<double> getHistogram(const std::vector<double>& intervalPoints) const;                     // :1026-1068
@@ -323,6 +328,7 @@ public:
     // ---- reductions on the device (replaces :830-901).  With an expectation communicator (fmhip_set_expectation_comm) the moments
     // are those of the GLOBAL vector (this process holds one shard of its paths) and the sample size is that of all ranks.
     int64_t sampleSize() const override { int world = 1; check(fmhip_expectation_world(&world, nullptr)); return size() * world; }
+    fmhip_vec orderStatisticsHandle() const override { return isDeterministic() ? 0 : vec_.handle(); }
     double getAverage() const override {
         if (isDeterministic()) return value_;
         if (n_ == 0) return std::nan("");
@@ -502,6 +508,13 @@ inline double RandomVariable::getQuantile(double quantile) const {
     if (isDeterministic()) return doubleValue();
     const int64_t n = size();
     if (n == 0) return std::nan("");
+    if (const fmhip_vec h = deviceOrderStatistics() ? orderStatisticsHandle() : 0) {
+        const int64_t m = sampleSize();           // (the global sample under an expectation communicator)
+        const int64_t rank = std::min(std::max<int64_t>((int64_t)std::floor((double)(m + 1) * (1.0 - quantile) - 1.0 + 0.5), 0), m - 1);
+        double value = 0.0;
+        check(fmhip_select_ranks_batch(&h, 1, &rank, 1, &value));
+        return value;
+    }
     std::vector<double> v = getRealizations();
     std::sort(v.begin(), v.end());
     const int64_t idx = (int64_t)std::floor((double)(n + 1) * (1.0 - quantile) - 1.0 + 0.5);
@@ -512,6 +525,14 @@ inline double RandomVariable::getQuantileExpectation(double quantileStart, doubl
     const int64_t n = size();
     if (n == 0) return std::nan("");
     if (quantileStart > quantileEnd) return getQuantileExpectation(quantileEnd, quantileStart);
+    if (const fmhip_vec h = deviceOrderStatistics() ? orderStatisticsHandle() : 0) {
+        const int64_t m = sampleSize();
+        auto rank = [m](double q) { return std::min(std::max<int64_t>((int64_t)std::floor((double)(m + 1) * q - 1.0 + 0.5), 0), m - 1); };
+        const int64_t r0 = rank(quantileStart), r1 = rank(quantileEnd);
+        double sum = 0.0;
+        check(fmhip_rank_sums_batch(&h, 1, r0, r1, &sum));
+        return sum / (double)(r1 - r0 + 1);
+    }
     std::vector<double> v = getRealizations();
     std::sort(v.begin(), v.end());
     auto index = [n](double q) { return std::min(std::max<int64_t>((int64_t)std::floor((double)(n + 1) * q - 1.0 + 0.5), 0), n - 1); };
@@ -526,6 +547,16 @@ inline std::vector<double> RandomVariable::getHistogram(const std::vector<double
         const double value = doubleValue();
         for (size_t k = 0; k < intervalPoints.size(); ++k) if (value > intervalPoints[k]) { hist[k] = 1.0; break; }
         hist[intervalPoints.size()] = 1.0;
+        return hist;
+    }
+    if (const fmhip_vec h = (deviceOrderStatistics() && size() > 0) ? orderStatisticsHandle() : 0) {
+        std::vector<int64_t> notAbove(intervalPoints.size(), 0);
+        if (!intervalPoints.empty()) check(fmhip_count_not_above(h, intervalPoints.data(), (int)intervalPoints.size(), notAbove.data()));
+        const int64_t m = sampleSize();
+        int64_t prev = 0;                          // the reference's running index never goes back (unsorted points)
+        for (size_t k = 0; k < intervalPoints.size(); ++k) { const int64_t cur = std::max(notAbove[k], prev); hist[k] = (double)(cur - prev); prev = cur; }
+        hist[intervalPoints.size()] = (double)(m - prev);
+        for (double& x : hist) x /= (double)m;
         return hist;
     }
     std::vector<double> v = getRealizations();

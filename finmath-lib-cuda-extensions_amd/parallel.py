@@ -2,7 +2,11 @@
 vector; element-wise work needs no communication; the only exchange is one small collective over the per-rank
 reduction partials {Σ, Σ², min, max}.  The reference has no multi-GPU support at all (README.md:33-35 names GPU memory
 as its limit) — this is new capability, built on torch.distributed (backend "nccl" = RCCL on ROCm, "gloo" in the
-CPU tests).  Pure host logic: nothing here touches the device library."""
+CPU tests).  Pure host logic: nothing here touches the device library.
+
+Order statistics (getQuantile, getQuantileExpectation, getHistogram) couple the paths too: with the engine's expectation communicator
+set (fmhip_set_expectation_comm) they are those of the GLOBAL sample — the per-pass digit counts of the device radix select go through
+the same gather as the moments, so every rank must ask for them in the same order, like expectations."""
 from __future__ import annotations
 
 import math

@@ -32,6 +32,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 
 import numpy as np
 
@@ -47,6 +48,38 @@ TYPE_PRIORITY_DEFAULT = 20          # RandomVariableCuda.java:568
 
 
 # ------------------------------------------------------------------ thin RAII wrapper of a vector handle
+def device_order_stats() -> bool:
+    """FMHIP_DEVICE_ORDER_STATS=0: quantiles, quantile expectations and histograms download the vector and sort it on the host, as the
+    reference does (the A/B switch and the fallback); anything else: selected and counted on the device."""
+    return os.environ.get("FMHIP_DEVICE_ORDER_STATS", "1") != "0"
+
+
+def select_ranks_batch(vectors, ranks) -> np.ndarray:
+    """out[k][j] = sorted(vectors[k])[ranks[j]]: ONE radix select for all vectors (same size) and ranks — four launches per eight ranks,
+    whatever the number of vectors (include/fmhip.h: fmhip_select_ranks_batch)."""
+    k = len(vectors)
+    r = np.ascontiguousarray(ranks, dtype=np.int64).ravel()
+    handles = (C.c_int64 * k)(*[getattr(v, "handle", v) for v in vectors])
+    out = np.empty((k, r.size), dtype=np.float64)
+    N.check(N.lib().fmhip_select_ranks_batch(handles, k, r.ctypes.data_as(C.POINTER(C.c_int64)), r.size, out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def quantile_index(n: int, quantile: float) -> int:
+    """Position in the ascending sample that getQuantile(quantile) returns (RandomVariableCuda.java:983)."""
+    return min(max(int(math.floor((n + 1) * (1 - quantile) - 1 + 0.5)), 0), n - 1)
+
+
+def quantiles(vectors, quantile: float) -> np.ndarray:
+    """getQuantile(quantile) of every random variable (or device vector) of a list in one device call: an exposure profile."""
+    vs = [getattr(v, "realizations", v) for v in vectors]
+    if not device_order_stats():
+        return np.array([float(np.sort(v.to_float32())[quantile_index(v.n, quantile)]) for v in vs])
+    w = C.c_int(1)
+    N.check(N.lib().fmhip_expectation_world(C.byref(w), None))
+    return select_ranks_batch(vs, [quantile_index(vs[0].n * w.value, quantile)])[:, 0]
+
+
 class DeviceVector:
     """Owns one fmhip_vec handle (released on garbage collection — explicit, never via device-memory polling)."""
     __slots__ = ("handle", "n")
@@ -117,6 +150,25 @@ class DeviceVector:
     def to_float64(self) -> np.ndarray:
         out = np.empty(self.n, dtype=np.float64)
         N.check(N.lib().fmhip_vec_read_double(self.handle, out.ctypes.data_as(C.POINTER(C.c_double)), self.n))
+        return out
+
+    def select_ranks(self, ranks) -> np.ndarray:
+        """sorted(self)[ranks] as float64 — selected on the device (fmhip_select_ranks_batch), the vector is neither sorted nor read."""
+        return select_ranks_batch([self], ranks)[0]
+
+    def rank_sum(self, rank_from: int, rank_to: int) -> float:
+        """Σ sorted(self)[rank_from .. rank_to] (inclusive) in fp64 (fmhip_rank_sums_batch)."""
+        h = (C.c_int64 * 1)(self.handle)
+        out = (C.c_double * 1)()
+        N.check(N.lib().fmhip_rank_sums_batch(h, 1, int(rank_from), int(rank_to), out))
+        return float(out[0])
+
+    def count_not_above(self, bounds) -> np.ndarray:
+        """#{ i : (double) self[i] <= bounds[j] } per bound (fmhip_count_not_above); NaN elements are never counted."""
+        b = np.ascontiguousarray(bounds, dtype=np.float64).ravel()
+        out = np.zeros(b.size, dtype=np.int64)
+        if b.size:
+            N.check(N.lib().fmhip_count_not_above(self.handle, b.ctypes.data_as(C.POINTER(C.c_double)), b.size, out.ctypes.data_as(C.POINTER(C.c_int64))))
         return out
 
     def moments(self, shift: float = 0.0) -> N.Moments:
@@ -252,23 +304,27 @@ class RandomVariableHip:
     def average(self):                                               # :1280
         return RandomVariableHip(-math.inf, self.getAverage())
 
-    # ---- host-side cold paths (sort on the host, as the reference does: :970-1091)
+    # ---- order statistics: selected / counted on the device (fmhip_select_ranks_batch, fmhip_rank_sums_batch, fmhip_count_not_above); the
+    # reference's download-and-sort (:970-1091) remains behind FMHIP_DEVICE_ORDER_STATS=0.  With an expectation communicator the device
+    # path answers for the GLOBAL sample (ranks over world·n, like the standard error); the host path only ever sees the local shard.
     def getQuantile(self, quantile):
         if self.isDeterministic(): return self.value
         if self.size() == 0: return math.nan
+        if device_order_stats():
+            return float(self.realizations.select_ranks([quantile_index(self._sample_size(), quantile)])[0])
         s = np.sort(self.getRealizations())
-        n = self.size()
-        idx = min(max(int(math.floor((n + 1) * (1 - quantile) - 1 + 0.5)), 0), n - 1)      # :983
-        return float(s[idx])
+        return float(s[quantile_index(self.size(), quantile)])
 
     def getQuantileExpectation(self, quantile_start, quantile_end):
         if self.isDeterministic(): return self.value
         if self.size() == 0: return math.nan
         if quantile_start > quantile_end: return self.getQuantileExpectation(quantile_end, quantile_start)
-        s = np.sort(self.getRealizations())
-        n = self.size()
+        n = self._sample_size() if device_order_stats() else self.size()
         i0 = min(max(int(math.floor((n + 1) * quantile_start - 1 + 0.5)), 0), n - 1)
         i1 = min(max(int(math.floor((n + 1) * quantile_end - 1 + 0.5)), 0), n - 1)
+        if device_order_stats():
+            return self.realizations.rank_sum(i0, i1) / (i1 - i0 + 1)
+        s = np.sort(self.getRealizations())
         return float(s[i0:i1 + 1].sum() / (i1 - i0 + 1))
 
     def getHistogram(self, interval_points, standard_deviations=None):
@@ -293,15 +349,20 @@ class RandomVariableHip:
                     break
             hist[pts.size] = 1.0
             return hist
-        s = np.sort(self.getRealizations())
-        idx = np.searchsorted(s, pts, side="right")
-        prev = 0
+        if device_order_stats() and self.size() > 0:
+            n = self._sample_size()
+            idx = self.realizations.count_not_above(pts) if pts.size else pts
+        else:
+            s = np.sort(self.getRealizations())
+            n = s.size
+            idx = np.searchsorted(s, pts, side="right")
+        prev = 0                                                      # the reference's running index never goes back (unsorted points)
         for k in range(pts.size):
             cur = max(int(idx[k]), prev)
             hist[k] = cur - prev
             prev = cur
-        hist[pts.size] = s.size - prev
-        if s.size > 0: hist /= s.size
+        hist[pts.size] = n - prev
+        if n > 0: hist /= n
         return hist
 
     # ---- helpers

@@ -318,6 +318,27 @@ int fmhip_reduce_moments_batch_end(fmhip_ticket ticket, fmhip_moments* out, int 
  * counterpart: its getAverage() copies the whole vector to the host (RandomVariableCuda.java:869-878). */
 int fmhip_vec_give_up_values(const fmhip_vec* vectors, int count);
 
+/* Order statistics on the device: what getQuantile, getQuantileExpectation and getHistogram need, without the vector
+ * leaving the device and without a sort (the reference downloads and sorts: RandomVariableCuda.java:970-1091).  The order is that of
+ * java.util.Arrays.sort(float[]): -0.0 before +0.0, every NaN equal and last.  RANKS cross this boundary, not quantiles: the index formula
+ * (and its rounding rule) stays with the caller.  All vectors of a batch have the same size n > 0; pending vectors are computed (one flush
+ * for the batch); a vector whose values were given up (fmhip_vec_give_up_values) is the error a read of it is.  Arguments are checked on
+ * the host before anything is launched: a rank outside [0, n), n == 0, count or n_ranks < 1 -> FMHIP_ERR_INVALID_ARGUMENT; vectors of
+ * different sizes -> FMHIP_ERR_SIZE_MISMATCH.  A selected value is an element of the vector: the answers are those of the sort, bit for bit.
+ * With a device list the shards' counts are added by the library; with an expectation communicator (below) the results are those of the
+ * GLOBAL sample of world*n elements on every rank — ranks in [0, world*n), one gather per pass, sums added in rank order.
+ *
+ * fmhip_select_ranks_batch: values_out[k*n_ranks + j] = sorted(vectors[k])[ranks[j]] as double (NaN for a position in the NaN tail).
+ *   A radix select of four 8-bit passes; count x n_ranks (vector, rank) pairs share the passes: four launches per eight ranks, whatever `count`.
+ * fmhip_rank_sums_batch: sums_out[k] = sum of sorted(vectors[k])[rank_from .. rank_to] (both inclusive, from <= to) in fp64: the two ends
+ *   selected as above, ties at the ends multiplied, the elements strictly between added in an order that depends on n alone.  A range that
+ *   reaches the NaN tail, or holds +inf and -inf, sums to NaN.
+ * fmhip_count_not_above: counts_out[j] = #{ i : (double)v[i] <= bounds[j] } (the comparison of the reference's histogram loop); NaN
+ *   elements are never counted, a NaN bound counts nothing; bounds in any order, any number of them (4096 per launch). */
+int fmhip_select_ranks_batch(const fmhip_vec* vectors, int count, const int64_t* ranks, int n_ranks, double* values_out);
+int fmhip_rank_sums_batch(const fmhip_vec* vectors, int count, int64_t rank_from, int64_t rank_to, double* sums_out);
+int fmhip_count_not_above(fmhip_vec v, const double* bounds, int n_bounds, int64_t* counts_out);
+
 /* Expectation communicator: Monte-Carlo paths sharded over processes (one GPU each) behind an UNCHANGED caller.
  * Every vector of this process holds the paths [rank·n, (rank+1)·n) of a global vector of world·n paths; all element-wise
  * work is local; the one thing that couples paths is an expectation.  With a communicator set, fmhip_reduce_moments and
@@ -328,6 +349,8 @@ int fmhip_vec_give_up_values(const fmhip_vec* vectors, int count);
  * (fmhip_expectation_world), so getAverage() / getVariance() of a finmath-lib product mean the same as on one GPU and every
  * rank's optimiser takes the same step.  The *_device variants stay local partials (for callers that run their own collective
  * on the device).  Every rank must ask for the same expectations in the same order.  world = 1 or gather = NULL removes it.
+ * The order statistics above are those of the GLOBAL sample too (their per-pass counts go through `gather` as doubles, exact below 2^53):
+ * every rank asks for the same ranks / bounds in the same order, like expectations.
  * The reference has nothing here: one process, one device (RandomVariableCuda.java:161,177). */
 typedef int (*fmhip_gather_fn)(void* context, const double* local, int count_doubles, double* gathered /* [world][count_doubles] */);
 int fmhip_set_expectation_comm(int world, int rank, fmhip_gather_fn gather, void* context);

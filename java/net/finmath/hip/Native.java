@@ -69,6 +69,13 @@ final class Native {
 	static native int reduceMomentsDevice(long vector, double shift, long deviceOut4Doubles);
 	static native int reduceMomentsBatch(long[] vectors, double[] shiftsOrNull, double[] moments4PerVector);
 	static native int reduceMomentsBatchDevice(long[] vectors, double[] shiftsOrNull, long deviceOut);
+	// ---- order statistics on the device (replace the download-and-sort of getQuantile / getQuantileExpectation / getHistogram, RandomVariableCuda.java:970-1091)
+	/** valuesOut[k * ranks.length + j] = the element at 0-based position ranks[j] of the ascending sample of vectors[k] (Arrays.sort order). */
+	static native int selectRanksBatch(long[] vectors, long[] ranks, double[] valuesOut);
+	/** sumsOut[k] = the fp64 sum of the positions rankFrom..rankTo (inclusive) of the ascending sample of vectors[k]. */
+	static native int rankSumsBatch(long[] vectors, long rankFrom, long rankTo, double[] sumsOut);
+	/** countsOut[j] = number of elements x with (double) x <= bounds[j]; NaN elements are not counted. */
+	static native int countNotAbove(long vector, double[] bounds, long[] countsOut);
 	/** With a device list: one device buffer per listed device (0 = not wanted there), each receives the moments of the whole vectors. */
 	static native int reduceMomentsBatchDevices(long[] vectors, double[] shiftsOrNull, long[] deviceOutPerDevice);
 	static native int getStreamOf(int shard, long[] stream);

@@ -282,6 +282,15 @@ public class RandomVariableHip implements RandomVariable {
 		if(size() == 0) {
 			return Double.NaN;
 		}
+		if(DEVICE_ORDER_STATISTICS) {
+			// selected on the device (fmhip_select_ranks_batch): the vector is neither downloaded nor sorted; under an expectation
+			// communicator the position is one of the global sample
+			final long n = sampleSize();
+			final long rank = Math.min(Math.max(Math.round((n + 1) * (1 - quantile) - 1), 0L), n - 1);
+			final double[] value = new double[1];
+			Native.check(Native.selectRanksBatch(new long[] { realizations.handle }, new long[] { rank }, value));
+			return value[0];
+		}
 		final double[] sorted = getRealizations();
 		Arrays.sort(sorted);
 		final int index = (int)Math.round((size() + 1) * (1 - quantile) - 1);			// index convention of the GPU class (:983)
@@ -297,6 +306,9 @@ public class RandomVariableHip implements RandomVariable {
 	// do): the position a quantile falls on, and the number of sample points not above a bound (binary search).  Semantics as the
 	// reference's (:1001-1091): mean of the sorted sample between two quantile positions; shares of the sample per interval
 	// (points[k-1], points[k]] plus the share above the last point; a symmetric grid of points around the mean with its bin edges.
+
+	/** FMHIP_DEVICE_ORDER_STATS=0: download and sort on the host, as the reference does (:970-1091) — the A/B switch and the fallback. */
+	private static final boolean DEVICE_ORDER_STATISTICS = !"0".equals(System.getenv("FMHIP_DEVICE_ORDER_STATS"));
 
 	private double[] sortedSample() {
 		final double[] sample = getRealizations();
@@ -333,6 +345,14 @@ public class RandomVariableHip implements RandomVariable {
 		if(size() == 0) {
 			return Double.NaN;
 		}
+		if(DEVICE_ORDER_STATISTICS) {
+			final long n = sampleSize();
+			final long first = Math.min(Math.max(Math.round((n + 1) * Math.min(quantileStart, quantileEnd) - 1), 0L), n - 1);
+			final long last = Math.min(Math.max(Math.round((n + 1) * Math.max(quantileStart, quantileEnd) - 1), 0L), n - 1);
+			final double[] rankSum = new double[1];
+			Native.check(Native.rankSumsBatch(new long[] { realizations.handle }, first, last, rankSum));
+			return rankSum[0] / (last - first + 1);
+		}
 		final double[] sample = sortedSample();
 		final int from = quantilePosition(Math.min(quantileStart, quantileEnd), sample.length);
 		final int to = quantilePosition(Math.max(quantileStart, quantileEnd), sample.length);
@@ -356,6 +376,24 @@ public class RandomVariableHip implements RandomVariable {
 				}
 			}
 			shares[bins - 1] = 1.0;
+			return shares;
+		}
+		if(DEVICE_ORDER_STATISTICS && size() > 0) {
+			final long[] notAbove = new long[intervalPoints.length];
+			if(intervalPoints.length > 0) {
+				Native.check(Native.countNotAbove(realizations.handle, intervalPoints, notAbove));
+			}
+			final long n = sampleSize();
+			long counted = 0;
+			for(int k = 0; k < intervalPoints.length; k++) {
+				final long upTo = Math.max(notAbove[k], counted);
+				shares[k] = upTo - counted;
+				counted = upTo;
+			}
+			shares[bins - 1] = n - counted;
+			for(int k = 0; k < bins; k++) {
+				shares[k] /= n;
+			}
 			return shares;
 		}
 		final double[] sample = sortedSample();

@@ -167,6 +167,23 @@ FMJ(jint, reduceMomentsBatch)(JNIEnv* env, jclass, jlongArray vectors, jdoubleAr
     if (!pv.p || !pm.p || (int64_t)pm.length() < 4 * (int64_t)pv.length() || (ps.p && ps.length() < pv.length())) return FMHIP_ERR_INVALID_ARGUMENT;
     return fmhip_reduce_moments_batch((const fmhip_vec*)pv.p, pv.length(), ps.p, (fmhip_moments*)pm.p);
 }
+// ---------------------------------------------------------------- order statistics
+FMJ(jint, selectRanksBatch)(JNIEnv* env, jclass, jlongArray vectors, jlongArray ranks, jdoubleArray valuesOut) {
+    Pin<jlong> pv(env, vectors, JNI_ABORT); Pin<jlong> pr(env, ranks, JNI_ABORT); Pin<jdouble> po(env, valuesOut);
+    static_assert(sizeof(jlong) == sizeof(int64_t), "ranks travel as 64-bit integers");
+    if (!pv.p || !pr.p || !po.p || (int64_t)po.length() < (int64_t)pv.length() * (int64_t)pr.length()) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_select_ranks_batch((const fmhip_vec*)pv.p, pv.length(), (const int64_t*)pr.p, pr.length(), po.p);
+}
+FMJ(jint, rankSumsBatch)(JNIEnv* env, jclass, jlongArray vectors, jlong rankFrom, jlong rankTo, jdoubleArray sumsOut) {
+    Pin<jlong> pv(env, vectors, JNI_ABORT); Pin<jdouble> po(env, sumsOut);
+    if (!pv.p || !po.p || po.length() < pv.length()) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_rank_sums_batch((const fmhip_vec*)pv.p, pv.length(), rankFrom, rankTo, po.p);
+}
+FMJ(jint, countNotAbove)(JNIEnv* env, jclass, jlong v, jdoubleArray bounds, jlongArray countsOut) {
+    Pin<jdouble> pb(env, bounds, JNI_ABORT); Pin<jlong> po(env, countsOut);
+    if (!pb.p || !po.p || po.length() < pb.length()) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_count_not_above(v, pb.p, pb.length(), (int64_t*)po.p);
+}
 FMJ(jint, reduceMomentsBatchDevice)(JNIEnv* env, jclass, jlongArray vectors, jdoubleArray shifts, jlong deviceOut) {
     Pin<jlong> pv(env, vectors, JNI_ABORT); Pin<jdouble> ps(env, shifts, JNI_ABORT);
     if (!pv.p || (ps.p && ps.length() < pv.length())) return FMHIP_ERR_INVALID_ARGUMENT;

@@ -1,0 +1,46 @@
+"""The host side of the device order statistics, without a GPU: the key order and the digit-picking loop of csrc/order_stats.hpp against
+histograms counted on the CPU (tests/cpp/test_order_stats_host.cpp), and the engine's passes — one flush for a batch of stored, pending
+and storage-sharing vectors, another thread releasing meanwhile, a tiny ring — against the null device under AddressSanitizer / UBSan and
+ThreadSanitizer (tests/nulldev_order: the null device of tests/nulldev plus stand-ins for the three new launchers, and a driver of its
+own), on one engine, behind a device list and with thread engines."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NULLDEV = os.path.join(ROOT, "tests", "nulldev_order")
+
+
+def test_key_order_and_digit_picking_loop(tmp_path):
+    gxx = shutil.which("g++")
+    if not gxx:
+        pytest.skip("needs g++")
+    exe = tmp_path / "order_stats_host"
+    r = subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                        os.path.join(ROOT, "tests", "cpp", "test_order_stats_host.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "order statistics host loop ok" in r.stdout, r.stdout[-500:] + r.stderr[-3000:]
+
+
+@pytest.fixture(scope="module")
+def built():
+    if not shutil.which("g++") or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
+        pytest.skip("needs g++ and the HIP headers")
+    r = subprocess.run(["make", "-C", NULLDEV, "-j8", "asan", "tsan"], capture_output=True, text=True, timeout=1200)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    return os.path.join(NULLDEV, "build")
+
+
+@pytest.mark.parametrize("env", [{}, {"FMNULL_DEVICES": "2"}, {"FMNULL_DEVICES": "3"}, {"FMNULL_THREAD_ENGINES": "1"}])
+def test_engine_passes_are_clean_under_the_sanitizers(built, tmp_path, env):
+    full = dict(os.environ, FMHIP_JIT_CACHE_DIR=str(tmp_path / "code_objects"), FMHIP_JIT_PACK_DIR="off", FMHIP_RING_BYTES="16384", FMHIP_ARENA_BYTES="4096",
+                ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1", TSAN_OPTIONS="halt_on_error=1", **env)
+    a = subprocess.run([os.path.join(built, "drive_order_asan")], capture_output=True, text=True, timeout=600, env=full)
+    assert a.returncode == 0 and "Sanitizer" not in a.stderr and "runtime error" not in a.stderr, a.stdout[-500:] + a.stderr[-6000:]
+    assert a.stdout.count("order done") == 2
+    t = subprocess.run([os.path.join(built, "drive_order_tsan")], capture_output=True, text=True, timeout=600, env=full)
+    assert t.returncode == 0 and "ThreadSanitizer" not in t.stderr, t.stdout[-500:] + t.stderr[-6000:]
+    assert t.stdout.count("order done") == 2
