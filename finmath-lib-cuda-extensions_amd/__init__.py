@@ -17,6 +17,7 @@ from ._native import FmhipError, Moments, PoolStats, ProgOp, build
 from .random_variable import OP, DeviceVector, RandomVariableHip, RandomVariableHipFactory, quantiles, select_ranks_batch
 from .brownian_motion import BrownianMotionHip, BrownianMotionFromMersenneRandomNumbers, TimeDiscretization, mersenne_increments
 from .program import Program
+from .regression import MonteCarloConditionalExpectationRegression, covariance_matrix, cross_moments, solve_normal_equations
 from .differentiable import RandomVariableDifferentiableAAD, RandomVariableDifferentiableAADFactory
 
 

@@ -672,6 +672,29 @@ int fmhip_count_not_above(fmhip_vec v, const double* bounds, int n_bounds, int64
     });
 }
 
+// ---------------------------------------------------------------- cross moments (cross_moments_engine.hpp)
+extern "C++" {
+namespace fm {
+int xmom_local(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums) { return guarded([&] { Engine::get().xmom_pass(x, n_x, y, n_y, sums); }); }
+}
+}
+int fmhip_cross_moments(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out) {
+    FRONT(cross_moments(x, n_x, y, n_y, sums_out));
+    if (te::active()) {
+        // thread engines: both lists as one, so that foreign operands of either are imported by one call
+        const int rc = guarded([&] { fm::xmom_check_counts(x, n_x, y, n_y, sums_out); });
+        if (rc != FMHIP_OK) return rc;
+        std::vector<fmhip_vec> all(x, x + n_x);
+        all.insert(all.end(), y, y + n_y);
+        TE_LOCAL(all.data(), n_x + n_y, L, fmhip_cross_moments(L, n_x, L + n_x, n_y, sums_out));
+    }
+    return guarded([&] {
+        Engine& e = Engine::get();
+        e.xmom_pass(x, n_x, y, n_y, sums_out);
+        comm_add_sums(e, sums_out, (size_t)n_x * (n_x + 1) / 2 + (size_t)n_x * n_y);      // one gather, rank order: the sums of the global sample
+    });
+}
+
 // The one call of a caller that values product after product: the engine lock is held for the bookkeeping (graph → launch → commit),
 // NOT while the device computes — other threads record and launch meanwhile.  The moments arrive in a slot of pinned memory of their
 // own; this thread polls its flag, then takes the lock again to copy them out and give the launch's buffers back.

@@ -96,4 +96,37 @@ hipError_t launch_os_sum(const DevRankSumArgs& a, const uint64_t* vecs, const ui
 // bounds: [m] ascending doubles on the device; counts[i] = elements x (not NaN) with exactly i bounds < x
 hipError_t launch_os_count(const DevCountArgs& a, const double* bounds, hipStream_t st);
 
+// ---- cross moments (cross_moments_engine.hpp): S[i][j] = Σ_p x_i[p]·x_j[p] and T[i][m] = Σ_p x_i[p]·y_m[p] in fp64 for up
+// to 12 + 4 vectors of one size, in ONE launch.  The vectors form one list (x then y; an address of 0 is the constant 1 and is not loaded);
+// the list is cut into groups of FM_XMOM_GROUP = 8 and blockIdx.y names a pair of groups: a workgroup reads the (at most 16) vectors of its
+// two groups once per tile and keeps all 8 x 8 products' running sums in registers.  Up to 8 vectors that is one block and every vector is
+// read once; 9 … 16 vectors are three blocks (two when the second group holds dependents only) and 2 x the bytes at most.  The order of
+// the additions of ONE pair — lane, tile by tile; butterfly over the lanes; waves; workgroups, lane-strided, by the last to arrive — depends
+// on n alone: not on the block the pair falls into, the number of vectors, their roles or their positions.
+constexpr int FM_XMOM_MAX_X = 12;
+constexpr int FM_XMOM_MAX_Y = 4;
+constexpr int FM_XMOM_GROUP = 8;
+constexpr int FM_XMOM_PAIRS = FM_XMOM_GROUP * FM_XMOM_GROUP;      // running sums per workgroup
+constexpr int FM_XMOM_MAX_BLOCKS = 3;                             // (0,0) (0,1) (1,1)
+constexpr int FM_XMOM_TILE = 1024;                                // elements per workgroup and iteration: 256 lanes x 16 bytes
+struct DevXmomArgs {
+    uint32_t* counters;        // [FM_XMOM_MAX_BLOCKS + 1] arrival counters: one per block, one for the launch; zero before and after
+    uint64_t* done_flag;       // pinned; receives done_value when out_host is in host memory
+    uint64_t  done_value;
+    int64_t   n;
+    uint32_t  tiles;           // ceil(n / FM_XMOM_TILE)
+    uint32_t  n_blocks;
+    double*   partials;        // [n_blocks][FM_XMOM_PAIRS][grid.x]
+    double*   out_host;        // pinned [n_blocks][FM_XMOM_PAIRS]: entry r * 8 + c = Σ (row group)[r] · (column group)[c]
+    uint64_t  vec[2 * FM_XMOM_GROUP];            // addresses; 0 = the constant 1 (also what pads a group)
+    uint8_t   row_group[4], col_group[4];        // per block
+};
+// workgroups per block: a function of n ONLY — the order of the fp64 additions depends on nothing else
+inline uint32_t xmom_blocks(int64_t n)
+{
+    const int64_t tiles = (n + FM_XMOM_TILE - 1) / FM_XMOM_TILE;
+    return (uint32_t)(tiles < 1 ? 1 : tiles > 512 ? 512 : tiles);
+}
+hipError_t launch_xmom(const DevXmomArgs& a, hipStream_t st);
+
 } // namespace fm

@@ -555,6 +555,95 @@ __global__ void __launch_bounds__(FM_BLOCK) fm_os_count_kernel(const DevCountArg
 }
 
 // ---------------------------------------------------------------------------------------------
+// Cross moments: the normal equations of a least-squares regression — Σ x_i·x_j and Σ x_i·y_m for up to 12 + 4 vectors —
+// in one pass.  blockIdx.y names a pair of groups of eight vectors (kernels.h); a workgroup loads the vectors of its two groups with
+// 16-byte loads, once per tile, and keeps 64 running sums per lane.
+//
+// A product of two fp32 values has at most 48 significant bits and an exponent far inside fp64's range: (double)a * (double)b is EXACT, so
+// `acc += (double)a * (double)b` adds the exact product and rounds once whether or not the compiler contracts it into an FMA.  That is why
+// the no-FMA contract of the element-wise path (fp32 products that round) is not at stake here.  No fp32 product, no float atomics.
+//
+// Order of the additions of one pair: a lane adds its elements tile by tile (elements past n add +0.0, which changes no sum: a running sum
+// that starts at +0.0 is never -0.0); the 64 lanes of a wave are added by a butterfly (bit 5 of the lane first) that leaves the total of pair
+// q in lane q — 63 exchanges for all 64 pairs —; the four waves in order; the last workgroup of the block adds the workgroups' partials
+// lane-strided, then the plain butterfly.  The grid along x is xmom_blocks(n): the bits depend on the data and on n, on nothing else.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(FM_BLOCK) fm_xmom_kernel(const DevXmomArgs A)
+{
+    constexpr int G = FM_XMOM_GROUP;
+    __shared__ double wave_part[FM_BLOCK / 64][FM_XMOM_PAIRS];
+    const uint32_t by = blockIdx.y;
+    const uint32_t r0 = (uint32_t)A.row_group[by] * G, c0 = (uint32_t)A.col_group[by] * G;
+    const bool diag = r0 == c0;
+    const int64_t n = A.n;
+    const f32x4 ones = { 1.0f, 1.0f, 1.0f, 1.0f };
+    double acc[G][G];
+#pragma unroll
+    for (int i = 0; i < G; ++i)
+#pragma unroll
+        for (int k = 0; k < G; ++k) acc[i][k] = 0.0;
+#pragma unroll 1
+    for (uint32_t tile = blockIdx.x; tile < A.tiles; tile += gridDim.x) {
+        const uint32_t i4 = tile * FM_BLOCK + threadIdx.x;
+        const uint32_t at = (int64_t)i4 * 4 < n ? i4 : 0u;         // a partially valid float4 is in bounds: vectors are padded to 256 B
+        f32x4 va[G], vb[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const gfloat4* __restrict__ p = reinterpret_cast<const gfloat4*>(A.vec[r0 + i]);
+            va[i] = p ? p[at] : ones;
+        }
+#pragma unroll
+        for (int k = 0; k < G; ++k) {
+            const gfloat4* __restrict__ p = reinterpret_cast<const gfloat4*>(A.vec[c0 + k]);
+            vb[k] = diag ? va[k] : (p ? p[at] : ones);      // (plain loads, not streaming ones: the other blocks read these lines again)
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool in_range = (int64_t)i4 * 4 + j < n;
+            double a[G], b[G];
+#pragma unroll
+            for (int i = 0; i < G; ++i) { a[i] = in_range ? (double)va[i][j] : 0.0; b[i] = in_range ? (double)vb[i][j] : 0.0; }
+#pragma unroll
+            for (int i = 0; i < G; ++i)
+#pragma unroll
+                for (int k = 0; k < G; ++k) acc[i][k] = __builtin_fma(a[i], b[k], acc[i][k]);       // the product is exact: one rounding, as acc + a·b has
+        }
+    }
+    // butterfly: the step over lane bit `off` halves the pairs a lane still carries; lane q ends with the wave's total of pair q
+    double v[FM_XMOM_PAIRS];
+#pragma unroll
+    for (int i = 0; i < G; ++i)
+#pragma unroll
+        for (int k = 0; k < G; ++k) v[i * G + k] = acc[i][k];
+    const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+    for (int off = 32, cnt = FM_XMOM_PAIRS / 2; off > 0; off >>= 1, cnt >>= 1) {
+        const bool upper = (lane & (uint32_t)off) != 0u;
+#pragma unroll
+        for (int q = 0; q < cnt; ++q) {
+            const double keep = upper ? v[q + cnt] : v[q];
+            const double send = upper ? v[q] : v[q + cnt];
+            v[q] = keep + __shfl_xor(send, off, 64);
+        }
+    }
+    wave_part[threadIdx.x >> 6][lane] = v[0];
+    __syncthreads();
+    double* part = A.partials + (size_t)by * FM_XMOM_PAIRS * gridDim.x;
+    if (threadIdx.x < (uint32_t)FM_XMOM_PAIRS)
+        part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = ((wave_part[0][threadIdx.x] + wave_part[1][threadIdx.x]) + wave_part[2][threadIdx.x]) + wave_part[3][threadIdx.x];
+    if (!os_arrive_last(A.counters + by, gridDim.x)) return;
+    for (uint32_t q = threadIdx.x >> 6; q < (uint32_t)FM_XMOM_PAIRS; q += FM_BLOCK / 64) {
+        double s = 0.0;
+        for (uint32_t b = lane; b < gridDim.x; b += 64u) s += part[(size_t)q * gridDim.x + b];
+        s = os_wave_sum(s);
+        if (lane == 0u) A.out_host[by * FM_XMOM_PAIRS + q] = s;
+    }
+    __threadfence_system();
+    if (!os_arrive_last(A.counters + FM_XMOM_MAX_BLOCKS, gridDim.y)) return;
+    if (threadIdx.x == 0u) __hip_atomic_store(A.done_flag, A.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Host-side launchers (the only functions the runtime calls)
 // ---------------------------------------------------------------------------------------------
 
@@ -634,6 +723,7 @@ hipError_t preload_kernels()
     if (e == hipSuccess) e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&fm_os_hist_kernel));
     if (e == hipSuccess) e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&fm_os_sum_kernel));
     if (e == hipSuccess) e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&fm_os_count_kernel));
+    if (e == hipSuccess) e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&fm_xmom_kernel));
     return e;
 }
 
@@ -667,6 +757,14 @@ hipError_t launch_os_count(const DevCountArgs& a, const double* bounds, hipStrea
 {
     if (a.c.n <= 0 || a.m == 0 || a.m > (uint32_t)FM_OS_MAX_BOUNDS) return hipErrorInvalidValue;
     hipLaunchKernelGGL(fm_os_count_kernel, dim3(os_blocks_per_vector(a.c.n, 1u), 1, 1), dim3(FM_BLOCK), 0, st, a, bounds);
+    return hipGetLastError();
+}
+
+hipError_t launch_xmom(const DevXmomArgs& a, hipStream_t st)
+{
+    if (a.n <= 0 || a.n_blocks == 0 || a.n_blocks > (uint32_t)FM_XMOM_MAX_BLOCKS || a.tiles != (uint32_t)((a.n + FM_XMOM_TILE - 1) / FM_XMOM_TILE)) return hipErrorInvalidValue;
+    for (uint32_t b = 0; b < a.n_blocks; ++b) if (a.row_group[b] > 1 || a.col_group[b] > 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fm_xmom_kernel, dim3(xmom_blocks(a.n), a.n_blocks, 1), dim3(FM_BLOCK), 0, st, a);
     return hipGetLastError();
 }
 

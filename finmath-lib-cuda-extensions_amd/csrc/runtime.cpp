@@ -4219,3 +4219,4 @@ void Engine::profile_read(double* ms_total, int64_t* n) {
 } // namespace fm
 
 #include "order_stats_engine.hpp"      // Engine::os_*: the order-statistics passes
+#include "cross_moments_engine.hpp"    // Engine::xmom_pass: the cross moments of a regression in one launch

@@ -374,6 +374,11 @@ public:
     void os_sum_pass(const fmhip_vec* hs, int count, const uint32_t* keys, double* sums_out);
     void os_count_pass(fmhip_vec h, const double* ascending_bounds, int m, uint64_t* counts_out);      // counts_out[m + 1]
 
+    // cross moments (cross_moments_engine.hpp): sums_out = the n_x(n_x+1)/2 sums Σ x_i·x_j (i <= j, row-major) followed by the
+    // n_x·n_y sums Σ x_i·y_m, in fp64, from ONE launch; a handle of 0 among x is the constant 1.  Arguments are checked before anything is
+    // flushed or launched; otherwise the pass behaves as the order-statistics passes do (one flush, storage held across the wait).
+    void xmom_pass(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out);
+
     // programs
     fmhip_program program_create(const fmhip_prog_op* ops, int n_ops, int n_in, const int32_t* outs, int n_out,
                                  const int32_t* reds, int n_red);
@@ -685,5 +690,8 @@ struct HostTimer {
     explicit HostTimer(HostProfile::Slot s) : slot(s), on(g_host_profile.on) { if (on) t0 = std::chrono::steady_clock::now(); }
     ~HostTimer() { if (on) { g_host_profile.seconds[slot] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); g_host_profile.count[slot]++; } }
 };
+
+// what can be said about the arguments of fmhip_cross_moments without looking at a vector: counts in range, pointers, no 0 among y, a vector among x
+void xmom_check_counts(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, const double* sums_out);
 
 } // namespace fm

@@ -745,6 +745,38 @@ int count_not_above(fmhip_vec v, const double* bounds, int n_bounds, int64_t* co
     });
 }
 
+// Cross moments: every shard runs the pass on its block of paths, the front adds the shards' sums in shard order (like combine()); a shard
+// that holds no path of a short vector is left out.
+int cross_moments(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out) {
+    return fronted([&](Shards& s) {
+        xmom_check_counts(x, n_x, y, n_y, sums_out);
+        std::vector<fmhip_vec> all(x, x + n_x);
+        all.insert(all.end(), y, y + n_y);
+        int64_t n = -1;
+        for (fmhip_vec h : all) {
+            if (!h) continue;
+            const int64_t nh = s.vec(h).n;
+            if (n >= 0 && nh != n) throw Error(FMHIP_ERR_SIZE_MISMATCH, "cross moments over vectors of different size");
+            n = nh;
+        }
+        if (n <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "cross moments of an empty vector");
+        const size_t m = (size_t)n_x * (n_x + 1) / 2 + (size_t)n_x * n_y;
+        std::vector<std::vector<double>> per((size_t)s.D(), std::vector<double>(m, 0.0));
+        std::vector<char> took((size_t)s.D(), 0);
+        s.post([&](Worker& w) {
+            if (!os_shard_has_paths(w, n)) return;
+            std::vector<fmhip_vec> l; for (fmhip_vec h : all) l.push_back(h ? w.at(h) : 0);
+            took[(size_t)w.shard] = w.ok(xmom_local(l.data(), n_x, l.data() + n_x, n_y, per[(size_t)w.shard].data())) ? 1 : 0;
+        });
+        s.wait();
+        for (size_t i = 0; i < m; ++i) {
+            double t = 0.0; bool first = true;
+            for (size_t d = 0; d < per.size(); ++d) { if (!took[d]) continue; t = first ? per[d][i] : t + per[d][i]; first = false; }      // shard order
+            sums_out[i] = t;
+        }
+    });
+}
+
 int vec_give_up_values(const fmhip_vec* vectors, int count) {
     return fronted([&](Shards& s) {
         need(vectors, "vectors");

@@ -6,6 +6,8 @@ a RandomVariableFactory by injection (LIBORMarketModelCalibrationATMTest.java:35
     black_scholes_call_mc   MonteCarloBlackScholesModelTest.java:62-85,125-157 (Euler scheme on the log state,
                             numeraire exp(r t), European call)
     heston_call_mc          BASELINE.json configs[2]: Euler full-truncation Heston driven by BrownianMotionHip
+    bermudan_option_mc      Longstaff–Schwartz backward induction over MonteCarloConditionalExpectationRegression (regression.py):
+                            what finmath-lib's BermudanOption does with its conditional-expectation estimator
 """
 from __future__ import annotations
 
@@ -65,4 +67,43 @@ def heston_call_mc(brownian_motion, initial_value, risk_free_rate, v0, kappa, th
         t = td.getTime(i)
     payoff = x.exp().sub(strike).floor(0.0)
     value = payoff.div(math.exp(risk_free_rate * maturity))
+    return value.getAverage(), value
+
+
+def bermudan_option_mc(brownian_motion, initial_value, risk_free_rate, volatility, exercise_dates, strike, call=False, basis_order=3):
+    """Value of a Bermudan option under Black–Scholes by Longstaff–Schwartz backward induction.  States from the log-Euler scheme of
+    black_scholes_call_mc, kept at the exercise dates (points of the time discretisation).  The value starts as the last date's discounted
+    payoff; at each earlier date the current value is regressed on 1, S, …, S^basis_order over ALL paths (the constant is a deterministic
+    random variable: a host scalar to the estimator), and paths on which exercise − continuation estimate >= 0 take the discounted exercise
+    value.  Returns (value.getAverage(), value).  With one exercise date this is the European option on the same paths."""
+    from .regression import MonteCarloConditionalExpectationRegression
+    dates = sorted(float(d) for d in exercise_dates)
+    if not dates: raise ValueError("no exercise date")
+    td = brownian_motion.getTimeDiscretization()
+    x = brownian_motion.getRandomVariableForConstant(math.log(initial_value))
+    states, t, i = [], td.getTime(0), 0
+    if abs(t - dates[0]) <= 1e-12: states.append(x.exp())
+    while len(states) < len(dates):
+        dt = td.getTimeStep(i)
+        dw = brownian_motion.getBrownianIncrement(i, 0)
+        x = x.add((risk_free_rate - 0.5 * volatility * volatility) * dt).addProduct(dw, volatility)
+        i += 1
+        t = td.getTime(i)
+        if t > dates[len(states)] + 1e-12: raise ValueError("an exercise date is not a point of the time discretisation")
+        if abs(t - dates[len(states)]) <= 1e-12: states.append(x.exp())
+
+    def exercise_value(s, date):
+        payoff = s.sub(strike).floor(0.0) if call else s.bus(strike).floor(0.0)
+        return payoff.div(math.exp(risk_free_rate * date))
+
+    value = exercise_value(states[-1], dates[-1])
+    one = brownian_motion.getRandomVariableForConstant(1.0)
+    for k in range(len(dates) - 2, -1, -1):
+        s = states[k]
+        basis = [one, s]
+        for _ in range(2, basis_order + 1): basis.append(basis[-1].mult(s))
+        basis = basis[:basis_order + 1]
+        continuation = MonteCarloConditionalExpectationRegression(basis).getConditionalExpectation(value)
+        exercise = exercise_value(s, dates[k])
+        value = exercise.sub(continuation).choose(exercise, value)
     return value.getAverage(), value

@@ -339,6 +339,21 @@ int fmhip_select_ranks_batch(const fmhip_vec* vectors, int count, const int64_t*
 int fmhip_rank_sums_batch(const fmhip_vec* vectors, int count, int64_t rank_from, int64_t rank_to, double* sums_out);
 int fmhip_count_not_above(fmhip_vec v, const double* bounds, int n_bounds, int64_t* counts_out);
 
+/* Cross moments: the normal equations of a least-squares regression in one pass over the data — what finmath-lib's
+ * MonteCarloConditionalExpectationRegression assembles from b_i.mult(b_j).getAverage(), product by product.  n_x vectors x (1 … 12) and
+ * n_y vectors y (0 … 4), all of one size n > 0; a handle of 0 among x stands for the constant 1 (it is not loaded), so the same pass also
+ * yields the sums of the x_j and n itself: a regression with an intercept, a covariance.  The same handle may appear several times and in
+ * both lists.  Every product of two fp32 values is exact in fp64 and is added in fp64; the order of the additions of one pair depends on n
+ * alone, so the bits of a sum do not depend on how many other vectors the call names, on the roles (x or y) or on the positions.
+ * sums_out: n_x(n_x+1)/2 doubles (S, upper triangle, row-major: (0,0) (0,1) … (0,n_x-1) (1,1) …) followed by n_x*n_y doubles (T[i*n_y + m]).
+ * SUMS, not averages: shards and ranks add.  With a device list the library adds the shards' sums in shard order; with an expectation
+ * communicator (below) every rank receives the sums of the GLOBAL sample (one gather, added in rank order).
+ * Arguments are checked on the host before anything is launched: counts out of range, a NULL pointer, a 0 among y, no vector among x or
+ * n == 0 -> FMHIP_ERR_INVALID_ARGUMENT; vectors of different sizes -> FMHIP_ERR_SIZE_MISMATCH; FMHIP_ERR_INVALID_HANDLE.  Pending vectors
+ * are computed in one flush for the call, ONE kernel launch follows; a vector whose values were given up (fmhip_vec_give_up_values) is the
+ * error a read of it is.  IEEE semantics: a NaN in x_3 makes exactly the entries that involve x_3 NaN, inf*0 is NaN. */
+int fmhip_cross_moments(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out);
+
 /* Expectation communicator: Monte-Carlo paths sharded over processes (one GPU each) behind an UNCHANGED caller.
  * Every vector of this process holds the paths [rank·n, (rank+1)·n) of a global vector of world·n paths; all element-wise
  * work is local; the one thing that couples paths is an expectation.  With a communicator set, fmhip_reduce_moments and
@@ -350,7 +365,7 @@ int fmhip_count_not_above(fmhip_vec v, const double* bounds, int n_bounds, int64
  * rank's optimiser takes the same step.  The *_device variants stay local partials (for callers that run their own collective
  * on the device).  Every rank must ask for the same expectations in the same order.  world = 1 or gather = NULL removes it.
  * The order statistics above are those of the GLOBAL sample too (their per-pass counts go through `gather` as doubles, exact below 2^53):
- * every rank asks for the same ranks / bounds in the same order, like expectations.
+ * every rank asks for the same ranks / bounds in the same order, like expectations.  So are the cross moments (their sums go through `gather` once).
  * The reference has nothing here: one process, one device (RandomVariableCuda.java:161,177). */
 typedef int (*fmhip_gather_fn)(void* context, const double* local, int count_doubles, double* gathered /* [world][count_doubles] */);
 int fmhip_set_expectation_comm(int world, int rank, fmhip_gather_fn gather, void* context);

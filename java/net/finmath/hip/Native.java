@@ -76,6 +76,9 @@ final class Native {
 	static native int rankSumsBatch(long[] vectors, long rankFrom, long rankTo, double[] sumsOut);
 	/** countsOut[j] = number of elements x with (double) x <= bounds[j]; NaN elements are not counted. */
 	static native int countNotAbove(long vector, double[] bounds, long[] countsOut);
+	// ---- cross moments: the normal equations of a regression in one pass (replace b_i.mult(b_j).getAverage() per pair, MonteCarloConditionalExpectationRegression)
+	/** sumsOut = the x.length(x.length+1)/2 sums of x_i*x_j (i <= j, row-major) followed by the x.length*y.length sums of x_i*y_m; a handle of 0 in x is the constant 1. */
+	static native int crossMoments(long[] x, long[] y, double[] sumsOut);
 	/** With a device list: one device buffer per listed device (0 = not wanted there), each receives the moments of the whole vectors. */
 	static native int reduceMomentsBatchDevices(long[] vectors, double[] shiftsOrNull, long[] deviceOutPerDevice);
 	static native int getStreamOf(int shard, long[] stream);

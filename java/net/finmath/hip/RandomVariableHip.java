@@ -209,6 +209,10 @@ public class RandomVariableHip implements RandomVariable {
 		return (long)size() * world[0];
 	}
 
+	/** The handle of the device vector (0 for a deterministic value) and the sample size behind an expectation: for the package's estimators (MonteCarloConditionalExpectationRegressionHip). */
+	long deviceHandle() { return realizations == null ? 0L : realizations.handle; }
+	long expectationSampleSize() { return sampleSize(); }
+
 	@Override
 	public double getAverage() {
 		if(isDeterministic()) {

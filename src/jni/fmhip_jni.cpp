@@ -184,6 +184,14 @@ FMJ(jint, countNotAbove)(JNIEnv* env, jclass, jlong v, jdoubleArray bounds, jlon
     if (!pb.p || !po.p || po.length() < pb.length()) return FMHIP_ERR_INVALID_ARGUMENT;
     return fmhip_count_not_above(v, pb.p, pb.length(), (int64_t*)po.p);
 }
+// ---------------------------------------------------------------- cross moments
+FMJ(jint, crossMoments)(JNIEnv* env, jclass, jlongArray x, jlongArray y, jdoubleArray sumsOut) {
+    Pin<jlong> px(env, x, JNI_ABORT); Pin<jlong> py(env, y, JNI_ABORT); Pin<jdouble> po(env, sumsOut);
+    if (!px.p || !po.p) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int64_t nx = px.length(), ny = py.p ? py.length() : 0;
+    if ((int64_t)po.length() < nx * (nx + 1) / 2 + nx * ny) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_cross_moments((const fmhip_vec*)px.p, (int)nx, ny ? (const fmhip_vec*)py.p : nullptr, (int)ny, po.p);
+}
 FMJ(jint, reduceMomentsBatchDevice)(JNIEnv* env, jclass, jlongArray vectors, jdoubleArray shifts, jlong deviceOut) {
     Pin<jlong> pv(env, vectors, JNI_ABORT); Pin<jdouble> ps(env, shifts, JNI_ABORT);
     if (!pv.p || (ps.p && ps.length() < pv.length())) return FMHIP_ERR_INVALID_ARGUMENT;
