@@ -108,19 +108,44 @@ class BrownianMotionHip:
                 f"numberOfPaths={self.numberOfPaths}, numberOfFactors={self.numberOfFactors}, seed={self.seed})")
 
 
+def _device_mersenne():
+    """FMHIP_DEVICE_MERSENNE=0: the increments are drawn on one host core and uploaded, as before (the A/B switch); anything else:
+    they are generated on the device (fmhip_bm_generate_mersenne_device)."""
+    return os.environ.get("FMHIP_DEVICE_MERSENNE", "1") != "0"
+
+
 class BrownianMotionFromMersenneRandomNumbers(BrownianMotionHip):
     """finmath-lib's CPU generator (MT19937 + inverse normal CDF), the Brownian motion every reference test uses
-    (LIBORMarketModelCalibrationATMTest.java:283, MonteCarloBlackScholesModelTest.java:78-85); increments are generated on
-    the host and uploaded through the factory path (double[] → fp32).  Restated from published specifications — the draw
-    order is unverified (finmath-lib is not vendored), see csrc/mersenne.cpp."""
+    (LIBORMarketModelCalibrationATMTest.java:283, MonteCarloBlackScholesModelTest.java:78-85).  The increments are generated on the
+    device to the bits of the host generator (fmhip_bm_generate_mersenne_device: every workgroup enters the one MT19937 stream by
+    jump-ahead; central draws equal, a tail draw in some 10^8 may differ by one fp32 ulp — DESIGN.md §4.9); with FMHIP_DEVICE_MERSENNE=0
+    they are drawn on the host and uploaded through the factory path (double[] → fp32), which is the definition.  `path_offset`: this
+    object holds paths path_offset … path_offset + numberOfPaths of the whole motion (a rank's block, parallel.py), on either path.
+    Restated from published specifications — the draw order is unverified (finmath-lib is not vendored), see csrc/mersenne.cpp."""
+
+    def getCloneWithModifiedSeed(self, seed):
+        return BrownianMotionFromMersenneRandomNumbers(self.timeDiscretization, self.numberOfFactors, self.numberOfPaths, seed,
+                                                       self.randomVariableFactory, self.pathOffset)
 
     def _generate(self):
         td = self.timeDiscretization
         n_steps = td.getNumberOfTimeSteps()
         dt = np.array([td.getTimeStep(i) for i in range(n_steps)], dtype=np.float64)
-        handles = (C.c_int64 * (n_steps * self.numberOfFactors))()
-        N.check(N.lib().fmhip_bm_generate_mersenne(self.seed, n_steps, self.numberOfFactors, self.numberOfPaths,
-                                                   dt.ctypes.data_as(C.POINTER(C.c_double)), handles))
+        count = n_steps * self.numberOfFactors
+        handles = (C.c_int64 * count)()
+        if _device_mersenne():
+            N.check(N.lib().fmhip_bm_generate_mersenne_device(self.seed, n_steps, self.numberOfFactors, self.numberOfPaths, self.pathOffset,
+                                                              dt.ctypes.data_as(C.POINTER(C.c_double)), handles))
+        elif self.pathOffset == 0:
+            N.check(N.lib().fmhip_bm_generate_mersenne(self.seed, n_steps, self.numberOfFactors, self.numberOfPaths,
+                                                       dt.ctypes.data_as(C.POINTER(C.c_double)), handles))
+        else:                                   # the host stream is sequential: everything in front of the block is drawn, the block uploaded
+            block = mersenne_increments(self.seed, dt, self.numberOfFactors, self.pathOffset + self.numberOfPaths)[:, :, self.pathOffset:]
+            block = np.ascontiguousarray(block.reshape(count, self.numberOfPaths))
+            for k in range(count):
+                h = C.c_int64(0)
+                N.check(N.lib().fmhip_vec_create_from_double(block[k].ctypes.data_as(C.POINTER(C.c_double)), self.numberOfPaths, C.byref(h)))
+                handles[k] = h.value
         self._increments = [
             [RandomVariableHip(td.getTime(i + 1), DeviceVector(handles[i * self.numberOfFactors + f], self.numberOfPaths))
              for f in range(self.numberOfFactors)]

@@ -953,6 +953,11 @@ int fmhip_bm_generate_mersenne(int32_t seed, int n_steps, int n_factors, int64_t
         catch (...) { for (size_t k = 0; k < count; ++k) if (out[k]) { Engine::get().release(out[k]); out[k] = 0; } throw; }
     });
 }
+// the same numbers generated on the device (mersenne_device_engine.hpp): arguments are checked before anything is flushed or launched
+int fmhip_bm_generate_mersenne_device(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, fmhip_vec* out) {
+    FRONT(bm_generate_mersenne_device(seed, n_steps, n_factors, n_paths, path_offset, dt, out));
+    return guarded([&] { Engine::get().mt_bm_generate(seed, n_steps, n_factors, n_paths, path_offset, dt, out); });
+}
 double fmhip_inverse_normal_cdf(double p) { return fm::inverse_normal_cdf(p); }
 
 int fmhip_pool_clean(void) { FRONT(pool(0)); TE_ALL(mine, fmhip_pool_clean()); return guarded([&] { Engine::get().pool_clean(); }); }

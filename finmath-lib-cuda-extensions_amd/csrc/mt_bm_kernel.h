@@ -1,0 +1,30 @@
+// mt_bm_kernel.h — host-callable launchers of the Mersenne-Twister Brownian-increment kernels in mt_bm_kernel.hip.
+#pragma once
+#include <hip/hip_runtime_api.h>
+#include <stdint.h>
+
+namespace fm {
+
+constexpr int FM_MT_STATE_WORDS = 624;
+constexpr int FM_MT_TILE_FLOATS = 3200;            // floats of one of the two LDS store tiles: 16 paths of 200 step x factor vectors
+constexpr int FM_MT_MIN_SEGMENT_LOG2 = 1;          // segments are an even number of words: a draw is a pair of words
+constexpr int FM_MT_MAX_SEGMENT_LOG2 = 43;
+constexpr int FM_MT_JUMP_LIMIT_LOG2 = 44;         // fm_mt_jump_table.hpp holds 2^0 … 2^43: every word drawn lies below 2^44
+
+struct DevMtBmArgs {
+    float*          slab;           // n_streams vectors, `stride_floats` apart (stride is a multiple of 64 floats)
+    int64_t         stride_floats;
+    const double*   sqrt_dt;        // [n_streams]  sqrt(dt[step of the stream]) in fp64, one entry per stream
+    const uint32_t* state;          // 624 words: the seeded state jumped to the first word of local path 0
+    int64_t         n_paths;        // paths held by this process
+    uint32_t        n_streams;      // n_steps * n_factors: draws per path
+    uint32_t        segment_log2;   // a workgroup owns the paths whose first word lies in its segment of 2^segment_log2 words
+    uint32_t        tile_paths;     // paths per LDS store tile (a multiple of 4), 0: element-wise stores
+    uint32_t        n_segments;     // workgroups
+};
+
+// out[0 … 624) = the state `distance` words behind in[0 … 624) (one workgroup); distance < 2^44
+hipError_t launch_mt_jump(const uint32_t* in, uint64_t distance, uint32_t* out, hipStream_t st);
+hipError_t launch_mt_bm(const DevMtBmArgs& a, hipStream_t st);
+
+} // namespace fm

@@ -400,6 +400,8 @@ public:
     // brownian increments
     void bm_generate(int64_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset,
                      const double* dt, fmhip_vec* out);
+    // finmath-lib's Mersenne-Twister increments to the bits of host/mersenne.hpp, generated on the device (mersenne_device_engine.hpp)
+    void mt_bm_generate(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, fmhip_vec* out);
 
     // pool
     void pool_clean();
@@ -693,5 +695,7 @@ struct HostTimer {
 
 // what can be said about the arguments of fmhip_cross_moments without looking at a vector: counts in range, pointers, no 0 among y, a vector among x
 void xmom_check_counts(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, const double* sums_out);
+// what can be said about the arguments of fmhip_bm_generate_mersenne_device without a device (mersenne_device_engine.hpp)
+void mt_bm_check(int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, const fmhip_vec* out);
 
 } // namespace fm

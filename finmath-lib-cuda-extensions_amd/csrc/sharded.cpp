@@ -889,6 +889,25 @@ int bm_generate(int64_t seed, int n_steps, int n_factors, int64_t n_paths, int64
     });
 }
 
+// finmath-lib's Mersenne-Twister increments on a device list: every shard enters the ONE stream at its own block of paths (jump-ahead,
+// mersenne_device_engine.hpp) — no host vector, no upload, and no rule about the offset (a draw is not a block of four as Philox's is)
+int bm_generate_mersenne_device(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, fmhip_vec* out) {
+    return fronted([&](Shards& s) {
+        fm::mt_bm_check(n_steps, n_factors, n_paths, path_offset, dt, out);
+        const size_t streams = (size_t)n_steps * n_factors;
+        auto ids = std::make_shared<std::vector<fmhip_vec>>(streams);
+        for (size_t k = 0; k < streams; ++k) (*ids)[k] = s.fresh(n_paths);
+        auto steps = std::make_shared<std::vector<double>>(dt, dt + n_steps);
+        s.post([=](Worker& w) {
+            int64_t off, cnt; shard_range(n_paths, w.shards, w.shard, &off, &cnt);
+            std::vector<fmhip_vec> got(ids->size(), 0);
+            if (w.ok(fmhip_bm_generate_mersenne_device(seed, n_steps, n_factors, cnt, path_offset + off, steps->data(), got.data())))
+                for (size_t k = 0; k < got.size(); ++k) w.bind((*ids)[k], got[k]);
+        });
+        std::memcpy(out, ids->data(), streams * sizeof(fmhip_vec));
+    });
+}
+
 int pool(int what) { return fronted([&](Shards& s) { s.post([=](Worker& w) { w.ok(what == 0 ? fmhip_pool_clean() : fmhip_pool_purge()); }); s.wait(); }); }
 int pool_stats(fmhip_pool_stats_t* out) {
     return fronted([&](Shards& s) {

@@ -8,6 +8,43 @@
 
 namespace fmhost {
 
+// finmath-lib's BrownianMotionFromMersenneRandomNumbers with its increments GENERATED ON THE DEVICE (fmhip_bm_generate_mersenne_device:
+// every workgroup enters the one MT19937 stream by jump-ahead): the numbers of host/mersenne.hpp — central draws equal, a tail draw in
+// some 10^8 one fp32 ulp off — without the host vector and its upload, and with a path offset, so a rank generates its own block.
+// The class that draws on the host and goes through any factory (random_variable.hpp) stays: it is the definition, and the CPU twin's.
+class BrownianMotionFromMersenneRandomNumbersHip final : public BrownianMotion {
+public:
+    BrownianMotionFromMersenneRandomNumbersHip(TimeDiscretization td, int numberOfFactors, int64_t numberOfPaths, int seed, int64_t pathOffset = 0)
+        : td_(std::move(td)), factors_(numberOfFactors), paths_(numberOfPaths), offset_(pathOffset), seed_(seed) {}
+    RV getBrownianIncrement(int timeIndex, int factor) const override {
+        std::call_once(generated_, [this] { generate(); });
+        return inc_.at((size_t)timeIndex * factors_ + factor);
+    }
+    const TimeDiscretization& getTimeDiscretization() const override { return td_; }
+    int getNumberOfFactors() const override { return factors_; }
+    int64_t getNumberOfPaths() const override { return paths_; }
+    int getSeed() const { return seed_; }
+    RV getRandomVariableForConstant(double value) const override { return RandomVariableHip::of(-std::numeric_limits<double>::infinity(), value); }
+private:
+    void generate() const {
+        const int steps = td_.getNumberOfTimeSteps();
+        std::vector<double> dt((size_t)steps);
+        for (int i = 0; i < steps; ++i) dt[(size_t)i] = td_.getTimeStep(i);
+        std::vector<fmhip_vec> h((size_t)steps * factors_);
+        check(fmhip_bm_generate_mersenne_device(seed_, steps, factors_, paths_, offset_, dt.data(), h.data()));
+        inc_.reserve(h.size());
+        for (int i = 0; i < steps; ++i)
+            for (int f = 0; f < factors_; ++f)
+                inc_.push_back(RandomVariableHip::of(td_.getTime(i + 1), DeviceVector(h[(size_t)i * factors_ + f]), paths_));
+    }
+    TimeDiscretization td_;
+    int factors_;
+    int64_t paths_, offset_;
+    int seed_;
+    mutable std::vector<RV> inc_;
+    mutable std::once_flag generated_;
+};
+
 // chunk / stepsPerLaunch / jacobianBatch: 0 = the back end's default
 inline lmm::Backend makeHipBackend(const RandomVariableFactory* factory, const BrownianMotion* brownianMotion, int chunk = 0, int stepsPerLaunch = 0, int jacobianBatch = 0) {
     lmm::Backend be;

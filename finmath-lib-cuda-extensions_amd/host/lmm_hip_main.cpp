@@ -42,8 +42,11 @@ int main(int argc, char** argv) {
         // --brownian mersenne: the generator the reference's test injects (…ATMTest.java:283), drawn on the host and uploaded
         // through the factory; a sequential stream, so it cannot be sharded by path offset
         BrownianMotionFromMersenneRandomNumbers mersenne(m.timeDiscretization, 1, o.paths, (int)o.seed, &factory);
-        if (o.brownian == "mersenne" && o.world > 1) throw std::runtime_error("--brownian mersenne is a sequential stream: not available with --world > 1");
-        lmm::Backend be = makeHipBackend(&factory, (o.brownian == "mersenne") ? static_cast<const BrownianMotion*>(&mersenne) : &philox,
+        if (o.brownian == "mersenne" && o.world > 1) throw std::runtime_error("--brownian mersenne is a sequential stream: not available with --world > 1 (mersenne-device is)");
+        // --brownian mersenne-device: the same numbers generated on the device, every rank its own block of paths (jump-ahead)
+        BrownianMotionFromMersenneRandomNumbersHip mersenneDevice(m.timeDiscretization, 1, o.paths, (int)o.seed, pathOffset);
+        lmm::Backend be = makeHipBackend(&factory, (o.brownian == "mersenne") ? static_cast<const BrownianMotion*>(&mersenne)
+                                                 : (o.brownian == "mersenne-device") ? static_cast<const BrownianMotion*>(&mersenneDevice) : &philox,
                                          o.chunk, o.stepsPerLaunch, o.jacobianBatch);
 
         if (o.finmathLike) {

@@ -19,7 +19,7 @@ struct Options {
     int chunk = 0;                                         // LIBOR components per fused launch; 0 = back end default
     int stepsPerLaunch = 0;                                // Euler steps recorded per engine flush; 0 = back end default (4)
     int jacobianBatch = 0;                                 // finite-difference bumps simulated in lock-step (rows of one launch); 0 = back end default
-    std::string brownian = "philox";                        // philox (counter-based, on the device) | mersenne (finmath's CPU generator through the factory)
+    std::string brownian = "philox";                        // philox (counter-based, on the device) | mersenne (finmath's CPU generator through the factory) | mersenne-device (lmm_hip: its numbers, generated on the device)
     int threads = 1;                                       // --threads T (with --finmath-like): Jacobian columns on T threads, an engine each
     double releaseLagMs = 0.0;                             // --release-lag MS: handles are released as a JVM would release them — by a collector thread, every MS milliseconds,
     long long releaseLagBytes = 0;                         //   everything dead at that moment (ReleaseLag, random_variable.hpp); --release-lag-bytes B: … or once B bytes of dead wrappers have piled up

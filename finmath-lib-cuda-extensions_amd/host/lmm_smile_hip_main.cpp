@@ -15,7 +15,9 @@ int main(int argc, char** argv) {
         smile::Market m;
         BrownianMotionHip philox(m.timeDiscretization, 6, o.paths, o.seed, 0);                                       // :267: 5 factors + 1 for the volatility
         BrownianMotionFromMersenneRandomNumbers mersenne(m.timeDiscretization, 6, o.paths, (int)o.seed, &factory);   // drawn on the host, uploaded through the factory
-        lmm::Backend be = makeHipBackend(&factory, (o.brownian == "mersenne") ? static_cast<const BrownianMotion*>(&mersenne) : &philox, 0, 0, o.jacobianBatch);
+        BrownianMotionFromMersenneRandomNumbersHip mersenneDevice(m.timeDiscretization, 6, o.paths, (int)o.seed);   // the same numbers, generated on the device
+        lmm::Backend be = makeHipBackend(&factory, (o.brownian == "mersenne") ? static_cast<const BrownianMotion*>(&mersenne)
+                                                 : (o.brownian == "mersenne-device") ? static_cast<const BrownianMotion*>(&mersenneDevice) : &philox, 0, 0, o.jacobianBatch);
         fmhip_pool_stats_t s0; check(fmhip_pool_stats(&s0));
         int64_t bytes0 = 0; check(fmhip_traffic_stats(&bytes0, nullptr));
         if (o.profile) check(fmhip_profile_enable(1));

@@ -11,7 +11,7 @@ struct Options {
     int maxIterations = 30; std::string mode = "calibrate"; bool verbose = false, profile = false;
     int evaluations = 1, jacobianBatch = 0;
     bool fullHorizon = true;                                           // all 40 Euler steps, as the reference's Euler scheme simulates them
-    std::string brownian = "philox";                                    // philox (on the device) | mersenne (finmath's generator, the one the test injects)
+    std::string brownian = "philox";                                    // philox (on the device) | mersenne (finmath's generator, the one the test injects) | mersenne-device (lmm_smile_hip: its numbers, generated on the device)
 };
 inline Options parseOptions(int argc, char** argv) {
     Options o;

@@ -451,6 +451,15 @@ int fmhip_bm_generate(int64_t seed, int n_steps, int n_factors, int64_t n_paths,
  * fmhip_bm_generate_mersenne uploads them as n_steps*n_factors vectors (narrowed to fp32 like any double[] upload). */
 int fmhip_mersenne_increments(int32_t seed, int n_steps, int n_factors, int64_t n_paths, const double* dt, double* host_out);
 int fmhip_bm_generate_mersenne(int32_t seed, int n_steps, int n_factors, int64_t n_paths, const double* dt, fmhip_vec* out);
+/* The same increments GENERATED ON THE DEVICE: MT19937 is linear over GF(2), so every workgroup enters the one stream at its own
+ * segment by jump-ahead; no host vector, no upload.  out[k] holds paths path_offset … path_offset + n_paths of vector k of the
+ * whole motion, so a shard or a rank generates its own block without drawing what precedes it (2·n_steps·n_factors·(path_offset +
+ * n_paths) <= 2^44 words, an error beyond).  Contract against fmhip_mersenne_increments narrowed to fp32: the 52-bit uniforms are
+ * the host's bit for bit; a draw with |u - 0.5| <= 0.425 (85 %) goes through + - * / only and is EQUAL; a tail draw goes through
+ * log, where the device library and the host's libm may differ by an fp64 ulp: equal too, except that about one in 10^8 may differ
+ * by one fp32 ulp.  Arguments are checked on the host before anything is flushed or launched (negative time steps are an error
+ * here).  A build without the kernel returns FMHIP_ERR_UNSUPPORTED; it never falls back to the host generator. */
+int fmhip_bm_generate_mersenne_device(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, fmhip_vec* out);
 /* Inverse of the standard normal CDF (Wichura AS 241 / PPND16), exposed for tests. Returns the value (no status). */
 double fmhip_inverse_normal_cdf(double p);
 

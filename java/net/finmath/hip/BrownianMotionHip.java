@@ -28,6 +28,12 @@ public class BrownianMotionHip implements BrownianMotion, Serializable {
 	private final int numberOfPaths;
 	private final int seed;
 	private final long pathOffset;
+	/** Which stream the increments come from: the engine's counter-based Philox generator, or finmath-lib's
+	 * BrownianMotionFromMersenneRandomNumbers generated on the device (fmhip_bm_generate_mersenne_device: the numbers of the CPU class). */
+	public enum Generator { PHILOX, MERSENNE_DEVICE }
+	private Generator generator = Generator.PHILOX;
+	/** Chooses the generator; to be called before the first increment is asked for. */
+	public BrownianMotionHip withGenerator(final Generator generator) { this.generator = generator; return this; }
 
 	private transient RandomVariable[][] brownianIncrements;
 	private final Object brownianIncrementsLazyInitLock = new Object();
@@ -97,7 +103,11 @@ public class BrownianMotionHip implements BrownianMotion, Serializable {
 			timeSteps[timeIndex] = timeDiscretization.getTimeStep(timeIndex);
 		}
 		final long[] handles = new long[numberOfTimeSteps * numberOfFactors];
-		Native.check(Native.bmGenerate(seed, numberOfTimeSteps, numberOfFactors, numberOfPaths, pathOffset, timeSteps, handles));
+		if(generator == Generator.MERSENNE_DEVICE) {
+			Native.check(Native.bmGenerateMersenneDevice(seed, numberOfTimeSteps, numberOfFactors, numberOfPaths, pathOffset, timeSteps, handles));
+		} else {
+			Native.check(Native.bmGenerate(seed, numberOfTimeSteps, numberOfFactors, numberOfPaths, pathOffset, timeSteps, handles));
+		}
 		final RandomVariable[][] increments = new RandomVariable[numberOfTimeSteps][numberOfFactors];
 		for(int timeIndex = 0; timeIndex < numberOfTimeSteps; timeIndex++) {
 			final double time = timeDiscretization.getTime(timeIndex + 1);					// :175

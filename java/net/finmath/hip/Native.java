@@ -113,6 +113,7 @@ final class Native {
 	static native int bmGenerate(long seed, int nSteps, int nFactors, long nPaths, long pathOffset, double[] dt, long[] outHandles);
 	static native int mersenneIncrements(int seed, int nSteps, int nFactors, long nPaths, double[] dt, double[] hostOut);
 	static native int bmGenerateMersenne(int seed, int nSteps, int nFactors, long nPaths, double[] dt, long[] outHandles);
+	static native int bmGenerateMersenneDevice(int seed, int nSteps, int nFactors, long nPaths, long pathOffset, double[] dt, long[] outHandles);
 	static native double inverseNormalCdf(double p);
 
 	// ---- pool (replace DeviceMemoryPool.clean / purge / getDeviceFreeMemPercentage, RandomVariableCuda.java:393-449)

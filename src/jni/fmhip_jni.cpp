@@ -333,6 +333,11 @@ FMJ(jint, bmGenerateMersenne)(JNIEnv* env, jclass, jint seed, jint nSteps, jint 
     if (nSteps <= 0 || nFactors <= 0 || !po.p || !pd.p || (int64_t)po.length() < (int64_t)nSteps * nFactors || pd.length() < nSteps) return FMHIP_ERR_INVALID_ARGUMENT;
     return fmhip_bm_generate_mersenne(seed, nSteps, nFactors, nPaths, pd.p, (fmhip_vec*)po.p);
 }
+FMJ(jint, bmGenerateMersenneDevice)(JNIEnv* env, jclass, jint seed, jint nSteps, jint nFactors, jlong nPaths, jlong pathOffset, jdoubleArray dt, jlongArray outHandles) {
+    Pin<jdouble> pd(env, dt, JNI_ABORT); Pin<jlong> po(env, outHandles);
+    if (nSteps <= 0 || nFactors <= 0 || !po.p || !pd.p || (int64_t)po.length() < (int64_t)nSteps * nFactors || pd.length() < nSteps) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_bm_generate_mersenne_device(seed, nSteps, nFactors, nPaths, pathOffset, pd.p, (fmhip_vec*)po.p);
+}
 FMJ(jdouble, inverseNormalCdf)(JNIEnv*, jclass, jdouble p) { return fmhip_inverse_normal_cdf(p); }
 
 // ---------------------------------------------------------------- pool

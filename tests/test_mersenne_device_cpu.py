@@ -1,0 +1,51 @@
+"""The host side of the device Mersenne-Twister generator, without a GPU: the entry point is bound, the Python mirror's switch, and the
+engine's generation pass (csrc/mersenne_device_engine.hpp) against the null device under AddressSanitizer / UBSan and ThreadSanitizer
+(tests/nulldev_mersenne: the null device of tests/nulldev plus stand-ins for the two launchers, which generate with the host code from the
+state the engine hands them, and a driver of its own) on one engine, behind device lists and with thread engines — path offsets and shards
+reproduce fmhip_mersenne_increments exactly there, which pins the engine's seeding, jump distances and slab layout."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NULLDEV = os.path.join(ROOT, "tests", "nulldev_mersenne")
+
+
+def test_entry_point_is_bound(fm):
+    assert "fmhip_bm_generate_mersenne_device" in fm._native.SYMBOLS and hasattr(fm.lib(), "fmhip_bm_generate_mersenne_device")
+    header = open(os.path.join(ROOT, "include", "fmhip.h"), encoding="utf-8").read()
+    assert "int fmhip_bm_generate_mersenne_device(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, fmhip_vec* out);" in header
+
+
+def test_mirror_switch(fm, monkeypatch):
+    from importlib import import_module
+    bm = import_module("finmath-lib-cuda-extensions_amd.brownian_motion")
+    monkeypatch.delenv("FMHIP_DEVICE_MERSENNE", raising=False)
+    assert bm._device_mersenne()
+    monkeypatch.setenv("FMHIP_DEVICE_MERSENNE", "0")
+    assert not bm._device_mersenne()
+    b = fm.BrownianMotionFromMersenneRandomNumbers(fm.TimeDiscretization(0.0, 2, 0.5), 1, 10, 7, None, 40)
+    assert b.pathOffset == 40 and b.getCloneWithModifiedSeed(8).pathOffset == 40
+
+
+@pytest.fixture(scope="module")
+def built():
+    if not shutil.which("g++") or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
+        pytest.skip("needs g++ and the HIP headers")
+    r = subprocess.run(["make", "-C", NULLDEV, "-j8", "asan", "tsan"], capture_output=True, text=True, timeout=1200)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    return os.path.join(NULLDEV, "build")
+
+
+@pytest.mark.parametrize("env", [{}, {"FMNULL_DEVICES": "2"}, {"FMNULL_DEVICES": "3"}, {"FMNULL_THREAD_ENGINES": "1"}])
+def test_engine_pass_is_clean_under_the_sanitizers(built, tmp_path, env):
+    full = dict(os.environ, FMHIP_JIT_CACHE_DIR=str(tmp_path / "code_objects"), FMHIP_JIT_PACK_DIR="off", FMHIP_RING_BYTES="16384", FMHIP_ARENA_BYTES="4096",
+                ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1", TSAN_OPTIONS="halt_on_error=1", **env)
+    a = subprocess.run([os.path.join(built, "drive_mersenne_asan")], capture_output=True, text=True, timeout=600, env=full)
+    assert a.returncode == 0 and "Sanitizer" not in a.stderr and "runtime error" not in a.stderr, a.stdout[-500:] + a.stderr[-6000:]
+    assert a.stdout.count("mersenne done") == 2
+    t = subprocess.run([os.path.join(built, "drive_mersenne_tsan")], capture_output=True, text=True, timeout=600, env=full)
+    assert t.returncode == 0 and "ThreadSanitizer" not in t.stderr, t.stdout[-500:] + t.stderr[-6000:]
+    assert t.stdout.count("mersenne done") == 2
