@@ -5,7 +5,11 @@
 
 --fast measures FMHIP_MATH_FAST (hardware exp/log): there the figure of interest is max_ulp (stated bound: 2).
 
-Reports, per opcode: elements whose bits differ, the largest difference in fp32 ulp, and NaN-ness mismatches."""
+Reports, per opcode: elements whose bits differ, the largest difference in fp32 ulp, and NaN-ness mismatches.
+
+Its descendant in the suite is tests/test_gpu_arith_gates.py::test_strided_sweep_over_all_bit_patterns: every 257th bit pattern of SQRT,
+INVERT, DIV_S:3, VID_S:3, POW_S with 0.5 / -1 / 1.5 / 2.5 / -2 / 4 and EXP on the specialised tier (seconds), so that a regression
+reaches somebody between two runs of this script."""
 import importlib, json, os, sys, time
 from concurrent.futures import ProcessPoolExecutor
 
