@@ -8,13 +8,13 @@ A step = ONE pass of the canonical fused RandomVariable stream S (SURVEY.md §8d
 (x,y,z) triples of N = 1 000 000 paths, executed as ONE horizontally batched launch through the C-ABI
 (fmhip_program_run_into).  B·16 MB ≫ 256 MB Infinity Cache, so the traffic is HBM traffic.
 Inputs: x, y, z = java.util.Random(31415 / 27182 / 16180).nextDouble() (+0.5 for y and z) as config 2 specifies, narrowed to
-fp32 and resident in HBM before the timed region starts; the expectations of triple 0 are checked against the CPU twin on the
-same inputs in the run itself ("parity_triple0").
+fp32 and resident in HBM before the timed region starts; with --full the expectations of triple 0 are checked against the CPU
+twin on the same inputs in the run itself ("parity_triple0").
 
 metric  path-ops/s = 12 · N · B · n_gpus / step time        (whole job, all ranks)
 roofline achieved = algorithmic bytes per launch (4 B · (3 in + 1 out) · N · B) / average device duration of the
          fused-program kernel, measured live with HIP events on the runtime's own stream (fmhip_profile_*).
-cpu_baseline: the oracle (C restatement of the reference's CPU class, one single-threaded loop and one fresh
+cpu_baseline (--full): the oracle (C restatement of the reference's CPU class, one single-threaded loop and one fresh
          array per method call — the reference's cost model) timed on this host, rank 0, N=1 only.
 
 Multi-GPU (torchrun, one rank per GPU): independent Monte-Carlo path blocks per rank (weak scaling, no data-path
@@ -24,10 +24,17 @@ collective); the only exchange is ONE small RCCL all-gather of the per-rank expe
 The default run carries BOTH halves of BASELINE.json's metric in ONE JSON line: the stream line above (top level,
 contract keys unchanged) and, under "lmm", the LIBOR-Market-Model ATM calibration at 1 M paths per GPU (configs[3]; with
 N ranks configs[4]: N x 1 M paths, one RCCL all-gather of the 144 expectation partials per objective evaluation) — wall
-seconds, LM iterations, evaluations, mean deviation against the reference's 2e-4 acceptance, its own roofline (algorithmic
-bytes of ALL program launches of the real calibration / their summed device time) and its own cpu_baseline.  The
-calibration runs in the native driver bin/lmm_hip (C++ over the C-ABI), started as a child process BEFORE this process
-touches the GPU.  `--workload stream` / `--workload lmm` run one half only.
+seconds, LM iterations, evaluations, mean deviation against the reference's 2e-4 acceptance.  The calibration runs ONCE in the
+native driver bin/lmm_hip (C++ over the C-ABI), started as a child process BEFORE this process touches the GPU.
+`--workload stream` / `--workload lmm` run one half only.
+
+A plain run does what these two figures need and nothing else: the calibration, set-up, warm-up, the sustained leg that puts the
+chip into its steady state, the K timed steps, the dump if one is asked for, the line.  What it reports beside `value` costs no run
+of its own: the roofline fraction is the device time of the timed region itself, `traffic` is read from profiles/.  `--full` adds
+every other measurement and check, each a run or a pass of its own, to the same line (top level: `cpu_baseline`, `parity_triple0`,
+`interpreter_tier`, `fast_math`, `roofline.avg_kernel_us_one_event_pair_per_launch`, `brownian`; under "lmm": `box_speed`, the
+profiled second run and its `roofline`, `cpu_baseline`, the smile calibration, the caller without hints and its variants) — minutes
+instead of seconds.  The line says which of the two it is ("full").
 
 `--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (dump_stream_outputs, lmm_leg): every
 input is generated from fixed seeds, so two builds run with the same arguments can be compared output for output.
@@ -196,11 +203,12 @@ def lmm_traffic_ratio():
         return None
 
 
-def lmm_leg(args, world, rank, nonce, cpu_base=True, store=None):
+def lmm_leg(args, world, rank, nonce, cpu_base=True, store=None, full=False):
     """BASELINE.json configs[3] / [4]: LMM ATM swaption calibration (LIBORMarketModelCalibrationATMTest.java:186-340 inputs,
     acceptance :466) at `--paths` paths per GPU in the native driver host/lmm.hpp over the C-ABI.  Runs in child processes
     (one lmm_hip per rank; LOCAL_RANK picks the device) and must be called BEFORE this process touches the GPU.
       run 1  the calibration, unprofiled: wall seconds = the metric's second half (cold code-object cache on a fresh box);
+    A plain run ends here.  With `full`:
       run 2  the same calibration with every program launch bracketed by HIP events on the runtime stream (--profile):
              roofline.achieved = algorithmic bytes of all launches (fmhip_traffic_stats) / their summed device time;
       N = 1 also: profiled replay of objective evaluations one at a time and 8 in lock-step (what a launch shape is worth),
@@ -232,19 +240,19 @@ def lmm_leg(args, world, rank, nonce, cpu_base=True, store=None):
     # what THIS box's memory system and clocks give (bin/box_speed: non-temporal copy and read-only sweep of 2 GiB, clock under vector
     # load): the same binary reads 0.65 of the HBM peak on one MI355X box and 0.71 on another — context for every fraction below
     box = None
-    if rank == 0:
+    if full and rank == 0:
         try:
             box = json.loads(subprocess.run([os.path.join(ROOT, "finmath-lib-cuda-extensions_amd", "bin", "box_speed")], capture_output=True, text=True, timeout=120).stdout.strip().splitlines()[-1])
         except Exception as e:
             box = {"error": str(e)[-200:]}
     r, wall = run(base + dist_args("a"))
-    rp, _ = run(base + ["--profile"] + dist_args("b"))
+    rp = run(base + ["--profile"] + dist_args("b"))[0] if full else None
     per_rank = None
     if store is not None and world > 1:
         # every rank ran the same optimiser on the same (all-gathered, rank-ordered) expectations: the calibrated parameter vectors
         # must be equal BIT FOR BIT on all ranks — checked here, through the launcher's store, before anything is reported
         store.set(f"fmhip_lmm_{nonce}_{rank}", json.dumps({"seconds": r["seconds"], "parameters": r["parameters"], "evaluations": r["evaluations"],
-                                                          "kernel_s": rp["kernel_ms_total"] / 1e3, "achieved_GBps": rp["achieved_GBps"]}))
+                                                          "kernel_s": rp["kernel_ms_total"] / 1e3 if full else None, "achieved_GBps": rp["achieved_GBps"] if full else None}))
         if rank == 0:
             per_rank = [json.loads(store.get(f"fmhip_lmm_{nonce}_{k}").decode()) for k in range(world)]
             for k in range(1, world):
@@ -255,6 +263,23 @@ def lmm_leg(args, world, rank, nonce, cpu_base=True, store=None):
     if args.dump_outputs:
         # --dump-outputs, LMM half: the volatility parameters the timed calibration (run 1) ended on, float64
         dump_array(args.dump_outputs, "lmm_parameters", np.asarray(r["parameters"], dtype=np.float64))
+    lmm = {"metric": "LMM calib wall-time, 1M paths" if world == 1 else f"LMM calib wall-time, {world}x1M paths (path-sharded)",
+           "value": r["seconds"], "unit": "s", "higher_is_better": False, "n_gpus": world, "paths_per_gpu": paths, "paths": paths * world,
+           "lm_iterations": r["iterations"], "objective_evaluations": r["evaluations"],
+           "seconds_per_objective_evaluation": r["seconds"] / r["evaluations"],
+           "mean_deviation": r["mean_deviation"], "rms_deviation": r["rms_deviation"], "initial_rms": r["initial_rms"],
+           "acceptance": "abs(mean_deviation) < 2e-4 (LIBORMarketModelCalibrationATMTest.java:466)",
+           "accepted": abs(r["mean_deviation"]) < 2e-4,
+           "workload": "LIBORMarketModelCalibrationATMTest inputs: 80 forward rates, 1 factor, spot measure, normal state space, 144 ATM swaptions, "
+                       "50 volatility parameters, Levenberg-Marquardt with finite differences; native driver over the C-ABI",
+           "kernel_launches": r["kernel_launches"], "path_ops_per_s": r["path_ops"] / r["seconds"], "process_wall_s": wall,
+           "specialised_kernels": r.get("specialised_kernels"), "specialisations_from_disk_cache": r.get("specialisations_from_disk_cache"),
+           "per_rank_seconds": None if per_rank is None else [x["seconds"] for x in per_rank],
+           "ranks_calibrated_identical_parameters": None if per_rank is None else True,
+           "rccl": {"calls": r.get("rccl_collectives", 0), "summed_latency_s": r.get("rccl_collective_seconds", 0.0),
+                    "what": "one all-gather of 144 x {sum, sumsq, min, max} fp64 partials per objective evaluation; latency = enqueue to result on the host"}}
+    if not full:
+        return lmm
     kernel_s = rp["kernel_ms_total"] / 1e3
     # Where the host's own time goes (the engine's FMHIP_HOST_PROFILE table of a third run, N = 1 only): the slots that do not contain
     # each other, largest first.  host_idle_s = wall time of the profiled run the device spent without a kernel.
@@ -271,23 +296,9 @@ def lmm_leg(args, world, rank, nonce, cpu_base=True, store=None):
             host_top = [{"what": k, "seconds": v} for k, v in sorted(leaf.items(), key=lambda kv: -kv[1])[:3]]
         except Exception as e:
             host_top = [{"error": str(e)[-200:]}]
-    lmm = {"metric": "LMM calib wall-time, 1M paths" if world == 1 else f"LMM calib wall-time, {world}x1M paths (path-sharded)",
-           "value": r["seconds"], "unit": "s", "higher_is_better": False, "n_gpus": world, "paths_per_gpu": paths, "paths": paths * world,
-           "lm_iterations": r["iterations"], "objective_evaluations": r["evaluations"],
-           "seconds_per_objective_evaluation": r["seconds"] / r["evaluations"],
-           "mean_deviation": r["mean_deviation"], "rms_deviation": r["rms_deviation"], "initial_rms": r["initial_rms"],
-           "acceptance": "abs(mean_deviation) < 2e-4 (LIBORMarketModelCalibrationATMTest.java:466)",
-           "accepted": abs(r["mean_deviation"]) < 2e-4,
-           "workload": "LIBORMarketModelCalibrationATMTest inputs: 80 forward rates, 1 factor, spot measure, normal state space, 144 ATM swaptions, "
-                       "50 volatility parameters, Levenberg-Marquardt with finite differences; native driver over the C-ABI",
-           "kernel_launches": r["kernel_launches"], "path_ops_per_s": r["path_ops"] / r["seconds"], "box_speed": box,
-           "process_wall_s": wall, "seconds_second_run_warm_code_object_cache_profiled": rp["seconds"],
-           "specialised_kernels": r.get("specialised_kernels"), "specialisations_from_disk_cache": r.get("specialisations_from_disk_cache"),
-           "per_rank_seconds": None if per_rank is None else [x["seconds"] for x in per_rank],
+    lmm.update({
+           "box_speed": box, "seconds_second_run_warm_code_object_cache_profiled": rp["seconds"],
            "per_rank_roofline_frac": None if per_rank is None else [x["achieved_GBps"] / HBM_PEAK_GBS for x in per_rank],
-           "ranks_calibrated_identical_parameters": None if per_rank is None else True,
-           "rccl": {"calls": r.get("rccl_collectives", 0), "summed_latency_s": r.get("rccl_collective_seconds", 0.0),
-                    "what": "one all-gather of 144 x {sum, sumsq, min, max} fp64 partials per objective evaluation; latency = enqueue to result on the host"},
            "roofline": {"bound": "hbm", "achieved": rp["achieved_GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": rp["achieved_GBps"] / HBM_PEAK_GBS,
                         "traffic": None, "traffic_over_algorithmic_offline": lmm_traffic_ratio(),
                         "kernel": "all fused-program launches of the calibration itself (rank 0)",
@@ -295,7 +306,7 @@ def lmm_leg(args, world, rank, nonce, cpu_base=True, store=None):
                         "algorithmic_bytes": rp["algorithmic_bytes"], "summed_kernel_s": kernel_s,
                         "device_busy_fraction_of_wall": kernel_s / rp["seconds"],
                         "host_idle_s": rp["seconds"] - kernel_s, "host_time_top3": host_top,
-                        "timing": "one HIP event pair per launch on the runtime stream, summed"}}
+                        "timing": "one HIP event pair per launch on the runtime stream, summed"}})
     eng = rp.get("engine") or {}
     lmm["roofline"]["merged_launches"] = eng.get("merged_launches")
     lmm["roofline"]["merged_chains"] = eng.get("merged_chains")
@@ -608,7 +619,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64, help="independent (x,y,z) triples per launch")
     ap.add_argument("--paths", type=int, default=N_PATHS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="beside the headline: CPU baselines and the parity check against the CPU twin, other tiers and math modes, "
+                                                        "the per-launch timing pass, the Brownian / Heston block, the LMM half's profiled and comparison runs (minutes)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU legs")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
                                                           "(rank 0; dump_stream_outputs and lmm_leg say which arrays)")
     ap.add_argument("--cpu-worker", type=float, default=0.0, help=argparse.SUPPRESS)      # internal: one process of the all-cores CPU baseline
@@ -638,7 +651,7 @@ def main():
     lmm = None
     if args.workload in ("both", "lmm"):
         try:
-            lmm = lmm_leg(args, world, rank, nonce, cpu_base=not args.no_cpu_baseline, store=store)     # child processes; this process has not touched the GPU yet
+            lmm = lmm_leg(args, world, rank, nonce, cpu_base=not args.no_cpu_baseline, store=store, full=args.full)     # child processes; this process has not touched the GPU yet
         except Exception as e:
             if args.workload == "lmm":
                 raise
@@ -646,7 +659,7 @@ def main():
     if args.workload == "lmm":
         if rank == 0:
             line = dict(lmm)
-            line.update({"steps": lmm["lm_iterations"], "warmup": 0, "ms_per_step": lmm["value"] / max(1, lmm["lm_iterations"]) * 1e3,
+            line.update({"full": args.full, "steps": lmm["lm_iterations"], "warmup": 0, "ms_per_step": lmm["value"] / max(1, lmm["lm_iterations"]) * 1e3,
                          "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "config": {"workload": lmm.pop("workload")}})
             print(json.dumps(line), flush=True)
         return
@@ -806,13 +819,15 @@ def main():
     assert np.isfinite(mean_w)
     m0 = [float(v) for v in comb[0].tolist()]      # {sum, sumsq about 0, min, max} of w for triple 0
 
-    # cross-check: one event pair per launch (what a tracing profiler sees), separate short pass right after the timed region
-    fm.profile_enable(True)
-    for _ in range(max(5, min(args.steps, 20))):
-        prog.run_into(rows, out_rows, want_moments=False, device_moments=partial.data_ptr())
-    kernel_ms, n_launch = fm.profile_read()
-    fm.profile_enable(False)
-    per_launch_kernel_s = kernel_ms / 1e3 / max(1, n_launch)
+    # --full, cross-check: one event pair per launch (what a tracing profiler sees), separate short pass right after the timed region
+    per_launch_kernel_s = None
+    if args.full:
+        fm.profile_enable(True)
+        for _ in range(max(5, min(args.steps, 20))):
+            prog.run_into(rows, out_rows, want_moments=False, device_moments=partial.data_ptr())
+        kernel_ms, n_launch = fm.profile_read()
+        fm.profile_enable(False)
+        per_launch_kernel_s = kernel_ms / 1e3 / max(1, n_launch)
     avg_kernel_s = region_kernel_s
     achieved = alg_bytes / avg_kernel_s / 1e9
 
@@ -829,21 +844,23 @@ def main():
         fm.synchronize()
         return a.elapsed_time(b) / 1e3 / launches
 
-    # additional information: the same program on the interpreter tier (what a program runs on until its kernel is compiled)
+    # --full, additional information: the same program on the interpreter tier (what a program runs on until its kernel is compiled)
     interp_kernel_s = None
-    if tier == 1:
+    if args.full and tier == 1:
         prev_jit = fm.set_jit(fm.JIT_OFF)
         interp_kernel_s = measure(prog)
         fm.set_jit(prev_jit)
 
-    # additional information (not the headline): the same stream with FMHIP_MATH_FAST (hardware exp/log, <= 2 ulp), and the
+    # --full, additional information (not the headline): the same stream with FMHIP_MATH_FAST (hardware exp/log, <= 2 ulp), and the
     # headline program again right after it under the same conditions (exact vs fast on the same box, same minute)
-    fm.set_math_mode(fm.MATH_FAST)
-    prog_fast = build_stream_s(fm)
-    fm.set_math_mode(fm.MATH_EXACT)
-    fm.jit_wait()
-    fast_kernel_s = measure(prog_fast)
-    exact_again_s = measure(prog)
+    fast_kernel_s = exact_again_s = None
+    if args.full:
+        fm.set_math_mode(fm.MATH_FAST)
+        prog_fast = build_stream_s(fm)
+        fm.set_math_mode(fm.MATH_EXACT)
+        fm.jit_wait()
+        fast_kernel_s = measure(prog_fast)
+        exact_again_s = measure(prog)
 
     # HBM traffic of the same kernel from the PMC counters (FETCH_SIZE / WRITE_SIZE, separate rocprofv3 --pmc passes, gfx950
     # correction applied): NOT measured in this run — counters need a profiler pass of their own — but OFFLINE on this exact
@@ -860,7 +877,7 @@ def main():
             continue
 
     brownian = None
-    if world == 1 and args.workload == "both":
+    if args.full and world == 1 and args.workload == "both":
         del rows, out_rows                      # the stream half's 1.5 GB of inputs are no longer needed
         rows = out_rows = None
         try:
@@ -873,7 +890,7 @@ def main():
         value = N_OPS * n * B * world / (elapsed / args.steps)
         line = {
             "metric": "Monte-Carlo path-ops/sec (fused RandomVariable stream)",
-            "value": value, "unit": "path-ops/s",
+            "value": value, "unit": "path-ops/s", "full": args.full,
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -890,7 +907,8 @@ def main():
                          "kernel": ("fm_jit_<hash>_t (specialised kernel of stream S, generated + compiled at run time)" if tier == 1
                                     else "fm::fm_program_kernel<1, false, 8, 9, 3, float __vector(9)>"),
                          "tier": "specialised" if tier == 1 else "interpreter", "vgprs": jit_vgprs,
-                         "avg_kernel_us": avg_kernel_s * 1e6, "avg_kernel_us_one_event_pair_per_launch": per_launch_kernel_s * 1e6,
+                         "avg_kernel_us": avg_kernel_s * 1e6,
+                         "avg_kernel_us_one_event_pair_per_launch": None if per_launch_kernel_s is None else per_launch_kernel_s * 1e6,
                          "timing": "HIP events on the runtime stream around the K timed launches, duration / K (launch gaps included)",
                          "algorithmic_bytes_per_launch": alg_bytes,
                          "per_gpu_frac": [alg_bytes / t / 1e9 / HBM_PEAK_GBS for t in per_gpu_kernel_s]},
@@ -902,15 +920,16 @@ def main():
                 "avg_kernel_us": interp_kernel_s * 1e6, "achieved_GBps": alg_bytes / interp_kernel_s / 1e9,
                 "frac": alg_bytes / interp_kernel_s / 1e9 / HBM_PEAK_GBS},
             "jit": fm.jit_stats(),
-            "fast_math": {"note": "same workload with fmhip_set_math_mode(FMHIP_MATH_FAST): exp/log on v_exp_f32/v_log_f32, "
-                                  "within 2 fp32 ulp (accuracy class of the reference kernels' CUDA expf/logf); not the headline",
-                          "avg_kernel_us": fast_kernel_s * 1e6, "achieved_GBps": alg_bytes / fast_kernel_s / 1e9,
-                          "frac": alg_bytes / fast_kernel_s / 1e9 / HBM_PEAK_GBS,
-                          "path_ops_per_s_per_gpu": N_OPS * n * B / fast_kernel_s,
-                          "exact_measured_the_same_way_us": exact_again_s * 1e6, "exact_over_fast": exact_again_s / fast_kernel_s,
-                          "timing": "300 back-to-back launches between two HIP events, entered from 150 launches of the same program"},
+            "fast_math": None if fast_kernel_s is None else {
+                "note": "same workload with fmhip_set_math_mode(FMHIP_MATH_FAST): exp/log on v_exp_f32/v_log_f32, "
+                        "within 2 fp32 ulp (accuracy class of the reference kernels' CUDA expf/logf); not the headline",
+                "avg_kernel_us": fast_kernel_s * 1e6, "achieved_GBps": alg_bytes / fast_kernel_s / 1e9,
+                "frac": alg_bytes / fast_kernel_s / 1e9 / HBM_PEAK_GBS,
+                "path_ops_per_s_per_gpu": N_OPS * n * B / fast_kernel_s,
+                "exact_measured_the_same_way_us": exact_again_s * 1e6, "exact_over_fast": exact_again_s / fast_kernel_s,
+                "timing": "300 back-to-back launches between two HIP events, entered from 150 launches of the same program"},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
             # parity in the run itself: the timed kernel's expectations for triple 0 against the CPU twin on the same inputs
             tw = line["cpu_baseline"].pop("twin_moments_triple0")

@@ -6,10 +6,11 @@
 #   bm_write/        --pmc WRITE_SIZE of the normal-increment generator (config 3)
 # rocprofv3 gets the program itself after `--` (python3 / the driver binary), never a shell or env wrapper.
 set -e
+ROOT=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$1
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="$GRAFT_REPO_ROOT/bench.py --workload stream --no-cpu-baseline"
+B="$ROOT/bench.py --full --workload stream --no-cpu-baseline"      # --full: the kernels of the other tier and math mode are in the statistics too
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_stats -o bench -- python3 $B --steps 20 --warmup 5 > $OUT/bench_profiled_line.json 2> $OUT/bench_stats.err
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o fetch -- python3 $B --steps 5 --warmup 2 --sustained-seconds 0 > /dev/null 2> $OUT/pmc_fetch.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o write -- python3 $B --steps 5 --warmup 2 --sustained-seconds 0 > /dev/null 2> $OUT/pmc_write.err

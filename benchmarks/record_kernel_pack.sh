@@ -30,8 +30,8 @@ $BIN/lmm_smile_hip --paths 163840 > /dev/null
 step "done: $BIN/lmm_smile_hip --paths 163840"
 $BIN/lmm_smile_hip --paths 1000000 > /dev/null
 step "done: $BIN/lmm_smile_hip --paths 1000000"
-python3 bench.py --workload stream --steps 5 --warmup 2 --sustained-seconds 0.2 --no-cpu-baseline > /dev/null
-step "done: python3 bench.py --workload stream --steps 5 --warmup 2 --sustained-seconds 0.2 --no-cpu-b"
+python3 bench.py --full --workload stream --steps 5 --warmup 2 --sustained-seconds 0.2 --no-cpu-baseline > /dev/null      # --full: the fast-math program is in the pack too
+step "done: python3 bench.py --full --workload stream --steps 5 --warmup 2 --sustained-seconds 0.2 --no-cpu-baseline"
 python3 benchmarks/config3_heston.py > /dev/null 2>&1 || true
 step "done: python3 benchmarks/config3_heston.py"
 sort -u "$RAW" > "$OUT"

@@ -25,4 +25,4 @@ for mode in ("native", "hintfree"):
             mode, m, c, d["seconds"], d["kernel_launches"], d["algorithmic_bytes"] / 1e12, d["path_ops"], p["kernel_ms_total"], p["achieved_GBps"], d["mean_deviation"], e.get("merged_launches"), e.get("merged_chains"), e.get("common_rows")))
 PY
 cat $OUT/ab_summary.txt
-python bench.py > $OUT/bench_line.json 2> $OUT/bench.err; echo "bench rc $?"
+python bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err; echo "bench rc $?"
