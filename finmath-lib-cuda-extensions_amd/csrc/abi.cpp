@@ -958,6 +958,20 @@ int fmhip_bm_generate_mersenne_device(int32_t seed, int n_steps, int n_factors, 
     FRONT(bm_generate_mersenne_device(seed, n_steps, n_factors, n_paths, path_offset, dt, out));
     return guarded([&] { Engine::get().mt_bm_generate(seed, n_steps, n_factors, n_paths, path_offset, dt, out); });
 }
+// Increments with a law per (step, factor) from the same MT19937 stream (host/increments.hpp): the definition on the host, and the same
+// numbers generated on the device (increments_device_engine.hpp).  One function checks the arguments of both.
+int fmhip_increments_host(int32_t seed, int n_steps, int n_factors, int64_t n_paths, const int32_t* kinds, const double* a, const double* b, double* host_out) {
+    try {
+        fm::increments_host(seed, n_steps, n_factors, n_paths, kinds, a, b, host_out);
+        return FMHIP_OK;
+    } catch (const Error& e) { g_last_error = e.what(); return e.code; }
+    catch (const std::bad_alloc&) { g_last_error = "host allocation failed"; return FMHIP_ERR_OUT_OF_MEMORY; }
+}
+int fmhip_increments_generate_device(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset,
+                                     const int32_t* kinds, const double* a, const double* b, fmhip_vec* out) {
+    FRONT(increments_generate_device(seed, n_steps, n_factors, n_paths, path_offset, kinds, a, b, out));
+    return guarded([&] { Engine::get().mt_increments_generate(seed, n_steps, n_factors, n_paths, path_offset, kinds, a, b, out); });
+}
 double fmhip_inverse_normal_cdf(double p) { return fm::inverse_normal_cdf(p); }
 
 int fmhip_pool_clean(void) { FRONT(pool(0)); TE_ALL(mine, fmhip_pool_clean()); return guarded([&] { Engine::get().pool_clean(); }); }

@@ -1,4 +1,5 @@
-// mt_bm_kernel.h — host-callable launchers of the Mersenne-Twister Brownian-increment kernels in mt_bm_kernel.hip.
+// mt_bm_kernel.h — host-callable launchers of the Mersenne-Twister increment kernels in mt_bm_kernel.hip: Brownian increments (DESIGN.md
+// §4.9) and increments with a law per stream through an inverse CDF (§4.10).
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -23,8 +24,25 @@ struct DevMtBmArgs {
     uint32_t        n_segments;     // workgroups
 };
 
+// One law of fm_mt_icdf_kernel: host/increments.hpp's IncrementLaws::Law, byte for byte (the engine uploads that array).
+struct DevMtLaw {
+    int32_t  kind;                  // 0 normal: inverse normal CDF(u) · a;  1 uniform: a + (b − a) · u;  2 Poisson: min { k : table[k] >= u }
+    uint32_t table_len;             // Poisson: entries of the law's CDF table, the last of them 1.0
+    uint32_t table_offset;          // Poisson: its first entry in `tables`
+    uint32_t reserved;
+    double   a, b;
+};
+
+struct DevMtIcdfArgs {
+    DevMtBmArgs     g;              // the generation pass as above; sqrt_dt is not read
+    const DevMtLaw* laws;           // [n_streams]
+    const double*   tables;         // the Poisson CDF tables the laws point into, built on the host (host/increments.hpp)
+    uint32_t        linear_max;     // a table of at most this many entries is searched from 0 upwards, a longer one by bisection
+};
+
 // out[0 … 624) = the state `distance` words behind in[0 … 624) (one workgroup); distance < 2^44
 hipError_t launch_mt_jump(const uint32_t* in, uint64_t distance, uint32_t* out, hipStream_t st);
 hipError_t launch_mt_bm(const DevMtBmArgs& a, hipStream_t st);
+hipError_t launch_mt_icdf(const DevMtIcdfArgs& a, hipStream_t st);
 
 } // namespace fm

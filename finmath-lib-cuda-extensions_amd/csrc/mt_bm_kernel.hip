@@ -19,6 +19,10 @@
 // + − × / only and equals (float) of the host's double exactly; a tail draw goes through log, where the device library and the host's
 // libm may differ by an fp64 ulp, which survives the rounding to fp32 with a probability of order 2^-29: equal, except that one in
 // some 10^8 may differ by one fp32 ulp.
+//
+// fm_mt_icdf_kernel is the same pass with another last step: a law per stream — normal, uniform or Poisson — from a
+// descriptor array (host/increments.hpp).  Poisson and uniform draws equal the host's exactly (a Poisson draw only compares the uniform
+// with the host's fp64 table); normal draws are under the contract above.  Tests: tests/test_gpu_increments.py.
 #include <hip/hip_runtime.h>
 #define FM_MT_JUMP_TABLE_QUALIFIER __device__
 #include "fm_mt_jump_table.hpp"
@@ -166,9 +170,43 @@ __device__ __forceinline__ void mt_flush_tile(const DevMtBmArgs& A, const float*
     }
 }
 
-__global__ void __launch_bounds__(MT_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) fm_mt_bm_kernel(const DevMtBmArgs A)
+// The last step of a draw, u → the increment narrowed to fp32, for stream s.  Brownian: AS 241 times sqrt(dt[step]).
+struct MtBrownianDraw {
+    const double* sqrt_dt;
+    __device__ __forceinline__ float operator()(double u, uint32_t s) const { return (float)(mt_inverse_normal(u) * sqrt_dt[s]); }
+};
+
+// A law per stream (host/increments.hpp: IncrementLaws::draw, operation for operation).  Lane t serves stream (e0 + t) mod S, so the
+// law differs from lane to lane.  A Poisson draw only compares u with the doubles of the host's table, which lie in global memory: a
+// call's tables are a few hundred bytes to 512 KB (more than LDS holds), every wave reads the same few lines, and they stay in the
+// vector cache; a short table is walked from 0 (most of the mass of a small mean sits in the first entries), a long one bisected.
+struct MtIcdfDraw {
+    const DevMtLaw* laws;
+    const double* tables;
+    uint32_t linear_max;
+    __device__ __forceinline__ float operator()(double u, uint32_t s) const
+    {
+        const DevMtLaw* L = laws + s;
+        const int32_t kind = L->kind;
+        if (kind == 0) return (float)(mt_inverse_normal(u) * L->a);
+        if (kind == 1) { const double a = L->a; const double width = L->b - a; const double scaled = width * u; return (float)(a + scaled); }
+        const uint32_t len = L->table_len;
+        const double* F = tables + L->table_offset;
+        uint32_t lo = 0;
+        if (len <= linear_max) {
+            while (lo + 1 < len && F[lo] < u) ++lo;                   // F[len − 1] = 1 > u is never read
+        } else {
+            uint32_t hi = len - 1;                                    // F[hi] >= u throughout
+            while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (F[mid] < u) lo = mid + 1; else hi = mid; }
+        }
+        return (float)lo;
+    }
+};
+
+// The generation pass of one workgroup (header comment), shared by both kernels; `draw` is the last step.
+template <class Draw>
+__device__ __forceinline__ void mt_generate(const DevMtBmArgs& A, uint32_t* x, const Draw& draw)
 {
-    __shared__ __attribute__((aligned(16))) uint32_t x[MT_LDS_WORDS];
     const uint32_t t = threadIdx.x;
     const uint64_t k = blockIdx.x;
     const uint32_t S = A.n_streams;
@@ -215,7 +253,7 @@ __global__ void __launch_bounds__(MT_BLOCK) __attribute__((amdgpu_waves_per_eu(4
             const uint2 w = *reinterpret_cast<const uint2*>(&x[(cons + 2 * t) & (MT_RING - 1)]);
             const uint64_t bits = ((uint64_t)(mt_temper(w.x) >> 6) << 26) | (uint64_t)(mt_temper(w.y) >> 6);
             const double u = (double)bits * 0x1.0p-52;
-            const float z = (float)(mt_inverse_normal(u) * A.sqrt_dt[s]);
+            const float z = draw(u, s);
             if (TP) tiles[par * FM_MT_TILE_FLOATS + off] = z;
             else __builtin_nontemporal_store(z, A.slab + (size_t)s * A.stride_floats + p);
         }
@@ -237,18 +275,44 @@ __global__ void __launch_bounds__(MT_BLOCK) __attribute__((amdgpu_waves_per_eu(4
     }
 }
 
+__global__ void __launch_bounds__(MT_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) fm_mt_bm_kernel(const DevMtBmArgs A)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t x[MT_LDS_WORDS];
+    mt_generate(A, x, MtBrownianDraw{ A.sqrt_dt });
+}
+
+__global__ void __launch_bounds__(MT_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) fm_mt_icdf_kernel(const DevMtIcdfArgs A)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t x[MT_LDS_WORDS];
+    mt_generate(A.g, x, MtIcdfDraw{ A.laws, A.tables, A.linear_max });
+}
+
 hipError_t launch_mt_jump(const uint32_t* in, uint64_t distance, uint32_t* out, hipStream_t st)
 {
     hipLaunchKernelGGL(fm_mt_jump_kernel, dim3(1), dim3(MT_BLOCK), 0, st, in, distance, out);
     return hipGetLastError();
 }
 
+static bool mt_shape_ok(const DevMtBmArgs& a)
+{
+    if (a.n_streams == 0 || a.segment_log2 < (uint32_t)FM_MT_MIN_SEGMENT_LOG2 || a.segment_log2 > (uint32_t)FM_MT_MAX_SEGMENT_LOG2) return false;
+    if (a.tile_paths && ((a.tile_paths & 3u) || (uint64_t)a.tile_paths * a.n_streams > (uint64_t)FM_MT_TILE_FLOATS || (uint64_t)a.tile_paths * a.n_streams < (uint64_t)MT_BLOCK)) return false;
+    return true;
+}
+
 hipError_t launch_mt_bm(const DevMtBmArgs& a, hipStream_t st)
 {
     if (a.n_paths <= 0 || a.n_segments == 0) return hipSuccess;
-    if (a.n_streams == 0 || a.segment_log2 < (uint32_t)FM_MT_MIN_SEGMENT_LOG2 || a.segment_log2 > (uint32_t)FM_MT_MAX_SEGMENT_LOG2) return hipErrorInvalidValue;
-    if (a.tile_paths && ((a.tile_paths & 3u) || (uint64_t)a.tile_paths * a.n_streams > (uint64_t)FM_MT_TILE_FLOATS || (uint64_t)a.tile_paths * a.n_streams < (uint64_t)MT_BLOCK)) return hipErrorInvalidValue;
+    if (!mt_shape_ok(a)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(fm_mt_bm_kernel, dim3(a.n_segments), dim3(MT_BLOCK), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_mt_icdf(const DevMtIcdfArgs& a, hipStream_t st)
+{
+    if (a.g.n_paths <= 0 || a.g.n_segments == 0) return hipSuccess;
+    if (!mt_shape_ok(a.g) || !a.laws || !a.tables) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fm_mt_icdf_kernel, dim3(a.g.n_segments), dim3(MT_BLOCK), 0, st, a);
     return hipGetLastError();
 }
 

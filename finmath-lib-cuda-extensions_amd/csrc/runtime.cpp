@@ -4221,3 +4221,4 @@ void Engine::profile_read(double* ms_total, int64_t* n) {
 #include "order_stats_engine.hpp"      // Engine::os_*: the order-statistics passes
 #include "cross_moments_engine.hpp"    // Engine::xmom_pass: the cross moments of a regression in one launch
 #include "mersenne_device_engine.hpp"  // Engine::mt_bm_generate: finmath's Mersenne-Twister increments, generated on the device
+#include "increments_device_engine.hpp" // Engine::mt_increments_generate: a law per (step, factor) through an inverse CDF, same stream

@@ -402,6 +402,9 @@ public:
                      const double* dt, fmhip_vec* out);
     // finmath-lib's Mersenne-Twister increments to the bits of host/mersenne.hpp, generated on the device (mersenne_device_engine.hpp)
     void mt_bm_generate(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, fmhip_vec* out);
+    // increments with a law per (step, factor) from the same stream, to the bits of host/increments.hpp (increments_device_engine.hpp)
+    void mt_increments_generate(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset,
+                                const int32_t* kinds, const double* a, const double* b, fmhip_vec* out);
 
     // pool
     void pool_clean();
@@ -697,5 +700,9 @@ struct HostTimer {
 void xmom_check_counts(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, const double* sums_out);
 // what can be said about the arguments of fmhip_bm_generate_mersenne_device without a device (mersenne_device_engine.hpp)
 void mt_bm_check(int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, const fmhip_vec* out);
+// the same for fmhip_increments_generate_device and, with a block at offset 0, fmhip_increments_host (increments_device_engine.hpp;
+// the rules are fmhost::checkedIncrementLaws's, host/increments.hpp): throws FMHIP_ERR_INVALID_ARGUMENT
+void mt_increments_check_only(int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const int32_t* kinds, const double* a, const double* b, const fmhip_vec* out);
+void increments_host(int32_t seed, int n_steps, int n_factors, int64_t n_paths, const int32_t* kinds, const double* a, const double* b, double* host_out);
 
 } // namespace fm

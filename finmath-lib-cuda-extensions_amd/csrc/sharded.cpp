@@ -908,6 +908,27 @@ int bm_generate_mersenne_device(int32_t seed, int n_steps, int n_factors, int64_
     });
 }
 
+// Increments with a law per (step, factor) on a device list: as above, every shard its own block of paths of the one stream; the laws are
+// checked here once, before anything is posted, and travel to the shards by value
+int increments_generate_device(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const int32_t* kinds, const double* a, const double* b, fmhip_vec* out) {
+    return fronted([&](Shards& s) {
+        fm::mt_increments_check_only(n_steps, n_factors, n_paths, path_offset, kinds, a, b, out);
+        const size_t streams = (size_t)n_steps * n_factors;
+        auto ids = std::make_shared<std::vector<fmhip_vec>>(streams);
+        for (size_t k = 0; k < streams; ++k) (*ids)[k] = s.fresh(n_paths);
+        auto law_kinds = std::make_shared<std::vector<int32_t>>(kinds, kinds + streams);
+        auto law_a = std::make_shared<std::vector<double>>(a, a + streams);
+        auto law_b = std::make_shared<std::vector<double>>(b, b + streams);
+        s.post([=](Worker& w) {
+            int64_t off, cnt; shard_range(n_paths, w.shards, w.shard, &off, &cnt);
+            std::vector<fmhip_vec> got(ids->size(), 0);
+            if (w.ok(fmhip_increments_generate_device(seed, n_steps, n_factors, cnt, path_offset + off, law_kinds->data(), law_a->data(), law_b->data(), got.data())))
+                for (size_t k = 0; k < got.size(); ++k) w.bind((*ids)[k], got[k]);
+        });
+        std::memcpy(out, ids->data(), streams * sizeof(fmhip_vec));
+    });
+}
+
 int pool(int what) { return fronted([&](Shards& s) { s.post([=](Worker& w) { w.ok(what == 0 ? fmhip_pool_clean() : fmhip_pool_purge()); }); s.wait(); }); }
 int pool_stats(fmhip_pool_stats_t* out) {
     return fronted([&](Shards& s) {

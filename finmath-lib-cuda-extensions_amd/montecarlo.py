@@ -6,6 +6,8 @@ a RandomVariableFactory by injection (LIBORMarketModelCalibrationATMTest.java:35
     black_scholes_call_mc   MonteCarloBlackScholesModelTest.java:62-85,125-157 (Euler scheme on the log state,
                             numeraire exp(r t), European call)
     heston_call_mc          BASELINE.json configs[2]: Euler full-truncation Heston driven by BrownianMotionHip
+    merton_call_mc          Merton's jump-diffusion driven by IndependentIncrementsFromICDF (increments.py: Brownian increment, normal
+                            jump size, Poisson jump count), with merton_call_analytic, Merton's series, as its closed-form check
     bermudan_option_mc      Longstaff–Schwartz backward induction over MonteCarloConditionalExpectationRegression (regression.py):
                             what finmath-lib's BermudanOption does with its conditional-expectation estimator
 """
@@ -39,6 +41,46 @@ def black_scholes_call_analytic(initial_value, risk_free_rate, volatility, matur
     d2 = d1 - volatility * sqrt(maturity)
     cdf = lambda z: 0.5 * (1.0 + erf(z / sqrt(2.0)))
     return initial_value * cdf(d1) - strike * exp(-risk_free_rate * maturity) * cdf(d2)
+
+
+def merton_call_mc(increments, initial_value, risk_free_rate, volatility, jump_intensity, jump_size_mean, jump_size_stddev, maturity, strike):
+    """Value of a European call under Merton's jump-diffusion by Monte-Carlo, log-Euler scheme: per time step
+    X += (r - σ²/2 - λ(e^{μ+δ²/2} - 1)) Δt + σ ΔW + μ ΔN + δ sqrt(ΔN) Z,  S = exp(X),
+    with ΔW = increments(i, 0) (normal, sqrt(Δt)), Z = increments(i, 1) (standard normal), ΔN = increments(i, 2) (Poisson, mean λ Δt):
+    given ΔN jumps their log sizes sum to a normal with mean μ ΔN and variance δ² ΔN, so one normal draw serves any jump count.
+    Written in RandomVariable methods only.  `maturity` must be a point of the time discretisation."""
+    td = increments.getTimeDiscretization()
+    x = increments.getRandomVariableForConstant(math.log(initial_value))
+    compensator = jump_intensity * (math.exp(jump_size_mean + 0.5 * jump_size_stddev * jump_size_stddev) - 1.0)
+    drift = risk_free_rate - 0.5 * volatility * volatility - compensator
+    t, i = td.getTime(0), 0
+    while t < maturity - 1e-12:
+        dt = td.getTimeStep(i)
+        dw, z, dn = increments.getIncrement(i, 0), increments.getIncrement(i, 1), increments.getIncrement(i, 2)
+        x = x.add(drift * dt).addProduct(dw, volatility).addProduct(dn, jump_size_mean).addProduct(dn.sqrt().mult(z), jump_size_stddev)
+        i += 1
+        t = td.getTime(i)
+    payoff = x.exp().sub(strike).floor(0.0)
+    value = payoff.div(math.exp(risk_free_rate * maturity))
+    return value.getAverage(), value
+
+
+def merton_call_analytic(initial_value, risk_free_rate, volatility, jump_intensity, jump_size_mean, jump_size_stddev, maturity, strike):
+    """Merton (1976): the call is a Poisson mixture of Black–Scholes prices.  With m = e^{μ+δ²/2}, λ' = λ m: Σ_n e^{-λ'T} (λ'T)^n / n! ·
+    BS(S, K, r_n, σ_n, T),  σ_n² = σ² + n δ² / T,  r_n = r - λ(m - 1) + n (μ + δ²/2) / T; summed until the weight is below 1e-16
+    past the mode."""
+    m = math.exp(jump_size_mean + 0.5 * jump_size_stddev * jump_size_stddev)
+    lam = jump_intensity * m * maturity
+    weight, total, n = math.exp(-lam), 0.0, 0
+    while True:
+        sigma_n = math.sqrt(volatility * volatility + n * jump_size_stddev * jump_size_stddev / maturity)
+        r_n = risk_free_rate - jump_intensity * (m - 1.0) + n * (jump_size_mean + 0.5 * jump_size_stddev * jump_size_stddev) / maturity
+        # BS with rate r_n discounts by e^{-r_n T}: the value under the mixture is that price as it stands (Merton's formula)
+        total += weight * black_scholes_call_analytic(initial_value, r_n, sigma_n, maturity, strike)
+        n += 1
+        weight *= lam / n
+        if n > lam and weight < 1e-16:
+            return total
 
 
 def heston_call_mc(brownian_motion, initial_value, risk_free_rate, v0, kappa, theta, xi, rho, maturity, strike):

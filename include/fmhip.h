@@ -460,6 +460,27 @@ int fmhip_bm_generate_mersenne(int32_t seed, int n_steps, int n_factors, int64_t
  * by one fp32 ulp.  Arguments are checked on the host before anything is flushed or launched (negative time steps are an error
  * here).  A build without the kernel returns FMHIP_ERR_UNSUPPORTED; it never falls back to the host generator. */
 int fmhip_bm_generate_mersenne_device(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, fmhip_vec* out);
+/* Independent increments with a LAW PER (TIME STEP, FACTOR) from the same MT19937 stream: one nextDouble() u per increment, path-major
+ * (path, step, factor), pushed through an inverse CDF — what finmath-lib's IndependentIncrementsFromICDF, JumpProcessIncrements and the
+ * three-factor layout of MonteCarloMertonModel draw [unverified: finmath-lib is not vendored; restated from its documentation].
+ * kinds, a, b: [n_steps * n_factors], index step * n_factors + factor.
+ *   FMHIP_LAW_NORMAL   inverseNormalCdf(u) * a      a >= 0 (sqrt(dt) for a Brownian factor, 1 for a jump size); b ignored
+ *   FMHIP_LAW_UNIFORM  a + (b - a) * u              a <= b, finite
+ *   FMHIP_LAW_POISSON  min { k >= 0 : F[k] >= u }   a = the mean (lambda * dt), 0 <= a <= 128; b ignored; F is a table built on the
+ *                      host in fp64, once per distinct mean: F[0] = p = exp(-a), p = p * a / k, F[k] = F[k-1] + p, last entry 1.0
+ * fmhip_increments_host is the definition (doubles, layout as fmhip_mersenne_increments, no device).  With every law NORMAL and
+ * a = sqrt(dt[step]) it returns fmhip_mersenne_increments' doubles bit for bit.
+ * fmhip_increments_generate_device generates paths path_offset ... path_offset + n_paths of the same numbers on the device (narrowed
+ * to fp32 once): Poisson and uniform draws EQUAL the definition's (the device only compares u with the host's table), normal draws
+ * under the contract of fmhip_bm_generate_mersenne_device.  Both check their arguments with one function, before anything is flushed
+ * or launched: an unknown kind, a NaN or negative scale or mean, a mean above 128, a > b or non-finite bounds, more than 2^24 laws, words
+ * beyond 2^44, more than 2^16 table entries over all distinct means -> FMHIP_ERR_INVALID_ARGUMENT.  A build without the kernel returns
+ * FMHIP_ERR_UNSUPPORTED; it never falls back to the host definition. */
+enum { FMHIP_LAW_NORMAL = 0, FMHIP_LAW_UNIFORM = 1, FMHIP_LAW_POISSON = 2 };
+int fmhip_increments_host(int32_t seed, int n_steps, int n_factors, int64_t n_paths,
+                          const int32_t* kinds, const double* a, const double* b, double* host_out);
+int fmhip_increments_generate_device(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset,
+                                     const int32_t* kinds, const double* a, const double* b, fmhip_vec* out);
 /* Inverse of the standard normal CDF (Wichura AS 241 / PPND16), exposed for tests. Returns the value (no status). */
 double fmhip_inverse_normal_cdf(double p);
 

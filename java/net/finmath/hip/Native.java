@@ -114,6 +114,8 @@ final class Native {
 	static native int mersenneIncrements(int seed, int nSteps, int nFactors, long nPaths, double[] dt, double[] hostOut);
 	static native int bmGenerateMersenne(int seed, int nSteps, int nFactors, long nPaths, double[] dt, long[] outHandles);
 	static native int bmGenerateMersenneDevice(int seed, int nSteps, int nFactors, long nPaths, long pathOffset, double[] dt, long[] outHandles);
+	static native int incrementsHost(int seed, int nSteps, int nFactors, long nPaths, int[] kinds, double[] a, double[] b, double[] hostOut);
+	static native int incrementsGenerateDevice(int seed, int nSteps, int nFactors, long nPaths, long pathOffset, int[] kinds, double[] a, double[] b, long[] outHandles);
 	static native double inverseNormalCdf(double p);
 
 	// ---- pool (replace DeviceMemoryPool.clean / purge / getDeviceFreeMemPercentage, RandomVariableCuda.java:393-449)

@@ -338,6 +338,18 @@ FMJ(jint, bmGenerateMersenneDevice)(JNIEnv* env, jclass, jint seed, jint nSteps,
     if (nSteps <= 0 || nFactors <= 0 || !po.p || !pd.p || (int64_t)po.length() < (int64_t)nSteps * nFactors || pd.length() < nSteps) return FMHIP_ERR_INVALID_ARGUMENT;
     return fmhip_bm_generate_mersenne_device(seed, nSteps, nFactors, nPaths, pathOffset, pd.p, (fmhip_vec*)po.p);
 }
+FMJ(jint, incrementsHost)(JNIEnv* env, jclass, jint seed, jint nSteps, jint nFactors, jlong nPaths, jintArray kinds, jdoubleArray a, jdoubleArray b, jdoubleArray hostOut) {
+    Pin<jint> pk(env, kinds, JNI_ABORT); Pin<jdouble> pa(env, a, JNI_ABORT), pb(env, b, JNI_ABORT), po(env, hostOut);
+    const int64_t laws = (int64_t)nSteps * nFactors;
+    if (nSteps <= 0 || nFactors <= 0 || nPaths < 0 || !pk.p || !pa.p || !pb.p || !po.p || pk.length() < laws || pa.length() < laws || pb.length() < laws || (int64_t)po.length() < laws * nPaths) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_increments_host(seed, nSteps, nFactors, nPaths, (const int32_t*)pk.p, pa.p, pb.p, po.p);
+}
+FMJ(jint, incrementsGenerateDevice)(JNIEnv* env, jclass, jint seed, jint nSteps, jint nFactors, jlong nPaths, jlong pathOffset, jintArray kinds, jdoubleArray a, jdoubleArray b, jlongArray outHandles) {
+    Pin<jint> pk(env, kinds, JNI_ABORT); Pin<jdouble> pa(env, a, JNI_ABORT), pb(env, b, JNI_ABORT); Pin<jlong> po(env, outHandles);
+    const int64_t laws = (int64_t)nSteps * nFactors;
+    if (nSteps <= 0 || nFactors <= 0 || !pk.p || !pa.p || !pb.p || !po.p || pk.length() < laws || pa.length() < laws || pb.length() < laws || (int64_t)po.length() < laws) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_increments_generate_device(seed, nSteps, nFactors, nPaths, pathOffset, (const int32_t*)pk.p, pa.p, pb.p, (fmhip_vec*)po.p);
+}
 FMJ(jdouble, inverseNormalCdf)(JNIEnv*, jclass, jdouble p) { return fmhip_inverse_normal_cdf(p); }
 
 // ---------------------------------------------------------------- pool
