@@ -953,13 +953,13 @@ int fmhip_bm_generate_mersenne(int32_t seed, int n_steps, int n_factors, int64_t
         catch (...) { for (size_t k = 0; k < count; ++k) if (out[k]) { Engine::get().release(out[k]); out[k] = 0; } throw; }
     });
 }
-// the same numbers generated on the device (mersenne_device_engine.hpp): arguments are checked before anything is flushed or launched
+// the same numbers generated on the device (mt_generate_engine.hpp): arguments are checked before anything is flushed or launched
 int fmhip_bm_generate_mersenne_device(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, fmhip_vec* out) {
     FRONT(bm_generate_mersenne_device(seed, n_steps, n_factors, n_paths, path_offset, dt, out));
     return guarded([&] { Engine::get().mt_bm_generate(seed, n_steps, n_factors, n_paths, path_offset, dt, out); });
 }
 // Increments with a law per (step, factor) from the same MT19937 stream (host/increments.hpp): the definition on the host, and the same
-// numbers generated on the device (increments_device_engine.hpp).  One function checks the arguments of both.
+// numbers generated on the device (mt_generate_engine.hpp).  One function checks the arguments of both.
 int fmhip_increments_host(int32_t seed, int n_steps, int n_factors, int64_t n_paths, const int32_t* kinds, const double* a, const double* b, double* host_out) {
     try {
         fm::increments_host(seed, n_steps, n_factors, n_paths, kinds, a, b, host_out);

@@ -7,6 +7,7 @@
 namespace fm {
 
 constexpr int FM_MT_STATE_WORDS = 624;
+constexpr int FM_MT_BLOCK = 256;                   // threads of a workgroup
 constexpr int FM_MT_TILE_FLOATS = 3200;            // floats of one of the two LDS store tiles: 16 paths of 200 step x factor vectors
 constexpr int FM_MT_MIN_SEGMENT_LOG2 = 1;          // segments are an even number of words: a draw is a pair of words
 constexpr int FM_MT_MAX_SEGMENT_LOG2 = 43;
@@ -39,6 +40,20 @@ struct DevMtIcdfArgs {
     const double*   tables;         // the Poisson CDF tables the laws point into, built on the host (host/increments.hpp)
     uint32_t        linear_max;     // a table of at most this many entries is searched from 0 upwards, a longer one by bisection
 };
+
+// What the generating kernels rely on in their arguments and do not check themselves; both launchers refuse anything else, and so do the
+// stand-ins of the null device (tests/nulldev/null_mt.cpp), which is how the engine's arguments are pinned without a GPU.
+// `icdf`: the arguments are fm_mt_icdf_kernel's (a = icdf->g).
+inline bool mt_shape_ok(const DevMtBmArgs& a, const DevMtIcdfArgs* icdf = nullptr)
+{
+    if (!a.slab || !a.state || ((uintptr_t)a.state & 3u) || a.n_streams == 0 || a.stride_floats < a.n_paths || (a.stride_floats & 63)) return false;
+    if (a.segment_log2 < (uint32_t)FM_MT_MIN_SEGMENT_LOG2 || a.segment_log2 > (uint32_t)FM_MT_MAX_SEGMENT_LOG2) return false;
+    const uint64_t words = 2ull * a.n_streams * (uint64_t)a.n_paths;
+    if (a.n_segments != (uint32_t)((words + (1ull << a.segment_log2) - 1) >> a.segment_log2)) return false;
+    if (a.tile_paths && ((a.tile_paths & 3u) || (uint64_t)a.tile_paths * a.n_streams > (uint64_t)FM_MT_TILE_FLOATS || (uint64_t)a.tile_paths * a.n_streams < (uint64_t)FM_MT_BLOCK)) return false;
+    if (!icdf) return a.sqrt_dt != nullptr;
+    return !a.sqrt_dt && icdf->laws && icdf->tables && !((uintptr_t)icdf->laws & 15u) && !((uintptr_t)icdf->tables & 7u);
+}
 
 // out[0 … 624) = the state `distance` words behind in[0 … 624) (one workgroup); distance < 2^44
 hipError_t launch_mt_jump(const uint32_t* in, uint64_t distance, uint32_t* out, hipStream_t st);

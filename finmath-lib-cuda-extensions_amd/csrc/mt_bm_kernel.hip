@@ -32,7 +32,7 @@ namespace fm {
 
 typedef float mt_f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int MT_BLOCK = 256;
+constexpr int MT_BLOCK = FM_MT_BLOCK;
 constexpr int MT_N = FM_MT_STATE_WORDS, MT_LAG = 227;                 // x[m] = x[m − 227] ^ twist(x[m − 624], x[m − 623])
 constexpr int MT_DEGREE = 19937;
 constexpr int MT_RING = 2048;                                         // body: words of the ring (624 of history + 512 new fit twice)
@@ -293,13 +293,6 @@ hipError_t launch_mt_jump(const uint32_t* in, uint64_t distance, uint32_t* out, 
     return hipGetLastError();
 }
 
-static bool mt_shape_ok(const DevMtBmArgs& a)
-{
-    if (a.n_streams == 0 || a.segment_log2 < (uint32_t)FM_MT_MIN_SEGMENT_LOG2 || a.segment_log2 > (uint32_t)FM_MT_MAX_SEGMENT_LOG2) return false;
-    if (a.tile_paths && ((a.tile_paths & 3u) || (uint64_t)a.tile_paths * a.n_streams > (uint64_t)FM_MT_TILE_FLOATS || (uint64_t)a.tile_paths * a.n_streams < (uint64_t)MT_BLOCK)) return false;
-    return true;
-}
-
 hipError_t launch_mt_bm(const DevMtBmArgs& a, hipStream_t st)
 {
     if (a.n_paths <= 0 || a.n_segments == 0) return hipSuccess;
@@ -311,7 +304,7 @@ hipError_t launch_mt_bm(const DevMtBmArgs& a, hipStream_t st)
 hipError_t launch_mt_icdf(const DevMtIcdfArgs& a, hipStream_t st)
 {
     if (a.g.n_paths <= 0 || a.g.n_segments == 0) return hipSuccess;
-    if (!mt_shape_ok(a.g) || !a.laws || !a.tables) return hipErrorInvalidValue;
+    if (!mt_shape_ok(a.g, &a)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(fm_mt_icdf_kernel, dim3(a.g.n_segments), dim3(MT_BLOCK), 0, st, a);
     return hipGetLastError();
 }

@@ -24,7 +24,7 @@
 namespace fm {
 
 // The three launchers are WEAK references here: a host-only build of the engine whose stand-in for kernels.hip does not know these kernels
-// (tests/nulldev/null_hip.cpp; tests/nulldev_order/null_os.cpp adds them) still links.  Calling one that is missing is an error — there is
+// (tests/nulldev/null_hip.cpp; tests/nulldev/null_os.cpp adds them) still links.  Calling one that is missing is an error — there is
 // no fallback: the mirrors' host sort is a caller's choice (FMHIP_DEVICE_ORDER_STATS=0), never the engine's.
 hipError_t launch_os_hist(const DevSelectArgs& a, const uint64_t* vecs, const uint32_t* slots, uint32_t batch, hipStream_t st) __attribute__((weak));
 hipError_t launch_os_sum(const DevRankSumArgs& a, const uint64_t* vecs, const uint32_t* keys, uint32_t batch, hipStream_t st) __attribute__((weak));

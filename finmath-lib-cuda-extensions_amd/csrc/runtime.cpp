@@ -4070,55 +4070,22 @@ void Engine::program_run(fmhip_program h, int batch, const fmhip_vec* inputs, fm
 
 // ---------------------------------------------------------------- brownian increments
 
-void Engine::bm_generate(int64_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset,
-                         const double* dt, fmhip_vec* out) {
-    require_init(); check_n(n_paths);
-    if (n_steps <= 0 || n_factors <= 0 || !dt || !out || path_offset < 0)
-        throw Error(FMHIP_ERR_INVALID_ARGUMENT, "bad Brownian motion description");
-    if (n_factors > 32768) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "more than 32768 factors");      // one launch keeps whole steps together (grid.y)
-    const int64_t n_streams = (int64_t)n_steps * n_factors;
-    const int64_t stride = (n_paths + 63) & ~int64_t(63);              // every vector 256-B aligned
-    Buffer* slab = new_buffer(std::max<int64_t>(stride, 64) * n_streams);
+// The vectors of one generation share ONE block of the pool: n_streams vectors `*stride` floats apart (every vector 256-B aligned), which
+// `fill(first vector)` writes; if it throws, the block goes back to the pool.  The slab itself has no handle: its views keep it (slab_views).
+template <class Fill>
+Buffer* Engine::slab_generate(int64_t n_paths, int64_t n_streams, int64_t* stride, Fill fill) {
+    *stride = (n_paths + 63) & ~int64_t(63);
+    Buffer* slab = new_buffer(std::max<int64_t>(*stride, 64) * n_streams);
     slab->refs = 0;
-    void* sq_dev = nullptr; size_t sq_cap = 0;
-    try {
-        float* st = (float*)ensure_stage((size_t)n_streams * 4);       // one entry per stream: the kernel reads it with a scalar load, no division
-        for (int i = 0; i < n_steps; ++i) {
-            if (!(dt[i] >= 0.0)) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "negative time step");
-            const float sq = (float)std::sqrt(dt[i]);                  // (float)Math.sqrt(timeStep), BrownianMotionCudaWithRandomVariableCuda.java:170
-            for (int f = 0; f < n_factors; ++f) st[(size_t)i * n_factors + f] = sq;
-        }
-        sq_dev = pool_.alloc((size_t)n_streams * 4, &sq_cap);
-        hip_check(hipMemcpyAsync(sq_dev, st, (size_t)n_streams * 4, hipMemcpyHostToDevice, stream_), "sqrt_dt H2D");
-        hip_check(hipStreamSynchronize(stream_), "sync");
-        if (n_paths > 0) {
-            const int64_t chunk = 32768 - (32768 % n_factors);         // grid.y limit; keep whole steps together
-            for (int64_t s0 = 0; s0 < n_streams; s0 += chunk) {
-                const int64_t ns = std::min(chunk, n_streams - s0);
-                DevBmArgs a{};
-                a.slab = slab->ptr + s0 * stride;
-                a.sqrt_dt = (const float*)sq_dev + s0;
-                a.stride_floats = stride; a.n_paths = n_paths; a.path_offset = path_offset;
-                a.key0 = (uint32_t)(uint64_t)seed; a.key1 = (uint32_t)((uint64_t)seed >> 32);
-                a.n_factors = (uint32_t)n_factors; a.stream0 = (uint32_t)s0;
-                hipEvent_t ev0 = nullptr, ev1 = nullptr;            // fmhip_profile_enable: the generator's launches are bracketed like program launches
-                if (profiling_) { hip_check(hipEventCreate(&ev0), "hipEventCreate"); hip_check(hipEventCreate(&ev1), "hipEventCreate"); hip_check(hipEventRecord(ev0, stream_), "hipEventRecord"); }
-                hip_check(launch_bm(a, (uint32_t)ns, stream_), "launch fm_bm_kernel");
-                if (profiling_) { hip_check(hipEventRecord(ev1, stream_), "hipEventRecord"); profile_events_.push_back({ ev0, ev1 });
-                                  profile_tags_.push_back({ 0, 0, (int)ns, 0, 1, 3, n_paths }); }
-                algorithmic_bytes_ += 4 * n_paths * ns;
-                bytes_written_ += 4 * n_paths * ns;
-                n_launches_++;
-            }
-        }
-    } catch (...) {
-        if (sq_dev) pool_.release(sq_dev, sq_cap);
-        slab->refs = 1; buffer_unref(slab);
-        throw;
-    }
-    pool_.release(sq_dev, sq_cap);
+    try { fill(slab->ptr); }
+    catch (...) { slab->refs = 1; buffer_unref(slab); throw; }
+    return slab;
+}
+
+// … and its n_steps · n_factors vectors as views into it, each with its place in the generation
+void Engine::slab_views(Buffer* slab, int64_t stride, int n_steps, int n_factors, int64_t n_paths, fmhip_vec* out) {
     const uint32_t bm_id = next_bm_id_++;
-    for (int64_t s = 0; s < n_streams; ++s) {
+    for (int64_t s = 0; s < (int64_t)n_steps * n_factors; ++s) {
         Buffer* v = new Buffer();
         v->ptr = slab->ptr + s * stride; v->cap = 0; v->refs = 1; v->parent = slab;
         slab->refs++;
@@ -4127,6 +4094,55 @@ void Engine::bm_generate(int64_t seed, int n_steps, int n_factors, int64_t n_pat
         nd->bm_id = bm_id; nd->bm_step = (int32_t)(s / n_factors); nd->bm_steps = n_steps;
         out[s] = nd->id;
     }
+}
+
+void Engine::bm_generate(int64_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset,
+                         const double* dt, fmhip_vec* out) {
+    require_init(); check_n(n_paths);
+    if (n_steps <= 0 || n_factors <= 0 || !dt || !out || path_offset < 0)
+        throw Error(FMHIP_ERR_INVALID_ARGUMENT, "bad Brownian motion description");
+    if (n_factors > 32768) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "more than 32768 factors");      // one launch keeps whole steps together (grid.y)
+    const int64_t n_streams = (int64_t)n_steps * n_factors;
+    int64_t stride = 0;
+    Buffer* slab = slab_generate(n_paths, n_streams, &stride, [&](float* vectors) {
+        void* sq_dev = nullptr; size_t sq_cap = 0;
+        try {
+            float* st = (float*)ensure_stage((size_t)n_streams * 4);       // one entry per stream: the kernel reads it with a scalar load, no division
+            for (int i = 0; i < n_steps; ++i) {
+                if (!(dt[i] >= 0.0)) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "negative time step");
+                const float sq = (float)std::sqrt(dt[i]);                  // (float)Math.sqrt(timeStep), BrownianMotionCudaWithRandomVariableCuda.java:170
+                for (int f = 0; f < n_factors; ++f) st[(size_t)i * n_factors + f] = sq;
+            }
+            sq_dev = pool_.alloc((size_t)n_streams * 4, &sq_cap);
+            hip_check(hipMemcpyAsync(sq_dev, st, (size_t)n_streams * 4, hipMemcpyHostToDevice, stream_), "sqrt_dt H2D");
+            hip_check(hipStreamSynchronize(stream_), "sync");
+            if (n_paths > 0) {
+                const int64_t chunk = 32768 - (32768 % n_factors);         // grid.y limit; keep whole steps together
+                for (int64_t s0 = 0; s0 < n_streams; s0 += chunk) {
+                    const int64_t ns = std::min(chunk, n_streams - s0);
+                    DevBmArgs a{};
+                    a.slab = vectors + s0 * stride;
+                    a.sqrt_dt = (const float*)sq_dev + s0;
+                    a.stride_floats = stride; a.n_paths = n_paths; a.path_offset = path_offset;
+                    a.key0 = (uint32_t)(uint64_t)seed; a.key1 = (uint32_t)((uint64_t)seed >> 32);
+                    a.n_factors = (uint32_t)n_factors; a.stream0 = (uint32_t)s0;
+                    hipEvent_t ev0 = nullptr, ev1 = nullptr;            // fmhip_profile_enable: the generator's launches are bracketed like program launches
+                    if (profiling_) { hip_check(hipEventCreate(&ev0), "hipEventCreate"); hip_check(hipEventCreate(&ev1), "hipEventCreate"); hip_check(hipEventRecord(ev0, stream_), "hipEventRecord"); }
+                    hip_check(launch_bm(a, (uint32_t)ns, stream_), "launch fm_bm_kernel");
+                    if (profiling_) { hip_check(hipEventRecord(ev1, stream_), "hipEventRecord"); profile_events_.push_back({ ev0, ev1 });
+                                      profile_tags_.push_back({ 0, 0, (int)ns, 0, 1, 3, n_paths }); }
+                    algorithmic_bytes_ += 4 * n_paths * ns;
+                    bytes_written_ += 4 * n_paths * ns;
+                    n_launches_++;
+                }
+            }
+        } catch (...) {
+            if (sq_dev) pool_.release(sq_dev, sq_cap);
+            throw;
+        }
+        pool_.release(sq_dev, sq_cap);
+    });
+    slab_views(slab, stride, n_steps, n_factors, n_paths, out);
 }
 
 // ---------------------------------------------------------------- pool entry points
@@ -4220,5 +4236,4 @@ void Engine::profile_read(double* ms_total, int64_t* n) {
 
 #include "order_stats_engine.hpp"      // Engine::os_*: the order-statistics passes
 #include "cross_moments_engine.hpp"    // Engine::xmom_pass: the cross moments of a regression in one launch
-#include "mersenne_device_engine.hpp"  // Engine::mt_bm_generate: finmath's Mersenne-Twister increments, generated on the device
-#include "increments_device_engine.hpp" // Engine::mt_increments_generate: a law per (step, factor) through an inverse CDF, same stream
+#include "mt_generate_engine.hpp"      // Engine::mt_bm_generate, mt_increments_generate: finmath's Mersenne-Twister stream entered on the device

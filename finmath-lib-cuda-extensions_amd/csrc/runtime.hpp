@@ -239,6 +239,8 @@ public:
     EngineMutex() { (void)pad_; }
 };
 
+struct DevMtBmArgs;             // mt_bm_kernel.h
+
 class Engine {
 public:
     static Engine& get();
@@ -400,9 +402,9 @@ public:
     // brownian increments
     void bm_generate(int64_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset,
                      const double* dt, fmhip_vec* out);
-    // finmath-lib's Mersenne-Twister increments to the bits of host/mersenne.hpp, generated on the device (mersenne_device_engine.hpp)
+    // finmath-lib's Mersenne-Twister increments to the bits of host/mersenne.hpp, generated on the device (mt_generate_engine.hpp)
     void mt_bm_generate(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, fmhip_vec* out);
-    // increments with a law per (step, factor) from the same stream, to the bits of host/increments.hpp (increments_device_engine.hpp)
+    // increments with a law per (step, factor) from the same stream, to the bits of host/increments.hpp (mt_generate_engine.hpp)
     void mt_increments_generate(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset,
                                 const int32_t* kinds, const double* a, const double* b, fmhip_vec* out);
 
@@ -478,6 +480,12 @@ private:
     void collect_pending(const fmhip_vec* roots, int n_roots, std::vector<Node*>& graph);      // pending nodes below the roots, in recording order
     Buffer* new_buffer(int64_t n_floats);
     void buffer_unref(Buffer* b);
+    // the generators: the one block that holds the vectors of a generation, and the vectors as views into it (runtime.cpp, at bm_generate)
+    template <class Fill> Buffer* slab_generate(int64_t n_paths, int64_t n_streams, int64_t* stride, Fill fill);
+    void slab_views(Buffer* slab, int64_t stride, int n_steps, int n_factors, int64_t n_paths, fmhip_vec* out);
+    // the generation pass the two Mersenne-Twister generators share (mt_generate_engine.hpp)
+    template <class Stage, class Launch>
+    void mt_generate(DevMtBmArgs a, int32_t seed, int n_steps, int n_factors, int64_t path_offset, size_t front_bytes, const char* upload, Stage stage, Launch launch, fmhip_vec* out);
     void node_unref_int(Node* nd);
     void node_maybe_free(Node* nd);
     void drop_expression(Node* nd);
@@ -698,9 +706,9 @@ struct HostTimer {
 
 // what can be said about the arguments of fmhip_cross_moments without looking at a vector: counts in range, pointers, no 0 among y, a vector among x
 void xmom_check_counts(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, const double* sums_out);
-// what can be said about the arguments of fmhip_bm_generate_mersenne_device without a device (mersenne_device_engine.hpp)
+// what can be said about the arguments of fmhip_bm_generate_mersenne_device without a device (mt_generate_engine.hpp)
 void mt_bm_check(int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, const fmhip_vec* out);
-// the same for fmhip_increments_generate_device and, with a block at offset 0, fmhip_increments_host (increments_device_engine.hpp;
+// the same for fmhip_increments_generate_device and, with a block at offset 0, fmhip_increments_host (mt_generate_engine.hpp;
 // the rules are fmhost::checkedIncrementLaws's, host/increments.hpp): throws FMHIP_ERR_INVALID_ARGUMENT
 void mt_increments_check_only(int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const int32_t* kinds, const double* a, const double* b, const fmhip_vec* out);
 void increments_host(int32_t seed, int n_steps, int n_factors, int64_t n_paths, const int32_t* kinds, const double* a, const double* b, double* host_out);

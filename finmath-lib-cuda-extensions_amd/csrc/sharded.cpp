@@ -870,41 +870,42 @@ int jit_stats(int64_t* compiled, int64_t* failed, int64_t* pending, double* comp
     });
 }
 
+// A generator on a device list: fresh ids for `streams` vectors of n_paths; shard d generates ITS block [off, off + cnt) of every one of
+// them — `one(w, cnt, off, got)` is the single-device entry point at that block, its status returned — and binds what it got
+template <class One>
+static void generate_blocks(Shards& s, int64_t n_paths, size_t streams, fmhip_vec* out, One one) {
+    auto ids = std::make_shared<std::vector<fmhip_vec>>(streams);
+    for (size_t k = 0; k < streams; ++k) (*ids)[k] = s.fresh(n_paths);
+    s.post([=](Worker& w) {
+        int64_t off, cnt; shard_range(n_paths, w.shards, w.shard, &off, &cnt);
+        std::vector<fmhip_vec> got(ids->size(), 0);
+        if (w.ok(one(w, cnt, off, got.data())))
+            for (size_t k = 0; k < got.size(); ++k) w.bind((*ids)[k], got[k]);
+    });
+    std::memcpy(out, ids->data(), streams * sizeof(fmhip_vec));
+}
+
 int bm_generate(int64_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, fmhip_vec* out) {
     return fronted([&](Shards& s) {
         if (n_steps <= 0 || n_factors <= 0 || !dt || !out || path_offset < 0 || n_paths < 0 || n_paths > (int64_t(1) << 31)) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "bad Brownian motion description");
         if (path_offset % 4 != 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "with a device list the path offset of a Brownian motion must be a multiple of four");
         for (int i = 0; i < n_steps; ++i) if (!(dt[i] >= 0.0)) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "negative time step");
-        const size_t streams = (size_t)n_steps * n_factors;
-        auto ids = std::make_shared<std::vector<fmhip_vec>>(streams);
-        for (size_t k = 0; k < streams; ++k) (*ids)[k] = s.fresh(n_paths);
         auto steps = std::make_shared<std::vector<double>>(dt, dt + n_steps);
-        s.post([=](Worker& w) {                                // shard d generates ITS block of every increment: the counter is the global path index
-            int64_t off, cnt; shard_range(n_paths, w.shards, w.shard, &off, &cnt);
-            std::vector<fmhip_vec> got(ids->size(), 0);
-            if (w.ok(fmhip_bm_generate(seed, n_steps, n_factors, cnt, path_offset + off, steps->data(), got.data())))
-                for (size_t k = 0; k < got.size(); ++k) w.bind((*ids)[k], got[k]);
+        generate_blocks(s, n_paths, (size_t)n_steps * n_factors, out, [=](Worker&, int64_t cnt, int64_t off, fmhip_vec* got) {      // the counter is the global path index
+            return fmhip_bm_generate(seed, n_steps, n_factors, cnt, path_offset + off, steps->data(), got);
         });
-        std::memcpy(out, ids->data(), streams * sizeof(fmhip_vec));
     });
 }
 
 // finmath-lib's Mersenne-Twister increments on a device list: every shard enters the ONE stream at its own block of paths (jump-ahead,
-// mersenne_device_engine.hpp) — no host vector, no upload, and no rule about the offset (a draw is not a block of four as Philox's is)
+// mt_generate_engine.hpp) — no host vector, no upload, and no rule about the offset (a draw is not a block of four as Philox's is)
 int bm_generate_mersenne_device(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, fmhip_vec* out) {
     return fronted([&](Shards& s) {
         fm::mt_bm_check(n_steps, n_factors, n_paths, path_offset, dt, out);
-        const size_t streams = (size_t)n_steps * n_factors;
-        auto ids = std::make_shared<std::vector<fmhip_vec>>(streams);
-        for (size_t k = 0; k < streams; ++k) (*ids)[k] = s.fresh(n_paths);
         auto steps = std::make_shared<std::vector<double>>(dt, dt + n_steps);
-        s.post([=](Worker& w) {
-            int64_t off, cnt; shard_range(n_paths, w.shards, w.shard, &off, &cnt);
-            std::vector<fmhip_vec> got(ids->size(), 0);
-            if (w.ok(fmhip_bm_generate_mersenne_device(seed, n_steps, n_factors, cnt, path_offset + off, steps->data(), got.data())))
-                for (size_t k = 0; k < got.size(); ++k) w.bind((*ids)[k], got[k]);
+        generate_blocks(s, n_paths, (size_t)n_steps * n_factors, out, [=](Worker&, int64_t cnt, int64_t off, fmhip_vec* got) {
+            return fmhip_bm_generate_mersenne_device(seed, n_steps, n_factors, cnt, path_offset + off, steps->data(), got);
         });
-        std::memcpy(out, ids->data(), streams * sizeof(fmhip_vec));
     });
 }
 
@@ -914,18 +915,12 @@ int increments_generate_device(int32_t seed, int n_steps, int n_factors, int64_t
     return fronted([&](Shards& s) {
         fm::mt_increments_check_only(n_steps, n_factors, n_paths, path_offset, kinds, a, b, out);
         const size_t streams = (size_t)n_steps * n_factors;
-        auto ids = std::make_shared<std::vector<fmhip_vec>>(streams);
-        for (size_t k = 0; k < streams; ++k) (*ids)[k] = s.fresh(n_paths);
         auto law_kinds = std::make_shared<std::vector<int32_t>>(kinds, kinds + streams);
         auto law_a = std::make_shared<std::vector<double>>(a, a + streams);
         auto law_b = std::make_shared<std::vector<double>>(b, b + streams);
-        s.post([=](Worker& w) {
-            int64_t off, cnt; shard_range(n_paths, w.shards, w.shard, &off, &cnt);
-            std::vector<fmhip_vec> got(ids->size(), 0);
-            if (w.ok(fmhip_increments_generate_device(seed, n_steps, n_factors, cnt, path_offset + off, law_kinds->data(), law_a->data(), law_b->data(), got.data())))
-                for (size_t k = 0; k < got.size(); ++k) w.bind((*ids)[k], got[k]);
+        generate_blocks(s, n_paths, streams, out, [=](Worker&, int64_t cnt, int64_t off, fmhip_vec* got) {
+            return fmhip_increments_generate_device(seed, n_steps, n_factors, cnt, path_offset + off, law_kinds->data(), law_a->data(), law_b->data(), got);
         });
-        std::memcpy(out, ids->data(), streams * sizeof(fmhip_vec));
     });
 }
 

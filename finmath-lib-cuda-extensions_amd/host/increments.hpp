@@ -1,6 +1,6 @@
 // increments.hpp — header-only definition of independent increments with a law per (time step, factor), drawn from finmath-lib's
 // MT19937 stream through an inverse cumulative distribution function: the general case of which the Brownian motion of mersenne.hpp is
-// one.  Shared by libfmhip (csrc/abi.cpp → fmhip_increments_host; csrc/increments_device_engine.hpp → the device pass, which must
+// one.  Shared by libfmhip (csrc/abi.cpp → fmhip_increments_host; csrc/mt_generate_engine.hpp → the device pass, which must
 // reproduce these numbers), by the null-device stand-in of the kernel and by the C++ host mirror (host/independent_increments.hpp).
 //
 // It stands in for finmath-lib's IndependentIncrementsFromICDF (one MersenneTwister.nextDouble() per increment, pushed through an

@@ -1,24 +1,17 @@
 // drive_increments.cpp — drives fmhip_increments_generate_device through the C-ABI on the TEST-ONLY null device under the sanitizers: whole
 // processes and blocks behind a path offset (one engine; FMNULL_DEVICES=N: behind a device list of N shards, every shard its own block;
 // FMNULL_THREAD_ENGINES=1: an engine per caller thread), downloaded and compared with fmhip_increments_host narrowed to fp32 — the stand-in
-// launcher (null_icdf.cpp) generates with the host code from the state, the descriptors and the tables the engine hands it, so what is
+// launcher (null_mt.cpp) generates with the host code from the state, the descriptors and the tables the engine hands it, so what is
 // checked is the engine: seeding, jump distances, tables shared between equal means, the layout of descriptors, tables and slab, the
 // handles; then the errors that are found on the host, with another thread creating and releasing vectors meanwhile.  Twice, with a
 // shutdown and a re-initialisation in between.
 #include <atomic>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <thread>
-#include <vector>
 
-#include "../../include/fmhip.h"
+#include "drive_common.hpp"
 
 namespace fm { extern std::atomic<int> g_null_icdf_tables, g_null_icdf_table_doubles; }
-
-#define OK(x) do { const int st_ = (x); if (st_ != FMHIP_OK) { std::fprintf(stderr, "%s:%d: %s -> %d (%s)\n", __FILE__, __LINE__, #x, st_, fmhip_last_error()); std::abort(); } } while (0)
-#define EXPECT(x, code) do { const int st_ = (x); if (st_ != (code)) { std::fprintf(stderr, "%s:%d: %s -> %d, expected %d (%s)\n", __FILE__, __LINE__, #x, st_, (int)(code), fmhip_last_error()); std::abort(); } } while (0)
 
 struct Laws {
     int steps, factors;
@@ -35,23 +28,9 @@ static Laws merton(const std::vector<double>& dt, double intensity) {
 }
 
 static void block(int32_t seed, const Laws& L, int64_t n, int64_t offset) {
-    const size_t count = L.kind.size();
-    std::vector<fmhip_vec> h(count, 0);
-    OK(fmhip_increments_generate_device(seed, L.steps, L.factors, n, offset, L.kind.data(), L.a.data(), L.b.data(), h.data()));
-    std::vector<double> host(count * (size_t)(offset + n));
-    OK(fmhip_increments_host(seed, L.steps, L.factors, offset + n, L.kind.data(), L.a.data(), L.b.data(), host.data()));
-    std::vector<float> got((size_t)n + 1);
-    for (size_t k = 0; k < count; ++k) {
-        int64_t size = -1;
-        OK(fmhip_vec_size(h[k], &size));
-        if (size != n) { std::fprintf(stderr, "vector %zu has %lld elements, expected %lld\n", k, (long long)size, (long long)n); std::abort(); }
-        if (n > 0) OK(fmhip_vec_read_float(h[k], got.data(), n));
-        for (int64_t p = 0; p < n; ++p) {
-            const float want = (float)host[k * (size_t)(offset + n) + (size_t)(offset + p)];
-            if (std::memcmp(&want, &got[(size_t)p], 4) != 0) { std::fprintf(stderr, "seed %d vector %zu path %lld (+%lld): %a, expected %a\n", seed, k, (long long)p, (long long)offset, got[(size_t)p], want); std::abort(); }
-        }
-        OK(fmhip_vec_release(h[k]));
-    }
+    compare_block(seed, L.kind.size(), n, offset,
+                  [&](fmhip_vec* h) { return fmhip_increments_generate_device(seed, L.steps, L.factors, n, offset, L.kind.data(), L.a.data(), L.b.data(), h); },
+                  [&](double* host) { return fmhip_increments_host(seed, L.steps, L.factors, offset + n, L.kind.data(), L.a.data(), L.b.data(), host); });
 }
 
 static void scenario(bool thread_engines, bool single_engine) {
@@ -108,15 +87,4 @@ static void scenario(bool thread_engines, bool single_engine) {
     std::printf("increments done\n");
 }
 
-int main() {
-    for (int round = 0; round < 2; ++round) {
-        const int n_devices = std::getenv("FMNULL_DEVICES") ? std::atoi(std::getenv("FMNULL_DEVICES")) : 1;
-        const bool thread_engines = n_devices <= 1 && std::getenv("FMNULL_THREAD_ENGINES");
-        if (n_devices > 1) { std::vector<int> devices((size_t)n_devices, 0); OK(fmhip_init_devices(devices.data(), n_devices)); }
-        else OK(fmhip_init(0));
-        if (thread_engines) OK(fmhip_set_thread_engines(1, nullptr));
-        scenario(thread_engines, n_devices <= 1 && !thread_engines);
-        OK(fmhip_shutdown());
-    }
-    return 0;
-}
+int main() { return two_rounds([](int, bool thread_engines, bool single_engine) { scenario(thread_engines, single_engine); }); }

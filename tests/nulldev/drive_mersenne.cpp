@@ -4,36 +4,15 @@
 // stand-in launchers (null_mt.cpp) generate with the host code from the state the engine hands them, so what is checked is the engine:
 // seeding, distances, the layout of the slab, the handles; then the errors that are found on the host, with another thread creating and
 // releasing vectors meanwhile.  Twice, with a shutdown and a re-initialisation in between.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <thread>
-#include <vector>
 
-#include "../../include/fmhip.h"
-
-#define OK(x) do { const int st_ = (x); if (st_ != FMHIP_OK) { std::fprintf(stderr, "%s:%d: %s -> %d (%s)\n", __FILE__, __LINE__, #x, st_, fmhip_last_error()); std::abort(); } } while (0)
-#define EXPECT(x, code) do { const int st_ = (x); if (st_ != (code)) { std::fprintf(stderr, "%s:%d: %s -> %d, expected %d (%s)\n", __FILE__, __LINE__, #x, st_, (int)(code), fmhip_last_error()); std::abort(); } } while (0)
+#include "drive_common.hpp"
 
 static void block(int32_t seed, const std::vector<double>& dt, int factors, int64_t n, int64_t offset) {
     const int steps = (int)dt.size();
-    const size_t count = (size_t)steps * factors;
-    std::vector<fmhip_vec> h(count, 0);
-    OK(fmhip_bm_generate_mersenne_device(seed, steps, factors, n, offset, dt.data(), h.data()));
-    std::vector<double> host(count * (size_t)(offset + n));
-    OK(fmhip_mersenne_increments(seed, steps, factors, offset + n, dt.data(), host.data()));
-    std::vector<float> got((size_t)n + 1);
-    for (size_t k = 0; k < count; ++k) {
-        int64_t size = -1;
-        OK(fmhip_vec_size(h[k], &size));
-        if (size != n) { std::fprintf(stderr, "vector %zu has %lld elements, expected %lld\n", k, (long long)size, (long long)n); std::abort(); }
-        if (n > 0) OK(fmhip_vec_read_float(h[k], got.data(), n));
-        for (int64_t p = 0; p < n; ++p) {
-            const float want = (float)host[k * (size_t)(offset + n) + (size_t)(offset + p)];
-            if (std::memcmp(&want, &got[(size_t)p], 4) != 0) { std::fprintf(stderr, "seed %d vector %zu path %lld (+%lld): %a, expected %a\n", seed, k, (long long)p, (long long)offset, got[(size_t)p], want); std::abort(); }
-        }
-        OK(fmhip_vec_release(h[k]));
-    }
+    compare_block(seed, (size_t)steps * factors, n, offset,
+                  [&](fmhip_vec* h) { return fmhip_bm_generate_mersenne_device(seed, steps, factors, n, offset, dt.data(), h); },
+                  [&](double* host) { return fmhip_mersenne_increments(seed, steps, factors, offset + n, dt.data(), host); });
 }
 
 static void scenario(bool thread_engines) {
@@ -62,15 +41,4 @@ static void scenario(bool thread_engines) {
     std::printf("mersenne done\n");
 }
 
-int main() {
-    for (int round = 0; round < 2; ++round) {
-        const int n_devices = std::getenv("FMNULL_DEVICES") ? std::atoi(std::getenv("FMNULL_DEVICES")) : 1;
-        const bool thread_engines = n_devices <= 1 && std::getenv("FMNULL_THREAD_ENGINES");
-        if (n_devices > 1) { std::vector<int> devices((size_t)n_devices, 0); OK(fmhip_init_devices(devices.data(), n_devices)); }
-        else OK(fmhip_init(0));
-        if (thread_engines) OK(fmhip_set_thread_engines(1, nullptr));
-        scenario(thread_engines);
-        OK(fmhip_shutdown());
-    }
-    return 0;
-}
+int main() { return two_rounds([](int, bool thread_engines, bool) { scenario(thread_engines); }); }

@@ -5,15 +5,9 @@
 // between.  FMNULL_DEVICES=N: behind a device list of N shards; FMNULL_THREAD_ENGINES=1: an engine per caller thread, the vectors asked
 // about by a thread that does not own them.  The null device computes nothing element-wise (values are whatever the fills left), so only
 // the entries that do not depend on values are checked — (ones, ones) = n —; statuses are checked, the sanitizers do the rest.
-#include <cstdio>
-#include <cstdlib>
 #include <thread>
-#include <vector>
 
-#include "../../include/fmhip.h"
-
-#define OK(x) do { const int st_ = (x); if (st_ != FMHIP_OK) { std::fprintf(stderr, "%s:%d: %s -> %d (%s)\n", __FILE__, __LINE__, #x, st_, fmhip_last_error()); std::abort(); } } while (0)
-#define EXPECT(x, code) do { const int st_ = (x); if (st_ != (code)) { std::fprintf(stderr, "%s:%d: %s -> %d, expected %d (%s)\n", __FILE__, __LINE__, #x, st_, (int)(code), fmhip_last_error()); std::abort(); } } while (0)
+#include "drive_common.hpp"
 
 typedef fmhip_vec V;
 static V filled(int64_t n, double v) { V h = 0; OK(fmhip_vec_create_filled(n, v, &h)); return h; }
@@ -87,16 +81,9 @@ static void scenario(bool thread_engines) {
 }
 
 int main() {
-    for (int cycle = 0; cycle < 2; ++cycle) {
-        const int n_devices = std::getenv("FMNULL_DEVICES") ? std::atoi(std::getenv("FMNULL_DEVICES")) : 1;
-        const bool thread_engines = n_devices <= 1 && std::getenv("FMNULL_THREAD_ENGINES");
-        if (n_devices > 1) { std::vector<int> devices((size_t)n_devices, 0); OK(fmhip_init_devices(devices.data(), n_devices)); }
-        else OK(fmhip_init(0));
-        if (thread_engines) OK(fmhip_set_thread_engines(1, nullptr));
+    return two_rounds([](int cycle, bool thread_engines, bool) {
         scenario(thread_engines);
         std::printf("cycle %d: xmom done\n", cycle);
         std::fflush(stdout);
-        OK(fmhip_shutdown());
-    }
-    return 0;
+    });
 }

@@ -1,8 +1,8 @@
 """The host side of the device regression, without a GPU: the pivoted Cholesky of the normal equations (regression.py) on fixed matrices
 and on a singular one, the estimator's product-by-product path on the CPU twin's vectors against numpy's least squares, the Bermudan
 driver on the twin (one exercise date = the European option of the same paths), and the engine's cross-moments pass against the null
-device under AddressSanitizer / UBSan and ThreadSanitizer (tests/nulldev_xmom: the null device of tests/nulldev plus a stand-in for the
-launcher and a driver of its own) on one engine, behind a device list and with thread engines, a second thread releasing handles meanwhile."""
+device under AddressSanitizer / UBSan and ThreadSanitizer (tests/nulldev: the null device plus a stand-in for the launcher, null_xmom.cpp,
+and a driver of its own, drive_xmom.cpp) on one engine, behind a device list and with thread engines, a second thread releasing handles meanwhile."""
 import math
 import os
 import shutil
@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NULLDEV = os.path.join(ROOT, "tests", "nulldev_xmom")
+NULLDEV = os.path.join(ROOT, "tests", "nulldev")
 
 
 def test_entry_point_is_bound(fm):
@@ -97,7 +97,7 @@ def test_bermudan_driver_on_the_twin(fm, oracle):
 def built():
     if not shutil.which("g++") or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
         pytest.skip("needs g++ and the HIP headers")
-    r = subprocess.run(["make", "-C", NULLDEV, "-j8", "asan", "tsan"], capture_output=True, text=True, timeout=1200)
+    r = subprocess.run(["make", "-C", NULLDEV, "-j8", "xmom_asan", "xmom_tsan"], capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     return os.path.join(NULLDEV, "build")
 

@@ -1,7 +1,7 @@
-"""The engine's side of the inverse-CDF increments without a GPU: the generation pass (csrc/increments_device_engine.hpp) against the null
-device under AddressSanitizer / UBSan and ThreadSanitizer (tests/nulldev_increments: the null device of tests/nulldev and the jump stand-in
-of tests/nulldev_mersenne as they are, plus a stand-in for the launcher of fm_mt_icdf_kernel, which generates with the host code from the
-state, the descriptors and the tables the engine hands it, and a driver of its own) on one engine, behind device lists and with thread
+"""The engine's side of the inverse-CDF increments without a GPU: the generation pass (csrc/mt_generate_engine.hpp) against the null
+device under AddressSanitizer / UBSan and ThreadSanitizer (tests/nulldev: the null device, the jump stand-in and the stand-in for
+the launcher of fm_mt_icdf_kernel, null_mt.cpp, which generates with the host code from the state, the descriptors and the tables the
+engine hands it, and a driver of its own, drive_increments.cpp) on one engine, behind device lists and with thread
 engines — blocks behind path offsets reproduce fmhip_increments_host exactly there, which pins the engine's seeding, jump distances, the
 sharing of tables between equal means, and the layout of descriptors, tables and slab."""
 import os
@@ -11,14 +11,14 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NULLDEV = os.path.join(ROOT, "tests", "nulldev_increments")
+NULLDEV = os.path.join(ROOT, "tests", "nulldev")
 
 
 @pytest.fixture(scope="module")
 def built():
     if not shutil.which("g++") or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
         pytest.skip("needs g++ and the HIP headers")
-    r = subprocess.run(["make", "-C", NULLDEV, "-j8", "asan", "tsan"], capture_output=True, text=True, timeout=1200)
+    r = subprocess.run(["make", "-C", NULLDEV, "-j8", "increments_asan", "increments_tsan"], capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     return os.path.join(NULLDEV, "build")
 

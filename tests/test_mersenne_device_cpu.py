@@ -1,7 +1,7 @@
 """The host side of the device Mersenne-Twister generator, without a GPU: the entry point is bound, the Python mirror's switch, and the
-engine's generation pass (csrc/mersenne_device_engine.hpp) against the null device under AddressSanitizer / UBSan and ThreadSanitizer
-(tests/nulldev_mersenne: the null device of tests/nulldev plus stand-ins for the two launchers, which generate with the host code from the
-state the engine hands them, and a driver of its own) on one engine, behind device lists and with thread engines — path offsets and shards
+engine's generation pass (csrc/mt_generate_engine.hpp) against the null device under AddressSanitizer / UBSan and ThreadSanitizer
+(tests/nulldev: the null device plus stand-ins for the launchers, null_mt.cpp, which generate with the host code from the state the
+engine hands them, and a driver of its own, drive_mersenne.cpp) on one engine, behind device lists and with thread engines — path offsets and shards
 reproduce fmhip_mersenne_increments exactly there, which pins the engine's seeding, jump distances and slab layout."""
 import os
 import shutil
@@ -10,7 +10,7 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NULLDEV = os.path.join(ROOT, "tests", "nulldev_mersenne")
+NULLDEV = os.path.join(ROOT, "tests", "nulldev")
 
 
 def test_entry_point_is_bound(fm):
@@ -34,7 +34,7 @@ def test_mirror_switch(fm, monkeypatch):
 def built():
     if not shutil.which("g++") or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
         pytest.skip("needs g++ and the HIP headers")
-    r = subprocess.run(["make", "-C", NULLDEV, "-j8", "asan", "tsan"], capture_output=True, text=True, timeout=1200)
+    r = subprocess.run(["make", "-C", NULLDEV, "-j8", "mersenne_asan", "mersenne_tsan"], capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     return os.path.join(NULLDEV, "build")
 

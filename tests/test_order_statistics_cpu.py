@@ -1,8 +1,8 @@
 """The host side of the device order statistics, without a GPU: the key order and the digit-picking loop of csrc/order_stats.hpp against
 histograms counted on the CPU (tests/cpp/test_order_stats_host.cpp), and the engine's passes — one flush for a batch of stored, pending
 and storage-sharing vectors, another thread releasing meanwhile, a tiny ring — against the null device under AddressSanitizer / UBSan and
-ThreadSanitizer (tests/nulldev_order: the null device of tests/nulldev plus stand-ins for the three new launchers, and a driver of its
-own), on one engine, behind a device list and with thread engines."""
+ThreadSanitizer (tests/nulldev: the null device plus stand-ins for the three new launchers, null_os.cpp, and a driver of its own,
+drive_order.cpp), on one engine, behind a device list and with thread engines."""
 import os
 import shutil
 import subprocess
@@ -10,7 +10,7 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NULLDEV = os.path.join(ROOT, "tests", "nulldev_order")
+NULLDEV = os.path.join(ROOT, "tests", "nulldev")
 
 
 def test_key_order_and_digit_picking_loop(tmp_path):
@@ -29,7 +29,7 @@ def test_key_order_and_digit_picking_loop(tmp_path):
 def built():
     if not shutil.which("g++") or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
         pytest.skip("needs g++ and the HIP headers")
-    r = subprocess.run(["make", "-C", NULLDEV, "-j8", "asan", "tsan"], capture_output=True, text=True, timeout=1200)
+    r = subprocess.run(["make", "-C", NULLDEV, "-j8", "order_asan", "order_tsan"], capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     return os.path.join(NULLDEV, "build")
 
