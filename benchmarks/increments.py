@@ -5,6 +5,11 @@ increment being stored on the device, median of `--repeat` constructions after o
     40 x 3 x 10^6   the Merton shape: Brownian increment, normal jump size, Poisson jump count (mean 0.0125 per step)
     40 x 1 x 10^6   Poisson only, for means 0.0125, 1 and 30 (the table is walked from 0 / bisected: FMHIP_ICDF_LINEAR_MAX, --search)
     40 x 5 x 10^6   all normal — beside the same shape through BrownianMotionFromMersenneRandomNumbers (fm_mt_bm_kernel) in the same run
+--levy: instead, the shapes of the gamma and exponential laws (fm_mt_levy_kernel) —
+    40 x 2 x 10^6   variance-gamma: gamma clock (shape dt/nu = 1.25) and standard normal
+    40 x 1 x 10^6   gamma only, shapes 0.06, 1 and 30; exponential only
+  and, in the same run, the Merton and all-normal shapes, which run the untouched fm_mt_icdf_kernel.  The host definition of a gamma draw
+  takes about a microsecond on one core, so the host path is timed at --host-paths paths (default 10^5) and reported per draw.
 Writes one JSON document (--out) with the command that made it.  Kernel time: run this under
 `rocprofv3 --kernel-trace --stats -- python benchmarks/increments.py --device-only`."""
 import argparse
@@ -47,6 +52,8 @@ def main():
     ap.add_argument("--paths", type=int, default=1_000_000)
     ap.add_argument("--device-only", action="store_true")
     ap.add_argument("--search", action="store_true", help="Poisson shapes also with every table bisected and every table walked from 0")
+    ap.add_argument("--levy", action="store_true", help="the gamma / exponential shapes (and Merton, all-normal beside them)")
+    ap.add_argument("--host-paths", type=int, default=100_000, help="--levy: paths of the host-path timing")
     ap.add_argument("--out")
     a = ap.parse_args()
     fm = importlib.import_module("finmath-lib-cuda-extensions_amd")
@@ -58,11 +65,23 @@ def main():
     for mean in (0.0125, 1.0, 30.0):
         shapes.append((f"poisson 40 x 1, mean {mean}", 1, lambda mean=mean: fm.JumpProcessIncrements(td, [mean / 0.25], n, next(seeds))))
     shapes.append(("normal 40 x 5", 5, lambda: fm.IndependentIncrementsFromICDF(td, 5, n, next(seeds), lambda i, f: fm.NormalLaw(math.sqrt(td.getTimeStep(i))))))
+    if a.levy:
+        gamma_only = lambda shape, paths: fm.IndependentIncrementsFromICDF(td, 1, paths, next(seeds), lambda i, f: fm.GammaLaw(shape, 0.2))
+        levy = [("variance-gamma 40 x 2", 2, lambda paths=n: fm.VarianceGammaProcess(td, paths, next(seeds), 0.2, -0.14, 0.2).increments)]
+        for shape in (0.06, 1.0, 30.0):
+            levy.append((f"gamma 40 x 1, shape {shape}", 1, lambda paths=n, shape=shape: gamma_only(shape, paths)))
+        levy.append(("exponential 40 x 1", 1, lambda paths=n: fm.IndependentIncrementsFromICDF(td, 1, paths, next(seeds), lambda i, f: fm.ExponentialLaw(2.0))))
+        shapes = levy + [shapes[0], shapes[-1]]
     out = {"command": "python " + " ".join(sys.argv), "device": fm.device_info()[0], "paths": n, "repeat": a.repeat, "rows": []}
     for name, factors, make in shapes:
         row = {"shape": name, "draws": steps * factors * n}
         row["device_ms"], row["device_ms_all"] = median(fm, make, steps, factors, a.repeat, {"FMHIP_DEVICE_INCREMENTS": "1"})
-        if not a.device_only:
+        if a.levy and not a.device_only and name in [x[0] for x in shapes[:5]]:
+            row["host_paths"] = a.host_paths
+            ms, row["host_ms_all"] = median(fm, lambda: make(a.host_paths), steps, factors, a.repeat, {"FMHIP_DEVICE_INCREMENTS": "0"})
+            row["host_ns_per_draw"] = 1e6 * ms / (steps * factors * a.host_paths)
+            row["device_ns_per_draw"] = 1e6 * row["device_ms"] / row["draws"]
+        elif not a.device_only:
             row["host_ms"], row["host_ms_all"] = median(fm, make, steps, factors, a.repeat, {"FMHIP_DEVICE_INCREMENTS": "0"})
             row["host_ns_per_draw"] = 1e6 * row["host_ms"] / row["draws"]
         if a.search and name.startswith("poisson"):

@@ -16,8 +16,8 @@ from . import _native
 from ._native import FmhipError, Moments, PoolStats, ProgOp, build
 from .random_variable import OP, DeviceVector, RandomVariableHip, RandomVariableHipFactory, quantiles, select_ranks_batch
 from .brownian_motion import BrownianMotionHip, BrownianMotionFromMersenneRandomNumbers, TimeDiscretization, mersenne_increments
-from .increments import (IndependentIncrementsFromICDF, JumpProcessIncrements, NormalLaw, PoissonLaw, UniformLaw, host_increments,
-                         merton_increments)
+from .increments import (ExponentialLaw, GammaLaw, GammaProcess, IndependentIncrementsFromICDF, JumpProcessIncrements, NormalLaw, PoissonLaw,
+                         UniformLaw, VarianceGammaProcess, host_increments, merton_increments)
 from .program import Program
 from .regression import MonteCarloConditionalExpectationRegression, covariance_matrix, cross_moments, solve_normal_equations
 from .differentiable import RandomVariableDifferentiableAAD, RandomVariableDifferentiableAADFactory

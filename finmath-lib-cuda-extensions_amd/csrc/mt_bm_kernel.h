@@ -1,5 +1,5 @@
 // mt_bm_kernel.h — host-callable launchers of the Mersenne-Twister increment kernels in mt_bm_kernel.hip: Brownian increments (DESIGN.md
-// §4.9) and increments with a law per stream through an inverse CDF (§4.10).
+// §4.9), increments with a law per stream through an inverse CDF (§4.10), and the same with the gamma and exponential laws (§4.11).
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -28,8 +28,9 @@ struct DevMtBmArgs {
 // One law of fm_mt_icdf_kernel: host/increments.hpp's IncrementLaws::Law, byte for byte (the engine uploads that array).
 struct DevMtLaw {
     int32_t  kind;                  // 0 normal: inverse normal CDF(u) · a;  1 uniform: a + (b − a) · u;  2 Poisson: min { k : table[k] >= u }
-    uint32_t table_len;             // Poisson: entries of the law's CDF table, the last of them 1.0
-    uint32_t table_offset;          // Poisson: its first entry in `tables`
+                                    // fm_mt_levy_kernel only: 4 gamma: fm_inverse_gamma_cdf(a, consts, u) · b;  5 exponential: −fm_log64(1 − u) / a
+    uint32_t table_len;             // Poisson: entries of the law's CDF table, the last of them 1.0; gamma: FM_GAMMA_CONSTS
+    uint32_t table_offset;          // Poisson: its first entry in `tables`; gamma: the first of the shape's constants there
     uint32_t reserved;
     double   a, b;
 };
@@ -58,6 +59,7 @@ inline bool mt_shape_ok(const DevMtBmArgs& a, const DevMtIcdfArgs* icdf = nullpt
 // out[0 … 624) = the state `distance` words behind in[0 … 624) (one workgroup); distance < 2^44
 hipError_t launch_mt_jump(const uint32_t* in, uint64_t distance, uint32_t* out, hipStream_t st);
 hipError_t launch_mt_bm(const DevMtBmArgs& a, hipStream_t st);
-hipError_t launch_mt_icdf(const DevMtIcdfArgs& a, hipStream_t st);
+hipError_t launch_mt_icdf(const DevMtIcdfArgs& a, hipStream_t st);      // kinds 0, 1, 2
+hipError_t launch_mt_levy(const DevMtIcdfArgs& a, hipStream_t st);      // kinds 0, 1, 2, 4, 5 (fm_mt_levy_kernel)
 
 } // namespace fm

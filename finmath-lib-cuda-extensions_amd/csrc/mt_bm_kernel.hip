@@ -23,7 +23,13 @@
 // fm_mt_icdf_kernel is the same pass with another last step: a law per stream — normal, uniform or Poisson — from a
 // descriptor array (host/increments.hpp).  Poisson and uniform draws equal the host's exactly (a Poisson draw only compares the uniform
 // with the host's fp64 table); normal draws are under the contract above.  Tests: tests/test_gpu_increments.py.
+//
+// fm_mt_levy_kernel is the pass once more, with the gamma and the exponential law beside those three.  Their definition
+// (host/gamma_icdf.hpp) is compiled here and on the host from one text, with + − × /, sqrt and integer operations only: these draws are
+// EQUAL to the host's.  An instantiation of its own, because the gamma branch is an fp64 iteration that costs registers: a call without
+// these laws runs fm_mt_icdf_kernel as before.  Tests: tests/test_gpu_levy_increments.py.
 #include <hip/hip_runtime.h>
+#include "../host/gamma_icdf.hpp"
 #define FM_MT_JUMP_TABLE_QUALIFIER __device__
 #include "fm_mt_jump_table.hpp"
 #include "mt_bm_kernel.h"
@@ -203,6 +209,20 @@ struct MtIcdfDraw {
     }
 };
 
+// MtIcdfDraw's three laws and the two of host/gamma_icdf.hpp.  In a variance-gamma layout (gamma, normal, gamma, …) half the lanes of a
+// wave iterate while the other half wait: the stream order is the contract, draws are not regrouped.
+struct MtLevyDraw {
+    MtIcdfDraw old;
+    __device__ __forceinline__ float operator()(double u, uint32_t s) const
+    {
+        const DevMtLaw* L = old.laws + s;
+        const int32_t kind = L->kind;
+        if (kind == 4) return (float)(fmhost::fm_inverse_gamma_cdf(L->a, old.tables + L->table_offset, u) * L->b);
+        if (kind == 5) return (float)fmhost::fm_exponential_icdf(L->a, u);
+        return old(u, s);
+    }
+};
+
 // The generation pass of one workgroup (header comment), shared by both kernels; `draw` is the last step.
 template <class Draw>
 __device__ __forceinline__ void mt_generate(const DevMtBmArgs& A, uint32_t* x, const Draw& draw)
@@ -287,6 +307,12 @@ __global__ void __launch_bounds__(MT_BLOCK) __attribute__((amdgpu_waves_per_eu(4
     mt_generate(A.g, x, MtIcdfDraw{ A.laws, A.tables, A.linear_max });
 }
 
+__global__ void __launch_bounds__(MT_BLOCK) fm_mt_levy_kernel(const DevMtIcdfArgs A)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t x[MT_LDS_WORDS];
+    mt_generate(A.g, x, MtLevyDraw{ { A.laws, A.tables, A.linear_max } });
+}
+
 hipError_t launch_mt_jump(const uint32_t* in, uint64_t distance, uint32_t* out, hipStream_t st)
 {
     hipLaunchKernelGGL(fm_mt_jump_kernel, dim3(1), dim3(MT_BLOCK), 0, st, in, distance, out);
@@ -306,6 +332,14 @@ hipError_t launch_mt_icdf(const DevMtIcdfArgs& a, hipStream_t st)
     if (a.g.n_paths <= 0 || a.g.n_segments == 0) return hipSuccess;
     if (!mt_shape_ok(a.g, &a)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(fm_mt_icdf_kernel, dim3(a.g.n_segments), dim3(MT_BLOCK), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_mt_levy(const DevMtIcdfArgs& a, hipStream_t st)
+{
+    if (a.g.n_paths <= 0 || a.g.n_segments == 0) return hipSuccess;
+    if (!mt_shape_ok(a.g, &a)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fm_mt_levy_kernel, dim3(a.g.n_segments), dim3(MT_BLOCK), 0, st, a);
     return hipGetLastError();
 }
 

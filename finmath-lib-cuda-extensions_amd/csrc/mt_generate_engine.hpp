@@ -13,6 +13,9 @@
 //                            function, fmhost::checkedIncrementLaws, which fmhip_increments_host calls too); descriptors and tables go up;
 //                            fm_mt_icdf_kernel.  The device only compares a uniform with the host's table for a Poisson draw, so counts and
 //                            uniform draws are the host's exactly and normal draws are under the contract of mt_bm_kernel.hip.
+//                            A call with a gamma or an exponential law (§4.11) runs fm_mt_levy_kernel instead — the same pass with those
+//                            two laws from host/gamma_icdf.hpp, the text the host compiles: equal draws; the constants of a shape travel
+//                            with the tables.  Any other call runs the kernel it ran before.
 // Which path a caller takes is the caller's choice (FMHIP_DEVICE_MERSENNE=0, FMHIP_DEVICE_INCREMENTS=0 in the mirrors), never the engine's:
 // without its kernel a pass is FMHIP_ERR_UNSUPPORTED; it never draws on the host.
 #include "runtime.hpp"
@@ -30,6 +33,7 @@ namespace fm {
 hipError_t launch_mt_jump(const uint32_t* in, uint64_t distance, uint32_t* out, hipStream_t st) __attribute__((weak));
 hipError_t launch_mt_bm(const DevMtBmArgs& a, hipStream_t st) __attribute__((weak));
 hipError_t launch_mt_icdf(const DevMtIcdfArgs& a, hipStream_t st) __attribute__((weak));
+hipError_t launch_mt_levy(const DevMtIcdfArgs& a, hipStream_t st) __attribute__((weak));
 
 static_assert(sizeof(DevMtLaw) == sizeof(fmhost::IncrementLaws::Law) && offsetof(DevMtLaw, table_offset) == offsetof(fmhost::IncrementLaws::Law, table_offset)
               && offsetof(DevMtLaw, a) == offsetof(fmhost::IncrementLaws::Law, a) && offsetof(DevMtLaw, b) == offsetof(fmhost::IncrementLaws::Law, b),
@@ -168,7 +172,10 @@ void Engine::mt_increments_generate(int32_t seed, int n_steps, int n_factors, in
         if (end == e || *end || v < 0 || v > 512) throw Error(FMHIP_ERR_INVALID_ARGUMENT, std::string("FMHIP_ICDF_LINEAR_MAX=") + e + ": 0 … 512");
         a.linear_max = (uint32_t)v;
     }
+    bool levy = false;
+    for (const fmhost::IncrementLaws::Law& L : laws.laws) levy = levy || L.kind == fmhost::LAW_GAMMA || L.kind == fmhost::LAW_EXPONENTIAL;
     if (launch_mt_icdf == nullptr || launch_mt_jump == nullptr) throw Error(FMHIP_ERR_UNSUPPORTED, "this build of the engine has no inverse-CDF increment kernel");
+    if (levy && launch_mt_levy == nullptr) throw Error(FMHIP_ERR_UNSUPPORTED, "this build of the engine has no kernel for gamma and exponential increments");
     // in front of the state: descriptors (32 B each), tables (at least one double, so that the pointer is never a stranger's)
     const size_t law_bytes = (size_t)n_streams * sizeof(DevMtLaw), table_bytes = std::max<size_t>(laws.tables.size(), 1) * 8;
     mt_generate(a.g, seed, n_steps, n_factors, path_offset, law_bytes + table_bytes, "increment laws, tables and Mersenne-Twister state H2D",
@@ -181,7 +188,8 @@ void Engine::mt_increments_generate(int32_t seed, int n_steps, int n_factors, in
             a.g = g;
             a.laws = reinterpret_cast<const DevMtLaw*>(front);
             a.tables = reinterpret_cast<const double*>(front + law_bytes);
-            hip_check(launch_mt_icdf(a, stream_), "launch fm_mt_icdf_kernel");
+            if (levy) hip_check(launch_mt_levy(a, stream_), "launch fm_mt_levy_kernel");
+            else hip_check(launch_mt_icdf(a, stream_), "launch fm_mt_icdf_kernel");
         }, out);
 }
 

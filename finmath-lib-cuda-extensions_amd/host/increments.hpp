@@ -13,6 +13,11 @@
 //   NORMAL   inverseNormalCdf(u) · a                a >= 0: sqrt(dt) for a Brownian factor, 1 for a jump size
 //   UNIFORM  a + (b − a) · u                        a <= b, finite; every operation rounded once, in this order
 //   POISSON  min { k >= 0 : F[k] >= u }             a = the mean λ·dt, 0 <= a <= 128; F a table built here, once per distinct mean
+//   GAMMA    fm_inverse_gamma_cdf(a, consts, u) · b a = the shape, 0.01 <= a <= 1000, b = the scale, finite and positive (kind 4)
+//   EXPONENTIAL  −fm_log64(1 − u) / a               a = the rate, finite and positive (kind 5; kind 3 is no law)
+// The last two are defined in gamma_icdf.hpp, a header the device compiles too, without a library transcendental: equal by construction.
+// `consts` is what depends on the shape alone (lgamma(shape), 1/shape, …), computed here once per distinct shape; it lies in `tables`
+// beside the Poisson tables, addressed the same way.
 // The Poisson table is plain fp64: p = F[0] = exp(−a); p = p·a/k, F[k] = F[k−1] + p; it ends at the first k past the mode with
 // F[k] == F[k−1] or F[k] >= 1 − 2^-53, and its last entry is replaced by 1.0, so every u < 1 finds a k.  Whoever draws — this header or
 // the device — only compares u with these doubles: the counts are equal by construction.  The cap keeps a table under 300 entries.
@@ -25,15 +30,16 @@
 #include <string>
 #include <vector>
 
+#include "gamma_icdf.hpp"
 #include "mersenne.hpp"
 
 namespace fmhost {
 
-constexpr int32_t LAW_NORMAL = 0, LAW_UNIFORM = 1, LAW_POISSON = 2;
+constexpr int32_t LAW_NORMAL = 0, LAW_UNIFORM = 1, LAW_POISSON = 2, LAW_GAMMA = 4, LAW_EXPONENTIAL = 5;
 constexpr double POISSON_MEAN_CAP = 128.0;
 constexpr int64_t INCREMENT_STREAMS_CAP = int64_t(1) << 24;           // laws (steps · factors) per call
 constexpr int64_t INCREMENT_WORDS_CAP = int64_t(1) << 44;             // the jump-ahead table reaches 2^44 words of the stream
-constexpr size_t INCREMENT_TABLE_DOUBLES_CAP = size_t(1) << 16;       // all distinct Poisson tables of a call together
+constexpr size_t INCREMENT_TABLE_DOUBLES_CAP = size_t(1) << 16;       // all distinct Poisson tables and gamma constants of a call together
 
 inline std::vector<double> poissonTable(double mean) {
     std::vector<double> F;
@@ -56,6 +62,19 @@ inline int poissonFromTable(const double* F, int len, double u) {
     return lo;
 }
 
+// What fm_inverse_gamma_cdf reads per shape (gamma_icdf.hpp: FM_GC_…).  lgamma_r: std::lgamma writes the global signgam.
+inline std::vector<double> gammaConsts(double shape) {
+    std::vector<double> c((size_t)FM_GAMMA_CONSTS);
+    int sign = 0;
+    c[FM_GC_LGAMMA] = ::lgamma_r(shape, &sign);
+    c[FM_GC_INV_SHAPE] = 1.0 / shape;
+    c[FM_GC_LGAMMA1] = ::lgamma_r(shape + 1.0, &sign);
+    c[FM_GC_WH_CENTRE] = 1.0 - 1.0 / (9.0 * shape);
+    c[FM_GC_WH_SLOPE] = 1.0 / (3.0 * std::sqrt(shape));
+    c[FM_GC_SPLIT] = shape <= 1.0 ? 1.0 - shape * (0.253 + shape * 0.12) : 1.0;
+    return c;
+}
+
 // The laws of a call, checked, with the Poisson tables built and shared between equal means.
 struct IncrementLaws {
     struct Law { int32_t kind; uint32_t table_len; uint32_t table_offset; uint32_t reserved; double a, b; };   // the device's descriptor too
@@ -65,6 +84,8 @@ struct IncrementLaws {
         const Law& L = laws[stream];
         if (L.kind == LAW_NORMAL) return inverseNormalCdf(u) * L.a;
         if (L.kind == LAW_UNIFORM) { const double width = L.b - L.a; const double scaled = width * u; return L.a + scaled; }
+        if (L.kind == LAW_GAMMA) return fm_inverse_gamma_cdf(L.a, tables.data() + L.table_offset, u) * L.b;
+        if (L.kind == LAW_EXPONENTIAL) return fm_exponential_icdf(L.a, u);
         return (double)poissonFromTable(tables.data() + L.table_offset, (int)L.table_len, u);
     }
 };
@@ -83,6 +104,7 @@ inline IncrementLaws checkedIncrementLaws(int n_steps, int n_factors, int64_t n_
     IncrementLaws out;
     out.laws.resize((size_t)n_streams);
     std::map<uint64_t, std::pair<uint32_t, uint32_t>> seen;             // bits of a mean → (offset, length) of its table
+    std::map<uint64_t, std::pair<uint32_t, uint32_t>> seen_shapes;      // bits of a shape → (offset, length) of its constants
     for (size_t s = 0; s < (size_t)n_streams; ++s) {
         IncrementLaws::Law& L = out.laws[s];
         L.kind = kinds[s]; L.a = a[s]; L.b = b[s]; L.table_len = 0; L.table_offset = 0; L.reserved = 0;
@@ -108,6 +130,23 @@ inline IncrementLaws checkedIncrementLaws(int n_steps, int n_factors, int64_t n_
                 out.tables.insert(out.tables.end(), F.begin(), F.end());
             }
             L.table_offset = it->second.first; L.table_len = it->second.second;
+        } else if (L.kind == LAW_GAMMA) {
+            if (!std::isfinite(L.a) || !(L.a > 0.0)) throw std::invalid_argument("gamma law: the shape is not a positive finite number" + where);
+            if (L.a < FM_GAMMA_SHAPE_MIN || L.a > FM_GAMMA_SHAPE_MAX) throw std::invalid_argument("gamma law: the shape is outside 0.01 … 1000" + where);
+            if (!std::isfinite(L.b) || !(L.b > 0.0)) throw std::invalid_argument("gamma law: the scale is not a positive finite number" + where);
+            uint64_t bits; std::memcpy(&bits, &L.a, 8);
+            auto it = seen_shapes.find(bits);
+            if (it == seen_shapes.end()) {
+                const std::vector<double> c = gammaConsts(L.a);
+                if (out.tables.size() + c.size() > INCREMENT_TABLE_DOUBLES_CAP)
+                    throw std::invalid_argument("the Poisson tables and gamma constants of this call need more than 2^16 table entries" + where);
+                it = seen_shapes.emplace(bits, std::make_pair((uint32_t)out.tables.size(), (uint32_t)c.size())).first;
+                out.tables.insert(out.tables.end(), c.begin(), c.end());
+            }
+            L.table_offset = it->second.first; L.table_len = it->second.second;
+        } else if (L.kind == LAW_EXPONENTIAL) {
+            if (!std::isfinite(L.a) || !(L.a > 0.0)) throw std::invalid_argument("exponential law: the rate is not a positive finite number" + where);
+            L.b = 0.0;
         } else throw std::invalid_argument("unknown law " + std::to_string(L.kind) + where);
     }
     return out;

@@ -19,12 +19,25 @@ struct Law {
     static Law normal(double scale) { return { LAW_NORMAL, scale, 0.0 }; }
     static Law uniform(double lo, double hi) { return { LAW_UNIFORM, lo, hi }; }
     static Law poisson(double mean) { return { LAW_POISSON, mean, 0.0 }; }
+    static Law gamma(double shape, double scale) { return { LAW_GAMMA, shape, scale }; }          // host/gamma_icdf.hpp; 0.01 <= shape <= 1000
+    static Law exponential(double rate) { return { LAW_EXPONENTIAL, rate, 0.0 }; }
 };
 using LawChooser = std::function<Law(int timeIndex, int factor)>;
 
 // the three factors of a Merton jump-diffusion: Brownian increment, standard normal jump size, Poisson jump count with mean λ·dt
 inline LawChooser mertonLaws(const TimeDiscretization& td, double jumpIntensity) {
     return [td, jumpIntensity](int i, int f) { return f == 0 ? Law::normal(std::sqrt(td.getTimeStep(i))) : f == 1 ? Law::normal(1.0) : Law::poisson(jumpIntensity * td.getTimeStep(i)); };
+}
+
+// one factor: a gamma process, increment i ~ Gamma(shapePerTime · dt_i, scale) [unverified: finmath-lib's GammaProcess]
+inline LawChooser gammaProcessLaws(const TimeDiscretization& td, double shapePerTime, double scale) {
+    return [td, shapePerTime, scale](int i, int) { return Law::gamma(shapePerTime * td.getTimeStep(i), scale); };
+}
+
+// the two factors of a variance-gamma process: the gamma clock Γ_i ~ Gamma(dt_i/ν, ν) and a standard normal Z_i; the increment is
+// θ·Γ_i + σ·sqrt(Γ_i)·Z_i (varianceGammaIncrement) [unverified: the layout is this project's, as the Merton layout is]
+inline LawChooser varianceGammaLaws(const TimeDiscretization& td, double nu) {
+    return [td, nu](int i, int f) { return f == 0 ? Law::gamma(td.getTimeStep(i) / nu, nu) : Law::normal(1.0); };
 }
 
 class IndependentIncrementsBase : public BrownianMotion {
@@ -96,5 +109,11 @@ private:
     }
     int64_t offset_;
 };
+
+// θ·Γ_i + σ·sqrt(Γ_i)·Z_i from increments laid out by varianceGammaLaws, in RandomVariable methods (the fusion front-end sees them)
+inline RV varianceGammaIncrement(const BrownianMotion& increments, int timeIndex, double sigma, double theta) {
+    const RV g = increments.getIncrement(timeIndex, 0), z = increments.getIncrement(timeIndex, 1);
+    return g->mult(theta)->addProduct(g->sqrt()->mult(z), sigma);
+}
 
 } // namespace fmhost

@@ -9,10 +9,14 @@ One ``MersenneTwister.nextDouble()`` per increment, path-major (path, step, fact
     NormalLaw(scale)        inverse normal CDF (AS 241) times ``scale``: ``sqrt(dt)`` for a Brownian factor, 1 for a jump size
     UniformLaw(lo, hi)      ``lo + (hi - lo) * u``
     PoissonLaw(mean)        ``min { k : F[k] >= u }`` over a CDF table built on the host in fp64, ``0 <= mean <= 128``
+    GammaLaw(shape, scale)  inverse regularised incomplete gamma function times ``scale``, ``0.01 <= shape <= 1000``
+    ExponentialLaw(rate)    ``-log(1 - u) / rate``
 
 The increments are generated on the device (``fmhip_increments_generate_device``: every workgroup enters the one stream by jump-ahead)
 to the bits of the host definition ``fmhip_increments_host`` (host/increments.hpp): Poisson and uniform draws are equal, normal draws
-are under the contract of the Mersenne-Twister Brownian motion.  With ``FMHIP_DEVICE_INCREMENTS=0`` — or with a
+are under the contract of the Mersenne-Twister Brownian motion; gamma and exponential draws are equal too: their
+definition (host/gamma_icdf.hpp) is one text for the host and the device, without a library transcendental (§4.11).  ``GammaProcess`` and
+``VarianceGammaProcess`` are the pure-jump Lévy processes finmath-lib builds on these increments.  With ``FMHIP_DEVICE_INCREMENTS=0`` — or with a
 factory that is not the device's — they are drawn by the host definition and handed to the factory (double[] → fp32): the A/B switch,
 and the definition.
 """
@@ -29,6 +33,7 @@ from . import _native as N
 from .random_variable import DeviceVector, RandomVariableHip, RandomVariableHipFactory
 
 LAW_NORMAL, LAW_UNIFORM, LAW_POISSON = 0, 1, 2
+LAW_GAMMA, LAW_EXPONENTIAL = 4, 5               # 3 is no law
 
 
 class _Law:
@@ -39,7 +44,7 @@ class _Law:
 
     def __eq__(self, o): return isinstance(o, _Law) and (self.kind, self.a, self.b) == (o.kind, o.a, o.b)
     def __hash__(self): return hash((self.kind, self.a, self.b))
-    def __repr__(self): return f"{type(self).__name__}({self.a}" + (f", {self.b})" if self.kind == LAW_UNIFORM else ")")
+    def __repr__(self): return f"{type(self).__name__}({self.a}" + (f", {self.b})" if self.kind in (LAW_UNIFORM, LAW_GAMMA) else ")")
 
 
 class NormalLaw(_Law):
@@ -52,6 +57,14 @@ class UniformLaw(_Law):
 
 class PoissonLaw(_Law):
     def __init__(self, mean): super().__init__(LAW_POISSON, mean)
+
+
+class GammaLaw(_Law):
+    def __init__(self, shape, scale=1.0): super().__init__(LAW_GAMMA, shape, scale)
+
+
+class ExponentialLaw(_Law):
+    def __init__(self, rate=1.0): super().__init__(LAW_EXPONENTIAL, rate)
 
 
 def _device_increments():
@@ -183,3 +196,73 @@ def merton_increments(time_discretization, number_of_paths, seed, jump_intensity
         if f == 1: return NormalLaw(1.0)
         return PoissonLaw(jump_intensity * td.getTimeStep(i))
     return IndependentIncrementsFromICDF(td, 3, number_of_paths, seed, laws, random_variable_factory, path_offset)
+
+
+class GammaProcess(IndependentIncrementsFromICDF):
+    """One factor: the increment over time step i is Gamma(shape_per_time · dt_i, scale) — mean shape_per_time · scale · dt_i.  With
+    shape_per_time = 1/ν and scale = ν it is the gamma clock of a variance-gamma process [unverified: finmath-lib's GammaProcess
+    (timeDiscretization, numberOfPaths, seed, shape, scale)]."""
+
+    def __init__(self, time_discretization, number_of_paths, seed, shape_per_time, scale=1.0, random_variable_factory=None, path_offset=0):
+        self.shapePerTime, self.scale = float(shape_per_time), float(scale)
+
+        def laws(time_index, factor):
+            return GammaLaw(self.shapePerTime * self.timeDiscretization.getTimeStep(time_index), self.scale)
+        super().__init__(time_discretization, 1, number_of_paths, seed, laws, random_variable_factory, path_offset)
+
+    def getCloneWithModifiedSeed(self, seed):
+        return GammaProcess(self.timeDiscretization, self.numberOfPaths, seed, self.shapePerTime, self.scale, self.randomVariableFactory, self.pathOffset)
+
+    def getCloneWithModifiedTimeDiscretization(self, new_time_discretization):
+        return GammaProcess(new_time_discretization, self.numberOfPaths, self.seed, self.shapePerTime, self.scale, self.randomVariableFactory, self.pathOffset)
+
+
+class VarianceGammaProcess:
+    """Increments θ·Γ_i + σ·sqrt(Γ_i)·Z_i of a variance-gamma process: a Brownian motion with drift θ and volatility σ run on a gamma
+    clock Γ_i ~ Gamma(dt_i/ν, ν).  Γ_i is factor 0 and Z_i (standard normal) factor 1 of ONE IndependentIncrementsFromICDF — one stream, one
+    launch — combined with RandomVariable methods, so that the fusion front-end sees the combination [unverified: the factor layout is
+    this project's, as the Merton layout is].  One factor towards its callers; ``getGammaIncrement`` hands out the clock."""
+
+    def __init__(self, time_discretization, number_of_paths, seed, sigma, theta, nu, random_variable_factory=None, path_offset=0):
+        self.sigma, self.theta, self.nu = float(sigma), float(theta), float(nu)
+        td = time_discretization
+
+        def laws(i, f):
+            return GammaLaw(td.getTimeStep(i) / self.nu, self.nu) if f == 0 else NormalLaw(1.0)
+        self.increments = IndependentIncrementsFromICDF(td, 2, number_of_paths, seed, laws, random_variable_factory, path_offset)
+        self._combined = {}
+        self._lock = threading.Lock()
+
+    def getGammaIncrement(self, time_index): return self.increments.getIncrement(time_index, 0)
+
+    def getIncrement(self, time_index, factor=0):
+        if factor != 0: raise IndexError("a variance-gamma process has one factor")
+        with self._lock:
+            if time_index not in self._combined:
+                g, z = self.increments.getIncrement(time_index, 0), self.increments.getIncrement(time_index, 1)
+                self._combined[time_index] = g.mult(self.theta).addProduct(g.sqrt().mult(z), self.sigma)
+            return self._combined[time_index]
+
+    def getBrownianIncrement(self, time_index, factor=0): return self.getIncrement(time_index, factor)
+
+    def getCloneWithModifiedSeed(self, seed):
+        i = self.increments
+        return VarianceGammaProcess(i.timeDiscretization, i.numberOfPaths, seed, self.sigma, self.theta, self.nu, i.randomVariableFactory, i.pathOffset)
+
+    def getCloneWithModifiedTimeDiscretization(self, new_time_discretization):
+        i = self.increments
+        return VarianceGammaProcess(new_time_discretization, i.numberOfPaths, i.seed, self.sigma, self.theta, self.nu, i.randomVariableFactory, i.pathOffset)
+
+    def getTimeDiscretization(self): return self.increments.getTimeDiscretization()
+    def getNumberOfFactors(self): return 1
+    def getNumberOfPaths(self): return self.increments.getNumberOfPaths()
+    def getSeed(self): return self.increments.getSeed()
+    def getRandomVariableForConstant(self, value): return self.increments.getRandomVariableForConstant(value)
+
+    def __eq__(self, o):
+        return isinstance(o, VarianceGammaProcess) and (self.sigma, self.theta, self.nu) == (o.sigma, o.theta, o.nu) and self.increments == o.increments
+
+    def __hash__(self): return hash((self.sigma, self.theta, self.nu, hash(self.increments)))
+
+    def __repr__(self):
+        return f"VarianceGammaProcess(sigma={self.sigma}, theta={self.theta}, nu={self.nu}, {self.increments!r})"

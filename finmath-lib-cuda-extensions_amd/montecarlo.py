@@ -8,6 +8,9 @@ a RandomVariableFactory by injection (LIBORMarketModelCalibrationATMTest.java:35
     heston_call_mc          BASELINE.json configs[2]: Euler full-truncation Heston driven by BrownianMotionHip
     merton_call_mc          Merton's jump-diffusion driven by IndependentIncrementsFromICDF (increments.py: Brownian increment, normal
                             jump size, Poisson jump count), with merton_call_analytic, Merton's series, as its closed-form check
+    variance_gamma_call_mc  the variance-gamma model (Madan, Carr, Chang 1998) driven by VarianceGammaProcess (increments.py: a gamma clock
+                            and a standard normal per step), with variance_gamma_call_analytic — Black–Scholes conditional on the gamma
+                            time, integrated against its density — as its check
     bermudan_option_mc      Longstaff–Schwartz backward induction over MonteCarloConditionalExpectationRegression (regression.py):
                             what finmath-lib's BermudanOption does with its conditional-expectation estimator
 """
@@ -81,6 +84,59 @@ def merton_call_analytic(initial_value, risk_free_rate, volatility, jump_intensi
         weight *= lam / n
         if n > lam and weight < 1e-16:
             return total
+
+
+def variance_gamma_martingale_correction(sigma, theta, nu):
+    """ω = ln(1 − θν − σ²ν/2)/ν:  E exp(X_t) = exp(−ω t) for the variance-gamma process X, so S = S₀ exp((r + ω) t + X_t) is a martingale
+    after discounting."""
+    taken = theta * nu + 0.5 * sigma * sigma * nu                       # small for a small ν: log1p keeps its digits
+    if not taken < 1.0: raise ValueError("1 - theta nu - sigma^2 nu / 2 must be positive")
+    return math.log1p(-taken) / nu
+
+
+def variance_gamma_call_mc(process, initial_value, risk_free_rate, maturity, strike):
+    """Value of a European call under the variance-gamma model by Monte-Carlo: per time step X += (r + ω) Δt + ΔV, S = exp(X), ΔV =
+    process.getIncrement(i, 0) = θ ΔΓ + σ sqrt(ΔΓ) Z (increments.VarianceGammaProcess), ω the martingale correction.  Written in
+    RandomVariable methods only.  `maturity` must be a point of the time discretisation."""
+    td = process.getTimeDiscretization()
+    x = process.getRandomVariableForConstant(math.log(initial_value))
+    drift = risk_free_rate + variance_gamma_martingale_correction(process.sigma, process.theta, process.nu)
+    t, i = td.getTime(0), 0
+    while t < maturity - 1e-12:
+        x = x.add(drift * td.getTimeStep(i)).add(process.getIncrement(i, 0))
+        i += 1
+        t = td.getTime(i)
+    payoff = x.exp().sub(strike).floor(0.0)
+    value = payoff.div(math.exp(risk_free_rate * maturity))
+    return value.getAverage(), value
+
+
+def variance_gamma_call_analytic(initial_value, risk_free_rate, sigma, theta, nu, maturity, strike, nodes=400):
+    """Given the gamma time g = Γ_T ~ Gamma(T/ν, ν), ln S_T is normal with mean ln S₀ + (r + ω) T + θ g and variance σ² g: the call is a
+    Black–Scholes price with forward F(g) = S₀ exp((r + ω) T + θ g + σ² g / 2) and total variance σ² g, and the value is its integral
+    against the gamma density.  With g = ν y the integral is ∫ y^(α−1) e^(−y) h(y) dy / Γ(α), α = T/ν: Gauss–Laguerre quadrature with
+    weight y^(α−1) e^(−y) — nodes and weights from the Jacobi matrix of the generalised Laguerre polynomials (Golub–Welsch), in numpy —
+    which takes the density's singularity at 0 (α < 1) into the weight."""
+    import numpy as np
+    alpha = maturity / nu
+    omega = variance_gamma_martingale_correction(sigma, theta, nu)
+    k = np.arange(nodes, dtype=np.float64)
+    diagonal = 2.0 * k + alpha                                           # recurrence of L_n^(α−1): a_k = 2k + α, b_k² = k (k + α − 1)
+    off = np.sqrt(k[1:] * (k[1:] + alpha - 1.0))
+    y, vectors = np.linalg.eigh(np.diag(diagonal) + np.diag(off, 1) + np.diag(off, -1))
+    weights = vectors[0] ** 2                                             # normalised: they sum to 1 = ∫ density
+    total = 0.0
+    discount = math.exp(-risk_free_rate * maturity)
+    sqrt2 = math.sqrt(2.0)
+    for yi, wi in zip(y, weights):
+        g = nu * yi
+        if not g > 0.0 or wi < 1e-300: continue
+        forward = initial_value * math.exp((risk_free_rate + omega) * maturity + theta * g + 0.5 * sigma * sigma * g)
+        s = sigma * math.sqrt(g)
+        d1 = (math.log(forward / strike) + 0.5 * s * s) / s
+        d2 = d1 - s
+        total += wi * discount * (forward * 0.5 * (1.0 + math.erf(d1 / sqrt2)) - strike * 0.5 * (1.0 + math.erf(d2 / sqrt2)))
+    return total
 
 
 def heston_call_mc(brownian_motion, initial_value, risk_free_rate, v0, kappa, theta, xi, rho, maturity, strike):

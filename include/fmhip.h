@@ -475,8 +475,18 @@ int fmhip_bm_generate_mersenne_device(int32_t seed, int n_steps, int n_factors, 
  * under the contract of fmhip_bm_generate_mersenne_device.  Both check their arguments with one function, before anything is flushed
  * or launched: an unknown kind, a NaN or negative scale or mean, a mean above 128, a > b or non-finite bounds, more than 2^24 laws, words
  * beyond 2^44, more than 2^16 table entries over all distinct means -> FMHIP_ERR_INVALID_ARGUMENT.  A build without the kernel returns
- * FMHIP_ERR_UNSUPPORTED; it never falls back to the host definition. */
+ * FMHIP_ERR_UNSUPPORTED; it never falls back to the host definition.
+ * Two more laws, for pure-jump Levy processes (gamma, variance-gamma), through the same two entry points:
+ *   FMHIP_LAW_GAMMA        fm_inverse_gamma_cdf(a, consts, u) * b   a = the shape, 0.01 <= a <= 1000; b = the scale, finite and > 0
+ *   FMHIP_LAW_EXPONENTIAL  -fm_log64(1 - u) / a                     a = the rate, finite and > 0; b ignored
+ * Their definition, host/gamma_icdf.hpp, is one header that the host and the device both compile: exp, log, the incomplete gamma function
+ * and its inverse (Halley steps) written with + - * /, sqrt and integer operations only, every operation rounded once.  These draws of
+ * fmhip_increments_generate_device EQUAL the definition's, every one; u = 0 gives +0.0.  consts (lgamma(shape), 1/shape, ...) is computed
+ * on the host once per distinct shape and shares the 2^16 table entries with the Poisson tables.  A call that names one of these laws
+ * runs fm_mt_levy_kernel, any other call the kernel it ran before.  A shape outside the range, a non-positive, NaN or infinite shape,
+ * scale or rate -> FMHIP_ERR_INVALID_ARGUMENT.  Kind 3 is not a law. */
 enum { FMHIP_LAW_NORMAL = 0, FMHIP_LAW_UNIFORM = 1, FMHIP_LAW_POISSON = 2 };
+enum { FMHIP_LAW_GAMMA = 4, FMHIP_LAW_EXPONENTIAL = 5 };
 int fmhip_increments_host(int32_t seed, int n_steps, int n_factors, int64_t n_paths,
                           const int32_t* kinds, const double* a, const double* b, double* host_out);
 int fmhip_increments_generate_device(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset,

@@ -18,9 +18,12 @@ import net.finmath.time.TimeDiscretization;
  * net.finmath.montecarlo.IndependentIncrementsFromICDF draws with one MersenneTwister.nextDouble() per increment, and on which
  * JumpProcessIncrements and the three-factor layout of MonteCarloMertonModel sit [unverified: restated from finmath-lib's documentation].
  *
- * The laws are the three the device knows: {@link Law#normal(double)}, {@link Law#uniform(double, double)}, {@link Law#poisson(double)}
- * (an arbitrary inverse CDF, as finmath's class accepts, cannot be handed to a kernel).  Poisson and uniform draws equal the host's, normal
- * draws are under the contract of {@link BrownianMotionHip.Generator#MERSENNE_DEVICE}.
+ * The laws are the five the device knows: {@link Law#normal(double)}, {@link Law#uniform(double, double)}, {@link Law#poisson(double)},
+ * {@link Law#gamma(double, double)}, {@link Law#exponential(double)} (an arbitrary inverse CDF, as finmath's class accepts, cannot be handed
+ * to a kernel).  Poisson, uniform, gamma and exponential draws equal the host's — the gamma and exponential laws are defined in one header
+ * the host and the device both compile (host/gamma_icdf.hpp) — normal draws are under the contract of
+ * {@link BrownianMotionHip.Generator#MERSENNE_DEVICE}.  {@link #gammaProcess} and {@link #varianceGamma} lay out the factors of
+ * finmath-lib's GammaProcess and VarianceGammaProcess [unverified: the variance-gamma factor layout is this project's].
  */
 public class IndependentIncrementsHip implements IndependentIncrements, Serializable {
 
@@ -29,7 +32,7 @@ public class IndependentIncrementsHip implements IndependentIncrements, Serializ
 	/** A law of one increment: kind and two arguments, as fmhip.h states them. */
 	public static final class Law implements Serializable {
 		private static final long serialVersionUID = 1L;
-		public static final int NORMAL = 0, UNIFORM = 1, POISSON = 2;
+		public static final int NORMAL = 0, UNIFORM = 1, POISSON = 2, GAMMA = 4, EXPONENTIAL = 5;      // 3 is no law
 		final int kind;
 		final double a, b;
 		private Law(final int kind, final double a, final double b) { this.kind = kind; this.a = a; this.b = b; }
@@ -38,6 +41,10 @@ public class IndependentIncrementsHip implements IndependentIncrements, Serializ
 		public static Law uniform(final double lowerBound, final double upperBound) { return new Law(UNIFORM, lowerBound, upperBound); }
 		/** a jump count with the given mean (lambda * dt), at most 128 */
 		public static Law poisson(final double mean) { return new Law(POISSON, mean, 0.0); }
+		/** inverse regularised incomplete gamma function times scale; 0.01 <= shape <= 1000, scale finite and positive */
+		public static Law gamma(final double shape, final double scale) { return new Law(GAMMA, shape, scale); }
+		/** -log(1 - u) / rate; rate finite and positive */
+		public static Law exponential(final double rate) { return new Law(EXPONENTIAL, rate, 0.0); }
 	}
 
 	private final TimeDiscretization timeDiscretization;
@@ -73,6 +80,24 @@ public class IndependentIncrementsHip implements IndependentIncrements, Serializ
 	public static IndependentIncrementsHip merton(final TimeDiscretization timeDiscretization, final int numberOfPaths, final int seed, final double jumpIntensity) {
 		return new IndependentIncrementsHip(timeDiscretization, 3, numberOfPaths, seed, timeIndex -> factor ->
 			factor == 0 ? Law.normal(Math.sqrt(timeDiscretization.getTimeStep(timeIndex))) : factor == 1 ? Law.normal(1.0) : Law.poisson(jumpIntensity * timeDiscretization.getTimeStep(timeIndex)));
+	}
+
+	/** One factor: a gamma process, increment i ~ Gamma(shapePerTime * dt_i, scale). */
+	public static IndependentIncrementsHip gammaProcess(final TimeDiscretization timeDiscretization, final int numberOfPaths, final int seed, final double shapePerTime, final double scale) {
+		return new IndependentIncrementsHip(timeDiscretization, 1, numberOfPaths, seed, timeIndex -> factor ->
+			Law.gamma(shapePerTime * timeDiscretization.getTimeStep(timeIndex), scale));
+	}
+
+	/** The two factors of a variance-gamma process: factor 0 the gamma clock Gamma(dt_i / nu, nu), factor 1 a standard normal. */
+	public static IndependentIncrementsHip varianceGamma(final TimeDiscretization timeDiscretization, final int numberOfPaths, final int seed, final double nu) {
+		return new IndependentIncrementsHip(timeDiscretization, 2, numberOfPaths, seed, timeIndex -> factor ->
+			factor == 0 ? Law.gamma(timeDiscretization.getTimeStep(timeIndex) / nu, nu) : Law.normal(1.0));
+	}
+
+	/** theta * Gamma_i + sigma * sqrt(Gamma_i) * Z_i from increments laid out by {@link #varianceGamma}, in RandomVariable methods. */
+	public static RandomVariable varianceGammaIncrement(final IndependentIncrements increments, final int timeIndex, final double sigma, final double theta) {
+		final RandomVariable gamma = increments.getIncrement(timeIndex, 0);
+		return gamma.mult(theta).addProduct(gamma.sqrt().mult(increments.getIncrement(timeIndex, 1)), sigma);
 	}
 
 	@Override
