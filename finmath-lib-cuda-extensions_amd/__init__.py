@@ -18,6 +18,7 @@ from .random_variable import OP, DeviceVector, RandomVariableHip, RandomVariable
 from .brownian_motion import BrownianMotionHip, BrownianMotionFromMersenneRandomNumbers, TimeDiscretization, mersenne_increments
 from .increments import (ExponentialLaw, GammaLaw, GammaProcess, IndependentIncrementsFromICDF, JumpProcessIncrements, NormalLaw, PoissonLaw,
                          UniformLaw, VarianceGammaProcess, host_increments, merton_increments)
+from .sobol import BrownianMotionFromSobolSequence, SobolSequence, sobol_increments
 from .program import Program
 from .regression import MonteCarloConditionalExpectationRegression, covariance_matrix, cross_moments, solve_normal_equations
 from .differentiable import RandomVariableDifferentiableAAD, RandomVariableDifferentiableAADFactory

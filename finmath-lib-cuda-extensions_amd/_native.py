@@ -30,6 +30,7 @@ SYMBOLS = [
     "fmhip_set_jit", "fmhip_jit_wait", "fmhip_jit_stats", "fmhip_program_tier", "fmhip_program_source",
     "fmhip_bm_generate", "fmhip_mersenne_increments", "fmhip_bm_generate_mersenne", "fmhip_bm_generate_mersenne_device", "fmhip_inverse_normal_cdf",
     "fmhip_increments_host", "fmhip_increments_generate_device",
+    "fmhip_sobol_points_host", "fmhip_sobol_increments_host", "fmhip_bm_generate_sobol_device",
     "fmhip_pool_clean", "fmhip_pool_purge", "fmhip_pool_stats",
     "fmhip_profile_enable", "fmhip_profile_read", "fmhip_traffic_stats", "fmhip_engine_stats",
 ]
@@ -176,6 +177,9 @@ def lib():
         "fmhip_bm_generate_mersenne_device": [C.c_int32, i32, i32, i64, i64, C.POINTER(dbl), pv],
         "fmhip_increments_host": [C.c_int32, i32, i32, i64, C.POINTER(C.c_int32), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)],
         "fmhip_increments_generate_device": [C.c_int32, i32, i32, i64, i64, C.POINTER(C.c_int32), C.POINTER(dbl), C.POINTER(dbl), pv],
+        "fmhip_sobol_points_host": [i32, i64, i64, C.c_int32, i32, C.POINTER(dbl)],
+        "fmhip_sobol_increments_host": [C.c_int32, i32, i32, i32, i32, i64, i64, C.POINTER(dbl), C.POINTER(dbl)],
+        "fmhip_bm_generate_sobol_device": [C.c_int32, i32, i32, i32, i32, i64, i64, C.POINTER(dbl), pv],
         "fmhip_pool_clean": [], "fmhip_pool_purge": [], "fmhip_pool_stats": [C.POINTER(PoolStats)],
         "fmhip_set_jit": [i32, C.POINTER(i32)], "fmhip_jit_wait": [],
         "fmhip_jit_stats": [C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(dbl), C.POINTER(i64)],

@@ -972,6 +972,26 @@ int fmhip_increments_generate_device(int32_t seed, int n_steps, int n_factors, i
     FRONT(increments_generate_device(seed, n_steps, n_factors, n_paths, path_offset, kinds, a, b, out));
     return guarded([&] { Engine::get().mt_increments_generate(seed, n_steps, n_factors, n_paths, path_offset, kinds, a, b, out); });
 }
+// Quasi-Monte-Carlo (host/sobol.hpp): Sobol' points and the Brownian increments built from them on the host — the definition — and the
+// same increments generated on the device (sobol_engine.hpp).  One function checks the arguments of both.
+int fmhip_sobol_points_host(int n_dims, int64_t first_index, int64_t count, int32_t seed, int randomize, double* u_out) {
+    try {
+        fm::sobol_points_host(n_dims, first_index, count, seed, randomize, u_out);
+        return FMHIP_OK;
+    } catch (const Error& e) { g_last_error = e.what(); return e.code; }
+    catch (const std::bad_alloc&) { g_last_error = "host allocation failed"; return FMHIP_ERR_OUT_OF_MEMORY; }
+}
+int fmhip_sobol_increments_host(int32_t seed, int randomize, int construction, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, double* host_out) {
+    try {
+        fm::sobol_increments_host(seed, randomize, construction, n_steps, n_factors, n_paths, path_offset, dt, host_out);
+        return FMHIP_OK;
+    } catch (const Error& e) { g_last_error = e.what(); return e.code; }
+    catch (const std::bad_alloc&) { g_last_error = "host allocation failed"; return FMHIP_ERR_OUT_OF_MEMORY; }
+}
+int fmhip_bm_generate_sobol_device(int32_t seed, int randomize, int construction, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, fmhip_vec* out) {
+    FRONT(bm_generate_sobol_device(seed, randomize, construction, n_steps, n_factors, n_paths, path_offset, dt, out));
+    return guarded([&] { Engine::get().sobol_bm_generate(seed, randomize, construction, n_steps, n_factors, n_paths, path_offset, dt, out); });
+}
 double fmhip_inverse_normal_cdf(double p) { return fm::inverse_normal_cdf(p); }
 
 int fmhip_pool_clean(void) { FRONT(pool(0)); TE_ALL(mine, fmhip_pool_clean()); return guarded([&] { Engine::get().pool_clean(); }); }

@@ -407,6 +407,8 @@ public:
     // increments with a law per (step, factor) from the same stream, to the bits of host/increments.hpp (mt_generate_engine.hpp)
     void mt_increments_generate(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset,
                                 const int32_t* kinds, const double* a, const double* b, fmhip_vec* out);
+    // Brownian increments from Sobol' points, Brownian bridge or increment by increment, to the bits of host/sobol.hpp (sobol_engine.hpp)
+    void sobol_bm_generate(int32_t seed, int randomize, int construction, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, fmhip_vec* out);
 
     // pool
     void pool_clean();
@@ -712,5 +714,10 @@ void mt_bm_check(int n_steps, int n_factors, int64_t n_paths, int64_t path_offse
 // the rules are fmhost::checkedIncrementLaws's, host/increments.hpp): throws FMHIP_ERR_INVALID_ARGUMENT
 void mt_increments_check_only(int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const int32_t* kinds, const double* a, const double* b, const fmhip_vec* out);
 void increments_host(int32_t seed, int n_steps, int n_factors, int64_t n_paths, const int32_t* kinds, const double* a, const double* b, double* host_out);
+// what can be said about the arguments of fmhip_bm_generate_sobol_device without a device (sobol_engine.hpp; the rules are fmhost::sobolCheck's,
+// host/sobol.hpp), and the host definitions behind fmhip_sobol_increments_host and fmhip_sobol_points_host: all throw FMHIP_ERR_INVALID_ARGUMENT
+void sobol_check(int randomize, int construction, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, const fmhip_vec* out);
+void sobol_increments_host(int32_t seed, int randomize, int construction, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, double* host_out);
+void sobol_points_host(int n_dims, int64_t first_index, int64_t count, int32_t seed, int randomize, double* u_out);
 
 } // namespace fm

@@ -924,6 +924,18 @@ int increments_generate_device(int32_t seed, int n_steps, int n_factors, int64_t
     });
 }
 
+// Sobol' Brownian increments on a device list: checked here once, before anything is posted; a point is a function of its index, so every
+// shard generates its own block of paths at its own offset
+int bm_generate_sobol_device(int32_t seed, int randomize, int construction, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, fmhip_vec* out) {
+    return fronted([&](Shards& s) {
+        fm::sobol_check(randomize, construction, n_steps, n_factors, n_paths, path_offset, dt, out);
+        auto steps = std::make_shared<std::vector<double>>(dt, dt + n_steps);
+        generate_blocks(s, n_paths, (size_t)n_steps * n_factors, out, [=](Worker&, int64_t cnt, int64_t off, fmhip_vec* got) {
+            return fmhip_bm_generate_sobol_device(seed, randomize, construction, n_steps, n_factors, cnt, path_offset + off, steps->data(), got);
+        });
+    });
+}
+
 int pool(int what) { return fronted([&](Shards& s) { s.post([=](Worker& w) { w.ok(what == 0 ? fmhip_pool_clean() : fmhip_pool_purge()); }); s.wait(); }); }
 int pool_stats(fmhip_pool_stats_t* out) {
     return fronted([&](Shards& s) {

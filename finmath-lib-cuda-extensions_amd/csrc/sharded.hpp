@@ -73,6 +73,7 @@ int jit_stats(int64_t* compiled, int64_t* failed, int64_t* pending, double* comp
 int bm_generate(int64_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, fmhip_vec* out);
 int bm_generate_mersenne_device(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, fmhip_vec* out);
 int increments_generate_device(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const int32_t* kinds, const double* a, const double* b, fmhip_vec* out);
+int bm_generate_sobol_device(int32_t seed, int randomize, int construction, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, fmhip_vec* out);
 int pool(int what);                                        // 0 clean, 1 purge
 int pool_stats(fmhip_pool_stats_t* out);
 int traffic_stats(int64_t* algorithmic_bytes, int64_t* specialised_launches);

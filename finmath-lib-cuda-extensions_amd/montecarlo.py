@@ -6,6 +6,9 @@ a RandomVariableFactory by injection (LIBORMarketModelCalibrationATMTest.java:35
     black_scholes_call_mc   MonteCarloBlackScholesModelTest.java:62-85,125-157 (Euler scheme on the log state,
                             numeraire exp(r t), European call)
     heston_call_mc          BASELINE.json configs[2]: Euler full-truncation Heston driven by BrownianMotionHip
+    geometric_asian_call_mc a call on the geometric average over the points of the time discretisation — a path-dependent product with a
+                            closed form (geometric_asian_call_analytic), where a Brownian bridge over Sobol' points (sobol.py) has
+                            something to show
     merton_call_mc          Merton's jump-diffusion driven by IndependentIncrementsFromICDF (increments.py: Brownian increment, normal
                             jump size, Poisson jump count), with merton_call_analytic, Merton's series, as its closed-form check
     variance_gamma_call_mc  the variance-gamma model (Madan, Carr, Chang 1998) driven by VarianceGammaProcess (increments.py: a gamma clock
@@ -44,6 +47,40 @@ def black_scholes_call_analytic(initial_value, risk_free_rate, volatility, matur
     d2 = d1 - volatility * sqrt(maturity)
     cdf = lambda z: 0.5 * (1.0 + erf(z / sqrt(2.0)))
     return initial_value * cdf(d1) - strike * exp(-risk_free_rate * maturity) * cdf(d2)
+
+
+def geometric_asian_call_mc(brownian_motion, initial_value, risk_free_rate, volatility, maturity, strike):
+    """Value of a call on the geometric average G = exp(mean of ln S(t_k), k = 1 … n) over the points of the time discretisation up to
+    `maturity` (the initial time excluded) under Black–Scholes by Monte-Carlo: the log-Euler scheme of black_scholes_call_mc, which is
+    exact for ln S; payoff max(G - K, 0) / exp(r T).  Written in RandomVariable methods only."""
+    td = brownian_motion.getTimeDiscretization()
+    x = brownian_motion.getRandomVariableForConstant(math.log(initial_value))
+    total = None
+    t, i = td.getTime(0), 0
+    while t < maturity - 1e-12:
+        dt = td.getTimeStep(i)
+        dw = brownian_motion.getBrownianIncrement(i, 0)
+        x = x.add((risk_free_rate - 0.5 * volatility * volatility) * dt).addProduct(dw, volatility)
+        total = x if total is None else total.add(x)
+        i += 1
+        t = td.getTime(i)
+    payoff = total.div(float(i)).exp().sub(strike).floor(0.0)
+    value = payoff.div(math.exp(risk_free_rate * maturity))
+    return value.getAverage(), value
+
+
+def geometric_asian_call_analytic(initial_value, risk_free_rate, volatility, times, strike):
+    """Closed form of geometric_asian_call_mc: `times` = the monitoring times t_1 … t_n (maturity t_n).  ln G is normal with mean
+    ln S0 + (r - σ²/2) · mean(t_k) and variance σ² / n² · Σ_i Σ_j min(t_i, t_j)."""
+    from math import erf, exp, log, sqrt
+    ts = [float(t) for t in times]
+    n = len(ts)
+    mean = log(initial_value) + (risk_free_rate - 0.5 * volatility ** 2) * sum(ts) / n
+    variance = volatility ** 2 / (n * n) * sum((2 * (n - k) - 1) * t for k, t in enumerate(sorted(ts)))
+    cdf = lambda z: 0.5 * (1.0 + erf(z / sqrt(2.0)))
+    d2 = (mean - log(strike)) / sqrt(variance)
+    d1 = d2 + sqrt(variance)
+    return exp(-risk_free_rate * ts[-1]) * (exp(mean + 0.5 * variance) * cdf(d1) - strike * cdf(d2))
 
 
 def merton_call_mc(increments, initial_value, risk_free_rate, volatility, jump_intensity, jump_size_mean, jump_size_stddev, maturity, strike):

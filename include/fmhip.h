@@ -491,6 +491,32 @@ int fmhip_increments_host(int32_t seed, int n_steps, int n_factors, int64_t n_pa
                           const int32_t* kinds, const double* a, const double* b, double* host_out);
 int fmhip_increments_generate_device(int32_t seed, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset,
                                      const int32_t* kinds, const double* a, const double* b, fmhip_vec* out);
+/* QUASI-MONTE-CARLO: Brownian increments from a Sobol' sequence, with a Brownian bridge (what finmath-lib's SobolSequence taken through
+ * BrownianMotionFromRandomNumberGenerator and BrownianBridge serve [unverified: finmath-lib is not vendored; names from its documentation]).
+ * The definition is host/sobol.hpp, one header that the host and the device both compile:
+ *   point        Joe & Kuo's direction numbers (new-joe-kuo-6), 1024 dimensions, 30 bits, Gray-code order, origin skipped: global path p
+ *                uses index i = p + 1, x(i, d) = XOR over the set bits j of i ^ (i >> 1) of v[d][j]; i < 2^30
+ *   shift        randomize = 1: shift[d] = MT19937(seed) next 32-bit word >> 2, d = 0, 1, ... (the seeding of fmhip_mersenne_increments);
+ *                randomize = 0: none.  u = (x ^ shift[d]) * 2^-30 + 2^-31, exact, never 0 or 1
+ *   normal       AS 241 with a portable logarithm in the tails (+ - * / sqrt only): the same bits on the host and on the device
+ *   construction FMHIP_SOBOL_INCREMENTAL: dimension step * n_factors + factor, increment z * sqrt(dt[step]).
+ *                FMHIP_SOBOL_BRIDGE: times t_0 = 0, t_(k+1) = t_k + dt[k]; node 0 is W(t_n) = sqrt(t_n - t_0) * z; then, breadth first from
+ *                (0, n): an interval (l, r) with r - l >= 2 gets m = (l + r) / 2, W_m = a W_l + (1 - a) W_r + sd z, a = (t_r - t_m) / (t_r -
+ *                t_l), sd = sqrt((t_m - t_l)(t_r - t_m) / (t_r - t_l)), and is split into (l, m), (m, r).  Node k of a factor uses
+ *                dimension k * n_factors + factor; the increment of step j is W_(j+1) - W_j.  fp64, narrowed to fp32 once.
+ * fmhip_sobol_points_host: u_out[k * n_dims + d] = u of index first_index + k (index 0 is the origin), no device.
+ * fmhip_sobol_increments_host: the definition; host_out[(step * n_factors + factor) * n_paths + k] = increment of global path path_offset + k
+ * (doubles; no device).  fmhip_bm_generate_sobol_device: the same paths generated on the device (fm_sobol_bm_kernel), every increment EQUAL
+ * to the definition's narrowed to fp32; out as fmhip_bm_generate_mersenne_device's.  One function checks the arguments of both, before
+ * anything is flushed or launched: n_steps * n_factors <= 1024, dt finite and > 0 (bridge) or >= 0 (incremental), a known construction,
+ * randomize 0 or 1, path_offset >= 0, path_offset + n_paths < 2^30, else FMHIP_ERR_INVALID_ARGUMENT.  A build without the kernel returns
+ * FMHIP_ERR_UNSUPPORTED; it never falls back to the host definition. */
+enum { FMHIP_SOBOL_INCREMENTAL = 0, FMHIP_SOBOL_BRIDGE = 1 };
+int fmhip_sobol_points_host(int n_dims, int64_t first_index, int64_t count, int32_t seed, int randomize, double* u_out);
+int fmhip_sobol_increments_host(int32_t seed, int randomize, int construction, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset,
+                                const double* dt, double* host_out);
+int fmhip_bm_generate_sobol_device(int32_t seed, int randomize, int construction, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset,
+                                   const double* dt, fmhip_vec* out);
 /* Inverse of the standard normal CDF (Wichura AS 241 / PPND16), exposed for tests. Returns the value (no status). */
 double fmhip_inverse_normal_cdf(double p);
 

@@ -116,6 +116,10 @@ final class Native {
 	static native int bmGenerateMersenneDevice(int seed, int nSteps, int nFactors, long nPaths, long pathOffset, double[] dt, long[] outHandles);
 	static native int incrementsHost(int seed, int nSteps, int nFactors, long nPaths, int[] kinds, double[] a, double[] b, double[] hostOut);
 	static native int incrementsGenerateDevice(int seed, int nSteps, int nFactors, long nPaths, long pathOffset, int[] kinds, double[] a, double[] b, long[] outHandles);
+	// quasi-Monte-Carlo: Sobol' points, the increments built from them on the host (the definition) and on the device (construction 0: increment by increment, 1: Brownian bridge)
+	static native int sobolPointsHost(int nDims, long firstIndex, long count, int seed, int randomize, double[] uOut);
+	static native int sobolIncrementsHost(int seed, int randomize, int construction, int nSteps, int nFactors, long nPaths, long pathOffset, double[] dt, double[] hostOut);
+	static native int bmGenerateSobolDevice(int seed, int randomize, int construction, int nSteps, int nFactors, long nPaths, long pathOffset, double[] dt, long[] outHandles);
 	static native double inverseNormalCdf(double p);
 
 	// ---- pool (replace DeviceMemoryPool.clean / purge / getDeviceFreeMemPercentage, RandomVariableCuda.java:393-449)

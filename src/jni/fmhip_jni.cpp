@@ -350,6 +350,21 @@ FMJ(jint, incrementsGenerateDevice)(JNIEnv* env, jclass, jint seed, jint nSteps,
     if (nSteps <= 0 || nFactors <= 0 || !pk.p || !pa.p || !pb.p || !po.p || pk.length() < laws || pa.length() < laws || pb.length() < laws || (int64_t)po.length() < laws) return FMHIP_ERR_INVALID_ARGUMENT;
     return fmhip_increments_generate_device(seed, nSteps, nFactors, nPaths, pathOffset, (const int32_t*)pk.p, pa.p, pb.p, (fmhip_vec*)po.p);
 }
+FMJ(jint, sobolPointsHost)(JNIEnv* env, jclass, jint nDims, jlong firstIndex, jlong count, jint seed, jint randomize, jdoubleArray uOut) {
+    Pin<jdouble> po(env, uOut);
+    if (nDims <= 0 || count < 0 || !po.p || (int64_t)po.length() < (int64_t)nDims * count) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_sobol_points_host(nDims, firstIndex, count, seed, randomize, po.p);
+}
+FMJ(jint, sobolIncrementsHost)(JNIEnv* env, jclass, jint seed, jint randomize, jint construction, jint nSteps, jint nFactors, jlong nPaths, jlong pathOffset, jdoubleArray dt, jdoubleArray hostOut) {
+    Pin<jdouble> pd(env, dt, JNI_ABORT), po(env, hostOut);
+    if (nSteps <= 0 || nFactors <= 0 || nPaths < 0 || !pd.p || !po.p || pd.length() < nSteps || (int64_t)po.length() < (int64_t)nSteps * nFactors * nPaths) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_sobol_increments_host(seed, randomize, construction, nSteps, nFactors, nPaths, pathOffset, pd.p, po.p);
+}
+FMJ(jint, bmGenerateSobolDevice)(JNIEnv* env, jclass, jint seed, jint randomize, jint construction, jint nSteps, jint nFactors, jlong nPaths, jlong pathOffset, jdoubleArray dt, jlongArray outHandles) {
+    Pin<jdouble> pd(env, dt, JNI_ABORT); Pin<jlong> po(env, outHandles);
+    if (nSteps <= 0 || nFactors <= 0 || !po.p || !pd.p || (int64_t)po.length() < (int64_t)nSteps * nFactors || pd.length() < nSteps) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_bm_generate_sobol_device(seed, randomize, construction, nSteps, nFactors, nPaths, pathOffset, pd.p, (fmhip_vec*)po.p);
+}
 FMJ(jdouble, inverseNormalCdf)(JNIEnv*, jclass, jdouble p) { return fmhip_inverse_normal_cdf(p); }
 
 // ---------------------------------------------------------------- pool
