@@ -208,16 +208,9 @@ __device__ __forceinline__ void red_tile_end(const uint32_t rel, const bool last
     if (slot == SLOTS - 1u || last) red_span_fold<NRED>(slot + 1u, unit < SLOTS);
 }
 
-// FM_HANDOFF_RELEASE: 1 = the arrival counter's add is an agent-scope release (see block_combine); 0 = relaxed behind sc1 stores
-// and an explicit drain.  Measured on the bench launch (profiles/round03_handoff_ab.txt) before choosing the default.
-#ifndef FM_HANDOFF_RELEASE
-#define FM_HANDOFF_RELEASE 0
-#endif
-#if FM_HANDOFF_RELEASE
-#define FM_HANDOFF_ADD_ORDER __ATOMIC_RELEASE
-#else
-#define FM_HANDOFF_ADD_ORDER __ATOMIC_RELAXED
-#endif
+// The arrival counter's add is RELAXED, behind sc1 stores and an explicit drain (see block_combine).  The alternative — an agent-scope
+// release on the add — was measured against it on the bench launch before this was chosen (profiles/round03_handoff_ab.txt).
+constexpr int FM_HANDOFF_ADD_ORDER = __ATOMIC_RELAXED;
 
 // Device-coherent accesses for the hand-off between workgroups (possibly on different XCDs, whose L2s are not coherent
 // with each other): `sc1` stores / loads go through to memory, no cache-wide write-back or invalidate is needed.
@@ -331,8 +324,8 @@ __device__ __forceinline__ void block_combine_values(const f64x2* wg_sums, const
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const uint32_t arrived = __hip_atomic_fetch_add(counter + (size_t)cg * FM_COUNTER_PLANE, 1u, FM_HANDOFF_ADD_ORDER, __HIP_MEMORY_SCOPE_AGENT);
         // Ordering of this hand-off.  Producer: every partial is an sc1 (write-through) store, drained by the s_waitcnt above before the
-        // counter moves (MI355X_MICROARCH.md, "Valid forms", sc1 table; FM_HANDOFF_RELEASE = 1 makes the add an agent-scope RELEASE on
-        // top: buffer_wbl2 + wait in front of it).  Consumer: the last arriver learns that it is last from the value its own add
+        // counter moves (MI355X_MICROARCH.md, "Valid forms", sc1 table; an agent-scope RELEASE on the add would put buffer_wbl2 + wait
+        // in front of it on top).  Consumer: the last arriver learns that it is last from the value its own add
         // RETURNED and only then loads the partials — all sc1 loads (wave_sum_partials), which do not hit in the L1 or in a foreign
         // XCD's L2 — and, since round 3, behind an agent-scope ACQUIRE fence (buffer_inv sc1: one wave per row and launch, free), so
         // the hand-off no longer rests on the measured envelope of the sc1-only form alone (that table is for one workgroup per CU;

@@ -26,7 +26,7 @@ int main(int argc, char** argv)
         std::printf("%d descriptions, %d round-trip differences\n", n, bad);
         return bad ? 1 : 0;
     }
-    if (argc == 4 && std::string(argv[1]) == "--source") {           // the generated source of the kernel fm_jit_<hash> (as --names lists it), under the current environment's generator knobs
+    if (argc == 4 && std::string(argv[1]) == "--source") {           // the generated source of the kernel fm_jit_<hash> (as --names lists it); loop kernels depend on their description alone, program kernels also on jit_shape's FMHIP_JIT_* knobs
         std::ifstream in(argv[2]);
         std::string line;
         while (std::getline(in, line)) {

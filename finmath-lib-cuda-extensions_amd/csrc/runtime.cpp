@@ -2311,9 +2311,8 @@ bool Engine::detect_loop(const BigDag& g, const std::vector<std::array<int32_t, 
         for (size_t m2 = 0; m2 < LI; ++m2) ro.iter_leaf[r * LI + m2] = -1 - operand[begin + r * P + ro.leaf_in[m2].first][(size_t)ro.leaf_in[m2].second];
     // ---- the kernel
     // elements per lane: 8 keeps more bytes in flight per wave, 4 halves the registers (more waves per SIMD to overlap the loop's
-    // load → compute → store with each other); FMHIP_ROLL_ELEMS overrides for measurements
-    static const int ELEMS_ENV = [] { const char* e = std::getenv("FMHIP_ROLL_ELEMS"); const int v = e ? std::atoi(e) : 0; return (v == 4 || v == 8) ? v : 0; }();
-    const int E = ELEMS_ENV ? ELEMS_ENV : (library_math ? 4 : 8);
+    // load → compute → store with each other) — which loops with library mathematics need
+    const int E = library_math ? 4 : 8;
     *elems_out = E;
     RolledBody body;
     body.elems = E; body.uses_log = uses_log; body.globals = (uint32_t)G; body.inputs = (uint32_t)LI;
@@ -2582,15 +2581,12 @@ void Engine::run_peeled(const BigPlan::Rolled& ro, std::vector<BigDag>& group, s
             hipEvent_t ev0 = nullptr, ev1 = nullptr;
             if (profiling_) { hip_check(hipEventCreate(&ev0), "hipEventCreate"); hip_check(hipEventCreate(&ev1), "hipEventCreate"); hip_check(hipEventRecord(ev0, stream_), "hipEventRecord"); }
             void* params[] = { &args, &rows_arg };
-            // Tiles per workgroup: ONE.  Measured (FMHIP_PEEL_TILES = 2 / 4, profiles/round04_peel_tiles_per_workgroup.txt): a workgroup
+            // Tiles per workgroup: ONE.  Measured against 2 and 4 (profiles/round04_peel_tiles_per_workgroup.txt): a workgroup
             // that walks two or four tiles one after the other — a quarter of the partials, arrival counts and lingering keeper waves of a
             // launch that takes the moments of its roots — is SLOWER on every kind of launch (valuation chains 5607 → 5527 → 5424 GB/s,
             // simulation components −2 % and −4 %): these kernels live on the number of independent tiles in flight.  Same moments either
             // way (the reduction tree is defined on the vector, fm_kernel_parts.hpp).
-            static const int64_t PEEL_TILES_ENV = [] { const char* e = std::getenv("FMHIP_PEEL_TILES"); const long long v = e ? std::atoll(e) : 0; return (v == 1 || v == 2 || v == 4) ? (int64_t)v : (int64_t)0; }();
-            int64_t tiles_per_wg = PEEL_TILES_ENV ? PEEL_TILES_ENV : 1;
-            int64_t grid_x = (tiles + tiles_per_wg - 1) / tiles_per_wg;
-            if ((tiles + grid_x - 1) / grid_x != tiles_per_wg) { tiles_per_wg = 1; grid_x = tiles; }       // (the kernel derives its stretch from the grid: it must come out as asked)
+            const int64_t grid_x = tiles;                                          // (the kernel derives its stretch from the grid)
             RedLaunch red;
             std::vector<fmhip_moments> by_row;                                     // host moments arrive per ROW; the caller's array is per member
             if (rr) {                           // the kernel with the fused reduction of the root (rr->host_out: one entry per member; rr->dev_out: one slot per row)
