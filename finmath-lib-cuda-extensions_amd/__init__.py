@@ -21,6 +21,7 @@ from .increments import (ExponentialLaw, GammaLaw, GammaProcess, IndependentIncr
 from .sobol import BrownianMotionFromSobolSequence, SobolSequence, sobol_increments
 from .program import Program
 from .regression import MonteCarloConditionalExpectationRegression, covariance_matrix, cross_moments, solve_normal_equations
+from .regression import MonteCarloConditionalExpectationLocalizedRegression, binned_cross_moments, binned_evaluate, quantile_bounds
 from .differentiable import RandomVariableDifferentiableAAD, RandomVariableDifferentiableAADFactory
 
 

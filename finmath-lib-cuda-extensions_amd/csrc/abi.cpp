@@ -695,6 +695,62 @@ int fmhip_cross_moments(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y
     });
 }
 
+// ---------------------------------------------------------------- localized regression (binned_engine.hpp)
+extern "C++" {
+namespace fm {
+int binned_xmom_local(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, int64_t* counts, double* sums) {
+    return guarded([&] { Engine::get().binned_xmom_pass(key, bounds, n_bins, x, n_x, y, n_y, counts, sums); });
+}
+}
+template <typename F> static int host_only(F&& f) {          // a definition or a check that needs no engine
+    try { f(); return FMHIP_OK; }
+    catch (const Error& e) { g_last_error = e.what(); return e.code; }
+    catch (const std::bad_alloc&) { g_last_error = "host allocation failed"; return FMHIP_ERR_OUT_OF_MEMORY; }
+}
+}
+int fmhip_binned_cross_moments_host(const float* key, int64_t n, const double* bounds, int n_bins, const float* const* x, int n_x, const float* const* y, int n_y, int64_t* counts_out, double* sums_out) {
+    return host_only([&] { fm::binned_cross_moments_host(key, n, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out); });
+}
+int fmhip_binned_evaluate_host(const float* key, int64_t n, const double* bounds, int n_bins, const float* const* x, int n_x, const double* coefficients, float* out) {
+    return host_only([&] { fm::binned_evaluate_host(key, n, bounds, n_bins, x, n_x, coefficients, out); });
+}
+int fmhip_binned_cross_moments(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, int64_t* counts_out, double* sums_out) {
+    FRONT(binned_cross_moments(key, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out));
+    if (te::active()) {
+        // thread engines: the key and both lists as one, so that foreign operands of any of them are imported by one call
+        const int rc = host_only([&] { fm::binned_check_moments(key, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out); });
+        if (rc != FMHIP_OK) return rc;
+        std::vector<fmhip_vec> all(1, key);
+        all.insert(all.end(), x, x + n_x);
+        all.insert(all.end(), y, y + n_y);
+        TE_LOCAL(all.data(), 1 + n_x + n_y, L, fmhip_binned_cross_moments(L[0], bounds, n_bins, L + 1, n_x, L + 1 + n_x, n_y, counts_out, sums_out));
+    }
+    return guarded([&] {
+        Engine& e = Engine::get();
+        e.binned_xmom_pass(key, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out);
+        if (e.comm_world > 1 && e.comm_gather) {                // one gather, rank order: counts (exact as doubles) and sums of the global sample
+            const size_t q = (size_t)n_x * (n_x + 1) / 2 + (size_t)n_x * n_y, m = (size_t)n_bins * (1 + q);
+            std::vector<double> both(m);
+            for (int b = 0; b < n_bins; ++b) both[(size_t)b] = (double)counts_out[b];
+            std::copy(sums_out, sums_out + (size_t)n_bins * q, both.begin() + n_bins);
+            comm_add_sums(e, both.data(), m);
+            for (int b = 0; b < n_bins; ++b) counts_out[b] = (int64_t)both[(size_t)b];
+            std::copy(both.begin() + n_bins, both.end(), sums_out);
+        }
+    });
+}
+int fmhip_binned_evaluate(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const double* coefficients, fmhip_vec* out) {
+    FRONT(binned_evaluate(key, bounds, n_bins, x, n_x, coefficients, out));
+    if (te::active()) {
+        const int rc = host_only([&] { fm::binned_check_evaluate(key, bounds, n_bins, x, n_x, coefficients, out); });
+        if (rc != FMHIP_OK) return rc;
+        std::vector<fmhip_vec> all(1, key);
+        all.insert(all.end(), x, x + n_x);
+        TE_LOCAL(all.data(), 1 + n_x, L, fmhip_binned_evaluate(L[0], bounds, n_bins, L + 1, n_x, coefficients, out));
+    }
+    return guarded([&] { const fmhip_vec r = Engine::get().binned_eval(key, bounds, n_bins, x, n_x, coefficients, out); *out = r; });
+}
+
 // The one call of a caller that values product after product: the engine lock is held for the bookkeeping (graph → launch → commit),
 // NOT while the device computes — other threads record and launch meanwhile.  The moments arrive in a slot of pinned memory of their
 // own; this thread polls its flag, then takes the lock again to copy them out and give the launch's buffers back.

@@ -1,0 +1,156 @@
+// binned_engine.hpp — the engine's side of the localized regression (kernels: binned_kernel.hip; definition and argument
+// checks: host/binned_regression.hpp).  Part of runtime.cpp's translation unit (included at its end, nowhere else), like
+// cross_moments_engine.hpp, whose pass the first of the two is modelled on.
+//
+// binned_xmom_pass: the count and the cross moments of up to 3 + 4 vectors PER BIN of a key vector — the block-diagonal normal equations of
+// a regression that is local in the key — from ONE launch.  It ends a step group, counts as a use of every vector, computes what is pending
+// below them in one flush, holds the vectors' storage across the wait, launches once and waits under the engine lock as read() does.
+// binned_eval: the piecewise estimate as a NEW, materialised vector: one flush for pending operands, the bounds and the narrowed coefficients
+// go up in one copy that the host waits for (the pinned staging block is the engine's: it must be free again when the call returns), one
+// launch, and no wait for the launch itself.
+// The arguments of both are checked by the functions the host entry points use, before anything is flushed or launched.  Without the
+// kernels a pass is FMHIP_ERR_UNSUPPORTED: the mirrors' generic path is a caller's choice (FMHIP_DEVICE_BINNED_MOMENTS=0), never the engine's.
+#include "runtime.hpp"
+#include "binned_kernel.h"
+#include "../host/binned_regression.hpp"
+
+#include <cstring>
+
+namespace fm {
+
+static_assert(FM_BINNED_MAX_BINS == fmhost::FM_BINNED_MAX_BINS && FM_BINNED_MAX_X == fmhost::FM_BINNED_MAX_X && FM_BINNED_MAX_Y == fmhost::FM_BINNED_MAX_Y,
+              "binned_kernel.h and host/binned_regression.hpp describe the same passes");
+
+// WEAK, like the cross-moments launcher: a host-only build whose stand-in for the kernels does not know these still links.
+hipError_t launch_binned_xmom(const DevBinnedXmomArgs& a, hipStream_t st) __attribute__((weak));
+hipError_t launch_binned_eval(const DevBinnedEvalArgs& a, hipStream_t st) __attribute__((weak));
+
+template <class F> static void binned_as_engine_error(F&& f) {
+    try { f(); }
+    catch (const std::invalid_argument& e) { throw Error(FMHIP_ERR_INVALID_ARGUMENT, e.what()); }
+}
+void binned_check_moments(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, const int64_t* counts_out, const double* sums_out) {
+    binned_as_engine_error([&] { fmhost::binnedCheckMoments<fmhip_vec>(key, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out); });
+}
+void binned_check_evaluate(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const double* coefficients, const fmhip_vec* out) {
+    binned_as_engine_error([&] { fmhost::binnedCheckEvaluate<fmhip_vec>(key, bounds, n_bins, x, n_x, coefficients, out); });
+}
+// fmhip_binned_cross_moments_host and fmhip_binned_evaluate_host: the definition, with its complaints as engine errors
+void binned_cross_moments_host(const float* key, int64_t n, const double* bounds, int n_bins, const float* const* x, int n_x, const float* const* y, int n_y, int64_t* counts_out, double* sums_out) {
+    binned_as_engine_error([&] { fmhost::binnedCrossMoments(key, n, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out); });
+}
+void binned_evaluate_host(const float* key, int64_t n, const double* bounds, int n_bins, const float* const* x, int n_x, const double* coefficients, float* out) {
+    binned_as_engine_error([&] { fmhost::binnedEvaluate(key, n, bounds, n_bins, x, n_x, coefficients, out); });
+}
+
+// key first, then the vectors among x and y: handles, one size, n > 0 — before anything is flushed or launched
+static int binned_real(Engine& e, fmhip_vec key, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, fmhip_vec* real, const char* what) {
+    int n_real = 0;
+    real[n_real++] = key;
+    for (int i = 0; i < n_x; ++i) if (x[i]) real[n_real++] = x[i];
+    for (int m = 0; m < n_y; ++m) real[n_real++] = y[m];
+    const int64_t n = e.node(real[0])->n;
+    for (int i = 1; i < n_real; ++i)
+        if (e.node(real[i])->n != n) throw Error(FMHIP_ERR_SIZE_MISMATCH, std::string(what) + " over vectors of different size");
+    if (n <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, std::string(what) + " of an empty vector");
+    return n_real;
+}
+
+void Engine::binned_xmom_pass(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, int64_t* counts_out, double* sums_out) {
+    require_init();
+    binned_check_moments(key, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out);
+    fmhip_vec real[1 + FM_BINNED_MAX_X + FM_BINNED_MAX_Y];
+    const int n_real = binned_real(*this, key, x, n_x, y, n_y, real, "binned cross moments");
+    os_need_kernel(launch_binned_xmom != nullptr, "binned cross-moments");
+    OsHold hold;
+    os_prepare(real, n_real, hold);
+    DevBinnedXmomArgs a{};
+    int r = 0;
+    a.key = hold.ptrs[(size_t)r++];
+    for (int i = 0; i < n_x; ++i) a.x[i] = x[i] ? hold.ptrs[(size_t)r++] : 0;
+    for (int m = 0; m < n_y; ++m) a.y[m] = hold.ptrs[(size_t)r++];
+    // the products the call asks for, as entries of a bin; the product of two constants is the bin's count and takes no entry
+    auto s_slot = [](int i, int c) { return i * FM_BINNED_MAX_X - i * (i - 1) / 2 + (c - i); };
+    auto t_slot = [](int i, int m) { return FM_BINNED_MAX_X * (FM_BINNED_MAX_X + 1) / 2 + i * FM_BINNED_MAX_Y + m; };
+    for (int s = 0; s < FM_BINNED_SLOTS + 2; ++s) a.slot_entry[s] = -1;
+    int qe = 0;
+    for (int i = 0; i < n_x; ++i) for (int c = i; c < n_x; ++c) if (x[i] || x[c]) a.slot_entry[s_slot(i, c)] = (int8_t)qe++;
+    for (int i = 0; i < n_x; ++i) for (int m = 0; m < n_y; ++m) a.slot_entry[t_slot(i, m)] = (int8_t)qe++;
+    if (qe == 0) a.slot_entry[s_slot(0, 0)] = (int8_t)qe++;      // constants alone: the counts are all there is, the kernel still wants an entry
+    a.n_bins = (uint32_t)n_bins; a.n_x = (uint32_t)n_x; a.n_y = (uint32_t)n_y;
+    a.entries_per_bin = (uint32_t)qe;
+    a.bins_per_slice = std::min<uint32_t>((uint32_t)n_bins, (uint32_t)FM_BINNED_ENTRIES / (uint32_t)qe);
+    a.n_slices = (a.n_bins + a.bins_per_slice - 1) / a.bins_per_slice;
+    const uint32_t blocks = binned_blocks(hold.n);
+    // pinned: [bounds (copied to the device in-stream)] [sums] [counts] [flag]; device: zero scratch = counters + counts, other = bounds + partials
+    const size_t tab_bytes = os_up256((size_t)FM_BINNED_MAX_BINS * 8), out_bytes = os_up256((size_t)n_bins * qe * 8), cnt_bytes = os_up256((size_t)FM_BINNED_MAX_BINS * 4);
+    const size_t counters_bytes = os_up256(((size_t)FM_BINNED_MAX_SLICES + 1) * 4);
+    char* stage = (char*)ensure_stage(tab_bytes + out_bytes + cnt_bytes + 64);
+    os_scratch(counters_bytes + cnt_bytes, tab_bytes + (size_t)a.n_slices * FM_BINNED_ENTRIES * blocks * 8);
+    double* out_host = reinterpret_cast<double*>(stage + tab_bytes);
+    uint32_t* counts_host = reinterpret_cast<uint32_t*>(stage + tab_bytes + out_bytes);
+    volatile uint64_t* flag = reinterpret_cast<volatile uint64_t*>(stage + tab_bytes + out_bytes + cnt_bytes);
+    a.counters = (uint32_t*)os_zero_;
+    a.counts_dev = reinterpret_cast<uint32_t*>((char*)os_zero_ + counters_bytes);
+    a.done_flag = const_cast<uint64_t*>(flag); a.done_value = ++os_seq_;
+    a.n = hold.n; a.tiles = (uint32_t)((hold.n + FM_BINNED_TILE - 1) / FM_BINNED_TILE);
+    a.bounds = (const double*)os_other_;
+    a.partials = reinterpret_cast<double*>((char*)os_other_ + tab_bytes);
+    a.out_host = out_host; a.counts_host = counts_host;
+    if (n_bins > 1) {
+        std::memcpy(stage, bounds, (size_t)(n_bins - 1) * 8);
+        hip_check(hipMemcpyAsync(os_other_, stage, tab_bytes, hipMemcpyHostToDevice, stream_), "H2D(bin bounds)");
+    }
+    *flag = 0;
+    os_dirty_ = true;
+    hip_check(launch_binned_xmom(a, stream_), "binned cross-moments pass");
+    ++n_launches_;
+    os_wait(flag, a.done_value);
+    const int q = fmhost::binnedSumsPerBin(n_x, n_y);
+    for (int b = 0; b < n_bins; ++b) {
+        counts_out[b] = (int64_t)counts_host[b];
+        double* o = sums_out + (size_t)b * q;
+        auto entry = [&](int slot) { const int e = a.slot_entry[slot]; return e >= 0 ? out_host[(size_t)b * qe + e] : (double)counts_host[b]; };
+        for (int i = 0; i < n_x; ++i) for (int c = i; c < n_x; ++c) *o++ = entry(s_slot(i, c));
+        for (int i = 0; i < n_x; ++i) for (int m = 0; m < n_y; ++m) *o++ = entry(t_slot(i, m));
+    }
+}
+
+fmhip_vec Engine::binned_eval(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const double* coefficients, const fmhip_vec* out_checked) {
+    require_init();
+    binned_check_evaluate(key, bounds, n_bins, x, n_x, coefficients, out_checked);
+    fmhip_vec real[1 + FM_BINNED_MAX_X];
+    const int n_real = binned_real(*this, key, x, n_x, nullptr, 0, real, "binned evaluation");
+    os_need_kernel(launch_binned_eval != nullptr, "binned evaluation");
+    OsHold hold;
+    os_prepare(real, n_real, hold);
+    DevBinnedEvalArgs a{};
+    int r = 0;
+    a.key = hold.ptrs[(size_t)r++];
+    for (int i = 0; i < n_x; ++i) a.x[i] = x[i] ? hold.ptrs[(size_t)r++] : 0;
+    a.n = hold.n; a.n_bins = (uint32_t)n_bins; a.n_x = (uint32_t)n_x;
+    // bounds and the coefficients narrowed to fp32 go up in one copy; the copy has left the pinned block before this call returns
+    const size_t tab_bytes = os_up256((size_t)FM_BINNED_MAX_BINS * 8), coef_bytes = os_up256((size_t)FM_BINNED_MAX_BINS * FM_BINNED_MAX_X * 4);
+    char* stage = (char*)ensure_stage(tab_bytes + coef_bytes);
+    os_scratch(os_up256(8), tab_bytes + coef_bytes);
+    std::memset(stage, 0, tab_bytes + coef_bytes);
+    if (n_bins > 1) std::memcpy(stage, bounds, (size_t)(n_bins - 1) * 8);
+    float* c = reinterpret_cast<float*>(stage + tab_bytes);
+    for (int i = 0; i < n_bins * n_x; ++i) c[i] = (float)coefficients[i];
+    hip_check(hipMemcpyAsync(os_other_, stage, tab_bytes + coef_bytes, hipMemcpyHostToDevice, stream_), "H2D(bin bounds and coefficients)");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+    a.bounds = (const double*)os_other_;
+    a.coefficients = reinterpret_cast<const float*>((const char*)os_other_ + tab_bytes);
+    Buffer* b = new_buffer(hold.n);
+    a.out = (uint64_t)(uintptr_t)b->ptr;
+    const hipError_t e = launch_binned_eval(a, stream_);
+    if (e != hipSuccess) { buffer_unref(b); hip_check(e, "launch fm_binned_eval_kernel"); }
+    ++n_launches_;
+    algorithmic_bytes_ += 4 * hold.n * (n_real + 1);
+    bytes_written_ += 4 * hold.n;
+    Node* nd = new_node(hold.n);
+    nd->buf = b;
+    return nd->id;
+}
+
+} // namespace fm

@@ -4234,3 +4234,4 @@ void Engine::profile_read(double* ms_total, int64_t* n) {
 #include "cross_moments_engine.hpp"    // Engine::xmom_pass: the cross moments of a regression in one launch
 #include "mt_generate_engine.hpp"      // Engine::mt_bm_generate, mt_increments_generate: finmath's Mersenne-Twister stream entered on the device
 #include "sobol_engine.hpp"            // Engine::sobol_bm_generate: Sobol' points through a Brownian bridge
+#include "binned_engine.hpp"           // Engine::binned_xmom_pass, binned_eval: the cross moments per bin of a key, the piecewise estimate

@@ -381,6 +381,12 @@ public:
     // flushed or launched; otherwise the pass behaves as the order-statistics passes do (one flush, storage held across the wait).
     void xmom_pass(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out);
 
+    // localized regression (binned_engine.hpp): per bin of `key` (bin(k) = #{ j : bounds[j] < k }) the count and the cross moments
+    // of fmhip_cross_moments' layout, from ONE launch; and Σ_i x_i·(float)coefficients[bin·n_x + i] as a new, materialised vector.  Arguments are
+    // checked before anything is flushed or launched.
+    void binned_xmom_pass(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, int64_t* counts_out, double* sums_out);
+    fmhip_vec binned_eval(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const double* coefficients, const fmhip_vec* out_checked);
+
     // programs
     fmhip_program program_create(const fmhip_prog_op* ops, int n_ops, int n_in, const int32_t* outs, int n_out,
                                  const int32_t* reds, int n_red);
@@ -719,5 +725,11 @@ void increments_host(int32_t seed, int n_steps, int n_factors, int64_t n_paths, 
 void sobol_check(int randomize, int construction, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, const fmhip_vec* out);
 void sobol_increments_host(int32_t seed, int randomize, int construction, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, double* host_out);
 void sobol_points_host(int n_dims, int64_t first_index, int64_t count, int32_t seed, int randomize, double* u_out);
+// what can be said about the arguments of fmhip_binned_cross_moments / fmhip_binned_evaluate without looking at a vector (binned_engine.hpp; the
+// rules are fmhost::binnedCheck*'s, host/binned_regression.hpp), and the host definitions: all throw FMHIP_ERR_INVALID_ARGUMENT
+void binned_check_moments(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, const int64_t* counts_out, const double* sums_out);
+void binned_check_evaluate(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const double* coefficients, const fmhip_vec* out);
+void binned_cross_moments_host(const float* key, int64_t n, const double* bounds, int n_bins, const float* const* x, int n_x, const float* const* y, int n_y, int64_t* counts_out, double* sums_out);
+void binned_evaluate_host(const float* key, int64_t n, const double* bounds, int n_bins, const float* const* x, int n_x, const double* coefficients, float* out);
 
 } // namespace fm

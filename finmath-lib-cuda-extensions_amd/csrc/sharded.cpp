@@ -777,6 +777,62 @@ int cross_moments(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, doub
     });
 }
 
+// Localized regression: every shard runs the pass on its block of paths; the front adds the shards' counts, and their sums in shard order.
+// The evaluation is per shard: a new vector whose blocks are the shards' results.
+static int64_t binned_front_size(Shards& s, fmhip_vec key, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, const char* what) {
+    const int64_t n = s.vec(key).n;
+    for (int i = 0; i < n_x + n_y; ++i) {
+        const fmhip_vec h = i < n_x ? x[i] : y[i - n_x];
+        if (h && s.vec(h).n != n) throw Error(FMHIP_ERR_SIZE_MISMATCH, std::string(what) + " over vectors of different size");
+    }
+    if (n <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, std::string(what) + " of an empty vector");
+    return n;
+}
+int binned_cross_moments(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, int64_t* counts_out, double* sums_out) {
+    return fronted([&](Shards& s) {
+        binned_check_moments(key, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out);
+        const int64_t n = binned_front_size(s, key, x, n_x, y, n_y, "binned cross moments");
+        const size_t m = (size_t)n_bins * ((size_t)n_x * (n_x + 1) / 2 + (size_t)n_x * n_y);
+        std::vector<std::vector<double>> per((size_t)s.D(), std::vector<double>(m, 0.0));
+        std::vector<std::vector<int64_t>> cnt((size_t)s.D(), std::vector<int64_t>((size_t)n_bins, 0));
+        std::vector<char> took((size_t)s.D(), 0);
+        s.post([&](Worker& w) {
+            if (!os_shard_has_paths(w, n)) return;
+            std::vector<fmhip_vec> lx, ly;
+            for (int i = 0; i < n_x; ++i) lx.push_back(x[i] ? w.at(x[i]) : 0);
+            for (int i = 0; i < n_y; ++i) ly.push_back(w.at(y[i]));
+            took[(size_t)w.shard] = w.ok(binned_xmom_local(w.at(key), bounds, n_bins, lx.data(), n_x, n_y ? ly.data() : nullptr, n_y, cnt[(size_t)w.shard].data(), per[(size_t)w.shard].data())) ? 1 : 0;
+        });
+        s.wait();
+        for (int b = 0; b < n_bins; ++b) { int64_t c = 0; for (size_t d = 0; d < cnt.size(); ++d) if (took[d]) c += cnt[d][(size_t)b]; counts_out[b] = c; }
+        for (size_t i = 0; i < m; ++i) {
+            double t = 0.0; bool first = true;
+            for (size_t d = 0; d < per.size(); ++d) { if (!took[d]) continue; t = first ? per[d][i] : t + per[d][i]; first = false; }      // shard order
+            sums_out[i] = t;
+        }
+    });
+}
+int binned_evaluate(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const double* coefficients, fmhip_vec* out) {
+    return fronted([&](Shards& s) {
+        binned_check_evaluate(key, bounds, n_bins, x, n_x, coefficients, out);
+        const int64_t n = binned_front_size(s, key, x, n_x, nullptr, 0, "binned evaluation");
+        auto bd = std::make_shared<std::vector<double>>(bounds ? bounds : coefficients, (bounds ? bounds : coefficients) + (bounds ? n_bins - 1 : 0));
+        auto co = std::make_shared<std::vector<double>>(coefficients, coefficients + (size_t)n_bins * n_x);
+        auto xs = std::make_shared<std::vector<fmhip_vec>>(x, x + n_x);
+        const fmhip_vec id = s.fresh(n);
+        s.post([=](Worker& w) {
+            int64_t off, cnt; shard_range(n, w.shards, w.shard, &off, &cnt);
+            fmhip_vec h = 0;
+            if (cnt <= 0) { if (w.ok(fmhip_vec_create_uninitialized(0, &h))) w.bind(id, h); return; }
+            std::vector<fmhip_vec> l; for (fmhip_vec v : *xs) l.push_back(v ? w.at(v) : 0);
+            if (w.ok(fmhip_binned_evaluate(w.at(key), bd->data(), n_bins, l.data(), n_x, co->data(), &h))) w.bind(id, h);
+        });
+        // eager, like the call on one engine: a shard's refusal (no kernel, a value that was given up) is THIS call's status
+        try { s.wait(); } catch (...) { s.post([=](Worker& w) { if (const fmhip_vec h = w.at(id)) { (void)fmhip_vec_release(h); w.local.erase(id); } }); s.meta.erase(id); throw; }
+        *out = id;
+    });
+}
+
 int vec_give_up_values(const fmhip_vec* vectors, int count) {
     return fronted([&](Shards& s) {
         need(vectors, "vectors");

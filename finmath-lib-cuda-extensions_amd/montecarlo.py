@@ -205,13 +205,16 @@ def heston_call_mc(brownian_motion, initial_value, risk_free_rate, v0, kappa, th
     return value.getAverage(), value
 
 
-def bermudan_option_mc(brownian_motion, initial_value, risk_free_rate, volatility, exercise_dates, strike, call=False, basis_order=3):
+def bermudan_option_mc(brownian_motion, initial_value, risk_free_rate, volatility, exercise_dates, strike, call=False, basis_order=3, bins=0):
     """Value of a Bermudan option under Black–Scholes by Longstaff–Schwartz backward induction.  States from the log-Euler scheme of
     black_scholes_call_mc, kept at the exercise dates (points of the time discretisation).  The value starts as the last date's discounted
     payoff; at each earlier date the current value is regressed on 1, S, …, S^basis_order over ALL paths (the constant is a deterministic
     random variable: a host scalar to the estimator), and paths on which exercise − continuation estimate >= 0 take the discounted exercise
-    value.  Returns (value.getAverage(), value).  With one exercise date this is the European option on the same paths."""
-    from .regression import MonteCarloConditionalExpectationRegression
+    value.  Returns (value.getAverage(), value).  With one exercise date this is the European option on the same paths.
+    bins > 0: the regression is LOCALIZED — per quantile bin of S (bins of equal count, at most 64) on 1, S, …, S^basis_order with
+    basis_order <= 2 (MonteCarloConditionalExpectationLocalizedRegression); bins = 0: the global fit."""
+    from .regression import MonteCarloConditionalExpectationLocalizedRegression, MonteCarloConditionalExpectationRegression
+    if bins and basis_order + 1 > 3: raise ValueError("a localized regression takes at most 3 basis functions per bin: basis_order <= 2")
     dates = sorted(float(d) for d in exercise_dates)
     if not dates: raise ValueError("no exercise date")
     td = brownian_motion.getTimeDiscretization()
@@ -238,7 +241,8 @@ def bermudan_option_mc(brownian_motion, initial_value, risk_free_rate, volatilit
         basis = [one, s]
         for _ in range(2, basis_order + 1): basis.append(basis[-1].mult(s))
         basis = basis[:basis_order + 1]
-        continuation = MonteCarloConditionalExpectationRegression(basis).getConditionalExpectation(value)
+        if bins: continuation = MonteCarloConditionalExpectationLocalizedRegression(s, bins, basis).getConditionalExpectation(value)
+        else: continuation = MonteCarloConditionalExpectationRegression(basis).getConditionalExpectation(value)
         exercise = exercise_value(s, dates[k])
         value = exercise.sub(continuation).choose(exercise, value)
     return value.getAverage(), value

@@ -6,7 +6,14 @@ MonteCarloConditionalExpectationRegression).
 finmath-lib assembles XᵀX and Xᵀy as b_i.mult(b_j).getAverage(): one recorded product and one blocking expectation per pair, every basis
 vector read about K times.  Here the K + 1 vectors are read once and the K(K+1)/2 + K sums come out of one launch.  The estimator is
 written against the RandomVariable interface and accepts any factory's vectors: the one-pass path is taken when every stochastic operand
-is a RandomVariableHip, the product-by-product path otherwise (and with FMHIP_DEVICE_CROSS_MOMENTS=0: the A/B switch and the fallback)."""
+is a RandomVariableHip, the product-by-product path otherwise (and with FMHIP_DEVICE_CROSS_MOMENTS=0: the A/B switch and the fallback).
+
+Localized regression: a global polynomial is the wrong tool for a kinked continuation value.  binned_cross_moments
+returns the cross moments PER BIN of a key vector from one launch (fmhip_binned_cross_moments) — the block-diagonal normal equations of a
+fit that is local in the key —, quantile_bounds the bounds of bins of equal count, binned_evaluate the piecewise estimate as a new vector,
+and MonteCarloConditionalExpectationLocalizedRegression the estimator on top of them (finmath-lib: BermudanOption's binning basis, the
+…LocalizedOnDependentRegression factories).  FMHIP_DEVICE_BINNED_MOMENTS=0 or any other RandomVariable class: indicators by choose and
+averages pair by pair."""
 from __future__ import annotations
 
 import ctypes as C
@@ -16,9 +23,10 @@ import os
 import numpy as np
 
 from . import _native as N
-from .random_variable import DeviceVector, RandomVariableHip
+from .random_variable import DeviceVector, RandomVariableHip, select_ranks_batch
 
 MAX_X, MAX_Y = 12, 4                     # fmhip_cross_moments' limits
+BINNED_MAX_X, BINNED_MAX_Y, MAX_BINS = 3, 4, 64      # fmhip_binned_cross_moments' limits
 PIVOT_TOLERANCE = 1e-12                  # a basis function whose remaining pivot is <= this x the largest diagonal entry is dropped
 
 
@@ -174,3 +182,188 @@ class MonteCarloConditionalExpectationRegression:
                 ce = ce.addProduct(basis[i], float(beta[i, m]))
             out.append(ce)
         return out[0] if one else out
+
+
+# ------------------------------------------------------------------ localized regression
+def device_binned_moments() -> bool:
+    """FMHIP_DEVICE_BINNED_MOMENTS=0: the localized estimator builds indicators by choose and averages pair by pair (the A/B switch and the
+    fallback); anything else: one fmhip_binned_cross_moments call per four dependents and one fmhip_binned_evaluate call per estimate."""
+    return os.environ.get("FMHIP_DEVICE_BINNED_MOMENTS", "1") != "0"
+
+
+def _bounds(bounds):
+    b = np.ascontiguousarray(bounds, dtype=np.float64).ravel()
+    return b, (b.ctypes.data_as(C.POINTER(C.c_double)) if b.size else None)
+
+
+def binned_cross_moments(key, bounds, xs, ys=()):
+    """(counts, S, T) per bin of `key`, bin(k) = #{ j : bounds[j] < k } (len(bounds) + 1 bins, at most 64): counts[b] paths (int64),
+    S[b] = Σ x_i·x_j (full symmetric n_x × n_x) and T[b] = Σ x_i·y_m (n_x × n_y) over the paths of bin b, fp64 SUMS from one device launch.
+    At most 3 xs (None or 1.0: the constant 1) and 4 ys."""
+    xs, ys = list(xs), list(ys)
+    nx, ny = len(xs), len(ys)
+    b, pb = _bounds(bounds)
+    n_bins = b.size + 1
+    hx = (C.c_int64 * max(nx, 1))(*[_handle(v, True) for v in xs])
+    hy = (C.c_int64 * max(ny, 1))(*[_handle(v, False) for v in ys])
+    q = nx * (nx + 1) // 2 + nx * ny
+    counts = np.zeros(n_bins, dtype=np.int64)
+    out = np.empty(max(n_bins, 1) * q, dtype=np.float64)
+    N.check(N.lib().fmhip_binned_cross_moments(_handle(key, False), pb, n_bins, hx, nx, hy if ny else None, ny,
+                                               counts.ctypes.data_as(C.POINTER(C.c_int64)), out.ctypes.data_as(C.POINTER(C.c_double))))
+    out = out.reshape(n_bins, q)
+    S = np.empty((n_bins, nx, nx), dtype=np.float64)
+    iu = np.triu_indices(nx)
+    S[:, iu[0], iu[1]] = out[:, :iu[0].size]
+    S[:, iu[1], iu[0]] = out[:, :iu[0].size]
+    return counts, S, out[:, iu[0].size:].reshape(n_bins, nx, ny).copy()
+
+
+def binned_evaluate(key, bounds, xs, coefficients) -> DeviceVector:
+    """The piecewise estimate as a new device vector: ((x_0·c_0) + x_1·c_1) + x_2·c_2 with c = (float)coefficients[bin(key)], every fp32
+    operation rounded on its own (fmhip_binned_evaluate).  coefficients: (len(bounds) + 1) × len(xs)."""
+    xs = list(xs)
+    b, pb = _bounds(bounds)
+    c = np.ascontiguousarray(coefficients, dtype=np.float64).reshape(b.size + 1, len(xs))
+    hx = (C.c_int64 * max(len(xs), 1))(*[_handle(v, True) for v in xs])
+    out = C.c_int64(0)
+    N.check(N.lib().fmhip_binned_evaluate(_handle(key, False), pb, b.size + 1, hx, len(xs), c.ctypes.data_as(C.POINTER(C.c_double)), C.byref(out)))
+    k = key.realizations if isinstance(key, RandomVariableHip) else key
+    return DeviceVector(out.value, k.n)
+
+
+def quantile_rank(j: int, n: int, n_bins: int) -> int:
+    """Rank (0-based, ascending) of the upper bound of bin j - 1 of n_bins bins of equal count: ceil(j·n / n_bins) − 1."""
+    return max((j * n + n_bins - 1) // n_bins - 1, 0)
+
+
+def quantile_bounds(key, n_bins: int) -> np.ndarray:
+    """Bounds of n_bins bins of (nearly) equal count: sorted(key)[ceil(j·n/n_bins) − 1] for j = 1 … n_bins − 1 — elements of the vector,
+    taken by ONE select_ranks_batch call on the device (n: the sample behind the expectation communicator, if one is set); a host sort for
+    any other RandomVariable class."""
+    if isinstance(key, (RandomVariableHip, DeviceVector)):
+        v = key.realizations if isinstance(key, RandomVariableHip) else key
+        w = C.c_int(1)
+        N.check(N.lib().fmhip_expectation_world(C.byref(w), None))
+        n = v.n * w.value
+        if n_bins <= 1: return np.empty(0, dtype=np.float64)
+        return select_ranks_batch([v], [quantile_rank(j, n, n_bins) for j in range(1, n_bins)])[0]
+    a = np.sort(np.asarray(key.getRealizations(), dtype=np.float64))
+    return np.array([a[quantile_rank(j, a.size, n_bins)] for j in range(1, n_bins)], dtype=np.float64)
+
+
+class MonteCarloConditionalExpectationLocalizedRegression:
+    """E[ · | key, basis functions] by a least-squares fit PER BIN of `key` (finmath-lib: the binning basis of BermudanOption, the
+    …LocalizedOnDependentRegression estimators): n_bins bins, bounded by `bounds` (n_bins − 1 ascending values; default: quantile_bounds, bins
+    of equal count), bin(k) = #{ j : bounds[j] < k }.  The normal equations are block diagonal — one K × K block per bin, solved by
+    solve_normal_equations, so an empty bin gets coefficients 0.  Written against the RandomVariable interface; the device path (one
+    fmhip_binned_cross_moments call, one fmhip_binned_evaluate call) is taken when every stochastic operand is a RandomVariableHip and
+    K <= 3, the generic path (indicators by choose, averages pair by pair) otherwise and with FMHIP_DEVICE_BINNED_MOMENTS=0.  The generic
+    path compares in the key class's own arithmetic: it agrees with the device path (NaN and infinite keys included) for bounds that are
+    fp32 values — quantile bounds are elements of the key — and deviates for bounds that are not, and for a key of −inf against a bound of
+    −inf (see _triggers)."""
+
+    def __init__(self, key, n_bins, basisFunctionsEstimator, basisFunctionsPredictor=None, bounds=None):
+        if not 1 <= int(n_bins) <= MAX_BINS: raise ValueError(f"n_bins must be 1 … {MAX_BINS}")
+        if key.isDeterministic(): raise ValueError("the key of a localized regression is a stochastic random variable")
+        self.key, self.n_bins = key, int(n_bins)
+        self.basisFunctionsEstimator = list(basisFunctionsEstimator)
+        self.basisFunctionsPredictor = list(basisFunctionsPredictor) if basisFunctionsPredictor is not None else self.basisFunctionsEstimator
+        if len(self.basisFunctionsPredictor) != len(self.basisFunctionsEstimator):
+            raise ValueError("estimator and predictor need the same number of basis functions")
+        self.bounds = np.asarray(bounds, dtype=np.float64).ravel() if bounds is not None else quantile_bounds(key, self.n_bins)
+        if self.bounds.size != self.n_bins - 1: raise ValueError("n_bins bins have n_bins − 1 bounds")
+        if np.isnan(self.bounds).any() or (np.diff(self.bounds) < 0).any(): raise ValueError("the bounds are ascending and not NaN")
+        self._indicators = None
+
+    # ---- which path
+    def _device(self, basis, others) -> bool:
+        if not device_binned_moments() or not 1 <= len(basis) <= BINNED_MAX_X: return False
+        if not all(isinstance(v, RandomVariableHip) for v in [self.key] + basis + others): return False
+        return all(not y.isDeterministic() for y in others)
+
+    # ---- generic path: the bins from the RandomVariable interface.  Membership is decided by the trigger bound − key >= 0 (⟺ key <= bound) in
+    # the arithmetic of the key's class.  NaN keys are taken out with isNaN (no bin; the estimate is NaN there), and an infinite bound is not
+    # subtracted (inf − inf is NaN): nothing is above +inf, everything is above −inf.  What still deviates from the device path: a bound that
+    # is not an fp32 value is rounded to one by an fp32 class before it is compared, and a key of −inf against a bound of −inf counts as
+    # above it.  Quantile bounds of finite keys produce neither.
+    def _zero(self):
+        return self.key.isNaN().mult(0.0)                              # 0 on every path, whatever the key holds
+
+    def _triggers(self):
+        return [self._zero().add(1.0 if b > 0 else -1.0) if math.isinf(b) else self.key.bus(float(b)) for b in self.bounds]
+
+    def _bin_indicators(self):
+        if self._indicators is None:
+            zero = self._zero()
+            one = zero.add(1.0)
+            valid = one.sub(self.key.isNaN())
+            below = [t.choose(valid, zero) for t in self._triggers()] + [valid]      # 1 where key <= bounds[b]; the last bin takes the rest
+            self._indicators = [below[0]] + [below[b].sub(below[b - 1]) for b in range(1, self.n_bins)]
+        return self._indicators
+
+    def _normal_equations_generic(self, dependents):
+        basis, K = self.basisFunctionsEstimator, len(self.basisFunctionsEstimator)
+        A = np.empty((self.n_bins, K, K)); T = np.empty((self.n_bins, K, len(dependents)))
+        zero = self._zero()
+        for b, ind in enumerate(self._bin_indicators()):
+            member = ind.sub(0.5)
+            local = [member.choose(f, zero) if not f.isDeterministic() else ind.mult(f.doubleValue()) for f in basis]      # SELECTED, not multiplied: a NaN outside the bin stays outside
+            for i in range(K):
+                for j in range(i, K):
+                    A[b, i, j] = A[b, j, i] = local[i].mult(local[j]).getAverage()
+                for m, y in enumerate(dependents):
+                    T[b, i, m] = local[i].mult(member.choose(y, zero)).getAverage()
+        return A, T
+
+    def _normal_equations_device(self, dependents):
+        basis = self.basisFunctionsEstimator
+        scale = np.array([f.doubleValue() if f.isDeterministic() else 1.0 for f in basis])
+        xs = [None if f.isDeterministic() else f for f in basis]
+        n = float(self.key._sample_size())
+        A, cols = None, []
+        for m0 in range(0, len(dependents), BINNED_MAX_Y):
+            _, S, T = binned_cross_moments(self.key, self.bounds, xs, dependents[m0:m0 + BINNED_MAX_Y])
+            A = S
+            cols.append(T)
+        return A * np.outer(scale, scale)[None] / n, np.concatenate(cols, axis=2) * scale[None, :, None] / n
+
+    def getBinCounts(self) -> np.ndarray:
+        """Paths per bin (of the global sample behind an expectation communicator)."""
+        if device_binned_moments() and isinstance(self.key, RandomVariableHip):
+            return binned_cross_moments(self.key, self.bounds, [None])[0]
+        n = self.key.size()
+        return np.array([int(round(ind.getAverage() * n)) for ind in self._bin_indicators()], dtype=np.int64)
+
+    def getLinearRegressionParameters(self, dependents) -> np.ndarray:
+        """β: n_bins × K for one dependent, n_bins × K × M for a sequence of M dependents (one pass per four of them)."""
+        one = not isinstance(dependents, (list, tuple))
+        ys = [dependents] if one else list(dependents)
+        A, T = self._normal_equations_device(ys) if self._device(self.basisFunctionsEstimator, ys) else self._normal_equations_generic(ys)
+        beta = np.stack([solve_normal_equations(A[b], T[b]) for b in range(self.n_bins)])
+        return beta[:, :, 0] if one else beta
+
+    def _evaluate(self, beta):
+        basis = self.basisFunctionsPredictor
+        if self._device(basis, []) and all((not f.isDeterministic()) or f.doubleValue() == 1.0 for f in basis) and any(not f.isDeterministic() for f in basis + [self.key]):
+            xs = [None if f.isDeterministic() else f for f in basis]
+            time = max([self.key.getFiltrationTime()] + [f.getFiltrationTime() for f in basis])
+            return RandomVariableHip(time, binned_evaluate(self.key, self.bounds, xs, beta))
+        chains = []
+        for b in range(self.n_bins):
+            ce = basis[0].mult(float(beta[b, 0]))
+            for i in range(1, len(basis)): ce = ce.addProduct(basis[i], float(beta[b, i]))
+            chains.append(ce)
+        zero = self._zero()
+        as_vector = lambda c: c if not c.isDeterministic() else zero.add(c.doubleValue())
+        out = as_vector(chains[-1])
+        for b, t in reversed(list(enumerate(self._triggers()))):
+            out = t.choose(as_vector(chains[b]), out)
+        return self.key.isNaN().sub(0.5).choose(zero.add(math.nan), out)      # a NaN key has no bin
+
+    def getConditionalExpectation(self, dependents):
+        """Per path the fit of its bin: Σ β[bin]_i·b_i over the predictor's basis functions, in the fp32 arithmetic of
+        basis[0].mult(β0).addProduct(basis[i], βi)."""
+        beta = self.getLinearRegressionParameters(dependents)
+        if beta.ndim == 2: return self._evaluate(beta)
+        return [self._evaluate(beta[:, :, m]) for m in range(beta.shape[2])]

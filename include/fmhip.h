@@ -354,6 +354,38 @@ int fmhip_count_not_above(fmhip_vec v, const double* bounds, int n_bounds, int64
  * error a read of it is.  IEEE semantics: a NaN in x_3 makes exactly the entries that involve x_3 NaN, inf*0 is NaN. */
 int fmhip_cross_moments(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out);
 
+/* Localized regression: the cross moments above PER BIN of a key vector — the block-diagonal normal equations of a
+ * regression that is local in the key (finmath-lib: BermudanOption's binning basis, the ...LocalizedOnDependentRegression estimators) — in
+ * one pass, and the piecewise estimate as a new vector.
+ * Bins: bounds[n_bins - 1] doubles, non-decreasing, +-inf allowed, 1 <= n_bins <= 64 (bounds may be NULL for one bin).
+ *   bin(k) = #{ j : bounds[j] < (double)k }: k lies in bin j iff bounds[j-1] < k <= bounds[j] — the comparison of fmhip_count_not_above, so
+ *   -0.0 and +0.0 fall on the same side of a bound of 0.  A NaN key belongs to no bin.
+ * fmhip_binned_cross_moments: n_x vectors x (1 ... 3; a handle of 0 is the constant 1 and is not loaded) and n_y vectors y (0 ... 4), all of
+ *   the key's size n > 0.  counts_out[n_bins]: the paths per bin.  sums_out[n_bins][q], q = n_x(n_x+1)/2 + n_x*n_y: per bin the fp64 SUMS in
+ *   the layout of fmhip_cross_moments (S packed upper triangle, then T).  Every product of two fp32 values is exact in fp64 and is added in
+ *   fp64; no float atomics.  The bits of one (bin, pair) sum are a function of n, of which path positions fall into that bin and of the two
+ *   vectors' values there — not of the other vectors the call names, of list order or role, or of the bounds of other bins (they need not
+ *   equal fmhip_cross_moments' bits at n_bins = 1).  ONE launch.
+ * fmhip_binned_evaluate: *out = a new, materialised vector r with r[p] = ((x_0[p]*c_0) + x_1[p]*c_1) + x_2[p]*c_2,
+ *   c_i = (float)coefficients[bin(key[p])*n_x + i]: every product and every sum rounded to fp32, nothing contracted — what
+ *   basis[0].mult(b0).addProduct(basis[i], bi) computes with that bin's coefficients.  The constant 1 is 1.0f; a NaN key gives NaN.  Eager:
+ *   pending operands are computed in one flush, one launch follows.
+ * The _host functions are the DEFINITION over host float arrays (a NULL among x is the constant 1) and need no device; a bin's members are
+ *   added in path order there.  The device's sums agree with any summation order's to count*2^-53*sum|terms| per bin.
+ * Everything is checked on the host before anything is flushed or launched, by one function for the device and the host entry point:
+ * counts out of range, a NULL pointer, unsorted bounds, a NaN bound, a 0 among y or as the key, n == 0 -> FMHIP_ERR_INVALID_ARGUMENT;
+ * vectors of different sizes -> FMHIP_ERR_SIZE_MISMATCH; FMHIP_ERR_INVALID_HANDLE.  A vector whose values were given up is the error a read
+ * of it is.  A build without the kernels answers FMHIP_ERR_UNSUPPORTED; it never falls back.  With a device list counts and sums add in shard
+ * order and the evaluation is per shard; with an expectation communicator counts and sums are those of the GLOBAL sample (one gather, added
+ * in rank order). */
+int fmhip_binned_cross_moments(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y,
+                               int64_t* counts_out, double* sums_out);
+int fmhip_binned_cross_moments_host(const float* key, int64_t n, const double* bounds, int n_bins, const float* const* x, int n_x,
+                                    const float* const* y, int n_y, int64_t* counts_out, double* sums_out);
+int fmhip_binned_evaluate(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const double* coefficients, fmhip_vec* out);
+int fmhip_binned_evaluate_host(const float* key, int64_t n, const double* bounds, int n_bins, const float* const* x, int n_x,
+                               const double* coefficients, float* out);
+
 /* Expectation communicator: Monte-Carlo paths sharded over processes (one GPU each) behind an UNCHANGED caller.
  * Every vector of this process holds the paths [rank·n, (rank+1)·n) of a global vector of world·n paths; all element-wise
  * work is local; the one thing that couples paths is an expectation.  With a communicator set, fmhip_reduce_moments and

@@ -79,6 +79,15 @@ final class Native {
 	// ---- cross moments: the normal equations of a regression in one pass (replace b_i.mult(b_j).getAverage() per pair, MonteCarloConditionalExpectationRegression)
 	/** sumsOut = the x.length(x.length+1)/2 sums of x_i*x_j (i <= j, row-major) followed by the x.length*y.length sums of x_i*y_m; a handle of 0 in x is the constant 1. */
 	static native int crossMoments(long[] x, long[] y, double[] sumsOut);
+	// ---- localized regression: the cross moments per bin of a key vector in one pass, and the piecewise estimate as a new vector (MonteCarloConditionalExpectationLocalizedRegressionHip)
+	/** bin(k) = number of bounds below k (bounds.length + 1 bins, at most 64; bounds may be null for one bin).  countsOut[b] = paths in bin b; sumsOut[b*q ...] = the sums of crossMoments over the paths of bin b, q = x.length(x.length+1)/2 + x.length*y.length; x.length <= 3, y.length <= 4. */
+	static native int binnedCrossMoments(long key, double[] bounds, long[] x, long[] y, long[] countsOut, double[] sumsOut);
+	/** The definition of binnedCrossMoments over host arrays: xColumns (yColumns) holds nX (nY) columns of key.length floats; bit i of onesMask makes x_i the constant 1. */
+	static native int binnedCrossMomentsHost(float[] key, double[] bounds, float[] xColumns, int nX, int onesMask, float[] yColumns, int nY, long[] countsOut, double[] sumsOut);
+	/** out[0] = a new vector: ((x_0*c_0) + x_1*c_1) + x_2*c_2 per path with c = (float) coefficients[bin(key)*x.length + i], every fp32 operation rounded on its own. */
+	static native int binnedEvaluate(long key, double[] bounds, long[] x, double[] coefficients, long[] out);
+	/** The definition of binnedEvaluate over host arrays (columns as in binnedCrossMomentsHost). */
+	static native int binnedEvaluateHost(float[] key, double[] bounds, float[] xColumns, int nX, int onesMask, double[] coefficients, float[] out);
 	/** With a device list: one device buffer per listed device (0 = not wanted there), each receives the moments of the whole vectors. */
 	static native int reduceMomentsBatchDevices(long[] vectors, double[] shiftsOrNull, long[] deviceOutPerDevice);
 	static native int getStreamOf(int shard, long[] stream);

@@ -192,6 +192,52 @@ FMJ(jint, crossMoments)(JNIEnv* env, jclass, jlongArray x, jlongArray y, jdouble
     if ((int64_t)po.length() < nx * (nx + 1) / 2 + nx * ny) return FMHIP_ERR_INVALID_ARGUMENT;
     return fmhip_cross_moments((const fmhip_vec*)px.p, (int)nx, ny ? (const fmhip_vec*)py.p : nullptr, (int)ny, po.p);
 }
+// ---------------------------------------------------------------- localized regression: cross moments per bin of a key, the piecewise estimate
+FMJ(jint, binnedCrossMoments)(JNIEnv* env, jclass, jlong key, jdoubleArray bounds, jlongArray x, jlongArray y, jlongArray countsOut, jdoubleArray sumsOut) {
+    Pin<jdouble> pb(env, bounds, JNI_ABORT); Pin<jlong> px(env, x, JNI_ABORT); Pin<jlong> py(env, y, JNI_ABORT); Pin<jlong> pc(env, countsOut); Pin<jdouble> po(env, sumsOut);
+    if (!px.p || !pc.p || !po.p) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int64_t nb = (pb.p ? pb.length() : 0) + 1, nx = px.length(), ny = py.p ? py.length() : 0;
+    if ((int64_t)pc.length() < nb || (int64_t)po.length() < nb * (nx * (nx + 1) / 2 + nx * ny)) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_binned_cross_moments(key, pb.p, (int)nb, (const fmhip_vec*)px.p, (int)nx, ny ? (const fmhip_vec*)py.p : nullptr, (int)ny, (int64_t*)pc.p, po.p);
+}
+// columns: nX (nY) columns of key.length floats each, one after the other; bit i of onesMask: x_i is the constant 1 and its column is not read
+static bool binned_columns(const jfloat* flat, int64_t flatLength, int64_t n, int count, int onesMask, std::vector<const float*>& out) {
+    if (count < 0 || count > 8) return false;
+    for (int i = 0; i < count; ++i) {
+        if ((onesMask >> i) & 1) { out.push_back(nullptr); continue; }
+        if (!flat || flatLength < (int64_t)(i + 1) * n) return false;
+        out.push_back(flat + (int64_t)i * n);
+    }
+    return true;
+}
+FMJ(jint, binnedCrossMomentsHost)(JNIEnv* env, jclass, jfloatArray key, jdoubleArray bounds, jfloatArray xColumns, jint nX, jint onesMask, jfloatArray yColumns, jint nY, jlongArray countsOut, jdoubleArray sumsOut) {
+    Pin<jfloat> pk(env, key, JNI_ABORT); Pin<jdouble> pb(env, bounds, JNI_ABORT); Pin<jfloat> px(env, xColumns, JNI_ABORT); Pin<jfloat> py(env, yColumns, JNI_ABORT); Pin<jlong> pc(env, countsOut); Pin<jdouble> po(env, sumsOut);
+    if (!pk.p || !pc.p || !po.p) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int64_t n = pk.length(), nb = (pb.p ? pb.length() : 0) + 1;
+    std::vector<const float*> xs, ys;
+    if (!binned_columns(px.p, px.p ? px.length() : 0, n, nX, onesMask, xs) || !binned_columns(py.p, py.p ? py.length() : 0, n, nY, 0, ys)) return FMHIP_ERR_INVALID_ARGUMENT;
+    if ((int64_t)pc.length() < nb || (int64_t)po.length() < nb * ((int64_t)nX * (nX + 1) / 2 + (int64_t)nX * nY)) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_binned_cross_moments_host(pk.p, n, pb.p, (int)nb, xs.data(), nX, nY ? ys.data() : nullptr, nY, (int64_t*)pc.p, po.p);
+}
+FMJ(jint, binnedEvaluate)(JNIEnv* env, jclass, jlong key, jdoubleArray bounds, jlongArray x, jdoubleArray coefficients, jlongArray out) {
+    Pin<jdouble> pb(env, bounds, JNI_ABORT); Pin<jlong> px(env, x, JNI_ABORT); Pin<jdouble> pc(env, coefficients, JNI_ABORT);
+    if (!px.p || !pc.p) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int64_t nb = (pb.p ? pb.length() : 0) + 1, nx = px.length();
+    if ((int64_t)pc.length() < nb * nx) return FMHIP_ERR_INVALID_ARGUMENT;
+    fmhip_vec h = 0;
+    const int st = fmhip_binned_evaluate(key, pb.p, (int)nb, (const fmhip_vec*)px.p, (int)nx, pc.p, &h);
+    if (st == FMHIP_OK) set1(env, out, (jlong)h);
+    return st;
+}
+FMJ(jint, binnedEvaluateHost)(JNIEnv* env, jclass, jfloatArray key, jdoubleArray bounds, jfloatArray xColumns, jint nX, jint onesMask, jdoubleArray coefficients, jfloatArray out) {
+    Pin<jfloat> pk(env, key, JNI_ABORT); Pin<jdouble> pb(env, bounds, JNI_ABORT); Pin<jfloat> px(env, xColumns, JNI_ABORT); Pin<jdouble> pc(env, coefficients, JNI_ABORT); Pin<jfloat> po(env, out);
+    if (!pk.p || !pc.p || !po.p) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int64_t n = pk.length(), nb = (pb.p ? pb.length() : 0) + 1;
+    std::vector<const float*> xs;
+    if (!binned_columns(px.p, px.p ? px.length() : 0, n, nX, onesMask, xs)) return FMHIP_ERR_INVALID_ARGUMENT;
+    if ((int64_t)pc.length() < nb * nX || (int64_t)po.length() < n) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_binned_evaluate_host(pk.p, n, pb.p, (int)nb, xs.data(), nX, pc.p, po.p);
+}
 FMJ(jint, reduceMomentsBatchDevice)(JNIEnv* env, jclass, jlongArray vectors, jdoubleArray shifts, jlong deviceOut) {
     Pin<jlong> pv(env, vectors, JNI_ABORT); Pin<jdouble> ps(env, shifts, JNI_ABORT);
     if (!pv.p || (ps.p && ps.length() < pv.length())) return FMHIP_ERR_INVALID_ARGUMENT;
