@@ -184,6 +184,12 @@ static int guarded(F&& f) {
     }
 }
 
+template <typename F> static int host_only(F&& f) {          // a definition or a check that needs no engine
+    try { f(); return FMHIP_OK; }
+    catch (const Error& e) { g_last_error = e.what(); return e.code; }
+    catch (const std::bad_alloc&) { g_last_error = "host allocation failed"; return FMHIP_ERR_OUT_OF_MEMORY; }
+}
+
 static void need(const void* p, const char* what) {
     if (!p) throw Error(FMHIP_ERR_INVALID_ARGUMENT, std::string("null pointer: ") + what);
 }
@@ -237,6 +243,14 @@ template <typename F> static int on_all(F&& call) {
 }
 #define TE_OWNER(h, call) do { if (te::active()) { const int te_rc = te::owner_routed((h), [&]() -> int { return call; }); if (te_rc != te::NOT_MINE_TO_HANDLE) return te_rc; } } while (0)
 #define TE_LOCAL(arr, n, L, call) do { if (te::active()) { const int te_rc = te::with_local((arr), (n), [&](const fmhip_vec* L) -> int { return call; }); if (te_rc != te::NOT_MINE_TO_HANDLE) return te_rc; } } while (0)
+// the operands of a side pass as ONE list for TE_LOCAL (key?, x…, y…), so that foreign operands of any of them are imported by one call
+static std::vector<fmhip_vec> te_operands(fmhip_vec key, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y) {
+    std::vector<fmhip_vec> all;
+    if (key) all.push_back(key);
+    all.insert(all.end(), x, x + n_x);
+    all.insert(all.end(), y, y + n_y);
+    return all;
+}
 #define TE_ALL(mine, call) do { if (te::active()) return te::on_all([&](bool mine) -> int { (void)mine; return call; }); } while (0)
 
 extern "C" {
@@ -681,11 +695,9 @@ int xmom_local(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double*
 int fmhip_cross_moments(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out) {
     FRONT(cross_moments(x, n_x, y, n_y, sums_out));
     if (te::active()) {
-        // thread engines: both lists as one, so that foreign operands of either are imported by one call
         const int rc = guarded([&] { fm::xmom_check_counts(x, n_x, y, n_y, sums_out); });
         if (rc != FMHIP_OK) return rc;
-        std::vector<fmhip_vec> all(x, x + n_x);
-        all.insert(all.end(), y, y + n_y);
+        const std::vector<fmhip_vec> all = te_operands(0, x, n_x, y, n_y);
         TE_LOCAL(all.data(), n_x + n_y, L, fmhip_cross_moments(L, n_x, L + n_x, n_y, sums_out));
     }
     return guarded([&] {
@@ -702,11 +714,6 @@ int binned_xmom_local(fmhip_vec key, const double* bounds, int n_bins, const fmh
     return guarded([&] { Engine::get().binned_xmom_pass(key, bounds, n_bins, x, n_x, y, n_y, counts, sums); });
 }
 }
-template <typename F> static int host_only(F&& f) {          // a definition or a check that needs no engine
-    try { f(); return FMHIP_OK; }
-    catch (const Error& e) { g_last_error = e.what(); return e.code; }
-    catch (const std::bad_alloc&) { g_last_error = "host allocation failed"; return FMHIP_ERR_OUT_OF_MEMORY; }
-}
 }
 int fmhip_binned_cross_moments_host(const float* key, int64_t n, const double* bounds, int n_bins, const float* const* x, int n_x, const float* const* y, int n_y, int64_t* counts_out, double* sums_out) {
     return host_only([&] { fm::binned_cross_moments_host(key, n, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out); });
@@ -717,12 +724,9 @@ int fmhip_binned_evaluate_host(const float* key, int64_t n, const double* bounds
 int fmhip_binned_cross_moments(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, int64_t* counts_out, double* sums_out) {
     FRONT(binned_cross_moments(key, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out));
     if (te::active()) {
-        // thread engines: the key and both lists as one, so that foreign operands of any of them are imported by one call
         const int rc = host_only([&] { fm::binned_check_moments(key, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out); });
         if (rc != FMHIP_OK) return rc;
-        std::vector<fmhip_vec> all(1, key);
-        all.insert(all.end(), x, x + n_x);
-        all.insert(all.end(), y, y + n_y);
+        const std::vector<fmhip_vec> all = te_operands(key, x, n_x, y, n_y);
         TE_LOCAL(all.data(), 1 + n_x + n_y, L, fmhip_binned_cross_moments(L[0], bounds, n_bins, L + 1, n_x, L + 1 + n_x, n_y, counts_out, sums_out));
     }
     return guarded([&] {
@@ -744,8 +748,7 @@ int fmhip_binned_evaluate(fmhip_vec key, const double* bounds, int n_bins, const
     if (te::active()) {
         const int rc = host_only([&] { fm::binned_check_evaluate(key, bounds, n_bins, x, n_x, coefficients, out); });
         if (rc != FMHIP_OK) return rc;
-        std::vector<fmhip_vec> all(1, key);
-        all.insert(all.end(), x, x + n_x);
+        const std::vector<fmhip_vec> all = te_operands(key, x, n_x, nullptr, 0);
         TE_LOCAL(all.data(), 1 + n_x, L, fmhip_binned_evaluate(L[0], bounds, n_bins, L + 1, n_x, coefficients, out));
     }
     return guarded([&] { const fmhip_vec r = Engine::get().binned_eval(key, bounds, n_bins, x, n_x, coefficients, out); *out = r; });

@@ -1,10 +1,9 @@
 // binned_engine.hpp — the engine's side of the localized regression (kernels: binned_kernel.hip; definition and argument
-// checks: host/binned_regression.hpp).  Part of runtime.cpp's translation unit (included at its end, nowhere else), like
-// cross_moments_engine.hpp, whose pass the first of the two is modelled on.
+// checks: host/binned_regression.hpp).  Part of runtime.cpp's translation unit (included at its end behind side_pass_engine.hpp, nowhere
+// else); the first of the two is a pass in that frame, as the cross moments are.
 //
 // binned_xmom_pass: the count and the cross moments of up to 3 + 4 vectors PER BIN of a key vector — the block-diagonal normal equations of
-// a regression that is local in the key — from ONE launch.  It ends a step group, counts as a use of every vector, computes what is pending
-// below them in one flush, holds the vectors' storage across the wait, launches once and waits under the engine lock as read() does.
+// a regression that is local in the key — from ONE launch: one flush, the vectors' storage held, the wait under the engine lock.
 // binned_eval: the piecewise estimate as a NEW, materialised vector: one flush for pending operands, the bounds and the narrowed coefficients
 // go up in one copy that the host waits for (the pinned staging block is the engine's: it must be free again when the call returns), one
 // launch, and no wait for the launch itself.
@@ -21,7 +20,7 @@ namespace fm {
 static_assert(FM_BINNED_MAX_BINS == fmhost::FM_BINNED_MAX_BINS && FM_BINNED_MAX_X == fmhost::FM_BINNED_MAX_X && FM_BINNED_MAX_Y == fmhost::FM_BINNED_MAX_Y,
               "binned_kernel.h and host/binned_regression.hpp describe the same passes");
 
-// WEAK, like the cross-moments launcher: a host-only build whose stand-in for the kernels does not know these still links.
+// WEAK: see pass_need_kernel (tests/nulldev/null_binned.cpp has the stand-ins).
 hipError_t launch_binned_xmom(const DevBinnedXmomArgs& a, hipStream_t st) __attribute__((weak));
 hipError_t launch_binned_eval(const DevBinnedEvalArgs& a, hipStream_t st) __attribute__((weak));
 
@@ -49,10 +48,7 @@ static int binned_real(Engine& e, fmhip_vec key, const fmhip_vec* x, int n_x, co
     real[n_real++] = key;
     for (int i = 0; i < n_x; ++i) if (x[i]) real[n_real++] = x[i];
     for (int m = 0; m < n_y; ++m) real[n_real++] = y[m];
-    const int64_t n = e.node(real[0])->n;
-    for (int i = 1; i < n_real; ++i)
-        if (e.node(real[i])->n != n) throw Error(FMHIP_ERR_SIZE_MISMATCH, std::string(what) + " over vectors of different size");
-    if (n <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, std::string(what) + " of an empty vector");
+    e.pass_size(real, n_real, what);
     return n_real;
 }
 
@@ -61,9 +57,9 @@ void Engine::binned_xmom_pass(fmhip_vec key, const double* bounds, int n_bins, c
     binned_check_moments(key, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out);
     fmhip_vec real[1 + FM_BINNED_MAX_X + FM_BINNED_MAX_Y];
     const int n_real = binned_real(*this, key, x, n_x, y, n_y, real, "binned cross moments");
-    os_need_kernel(launch_binned_xmom != nullptr, "binned cross-moments");
-    OsHold hold;
-    os_prepare(real, n_real, hold);
+    pass_need_kernel(launch_binned_xmom != nullptr, "binned cross-moments");
+    PassHold hold;
+    pass_prepare(real, n_real, hold, "binned cross moments");
     DevBinnedXmomArgs a{};
     int r = 0;
     a.key = hold.ptrs[(size_t)r++];
@@ -83,29 +79,24 @@ void Engine::binned_xmom_pass(fmhip_vec key, const double* bounds, int n_bins, c
     a.n_slices = (a.n_bins + a.bins_per_slice - 1) / a.bins_per_slice;
     const uint32_t blocks = binned_blocks(hold.n);
     // pinned: [bounds (copied to the device in-stream)] [sums] [counts] [flag]; device: zero scratch = counters + counts, other = bounds + partials
-    const size_t tab_bytes = os_up256((size_t)FM_BINNED_MAX_BINS * 8), out_bytes = os_up256((size_t)n_bins * qe * 8), cnt_bytes = os_up256((size_t)FM_BINNED_MAX_BINS * 4);
-    const size_t counters_bytes = os_up256(((size_t)FM_BINNED_MAX_SLICES + 1) * 4);
+    const size_t tab_bytes = pass_up256((size_t)FM_BINNED_MAX_BINS * 8), out_bytes = pass_up256((size_t)n_bins * qe * 8), cnt_bytes = pass_up256((size_t)FM_BINNED_MAX_BINS * 4);
+    const size_t counters_bytes = pass_up256(((size_t)FM_BINNED_MAX_SLICES + 1) * 4);
     char* stage = (char*)ensure_stage(tab_bytes + out_bytes + cnt_bytes + 64);
-    os_scratch(counters_bytes + cnt_bytes, tab_bytes + (size_t)a.n_slices * FM_BINNED_ENTRIES * blocks * 8);
+    pass_scratch(counters_bytes + cnt_bytes, tab_bytes + (size_t)a.n_slices * FM_BINNED_ENTRIES * blocks * 8);
     double* out_host = reinterpret_cast<double*>(stage + tab_bytes);
     uint32_t* counts_host = reinterpret_cast<uint32_t*>(stage + tab_bytes + out_bytes);
     volatile uint64_t* flag = reinterpret_cast<volatile uint64_t*>(stage + tab_bytes + out_bytes + cnt_bytes);
-    a.counters = (uint32_t*)os_zero_;
-    a.counts_dev = reinterpret_cast<uint32_t*>((char*)os_zero_ + counters_bytes);
-    a.done_flag = const_cast<uint64_t*>(flag); a.done_value = ++os_seq_;
+    a.counters = (uint32_t*)pass_zero_;
+    a.counts_dev = reinterpret_cast<uint32_t*>((char*)pass_zero_ + counters_bytes);
     a.n = hold.n; a.tiles = (uint32_t)((hold.n + FM_BINNED_TILE - 1) / FM_BINNED_TILE);
-    a.bounds = (const double*)os_other_;
-    a.partials = reinterpret_cast<double*>((char*)os_other_ + tab_bytes);
+    a.bounds = (const double*)pass_other_;
+    a.partials = reinterpret_cast<double*>((char*)pass_other_ + tab_bytes);
     a.out_host = out_host; a.counts_host = counts_host;
     if (n_bins > 1) {
         std::memcpy(stage, bounds, (size_t)(n_bins - 1) * 8);
-        hip_check(hipMemcpyAsync(os_other_, stage, tab_bytes, hipMemcpyHostToDevice, stream_), "H2D(bin bounds)");
+        hip_check(hipMemcpyAsync(pass_other_, stage, tab_bytes, hipMemcpyHostToDevice, stream_), "H2D(bin bounds)");
     }
-    *flag = 0;
-    os_dirty_ = true;
-    hip_check(launch_binned_xmom(a, stream_), "binned cross-moments pass");
-    ++n_launches_;
-    os_wait(flag, a.done_value);
+    pass_launch(flag, a.done_flag, a.done_value, "binned cross-moments pass", [&] { return launch_binned_xmom(a, stream_); });
     const int q = fmhost::binnedSumsPerBin(n_x, n_y);
     for (int b = 0; b < n_bins; ++b) {
         counts_out[b] = (int64_t)counts_host[b];
@@ -121,26 +112,26 @@ fmhip_vec Engine::binned_eval(fmhip_vec key, const double* bounds, int n_bins, c
     binned_check_evaluate(key, bounds, n_bins, x, n_x, coefficients, out_checked);
     fmhip_vec real[1 + FM_BINNED_MAX_X];
     const int n_real = binned_real(*this, key, x, n_x, nullptr, 0, real, "binned evaluation");
-    os_need_kernel(launch_binned_eval != nullptr, "binned evaluation");
-    OsHold hold;
-    os_prepare(real, n_real, hold);
+    pass_need_kernel(launch_binned_eval != nullptr, "binned evaluation");
+    PassHold hold;
+    pass_prepare(real, n_real, hold, "binned evaluation");
     DevBinnedEvalArgs a{};
     int r = 0;
     a.key = hold.ptrs[(size_t)r++];
     for (int i = 0; i < n_x; ++i) a.x[i] = x[i] ? hold.ptrs[(size_t)r++] : 0;
     a.n = hold.n; a.n_bins = (uint32_t)n_bins; a.n_x = (uint32_t)n_x;
     // bounds and the coefficients narrowed to fp32 go up in one copy; the copy has left the pinned block before this call returns
-    const size_t tab_bytes = os_up256((size_t)FM_BINNED_MAX_BINS * 8), coef_bytes = os_up256((size_t)FM_BINNED_MAX_BINS * FM_BINNED_MAX_X * 4);
+    const size_t tab_bytes = pass_up256((size_t)FM_BINNED_MAX_BINS * 8), coef_bytes = pass_up256((size_t)FM_BINNED_MAX_BINS * FM_BINNED_MAX_X * 4);
     char* stage = (char*)ensure_stage(tab_bytes + coef_bytes);
-    os_scratch(os_up256(8), tab_bytes + coef_bytes);
+    pass_scratch(pass_up256(8), tab_bytes + coef_bytes);
     std::memset(stage, 0, tab_bytes + coef_bytes);
     if (n_bins > 1) std::memcpy(stage, bounds, (size_t)(n_bins - 1) * 8);
     float* c = reinterpret_cast<float*>(stage + tab_bytes);
     for (int i = 0; i < n_bins * n_x; ++i) c[i] = (float)coefficients[i];
-    hip_check(hipMemcpyAsync(os_other_, stage, tab_bytes + coef_bytes, hipMemcpyHostToDevice, stream_), "H2D(bin bounds and coefficients)");
+    hip_check(hipMemcpyAsync(pass_other_, stage, tab_bytes + coef_bytes, hipMemcpyHostToDevice, stream_), "H2D(bin bounds and coefficients)");
     hip_check(hipStreamSynchronize(stream_), "sync");
-    a.bounds = (const double*)os_other_;
-    a.coefficients = reinterpret_cast<const float*>((const char*)os_other_ + tab_bytes);
+    a.bounds = (const double*)pass_other_;
+    a.coefficients = reinterpret_cast<const float*>((const char*)pass_other_ + tab_bytes);
     Buffer* b = new_buffer(hold.n);
     a.out = (uint64_t)(uintptr_t)b->ptr;
     const hipError_t e = launch_binned_eval(a, stream_);

@@ -1,12 +1,10 @@
 // cross_moments_engine.hpp — the engine's side of the cross moments (kernel: fm_xmom_kernel in kernels.hip).  Part of
-// runtime.cpp's translation unit (included at its end, nowhere else), like order_stats_engine.hpp and for the same reasons.
+// runtime.cpp's translation unit (included at its end behind side_pass_engine.hpp, nowhere else).
 //
 // S[i][j] = Σ x_i·x_j (i <= j) and T[i][m] = Σ x_i·y_m of up to 12 + 4 vectors of one size in ONE launch: the normal equations of a
 // least-squares regression, which the reference's callers assemble from K(K+3)/2 products and as many blocking averages
-// (MonteCarloConditionalExpectationRegression: b_i.mult(b_j).getAverage()).  The pass follows the order-statistics passes: it ends a step
-// group, counts as a use of every vector (escape policy), computes what is pending below them in ONE flush, takes a reference on every
-// vector's STORAGE and forgets the nodes, launches once, waits under the engine lock as read() does — no queued release is performed
-// meanwhile —, and copies the sums out of pinned memory.  Shared storage (common rows) is only read.
+// (MonteCarloConditionalExpectationRegression: b_i.mult(b_j).getAverage()).  The pass stands in the frame of side_pass_engine.hpp: one
+// flush, the vectors' storage held, one launch, the wait under the engine lock; then the sums are copied out of pinned memory.
 #include "runtime.hpp"
 #include "kernels.h"
 
@@ -14,8 +12,8 @@
 
 namespace fm {
 
-// WEAK, like the order-statistics launchers: a host-only build whose stand-in for kernels.hip does not know the kernel still links, and
-// calling it there is FMHIP_ERR_UNSUPPORTED — the mirrors' generic path is a caller's choice (FMHIP_DEVICE_CROSS_MOMENTS=0), never the engine's.
+// WEAK: see pass_need_kernel (tests/nulldev/null_xmom.cpp has the stand-in); the mirrors' generic path is a caller's choice
+// (FMHIP_DEVICE_CROSS_MOMENTS=0), never the engine's.
 hipError_t launch_xmom(const DevXmomArgs& a, hipStream_t st) __attribute__((weak));
 
 // Everything that can be said about the arguments without looking at a vector
@@ -37,15 +35,10 @@ void Engine::xmom_pass(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y,
     fmhip_vec list[FM_XMOM_MAX_X + FM_XMOM_MAX_Y], real[FM_XMOM_MAX_X + FM_XMOM_MAX_Y];
     int n_real = 0;
     for (int i = 0; i < m; ++i) { list[i] = i < n_x ? x[i] : y[i - n_x]; if (list[i]) real[n_real++] = list[i]; }
-    {                                                        // handles, sizes, n > 0: before anything is flushed or launched
-        const int64_t n = node(real[0])->n;
-        for (int i = 1; i < n_real; ++i)
-            if (node(real[i])->n != n) throw Error(FMHIP_ERR_SIZE_MISMATCH, "cross moments over vectors of different size");
-        if (n <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "cross moments of an empty vector");
-    }
-    os_need_kernel(launch_xmom != nullptr, "cross-moments");
-    OsHold hold;
-    os_prepare(real, n_real, hold);
+    pass_size(real, n_real, "cross moments");                // handles, sizes, n > 0: before anything is flushed or launched
+    pass_need_kernel(launch_xmom != nullptr, "cross-moments");
+    PassHold hold;
+    pass_prepare(real, n_real, hold, "cross moments");
     DevXmomArgs a{};
     for (int i = 0, r = 0; i < m; ++i) a.vec[i] = list[i] ? hold.ptrs[(size_t)r++] : 0;
     // blocks of pairs of groups: (0,0); a second group adds (0,1), and (1,1) unless it holds dependents only
@@ -55,21 +48,16 @@ void Engine::xmom_pass(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y,
         if (n_x > FM_XMOM_GROUP) { a.row_group[2] = 1; a.col_group[2] = 1; a.n_blocks = 3; }
     }
     const uint32_t blocks = xmom_blocks(hold.n);
-    const size_t out_bytes = os_up256((size_t)FM_XMOM_MAX_BLOCKS * FM_XMOM_PAIRS * 8);
+    const size_t out_bytes = pass_up256((size_t)FM_XMOM_MAX_BLOCKS * FM_XMOM_PAIRS * 8);
     char* stage = (char*)ensure_stage(out_bytes + 64);
-    os_scratch(os_up256((FM_XMOM_MAX_BLOCKS + 1) * 4), (size_t)a.n_blocks * FM_XMOM_PAIRS * blocks * 8);
+    pass_scratch(pass_up256((FM_XMOM_MAX_BLOCKS + 1) * 4), (size_t)a.n_blocks * FM_XMOM_PAIRS * blocks * 8);
     double* out_host = reinterpret_cast<double*>(stage);
     volatile uint64_t* flag = reinterpret_cast<volatile uint64_t*>(stage + out_bytes);
-    a.counters = (uint32_t*)os_zero_;
-    a.done_flag = const_cast<uint64_t*>(flag); a.done_value = ++os_seq_;
+    a.counters = (uint32_t*)pass_zero_;
     a.n = hold.n; a.tiles = (uint32_t)((hold.n + FM_XMOM_TILE - 1) / FM_XMOM_TILE);
-    a.partials = (double*)os_other_;
+    a.partials = (double*)pass_other_;
     a.out_host = out_host;
-    *flag = 0;
-    os_dirty_ = true;
-    hip_check(launch_xmom(a, stream_), "cross-moments pass");
-    ++n_launches_;
-    os_wait(flag, a.done_value);
+    pass_launch(flag, a.done_flag, a.done_value, "cross-moments pass", [&] { return launch_xmom(a, stream_); });
     auto entry = [&](int i, int j) {                         // i <= j in the list
         const int gi = i / FM_XMOM_GROUP, gj = j / FM_XMOM_GROUP;
         return out_host[(size_t)(gi + gj) * FM_XMOM_PAIRS + (size_t)(i % FM_XMOM_GROUP) * FM_XMOM_GROUP + (size_t)(j % FM_XMOM_GROUP)];

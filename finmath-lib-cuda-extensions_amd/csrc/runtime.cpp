@@ -304,7 +304,7 @@ void Engine::shutdown() {
     schedule_cache_.clear(); schedule_cache_bytes_ = 0; dag_policies_.clear(); policy_reset();
     for (auto& kv : program_cache_) if (--kv.second->refs == 0) delete kv.second;
     program_cache_.clear();
-    os_release();
+    pass_release();
     pool_.purge();
     pool_ = Pool();
     if (stage_) (void)hipHostFree(stage_);
@@ -4230,6 +4230,7 @@ void Engine::profile_read(double* ms_total, int64_t* n) {
 
 } // namespace fm
 
+#include "side_pass_engine.hpp"        // Engine::pass_*: the frame the reducing passes below stand in
 #include "order_stats_engine.hpp"      // Engine::os_*: the order-statistics passes
 #include "cross_moments_engine.hpp"    // Engine::xmom_pass: the cross moments of a regression in one launch
 #include "mt_generate_engine.hpp"      // Engine::mt_bm_generate, mt_increments_generate: finmath's Mersenne-Twister stream entered on the device

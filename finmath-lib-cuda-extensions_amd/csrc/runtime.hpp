@@ -371,7 +371,8 @@ public:
     // sums of the elements strictly between two keys, the counts per interval of ascending bounds.  Every call computes what is pending
     // below its vectors in one flush, launches once, waits for the integers in pinned memory (under the lock, as read() does) and holds
     // the vectors' storage — not their nodes — across the wait.  The loop over the passes is the caller's (order_stats.hpp).
-    int64_t os_size(const fmhip_vec* hs, int count);                                       // the common size; SIZE_MISMATCH / INVALID_ARGUMENT (empty)
+    int64_t pass_size(const fmhip_vec* hs, int count, const char* what);                   // the common size of a side pass's vectors; SIZE_MISMATCH / INVALID_ARGUMENT (none, empty)
+    int64_t os_size(const fmhip_vec* hs, int count);
     void os_hist_pass(const fmhip_vec* hs, int count, int S, const uint32_t* slots, uint32_t shift, uint64_t* hist_out);
     void os_sum_pass(const fmhip_vec* hs, int count, const uint32_t* keys, double* sums_out);
     void os_count_pass(fmhip_vec h, const double* ascending_bounds, int m, uint64_t* counts_out);      // counts_out[m + 1]
@@ -474,15 +475,17 @@ private:
     void*  ensure_stage(size_t bytes);
     size_t ring_reserve(size_t bytes);
 
-    // order statistics: device scratch that is ZERO between launches (arrival counters, histograms; the kernels leave it so), scratch that
-    // need not be (tables, partial sums), the sequence number the completion flag receives
-    struct OsHold;
-    void os_prepare(const fmhip_vec* hs, int count, OsHold& hold);
-    void os_scratch(size_t zero_bytes, size_t other_bytes);
-    void os_wait(volatile uint64_t* flag, uint64_t value);
-    void os_release();
-    void* os_zero_ = nullptr; size_t os_zero_cap_ = 0; void* os_other_ = nullptr; size_t os_other_cap_ = 0;
-    uint64_t os_seq_ = 0; bool os_dirty_ = false;
+    // the frame of the reducing side passes (side_pass_engine.hpp): device scratch that is ZERO between launches (arrival counters,
+    // histograms; the kernels leave it so), scratch that need not be (tables, partial sums), the sequence number the completion flag
+    // receives.  `what` names the pass in the frame's messages.
+    struct PassHold;
+    void pass_prepare(const fmhip_vec* hs, int count, PassHold& hold, const char* what);
+    void pass_scratch(size_t zero_bytes, size_t other_bytes);
+    template <class Launch> void pass_launch(volatile uint64_t* flag, uint64_t*& done_flag, uint64_t& done_value, const char* what, Launch launch);
+    void pass_wait(volatile uint64_t* flag, uint64_t value, const char* what);
+    void pass_release();
+    void* pass_zero_ = nullptr; size_t pass_zero_cap_ = 0; void* pass_other_ = nullptr; size_t pass_other_cap_ = 0;
+    uint64_t pass_seq_ = 0; bool pass_dirty_ = false;
 
     Node* new_node(int64_t n);
     void collect_pending(const fmhip_vec* roots, int n_roots, std::vector<Node*>& graph);      // pending nodes below the roots, in recording order

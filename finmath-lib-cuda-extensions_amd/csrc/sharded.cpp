@@ -670,35 +670,68 @@ int expectation_collective(int* kind, char* why, int why_len) {
     });
 }
 
-// Order statistics (order_stats.hpp): every shard runs the pass on its block, the front adds the shards' integers — histograms and
-// counts exactly, the fp64 sums of a rank sum in shard order (like combine()).  The host loop over the passes is the one a single
-// engine runs; a shard that holds no path of a short vector is left out.
-static int64_t os_front_size(Shards& s, const fmhip_vec* vectors, int count) {
-    need(vectors, "vectors");
+// The reducing side passes — order statistics (order_stats.hpp), cross moments, localized regression: every shard runs the pass on its block
+// of paths, the front adds the shards' integers (histograms, counts: exact) and their fp64 sums in shard order (like combine()).  A shard that
+// holds no path of a short vector is left out.  What they share:
+// the common size of the vectors of a pass, before anything is posted; ones: handle 0 is the constant 1 and has no size
+static int64_t front_size(Shards& s, const fmhip_vec* hs, int count, const char* what, bool ones) {
+    need(hs, "vectors");
     if (count <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "count must be positive");
-    const int64_t n = s.vec(vectors[0]).n;
-    for (int i = 1; i < count; ++i) if (s.vec(vectors[i]).n != n) throw Error(FMHIP_ERR_SIZE_MISMATCH, "order statistics over vectors of different size");
-    if (n <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "order statistics of an empty vector");
+    int64_t n = -1;
+    for (int i = 0; i < count; ++i) {
+        if (ones && !hs[i]) continue;
+        const int64_t nh = s.vec(hs[i]).n;
+        if (n >= 0 && nh != n) throw Error(FMHIP_ERR_SIZE_MISMATCH, std::string(what) + " over vectors of different size");
+        n = nh;
+    }
+    if (n <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, std::string(what) + " of an empty vector");
     return n;
 }
-static bool os_shard_has_paths(const Worker& w, int64_t n) { int64_t off, cnt; shard_range(n, w.shards, w.shard, &off, &cnt); return cnt > 0; }
+// front handles → this shard's (0, the constant 1, stays 0)
+static std::vector<fmhip_vec> localize(Worker& w, const fmhip_vec* hs, int count) {
+    std::vector<fmhip_vec> l((size_t)count);
+    for (int i = 0; i < count; ++i) l[(size_t)i] = w.at(hs[i]);
+    return l;
+}
+// pass(w) = the pass's status on shard w, run on the shards that hold paths of a vector of n and waited for; took[d]: shard d ran it
+template <class Pass>
+static std::vector<char> post_where_paths(Shards& s, int64_t n, Pass pass) {
+    std::vector<char> took((size_t)s.D(), 0);
+    s.post([&](Worker& w) {
+        int64_t off, cnt; shard_range(n, w.shards, w.shard, &off, &cnt);
+        if (cnt > 0) took[(size_t)w.shard] = w.ok(pass(w)) ? 1 : 0;
+    });
+    s.wait();
+    return took;
+}
+// out[i] = Σ_d per[d][i]: integers (a shard that took no part left zeros) …
+template <class I>
+static void add_counts(const std::vector<std::vector<I>>& per, size_t m, I* out) {
+    for (size_t i = 0; i < m; ++i) { I c = 0; for (const auto& p : per) c += p[i]; out[i] = c; }
+}
+// … and fp64 sums, in shard order.  With `took`, a shard that took no part is skipped; without, its +0.0 is added: the two differ where the
+// sum is -0.0, and each caller keeps what it has always done.
+static void add_sums(const std::vector<std::vector<double>>& per, size_t m, double* out, const std::vector<char>* took = nullptr) {
+    for (size_t i = 0; i < m; ++i) {
+        double t = 0.0; bool first = true;
+        for (size_t d = 0; d < per.size(); ++d) { if (took && !(*took)[d]) continue; t = first ? per[d][i] : t + per[d][i]; first = false; }
+        out[i] = t;
+    }
+}
+
+// Order statistics: the host loop over the passes is the one a single engine runs.
 static void os_front_select(Shards& s, const fmhip_vec* vectors, int count, int64_t n, const int64_t* ranks, int n_ranks, os::Selected* sel) {
     os::select([&](int S, const uint32_t* slots, uint32_t shift, uint64_t* hist) {
         const size_t m = (size_t)count * S * os::BINS;
         std::vector<std::vector<uint64_t>> per((size_t)s.D(), std::vector<uint64_t>(m, 0));
-        s.post([&](Worker& w) {
-            if (!os_shard_has_paths(w, n)) return;
-            std::vector<fmhip_vec> l; for (int i = 0; i < count; ++i) l.push_back(w.at(vectors[i]));
-            w.ok(os_local_hist(l.data(), count, S, slots, shift, per[(size_t)w.shard].data()));
-        });
-        s.wait();
-        for (size_t i = 0; i < m; ++i) { uint64_t c = 0; for (const auto& p : per) c += p[i]; hist[i] = c; }
+        post_where_paths(s, n, [&](Worker& w) { return os_local_hist(localize(w, vectors, count).data(), count, S, slots, shift, per[(size_t)w.shard].data()); });
+        add_counts(per, m, hist);
     }, count, ranks, n_ranks, sel);
 }
 int select_ranks_batch(const fmhip_vec* vectors, int count, const int64_t* ranks, int n_ranks, double* values_out) {
     return fronted([&](Shards& s) {
         need(ranks, "ranks"); need(values_out, "values_out");
-        const int64_t n = os_front_size(s, vectors, count);
+        const int64_t n = front_size(s, vectors, count, "order statistics", false);
         if (n_ranks < 1) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "n_ranks must be positive");
         for (int j = 0; j < n_ranks; ++j) if (ranks[j] < 0 || ranks[j] >= n) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "rank " + std::to_string(ranks[j]) + " outside a sample of " + std::to_string(n));
         std::vector<os::Selected> sel((size_t)count * n_ranks);
@@ -709,7 +742,7 @@ int select_ranks_batch(const fmhip_vec* vectors, int count, const int64_t* ranks
 int rank_sums_batch(const fmhip_vec* vectors, int count, int64_t rank_from, int64_t rank_to, double* sums_out) {
     return fronted([&](Shards& s) {
         need(sums_out, "sums_out");
-        const int64_t n = os_front_size(s, vectors, count);
+        const int64_t n = front_size(s, vectors, count, "order statistics", false);
         if (rank_from < 0 || rank_to >= n || rank_from > rank_to) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "bad rank range for a sample of " + std::to_string(n));
         const int64_t ranks[2] = { rank_from, rank_to };
         std::vector<os::Selected> sel((size_t)count * 2);
@@ -720,13 +753,8 @@ int rank_sums_batch(const fmhip_vec* vectors, int count, int64_t rank_from, int6
         std::vector<double> inner((size_t)count, 0.0);
         if (any) {
             std::vector<std::vector<double>> per((size_t)s.D(), std::vector<double>((size_t)count, 0.0));
-            s.post([&](Worker& w) {
-                if (!os_shard_has_paths(w, n)) return;
-                std::vector<fmhip_vec> l; for (int i = 0; i < count; ++i) l.push_back(w.at(vectors[i]));
-                w.ok(os_local_sum(l.data(), count, keys.data(), per[(size_t)w.shard].data()));
-            });
-            s.wait();
-            for (int k = 0; k < count; ++k) { double t = per[0][(size_t)k]; for (size_t d = 1; d < per.size(); ++d) t += per[d][(size_t)k]; inner[(size_t)k] = t; }      // shard order
+            post_where_paths(s, n, [&](Worker& w) { return os_local_sum(localize(w, vectors, count).data(), count, keys.data(), per[(size_t)w.shard].data()); });
+            add_sums(per, (size_t)count, inner.data());
         }
         for (int k = 0; k < count; ++k) sums_out[k] = os::rank_sum(sel[2 * (size_t)k], sel[2 * (size_t)k + 1], rank_from, rank_to, inner[(size_t)k]);
     });
@@ -735,97 +763,69 @@ int count_not_above(fmhip_vec v, const double* bounds, int n_bounds, int64_t* co
     return fronted([&](Shards& s) {
         need(bounds, "bounds"); need(counts_out, "counts_out");
         if (n_bounds < 1) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "n_bounds must be positive");
-        const int64_t n = os_front_size(s, &v, 1);
+        const int64_t n = front_size(s, &v, 1, "order statistics", false);
         os_counts_from_passes(bounds, n_bounds, counts_out, [&](const double* asc, int m, uint64_t* out) {
             std::vector<std::vector<uint64_t>> per((size_t)s.D(), std::vector<uint64_t>((size_t)m + 1, 0));
-            s.post([&](Worker& w) { if (os_shard_has_paths(w, n)) w.ok(os_local_count(w.at(v), asc, m, per[(size_t)w.shard].data())); });
-            s.wait();
-            for (int i = 0; i <= m; ++i) { uint64_t c = 0; for (const auto& p : per) c += p[(size_t)i]; out[i] = c; }
+            post_where_paths(s, n, [&](Worker& w) { return os_local_count(w.at(v), asc, m, per[(size_t)w.shard].data()); });
+            add_counts(per, (size_t)m + 1, out);
         });
     });
 }
 
-// Cross moments: every shard runs the pass on its block of paths, the front adds the shards' sums in shard order (like combine()); a shard
-// that holds no path of a short vector is left out.
+// Cross moments
 int cross_moments(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out) {
     return fronted([&](Shards& s) {
         xmom_check_counts(x, n_x, y, n_y, sums_out);
         std::vector<fmhip_vec> all(x, x + n_x);
         all.insert(all.end(), y, y + n_y);
-        int64_t n = -1;
-        for (fmhip_vec h : all) {
-            if (!h) continue;
-            const int64_t nh = s.vec(h).n;
-            if (n >= 0 && nh != n) throw Error(FMHIP_ERR_SIZE_MISMATCH, "cross moments over vectors of different size");
-            n = nh;
-        }
-        if (n <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "cross moments of an empty vector");
+        const int64_t n = front_size(s, all.data(), n_x + n_y, "cross moments", true);
         const size_t m = (size_t)n_x * (n_x + 1) / 2 + (size_t)n_x * n_y;
         std::vector<std::vector<double>> per((size_t)s.D(), std::vector<double>(m, 0.0));
-        std::vector<char> took((size_t)s.D(), 0);
-        s.post([&](Worker& w) {
-            if (!os_shard_has_paths(w, n)) return;
-            std::vector<fmhip_vec> l; for (fmhip_vec h : all) l.push_back(h ? w.at(h) : 0);
-            took[(size_t)w.shard] = w.ok(xmom_local(l.data(), n_x, l.data() + n_x, n_y, per[(size_t)w.shard].data())) ? 1 : 0;
+        const std::vector<char> took = post_where_paths(s, n, [&](Worker& w) {
+            const std::vector<fmhip_vec> l = localize(w, all.data(), n_x + n_y);
+            return xmom_local(l.data(), n_x, l.data() + n_x, n_y, per[(size_t)w.shard].data());
         });
-        s.wait();
-        for (size_t i = 0; i < m; ++i) {
-            double t = 0.0; bool first = true;
-            for (size_t d = 0; d < per.size(); ++d) { if (!took[d]) continue; t = first ? per[d][i] : t + per[d][i]; first = false; }      // shard order
-            sums_out[i] = t;
-        }
+        add_sums(per, m, sums_out, &took);
     });
 }
 
-// Localized regression: every shard runs the pass on its block of paths; the front adds the shards' counts, and their sums in shard order.
-// The evaluation is per shard: a new vector whose blocks are the shards' results.
-static int64_t binned_front_size(Shards& s, fmhip_vec key, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, const char* what) {
-    const int64_t n = s.vec(key).n;
-    for (int i = 0; i < n_x + n_y; ++i) {
-        const fmhip_vec h = i < n_x ? x[i] : y[i - n_x];
-        if (h && s.vec(h).n != n) throw Error(FMHIP_ERR_SIZE_MISMATCH, std::string(what) + " over vectors of different size");
-    }
-    if (n <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, std::string(what) + " of an empty vector");
-    return n;
+// Localized regression.  The evaluation is per shard: a new vector whose blocks are the shards' results.
+static std::vector<fmhip_vec> binned_all(fmhip_vec key, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y) {      // key, x…, y…
+    std::vector<fmhip_vec> all(1, key);
+    all.insert(all.end(), x, x + n_x);
+    all.insert(all.end(), y, y + n_y);
+    return all;
 }
 int binned_cross_moments(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, int64_t* counts_out, double* sums_out) {
     return fronted([&](Shards& s) {
         binned_check_moments(key, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out);
-        const int64_t n = binned_front_size(s, key, x, n_x, y, n_y, "binned cross moments");
+        const std::vector<fmhip_vec> all = binned_all(key, x, n_x, y, n_y);
+        const int64_t n = front_size(s, all.data(), (int)all.size(), "binned cross moments", true);
         const size_t m = (size_t)n_bins * ((size_t)n_x * (n_x + 1) / 2 + (size_t)n_x * n_y);
         std::vector<std::vector<double>> per((size_t)s.D(), std::vector<double>(m, 0.0));
         std::vector<std::vector<int64_t>> cnt((size_t)s.D(), std::vector<int64_t>((size_t)n_bins, 0));
-        std::vector<char> took((size_t)s.D(), 0);
-        s.post([&](Worker& w) {
-            if (!os_shard_has_paths(w, n)) return;
-            std::vector<fmhip_vec> lx, ly;
-            for (int i = 0; i < n_x; ++i) lx.push_back(x[i] ? w.at(x[i]) : 0);
-            for (int i = 0; i < n_y; ++i) ly.push_back(w.at(y[i]));
-            took[(size_t)w.shard] = w.ok(binned_xmom_local(w.at(key), bounds, n_bins, lx.data(), n_x, n_y ? ly.data() : nullptr, n_y, cnt[(size_t)w.shard].data(), per[(size_t)w.shard].data())) ? 1 : 0;
+        const std::vector<char> took = post_where_paths(s, n, [&](Worker& w) {
+            const std::vector<fmhip_vec> l = localize(w, all.data(), (int)all.size());
+            return binned_xmom_local(l[0], bounds, n_bins, l.data() + 1, n_x, n_y ? l.data() + 1 + n_x : nullptr, n_y, cnt[(size_t)w.shard].data(), per[(size_t)w.shard].data());
         });
-        s.wait();
-        for (int b = 0; b < n_bins; ++b) { int64_t c = 0; for (size_t d = 0; d < cnt.size(); ++d) if (took[d]) c += cnt[d][(size_t)b]; counts_out[b] = c; }
-        for (size_t i = 0; i < m; ++i) {
-            double t = 0.0; bool first = true;
-            for (size_t d = 0; d < per.size(); ++d) { if (!took[d]) continue; t = first ? per[d][i] : t + per[d][i]; first = false; }      // shard order
-            sums_out[i] = t;
-        }
+        add_counts(cnt, (size_t)n_bins, counts_out);
+        add_sums(per, m, sums_out, &took);
     });
 }
 int binned_evaluate(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const double* coefficients, fmhip_vec* out) {
     return fronted([&](Shards& s) {
         binned_check_evaluate(key, bounds, n_bins, x, n_x, coefficients, out);
-        const int64_t n = binned_front_size(s, key, x, n_x, nullptr, 0, "binned evaluation");
+        auto all = std::make_shared<std::vector<fmhip_vec>>(binned_all(key, x, n_x, nullptr, 0));
+        const int64_t n = front_size(s, all->data(), 1 + n_x, "binned evaluation", true);
         auto bd = std::make_shared<std::vector<double>>(bounds ? bounds : coefficients, (bounds ? bounds : coefficients) + (bounds ? n_bins - 1 : 0));
         auto co = std::make_shared<std::vector<double>>(coefficients, coefficients + (size_t)n_bins * n_x);
-        auto xs = std::make_shared<std::vector<fmhip_vec>>(x, x + n_x);
         const fmhip_vec id = s.fresh(n);
         s.post([=](Worker& w) {
             int64_t off, cnt; shard_range(n, w.shards, w.shard, &off, &cnt);
             fmhip_vec h = 0;
             if (cnt <= 0) { if (w.ok(fmhip_vec_create_uninitialized(0, &h))) w.bind(id, h); return; }
-            std::vector<fmhip_vec> l; for (fmhip_vec v : *xs) l.push_back(v ? w.at(v) : 0);
-            if (w.ok(fmhip_binned_evaluate(w.at(key), bd->data(), n_bins, l.data(), n_x, co->data(), &h))) w.bind(id, h);
+            const std::vector<fmhip_vec> l = localize(w, all->data(), 1 + n_x);
+            if (w.ok(fmhip_binned_evaluate(l[0], bd->data(), n_bins, l.data() + 1, n_x, co->data(), &h))) w.bind(id, h);
         });
         // eager, like the call on one engine: a shard's refusal (no kernel, a value that was given up) is THIS call's status
         try { s.wait(); } catch (...) { s.post([=](Worker& w) { if (const fmhip_vec h = w.at(id)) { (void)fmhip_vec_release(h); w.local.erase(id); } }); s.meta.erase(id); throw; }

@@ -1,0 +1,132 @@
+// side_pass_engine.hpp — the frame of the engine's reducing side passes: a kernel of its own beside the lazy graph that leaves a few numbers
+// in pinned memory (order_stats_engine.hpp, cross_moments_engine.hpp, binned_engine.hpp).  Part of runtime.cpp's translation unit (included
+// at its end, before the passes, nowhere else): Engine member functions in a file of their own because runtime.cpp is long enough, and in
+// that translation unit so that every build that lists the engine's sources — the library's, the sanitizer builds against the null device —
+// has them without being told.
+//
+// A pass: checks its arguments (pass_size among them) before anything is flushed or launched, ends a step group, counts as a use of every
+// vector (escape policy), computes what is pending or deferred below the batch in ONE flush, takes a reference on every vector's STORAGE and
+// forgets the nodes (pass_prepare) — the wait that follows may not rely on a Node* (queued releases are not performed during it either: it
+// polls the flag and falls back to the plain stream wait) —, lays out its pinned block as [tables the launch reads] [what it writes] [flag]
+// and its device scratch (pass_scratch), launches once and waits under the engine lock as read() does (pass_launch).  Shared storage (common
+// rows) is only read.  `what` names the pass in whatever the frame has to say.
+#include "runtime.hpp"
+
+#include <algorithm>
+#include <string>
+#if defined(__x86_64__)
+#include <immintrin.h>
+#endif
+
+namespace fm {
+
+// The passes' launchers are WEAK references: a host-only build of the engine whose stand-in for the kernels does not know one
+// (tests/nulldev/null_hip.cpp; null_os.cpp, null_xmom.cpp and null_binned.cpp add them) still links.  Calling one that is missing is an
+// error — there is no fallback: the mirrors' host path is a caller's choice, never the engine's.
+static void pass_need_kernel(bool present, const char* what) {
+    if (!present) throw Error(FMHIP_ERR_UNSUPPORTED, std::string("this build of the engine has no ") + what + " kernel");
+}
+
+static size_t pass_up256(size_t b) { return (b + 255) & ~size_t(255); }
+
+struct Engine::PassHold {          // the storage of a batch, referenced for the duration of a pass
+    Engine* e = nullptr;
+    std::vector<Buffer*> held;
+    std::vector<uint64_t> ptrs;
+    int64_t n = 0;
+    ~PassHold() { for (Buffer* b : held) e->buffer_unref(b); }
+};
+
+// hs: the handles of a pass that have a node (the constant 1, handle 0 among the x of a regression, has none and no size: its callers leave it out)
+int64_t Engine::pass_size(const fmhip_vec* hs, int count, const char* what) {
+    require_init();
+    if (!hs || count <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, std::string(what) + " of no vector");
+    const int64_t n = node(hs[0])->n;
+    for (int i = 1; i < count; ++i)
+        if (node(hs[i])->n != n) throw Error(FMHIP_ERR_SIZE_MISMATCH, std::string(what) + " over vectors of different size");
+    if (n <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, std::string(what) + " of an empty vector");
+    return n;
+}
+
+void Engine::pass_prepare(const fmhip_vec* hs, int count, PassHold& hold, const char* what) {
+    hold.e = this;
+    hold.n = pass_size(hs, count, what);
+    if (count > 65535) throw Error(FMHIP_ERR_INVALID_ARGUMENT, std::string("more than 65535 vectors in one ") + what + " call");
+    end_step_group();
+    std::vector<Node*> nds((size_t)count);
+    bool pending = false, missing = false;
+    for (int i = 0; i < count; ++i) {
+        Node* nd = nds[(size_t)i] = node(hs[i]);
+        if (nd->discarded && !nd->buf) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "the value of this vector does not exist: it was given up (fmhip_vec_give_up_values: only its moments were taken), or lost in a launch that failed");
+        touch(nd);
+        missing |= !nd->buf;
+        pending |= !nd->buf && !nd->deferred;
+    }
+    if (missing) {
+        // one flush for the batch: everything pending runs as the batched launches it would have run as anyway; a handle keeps its node
+        // alive through it (the caller holds every handle of the batch), so the nodes are looked at again, not remembered, behind it
+        if (pending && count > 1) flush_all();
+        for (int i = 0; i < count; ++i) { Node* nd = node(hs[i]); if (!nd->buf) materialize({ nd }); }
+        for (int i = 0; i < count; ++i) nds[(size_t)i] = node(hs[i]);
+    }
+    hold.held.reserve((size_t)count); hold.ptrs.reserve((size_t)count);
+    for (Node* nd : nds) {
+        if (!nd->buf) throw Error(FMHIP_ERR_HIP, "a vector of the batch could not be computed");
+        nd->buf->refs++;
+        hold.held.push_back(nd->buf);
+        hold.ptrs.push_back((uint64_t)(uintptr_t)nd->buf->ptr);
+    }
+}
+
+void Engine::pass_scratch(size_t zero_bytes, size_t other_bytes) {
+    auto grow = [&](void*& p, size_t& cap, size_t need, bool zero) {
+        if (need <= cap && !(zero && pass_dirty_)) return;
+        if (need > cap) {
+            if (p) { hip_check(hipStreamSynchronize(stream_), "sync"); (void)hipFree(p); p = nullptr; cap = 0; }
+            const size_t c = std::max(pass_up256(need), size_t(1) << 16);
+            hip_check(hipMalloc(&p, c), "hipMalloc(side pass scratch)");
+            cap = c;
+        }
+        if (zero) hip_check(hipMemsetAsync(p, 0, cap, stream_), "hipMemsetAsync(side pass scratch)");
+    };
+    grow(pass_zero_, pass_zero_cap_, zero_bytes, true);
+    pass_dirty_ = false;
+    grow(pass_other_, pass_other_cap_, other_bytes, false);
+}
+
+void Engine::pass_release() {
+    if (pass_zero_) (void)hipFree(pass_zero_);
+    if (pass_other_) (void)hipFree(pass_other_);
+    pass_zero_ = pass_other_ = nullptr; pass_zero_cap_ = pass_other_cap_ = 0; pass_dirty_ = false;
+}
+
+void Engine::pass_wait(volatile uint64_t* flag, uint64_t value, const char* what) {
+    const auto t0 = std::chrono::steady_clock::now();
+    bool arrived = *flag == value;
+    for (uint32_t spins = 1; !arrived; ++spins) {
+#if defined(__x86_64__)
+        _mm_pause();
+#endif
+        arrived = *flag == value;
+        if (!arrived && (spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
+    }
+    if (!arrived) { hip_check(hipStreamSynchronize(stream_), "side pass sync"); arrived = *flag == value; }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (!arrived) throw Error(FMHIP_ERR_HIP, std::string("the ") + what + " ended without delivering its results");
+    pass_dirty_ = false;
+}
+
+// The armed launch.  `flag`: the last word of the pass's pinned block; done_flag, done_value: where the launch's arguments want it and the
+// value it receives; launch(): the launcher's status.  The zero scratch counts as dirty until the flag has arrived: a launch that fails
+// half-way leaves counters behind, and the next pass clears them (pass_scratch).
+template <class Launch>
+inline void Engine::pass_launch(volatile uint64_t* flag, uint64_t*& done_flag, uint64_t& done_value, const char* what, Launch launch) {
+    done_flag = const_cast<uint64_t*>(flag); done_value = ++pass_seq_;
+    *flag = 0;
+    pass_dirty_ = true;
+    hip_check(launch(), what);
+    ++n_launches_;
+    pass_wait(flag, done_value, what);
+}
+
+} // namespace fm

@@ -18,7 +18,7 @@ NULLDEV = os.path.join(ROOT, "tests", "nulldev")
 def built():
     if not shutil.which("g++") or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
         pytest.skip("needs g++ and the HIP headers")
-    r = subprocess.run(["make", "-C", NULLDEV, "-f", "levy.mk", "-j8", "levy_asan", "levy_tsan"], capture_output=True, text=True, timeout=1200)
+    r = subprocess.run(["make", "-C", NULLDEV, "-j8", "levy_asan", "levy_tsan"], capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     return os.path.join(NULLDEV, "build")
 
