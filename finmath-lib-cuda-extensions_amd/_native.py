@@ -24,7 +24,7 @@ SYMBOLS = [
     "fmhip_reduce_moments", "fmhip_reduce_moments_batch", "fmhip_reduce_moments_batch_device", "fmhip_reduce_moments_device",
     "fmhip_reduce_moments_batch_begin", "fmhip_reduce_moments_batch_end", "fmhip_reduce_moments_batch_devices", "fmhip_get_stream_of", "fmhip_expectation_collective",
     "fmhip_set_expectation_comm", "fmhip_expectation_world", "fmhip_expectation_combine",
-    "fmhip_select_ranks_batch", "fmhip_rank_sums_batch", "fmhip_count_not_above", "fmhip_cross_moments",
+    "fmhip_select_ranks_batch", "fmhip_rank_sums_batch", "fmhip_count_not_above", "fmhip_cross_moments", "fmhip_cross_moments_wide",
     "fmhip_binned_cross_moments", "fmhip_binned_cross_moments_host", "fmhip_binned_evaluate", "fmhip_binned_evaluate_host",
     "fmhip_program_create", "fmhip_program_release", "fmhip_program_launch_count", "fmhip_program_shape",
     "fmhip_program_run", "fmhip_program_run_into",
@@ -165,6 +165,7 @@ def lib():
         "fmhip_reduce_moments_batch_begin": [pv, i32, C.POINTER(dbl), pv], "fmhip_vec_give_up_values": [pv, i32], "fmhip_reduce_moments_batch_end": [i64, C.POINTER(Moments), i32],
         "fmhip_select_ranks_batch": [pv, i32, C.POINTER(i64), i32, C.POINTER(dbl)], "fmhip_rank_sums_batch": [pv, i32, i64, i64, C.POINTER(dbl)], "fmhip_count_not_above": [vec, C.POINTER(dbl), i32, C.POINTER(i64)],
         "fmhip_cross_moments": [pv, i32, pv, i32, C.POINTER(dbl)],
+        "fmhip_cross_moments_wide": [pv, i32, pv, i32, C.POINTER(dbl)],
         "fmhip_binned_cross_moments": [vec, C.POINTER(dbl), i32, pv, i32, pv, i32, C.POINTER(i64), C.POINTER(dbl)],
         "fmhip_binned_cross_moments_host": [vp, i64, C.POINTER(dbl), i32, C.POINTER(vp), i32, C.POINTER(vp), i32, C.POINTER(i64), C.POINTER(dbl)],
         "fmhip_binned_evaluate": [vec, C.POINTER(dbl), i32, pv, i32, C.POINTER(dbl), pv],

@@ -707,6 +707,27 @@ int fmhip_cross_moments(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y
     });
 }
 
+// ---------------------------------------------------------------- wide cross moments (xmom_wide_engine.hpp)
+extern "C++" {
+namespace fm {
+int xmom_wide_local(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums) { return guarded([&] { Engine::get().xmom_wide_pass(x, n_x, y, n_y, sums); }); }
+}
+}
+int fmhip_cross_moments_wide(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out) {
+    FRONT(cross_moments_wide(x, n_x, y, n_y, sums_out));
+    if (te::active()) {
+        const int rc = guarded([&] { fm::xmom_wide_check_counts(x, n_x, y, n_y, sums_out); });
+        if (rc != FMHIP_OK) return rc;
+        const std::vector<fmhip_vec> all = te_operands(0, x, n_x, y, n_y);
+        TE_LOCAL(all.data(), n_x + n_y, L, fmhip_cross_moments_wide(L, n_x, L + n_x, n_y, sums_out));
+    }
+    return guarded([&] {
+        Engine& e = Engine::get();
+        e.xmom_wide_pass(x, n_x, y, n_y, sums_out);
+        comm_add_sums(e, sums_out, (size_t)n_x * (n_x + 1) / 2 + (size_t)n_x * n_y);      // one gather, rank order: the sums of the global sample
+    });
+}
+
 // ---------------------------------------------------------------- localized regression (binned_engine.hpp)
 extern "C++" {
 namespace fm {

@@ -4236,3 +4236,4 @@ void Engine::profile_read(double* ms_total, int64_t* n) {
 #include "mt_generate_engine.hpp"      // Engine::mt_bm_generate, mt_increments_generate: finmath's Mersenne-Twister stream entered on the device
 #include "sobol_engine.hpp"            // Engine::sobol_bm_generate: Sobol' points through a Brownian bridge
 #include "binned_engine.hpp"           // Engine::binned_xmom_pass, binned_eval: the cross moments per bin of a key, the piecewise estimate
+#include "xmom_wide_engine.hpp"        // Engine::xmom_wide_pass: the cross moments of up to 64 vectors in one launch on the matrix cores

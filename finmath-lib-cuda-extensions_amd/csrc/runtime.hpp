@@ -381,6 +381,8 @@ public:
     // n_x·n_y sums Σ x_i·y_m, in fp64, from ONE launch; a handle of 0 among x is the constant 1.  Arguments are checked before anything is
     // flushed or launched; otherwise the pass behaves as the order-statistics passes do (one flush, storage held across the wait).
     void xmom_pass(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out);
+    // the same for up to 64 vectors in all, on the matrix cores (xmom_wide_engine.hpp): same layout, same checks, its own bits
+    void xmom_wide_pass(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out);
 
     // localized regression (binned_engine.hpp): per bin of `key` (bin(k) = #{ j : bounds[j] < k }) the count and the cross moments
     // of fmhip_cross_moments' layout, from ONE launch; and Σ_i x_i·(float)coefficients[bin·n_x + i] as a new, materialised vector.  Arguments are
@@ -717,6 +719,8 @@ struct HostTimer {
 
 // what can be said about the arguments of fmhip_cross_moments without looking at a vector: counts in range, pointers, no 0 among y, a vector among x
 void xmom_check_counts(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, const double* sums_out);
+// the same for fmhip_cross_moments_wide: n_x >= 1, n_y >= 0, n_x + n_y <= 64
+void xmom_wide_check_counts(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, const double* sums_out);
 // what can be said about the arguments of fmhip_bm_generate_mersenne_device without a device (mt_generate_engine.hpp)
 void mt_bm_check(int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, const fmhip_vec* out);
 // the same for fmhip_increments_generate_device and, with a block at offset 0, fmhip_increments_host (mt_generate_engine.hpp;

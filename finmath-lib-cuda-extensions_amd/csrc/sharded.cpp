@@ -772,21 +772,28 @@ int count_not_above(fmhip_vec v, const double* bounds, int n_bounds, int64_t* co
     });
 }
 
-// Cross moments
-int cross_moments(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out) {
+// Cross moments, narrow (12 + 4 vectors) and wide (64): the shards' sums add in shard order
+template <class Check, class Local>
+static int front_cross_moments(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out, const char* what, Check check, Local local) {
     return fronted([&](Shards& s) {
-        xmom_check_counts(x, n_x, y, n_y, sums_out);
+        check(x, n_x, y, n_y, sums_out);
         std::vector<fmhip_vec> all(x, x + n_x);
         all.insert(all.end(), y, y + n_y);
-        const int64_t n = front_size(s, all.data(), n_x + n_y, "cross moments", true);
+        const int64_t n = front_size(s, all.data(), n_x + n_y, what, true);
         const size_t m = (size_t)n_x * (n_x + 1) / 2 + (size_t)n_x * n_y;
         std::vector<std::vector<double>> per((size_t)s.D(), std::vector<double>(m, 0.0));
         const std::vector<char> took = post_where_paths(s, n, [&](Worker& w) {
             const std::vector<fmhip_vec> l = localize(w, all.data(), n_x + n_y);
-            return xmom_local(l.data(), n_x, l.data() + n_x, n_y, per[(size_t)w.shard].data());
+            return local(l.data(), n_x, l.data() + n_x, n_y, per[(size_t)w.shard].data());
         });
         add_sums(per, m, sums_out, &took);
     });
+}
+int cross_moments(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out) {
+    return front_cross_moments(x, n_x, y, n_y, sums_out, "cross moments", xmom_check_counts, xmom_local);
+}
+int cross_moments_wide(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out) {
+    return front_cross_moments(x, n_x, y, n_y, sums_out, "wide cross moments", xmom_wide_check_counts, xmom_wide_local);
 }
 
 // Localized regression.  The evaluation is per shard: a new vector whose blocks are the shards' results.

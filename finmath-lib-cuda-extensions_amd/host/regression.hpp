@@ -92,7 +92,11 @@ private:
     // scalars folded through the constant-1 entry (c·Σx_j, c·c'·n)
     bool normalEquationsOnePass(const RV& dependent, std::vector<double>& A, std::vector<double>& b) const {
         const int K = (int)estimator_.size();
-        if (!deviceCrossMoments() || K < 1 || K > 12 || dependent->isDeterministic() || !dependent->orderStatisticsHandle()) return false;
+        // up to 12 basis functions: fmhip_cross_moments and its bits; up to 60: fmhip_cross_moments_wide, unless
+        // FMHIP_DEVICE_WIDE_MOMENTS=0 (read per call) sends them pair by pair
+        const bool wide = K > 12;
+        if (wide) { const char* knob = std::getenv("FMHIP_DEVICE_WIDE_MOMENTS"); if (knob && knob[0] == '0' && knob[1] == 0) return false; }
+        if (!deviceCrossMoments() || K < 1 || K > 60 || dependent->isDeterministic() || !dependent->orderStatisticsHandle()) return false;
         std::vector<fmhip_vec> x((size_t)K);
         std::vector<double> scale((size_t)K, 1.0);
         const RandomVariable* sized = nullptr;
@@ -107,7 +111,7 @@ private:
         if (!sized) return false;
         const fmhip_vec y = dependent->orderStatisticsHandle();
         std::vector<double> sums((size_t)K * (K + 1) / 2 + (size_t)K);
-        check(fmhip_cross_moments(x.data(), K, &y, 1, sums.data()));
+        check(wide ? fmhip_cross_moments_wide(x.data(), K, &y, 1, sums.data()) : fmhip_cross_moments(x.data(), K, &y, 1, sums.data()));
         const double n = (double)sized->sampleSize();
         size_t at = 0;
         for (int i = 0; i < K; ++i) for (int j = i; j < K; ++j, ++at) A[(size_t)i * K + j] = A[(size_t)j * K + i] = sums[at] * (scale[(size_t)i] * scale[(size_t)j]) / n;

@@ -16,6 +16,8 @@ a RandomVariableFactory by injection (LIBORMarketModelCalibrationATMTest.java:35
                             time, integrated against its density — as its check
     bermudan_option_mc      Longstaff–Schwartz backward induction over MonteCarloConditionalExpectationRegression (regression.py):
                             what finmath-lib's BermudanOption does with its conditional-expectation estimator
+    bermudan_max_call_mc    the same induction for a call on the maximum of several assets, regressed on all monomials of the assets up
+                            to a total degree: 10 … 56 basis functions, the wide one-pass normal equations
 """
 from __future__ import annotations
 
@@ -246,3 +248,65 @@ def bermudan_option_mc(brownian_motion, initial_value, risk_free_rate, volatilit
         exercise = exercise_value(s, dates[k])
         value = exercise.sub(continuation).choose(exercise, value)
     return value.getAverage(), value
+
+
+def monomial_exponents(n_assets, order):
+    """All exponent tuples of total degree <= order in n_assets variables — C(n_assets + order, order) of them —, by degree, then
+    lexicographically descending: (0, 0), (1, 0), (0, 1), (2, 0), (1, 1), (0, 2), …"""
+    out = []
+    def rest(prefix, left, slots):
+        if slots == 1: out.append(tuple(prefix + [left])); return
+        for e in range(left, -1, -1): rest(prefix + [e], left - e, slots - 1)
+    for degree in range(order + 1): rest([], degree, n_assets)
+    return out
+
+
+def bermudan_max_call_mc(brownian_motion, initial_values, risk_free_rate, dividend_yield, volatility, exercise_dates, strike, basis_order=2):
+    """Value of a Bermudan call on max_i S_i under Black–Scholes by Longstaff–Schwartz backward induction: independent assets, asset i driven
+    by factor i of `brownian_motion` (log-Euler, exact for ln S), drift r − δ − σ²/2, all with one dividend yield and one volatility.  States
+    are kept at the exercise dates (points of the time discretisation).  The value starts as the last date's discounted payoff; at each
+    earlier date it is regressed over ALL paths on all monomials of total degree <= basis_order in the assets, scaled by the strike —
+    C(A + basis_order, basis_order) basis functions, the constant among them as a deterministic random variable — and paths on which
+    exercise − continuation estimate >= 0 take the discounted exercise value.  One regression, that is one pass over the data on the device, per
+    exercise date but the last.  Returns (value, standard error).  With one exercise date this is the European max-call on the same paths."""
+    from .regression import MonteCarloConditionalExpectationRegression
+    dates = sorted(float(d) for d in exercise_dates)
+    if not dates: raise ValueError("no exercise date")
+    assets = len(initial_values)
+    if assets < 1 or assets > brownian_motion.getNumberOfFactors(): raise ValueError("one factor of the Brownian motion per asset")
+    td = brownian_motion.getTimeDiscretization()
+    xs = [brownian_motion.getRandomVariableForConstant(math.log(float(s0))) for s0 in initial_values]
+    drift = risk_free_rate - dividend_yield - 0.5 * volatility * volatility
+    states, t, i = [], td.getTime(0), 0
+    if abs(t - dates[0]) <= 1e-12: states.append([x.exp() for x in xs])
+    while len(states) < len(dates):
+        dt = td.getTimeStep(i)
+        xs = [x.add(drift * dt).addProduct(brownian_motion.getBrownianIncrement(i, a), volatility) for a, x in enumerate(xs)]
+        i += 1
+        t = td.getTime(i)
+        if t > dates[len(states)] + 1e-12: raise ValueError("an exercise date is not a point of the time discretisation")
+        if abs(t - dates[len(states)]) <= 1e-12: states.append([x.exp() for x in xs])
+
+    def exercise_value(s, date):
+        best = s[0]
+        for other in s[1:]: best = best.floor(other)             # max(best, other)
+        return best.sub(strike).floor(0.0).div(math.exp(risk_free_rate * date))
+
+    value = exercise_value(states[-1], dates[-1])
+    one = brownian_motion.getRandomVariableForConstant(1.0)
+    exponents = monomial_exponents(assets, basis_order)
+    for k in range(len(dates) - 2, -1, -1):
+        scaled = [s.div(strike) for s in states[k]]
+        powers = [[one, u] for u in scaled]
+        for p in powers:
+            for _ in range(2, basis_order + 1): p.append(p[-1].mult(p[1]))
+        basis = []
+        for e in exponents:
+            f = None
+            for a, ea in enumerate(e):
+                if ea: f = powers[a][ea] if f is None else f.mult(powers[a][ea])
+            basis.append(one if f is None else f)
+        continuation = MonteCarloConditionalExpectationRegression(basis).getConditionalExpectation(value)
+        exercise = exercise_value(states[k], dates[k])
+        value = exercise.sub(continuation).choose(exercise, value)
+    return value.getAverage(), value.getStandardError()

@@ -8,6 +8,11 @@ vector read about K times.  Here the K + 1 vectors are read once and the K(K+1)/
 written against the RandomVariable interface and accepts any factory's vectors: the one-pass path is taken when every stochastic operand
 is a RandomVariableHip, the product-by-product path otherwise (and with FMHIP_DEVICE_CROSS_MOMENTS=0: the A/B switch and the fallback).
 
+Wide regression: more than 12 + 4 vectors, up to 64 in all, go to fmhip_cross_moments_wide — the same sums from one
+pass on the matrix cores —, so the estimator keeps its one-pass path up to 60 basis functions (a Longstaff–Schwartz basis on several
+underlyings) and covariance_matrix takes 63 vectors.  FMHIP_DEVICE_WIDE_MOMENTS=0: the estimator goes pair by pair beyond 12 basis
+functions, as it did before the wide pass existed.
+
 Localized regression: a global polynomial is the wrong tool for a kinked continuation value.  binned_cross_moments
 returns the cross moments PER BIN of a key vector from one launch (fmhip_binned_cross_moments) — the block-diagonal normal equations of a
 fit that is local in the key —, quantile_bounds the bounds of bins of equal count, binned_evaluate the piecewise estimate as a new vector,
@@ -26,6 +31,8 @@ from . import _native as N
 from .random_variable import DeviceVector, RandomVariableHip, select_ranks_batch
 
 MAX_X, MAX_Y = 12, 4                     # fmhip_cross_moments' limits
+WIDE_MAX = 64                            # fmhip_cross_moments_wide's limit: x and y together
+WIDE_MAX_BASIS = 60                      # the estimator's one-pass path: at least four dependents per call
 BINNED_MAX_X, BINNED_MAX_Y, MAX_BINS = 3, 4, 64      # fmhip_binned_cross_moments' limits
 PIVOT_TOLERANCE = 1e-12                  # a basis function whose remaining pivot is <= this x the largest diagonal entry is dropped
 
@@ -34,6 +41,12 @@ def device_cross_moments() -> bool:
     """FMHIP_DEVICE_CROSS_MOMENTS=0: the estimator builds the normal equations product by product, as finmath-lib does; anything else:
     one fmhip_cross_moments call."""
     return os.environ.get("FMHIP_DEVICE_CROSS_MOMENTS", "1") != "0"
+
+
+def device_wide_moments() -> bool:
+    """FMHIP_DEVICE_WIDE_MOMENTS=0: beyond 12 basis functions the estimator builds the normal equations product by product (the A/B
+    switch and the fallback); anything else: fmhip_cross_moments_wide, one call per 64 − K dependents.  Read per call."""
+    return os.environ.get("FMHIP_DEVICE_WIDE_MOMENTS", "1") != "0"
 
 
 def _handle(v, allow_one: bool) -> int:
@@ -49,13 +62,17 @@ def _handle(v, allow_one: bool) -> int:
 def cross_moments(xs, ys=()):
     """(S, T): S[i][j] = Σ_p x_i[p]·x_j[p] (full symmetric n_x × n_x), T[i][m] = Σ_p x_i[p]·y_m[p] (n_x × n_y), fp64 SUMS from one device
     launch.  Entries: RandomVariableHip, DeviceVector or raw handles; an x may be None or 1.0 for the constant 1, which then also yields
-    the plain sums Σ x_j and, at (ones, ones), n.  At most 12 xs and 4 ys."""
+    the plain sums Σ x_j and, at (ones, ones), n.  Up to 12 xs and 4 ys go to fmhip_cross_moments (and keep its bits); anything larger, up
+    to 64 vectors in all, goes to fmhip_cross_moments_wide."""
     xs, ys = list(xs), list(ys)
     nx, ny = len(xs), len(ys)
+    wide = nx > MAX_X or ny > MAX_Y
+    if wide and nx + ny > WIDE_MAX: raise ValueError(f"cross moments of {nx} + {ny} vectors: at most {WIDE_MAX} in one call")
     hx = (C.c_int64 * max(nx, 1))(*[_handle(v, True) for v in xs])
     hy = (C.c_int64 * max(ny, 1))(*[_handle(v, False) for v in ys])
     out = np.empty(nx * (nx + 1) // 2 + nx * ny, dtype=np.float64)
-    N.check(N.lib().fmhip_cross_moments(hx, nx, hy if ny else None, ny, out.ctypes.data_as(C.POINTER(C.c_double))))
+    call = N.lib().fmhip_cross_moments_wide if wide else N.lib().fmhip_cross_moments
+    N.check(call(hx, nx, hy if ny else None, ny, out.ctypes.data_as(C.POINTER(C.c_double))))
     S = np.empty((nx, nx), dtype=np.float64)
     iu = np.triu_indices(nx)
     S[iu] = out[:iu[0].size]
@@ -64,7 +81,7 @@ def cross_moments(xs, ys=()):
 
 
 def covariance_matrix(vectors) -> np.ndarray:
-    """Population covariance of up to 11 vectors from ONE pass: S_ij/n − mean_i·mean_j in fp64, with the means and n from the ones entry.
+    """Population covariance of up to 63 vectors (up to 11: the narrow pass and its bits) from ONE pass: S_ij/n − mean_i·mean_j in fp64, with the means and n from the ones entry.
     The subtraction cancels: the result carries an absolute error of about 2⁻⁵³·(|S_ij|/n + |mean_i·mean_j|)·log2(n), which is all of it
     when the standard deviations are below ~1e-8 of the means — shift such data first."""
     vectors = list(vectors)
@@ -84,6 +101,9 @@ def solve_normal_equations(A, b) -> np.ndarray:
     one = B.ndim == 1
     B = B.reshape(A.shape[0], -1)
     K = A.shape[0]
+    if K > MAX_X:                        # the loops below are cubic in K in the interpreter: ~100 µs at K = 12, more than the pass at K = 56
+        x = _solve_normal_equations_rows(A, B)
+        return x[:, 0] if one else x
     perm = list(range(K))
     d = [float(A[i, i]) for i in range(K)]
     tol = PIVOT_TOLERANCE * max(d) if K else 0.0
@@ -119,6 +139,37 @@ def solve_normal_equations(A, b) -> np.ndarray:
     return x[:, 0] if one else x
 
 
+def _solve_normal_equations_rows(A, B) -> np.ndarray:
+    """solve_normal_equations for K > 12: the same algorithm — the same diagonal pivoting (the first of equals), the same 1e-12 rule — with
+    every loop over the remaining unknowns as one numpy row operation."""
+    K = A.shape[0]
+    perm = np.arange(K)
+    d = A.diagonal().copy()
+    tol = PIVOT_TOLERANCE * d.max()
+    L = np.zeros((K, K))                 # row = unknown, column = elimination step
+    rank = K
+    for k in range(K):
+        p = k + int(np.argmax(d[perm[k:]]))
+        if not d[perm[p]] > tol:
+            rank = k
+            break
+        perm[[k, p]] = perm[[p, k]]
+        i, rest = perm[k], perm[k + 1:]
+        L[i, k] = math.sqrt(d[i])
+        L[rest, k] = (A[rest, i] - L[rest, :k] @ L[i, :k]) / L[i, k]
+        d[rest] -= L[rest, k] * L[rest, k]
+    kept = perm[:rank]
+    Lp = L[kept, :rank]                  # lower triangular in elimination order
+    z = np.zeros((rank, B.shape[1]))
+    for k in range(rank):                # L z = b
+        z[k] = (B[kept[k]] - Lp[k, :k] @ z[:k]) / Lp[k, k]
+    for k in range(rank - 1, -1, -1):    # Lᵀ x = z, in place
+        z[k] = (z[k] - Lp[k + 1:, k] @ z[k + 1:]) / Lp[k, k]
+    x = np.zeros((K, B.shape[1]))
+    x[kept] = z
+    return x
+
+
 class MonteCarloConditionalExpectationRegression:
     """E[ · | basis functions] by least squares (finmath-lib: MonteCarloConditionalExpectationRegression).  `basisFunctionsEstimator`
     are the regressors the parameters are estimated on, `basisFunctionsPredictor` (default: the same) the ones the estimate is evaluated
@@ -133,7 +184,8 @@ class MonteCarloConditionalExpectationRegression:
     # ---- the normal equations, as averages
     def _one_pass(self, dependents) -> bool:
         basis = self.basisFunctionsEstimator
-        if not device_cross_moments() or not 1 <= len(basis) <= MAX_X or not dependents: return False
+        if not device_cross_moments() or not 1 <= len(basis) <= WIDE_MAX_BASIS or not dependents: return False
+        if len(basis) > MAX_X and not device_wide_moments(): return False
         if not all(isinstance(v, RandomVariableHip) for v in basis + dependents): return False
         # the constant 1 stands in for deterministic basis functions; dependents and at least one basis function must be vectors
         return all(not y.isDeterministic() for y in dependents) and any(not b.isDeterministic() for b in basis)
@@ -144,8 +196,9 @@ class MonteCarloConditionalExpectationRegression:
         xs = [None if b.isDeterministic() else b for b in basis]
         n = float(next(b for b in basis if not b.isDeterministic())._sample_size())
         A, cols = None, []
-        for m0 in range(0, len(dependents), MAX_Y):
-            S, T = cross_moments(xs, dependents[m0:m0 + MAX_Y])
+        step = MAX_Y if len(basis) <= MAX_X else WIDE_MAX - len(basis)      # beyond 12 basis functions: the wide pass, 64 − K dependents a call
+        for m0 in range(0, len(dependents), step):
+            S, T = cross_moments(xs, dependents[m0:m0 + step])
             A = S
             cols.append(T)
         return A * np.outer(scale, scale) / n, np.hstack(cols) * scale[:, None] / n
@@ -161,7 +214,8 @@ class MonteCarloConditionalExpectationRegression:
         return A, b
 
     def getLinearRegressionParameters(self, dependents) -> np.ndarray:
-        """β (K) for one dependent, K × M for a sequence of M dependents (one pass per four of them)."""
+        """β (K) for one dependent, K × M for a sequence of M dependents (one pass per four of them; per 64 − K beyond 12 basis
+        functions)."""
         one = not isinstance(dependents, (list, tuple))
         ys = [dependents] if one else list(dependents)
         A, b = self._normal_equations_device(ys) if self._one_pass(ys) else self._normal_equations_generic(ys)

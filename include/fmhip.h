@@ -354,6 +354,18 @@ int fmhip_count_not_above(fmhip_vec v, const double* bounds, int n_bounds, int64
  * error a read of it is.  IEEE semantics: a NaN in x_3 makes exactly the entries that involve x_3 NaN, inf*0 is NaN. */
 int fmhip_cross_moments(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out);
 
+/* Wide cross moments: the same normal equations for n_x >= 1 vectors x and n_y >= 0 vectors y with n_x + n_y <= 64, in one
+ * pass on the matrix cores (v_mfma_f64_16x16x4_f64) — a Longstaff-Schwartz basis on several underlyings, a covariance matrix of 63 vectors.
+ * Output layout, the handle-0 constant 1 among x, status codes, the checks on the host before anything is flushed or launched and the IEEE
+ * behaviour (a NaN in x_3 poisons exactly the entries with x_3; inf*0 is NaN) are exactly those of fmhip_cross_moments.
+ * Every product of two fp32 values is exact in fp64 and is added in fp64; no float atomics, no fp32 product.  The bits of one pair's sum
+ * are a function of n and of the two vectors' values only: not of how many vectors the call names, of where in the lists the two stand, of
+ * which of the two comes first, or of whether the pair is reported in S or in T.  They need not equal fmhip_cross_moments' bits for the
+ * same pair (the tree is another one; the longest chain of additions is xmom_wide_chain(n), csrc/xmom_wide_kernel.h, and the sums agree
+ * with any summation order's to (chain + 1)*2^-53*sum|terms|).  ONE launch.  A build without the kernel answers FMHIP_ERR_UNSUPPORTED; it
+ * never falls back.  Device lists add in shard order; an expectation communicator does one gather, added in rank order. */
+int fmhip_cross_moments_wide(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out);
+
 /* Localized regression: the cross moments above PER BIN of a key vector — the block-diagonal normal equations of a
  * regression that is local in the key (finmath-lib: BermudanOption's binning basis, the ...LocalizedOnDependentRegression estimators) — in
  * one pass, and the piecewise estimate as a new vector.

@@ -10,7 +10,8 @@ import net.finmath.stochastic.RandomVariable;
  * ({@link MonteCarloConditionalExpectationRegression}: {@code b_i.mult(b_j).getAverage()}).
  *
  * The one-pass path is taken when every stochastic operand is a {@link RandomVariableHip}; deterministic basis functions are host
- * scalars folded through the constant-1 entry.  Foreign vectors, more than 12 basis functions or {@code FMHIP_DEVICE_CROSS_MOMENTS=0}
+ * scalars folded through the constant-1 entry; beyond 12 basis functions the pass is {@code fmhip_cross_moments_wide} (DESIGN.md 4.14).
+ * Foreign vectors, more than 60 basis functions, {@code FMHIP_DEVICE_WIDE_MOMENTS=0} beyond 12, or {@code FMHIP_DEVICE_CROSS_MOMENTS=0}
  * delegate to finmath-lib's own estimator.  The normal equations are solved on the host by the pivoted Cholesky the Python and C++
  * mirrors use (regression.py, host/regression.hpp): the largest remaining pivot next, and a basis function whose remaining pivot is
  * at most 1e-12 times the largest diagonal entry gets the coefficient 0.
@@ -19,7 +20,8 @@ import net.finmath.stochastic.RandomVariable;
  */
 public class MonteCarloConditionalExpectationRegressionHip implements ConditionalExpectationEstimator {
 
-	private static final int MAX_BASIS_FUNCTIONS = 12;
+	private static final int MAX_BASIS_FUNCTIONS = 12;          // fmhip_cross_moments
+	private static final int MAX_BASIS_FUNCTIONS_WIDE = 60;     // fmhip_cross_moments_wide (DESIGN.md 4.14)
 	private static final double PIVOT_TOLERANCE = 1e-12;
 
 	private final RandomVariable[] basisFunctionsEstimator;
@@ -35,6 +37,10 @@ public class MonteCarloConditionalExpectationRegressionHip implements Conditiona
 		}
 		this.basisFunctionsEstimator = basisFunctionsEstimator.clone();
 		this.basisFunctionsPredictor = basisFunctionsPredictor.clone();
+	}
+
+	static boolean deviceWideMoments() {
+		return !"0".equals(System.getenv("FMHIP_DEVICE_WIDE_MOMENTS"));
 	}
 
 	static boolean deviceCrossMoments() {
@@ -56,7 +62,8 @@ public class MonteCarloConditionalExpectationRegressionHip implements Conditiona
 	/** The coefficients from the one-pass normal equations, or null when the operands do not allow it (the caller delegates). */
 	public double[] getLinearRegressionParameters(final RandomVariable dependent) {
 		final int numberOfBasisFunctions = basisFunctionsEstimator.length;
-		if(!deviceCrossMoments() || numberOfBasisFunctions < 1 || numberOfBasisFunctions > MAX_BASIS_FUNCTIONS) return null;
+		final boolean wide = numberOfBasisFunctions > MAX_BASIS_FUNCTIONS;
+		if(!deviceCrossMoments() || numberOfBasisFunctions < 1 || numberOfBasisFunctions > MAX_BASIS_FUNCTIONS_WIDE || (wide && !deviceWideMoments())) return null;
 		if(!(dependent instanceof RandomVariableHip) || dependent.isDeterministic()) return null;
 		final long[] x = new long[numberOfBasisFunctions];
 		final double[] scale = new double[numberOfBasisFunctions];
@@ -76,7 +83,8 @@ public class MonteCarloConditionalExpectationRegressionHip implements Conditiona
 		}
 		if(sized == null) return null;
 		final double[] sums = new double[numberOfBasisFunctions * (numberOfBasisFunctions + 1) / 2 + numberOfBasisFunctions];
-		Native.check(Native.crossMoments(x, new long[] { ((RandomVariableHip) dependent).deviceHandle() }, sums));
+		final long[] y = new long[] { ((RandomVariableHip) dependent).deviceHandle() };
+		Native.check(wide ? Native.crossMomentsWide(x, y, sums) : Native.crossMoments(x, y, sums));
 		final double n = sized.expectationSampleSize();
 		final double[][] a = new double[numberOfBasisFunctions][numberOfBasisFunctions];
 		final double[] b = new double[numberOfBasisFunctions];

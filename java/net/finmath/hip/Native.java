@@ -79,6 +79,8 @@ final class Native {
 	// ---- cross moments: the normal equations of a regression in one pass (replace b_i.mult(b_j).getAverage() per pair, MonteCarloConditionalExpectationRegression)
 	/** sumsOut = the x.length(x.length+1)/2 sums of x_i*x_j (i <= j, row-major) followed by the x.length*y.length sums of x_i*y_m; a handle of 0 in x is the constant 1. */
 	static native int crossMoments(long[] x, long[] y, double[] sumsOut);
+	/** crossMoments for x.length + y.length <= 64 (fmhip_cross_moments_wide: one pass on the matrix cores); same layout, its own bits. */
+	static native int crossMomentsWide(long[] x, long[] y, double[] sumsOut);
 	// ---- localized regression: the cross moments per bin of a key vector in one pass, and the piecewise estimate as a new vector (MonteCarloConditionalExpectationLocalizedRegressionHip)
 	/** bin(k) = number of bounds below k (bounds.length + 1 bins, at most 64; bounds may be null for one bin).  countsOut[b] = paths in bin b; sumsOut[b*q ...] = the sums of crossMoments over the paths of bin b, q = x.length(x.length+1)/2 + x.length*y.length; x.length <= 3, y.length <= 4. */
 	static native int binnedCrossMoments(long key, double[] bounds, long[] x, long[] y, long[] countsOut, double[] sumsOut);

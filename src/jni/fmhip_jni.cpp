@@ -192,6 +192,13 @@ FMJ(jint, crossMoments)(JNIEnv* env, jclass, jlongArray x, jlongArray y, jdouble
     if ((int64_t)po.length() < nx * (nx + 1) / 2 + nx * ny) return FMHIP_ERR_INVALID_ARGUMENT;
     return fmhip_cross_moments((const fmhip_vec*)px.p, (int)nx, ny ? (const fmhip_vec*)py.p : nullptr, (int)ny, po.p);
 }
+FMJ(jint, crossMomentsWide)(JNIEnv* env, jclass, jlongArray x, jlongArray y, jdoubleArray sumsOut) {
+    Pin<jlong> px(env, x, JNI_ABORT); Pin<jlong> py(env, y, JNI_ABORT); Pin<jdouble> po(env, sumsOut);
+    if (!px.p || !po.p) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int64_t nx = px.length(), ny = py.p ? py.length() : 0;
+    if ((int64_t)po.length() < nx * (nx + 1) / 2 + nx * ny) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_cross_moments_wide((const fmhip_vec*)px.p, (int)nx, ny ? (const fmhip_vec*)py.p : nullptr, (int)ny, po.p);
+}
 // ---------------------------------------------------------------- localized regression: cross moments per bin of a key, the piecewise estimate
 FMJ(jint, binnedCrossMoments)(JNIEnv* env, jclass, jlong key, jdoubleArray bounds, jlongArray x, jlongArray y, jlongArray countsOut, jdoubleArray sumsOut) {
     Pin<jdouble> pb(env, bounds, JNI_ABORT); Pin<jlong> px(env, x, JNI_ABORT); Pin<jlong> py(env, y, JNI_ABORT); Pin<jlong> pc(env, countsOut); Pin<jdouble> po(env, sumsOut);
