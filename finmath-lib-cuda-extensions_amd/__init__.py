@@ -22,6 +22,7 @@ from .sobol import BrownianMotionFromSobolSequence, SobolSequence, sobol_increme
 from .program import Program
 from .regression import MonteCarloConditionalExpectationRegression, covariance_matrix, cross_moments, solve_normal_equations
 from .regression import MonteCarloConditionalExpectationLocalizedRegression, binned_cross_moments, binned_evaluate, quantile_bounds
+from .regression import MonteCarloConditionalExpectationPolynomialRegression, polynomial_cross_moments, polynomial_evaluate
 from .differentiable import RandomVariableDifferentiableAAD, RandomVariableDifferentiableAADFactory
 
 

@@ -728,6 +728,53 @@ int fmhip_cross_moments_wide(const fmhip_vec* x, int n_x, const fmhip_vec* y, in
     });
 }
 
+// ---------------------------------------------------------------- polynomial regression in one pass (xmom_poly_engine.hpp)
+extern "C++" {
+namespace fm {
+int xmom_poly_local(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const fmhip_vec* y, int n_y, double* sums) {
+    return guarded([&] { Engine::get().xmom_poly_pass(states, n_states, exponents, n_terms, extra_x, n_extra, y, n_y, sums); });
+}
+}
+}
+int fmhip_polynomial_cross_moments_host(const float* const* states, int64_t n, int n_states, const uint8_t* exponents, int n_terms, const float* const* extra_x, int n_extra, const float* const* y, int n_y, double* sums_out) {
+    return host_only([&] { fm::poly_cross_moments_host(states, n, n_states, exponents, n_terms, extra_x, n_extra, y, n_y, sums_out); });
+}
+int fmhip_polynomial_evaluate_host(const float* const* states, int64_t n, int n_states, const uint8_t* exponents, int n_terms, const float* const* extra_x, int n_extra, const double* coefficients, float* out) {
+    return host_only([&] { fm::poly_evaluate_host(states, n, n_states, exponents, n_terms, extra_x, n_extra, coefficients, out); });
+}
+// the operands of a polynomial pass as ONE list for TE_LOCAL: states…, extra…, y…
+static std::vector<fmhip_vec> te_poly_operands(const fmhip_vec* states, int n_states, const fmhip_vec* extra_x, int n_extra, const fmhip_vec* y, int n_y) {
+    std::vector<fmhip_vec> all(states, states + n_states);
+    all.insert(all.end(), extra_x, extra_x + n_extra);
+    all.insert(all.end(), y, y + n_y);
+    return all;
+}
+int fmhip_polynomial_cross_moments(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const fmhip_vec* y, int n_y, double* sums_out) {
+    FRONT(polynomial_cross_moments(states, n_states, exponents, n_terms, extra_x, n_extra, y, n_y, sums_out));
+    if (te::active()) {
+        const int rc = host_only([&] { fm::poly_check_moments(states, n_states, exponents, n_terms, extra_x, n_extra, y, n_y, sums_out); });
+        if (rc != FMHIP_OK) return rc;
+        const std::vector<fmhip_vec> all = te_poly_operands(states, n_states, extra_x, n_extra, y, n_y);
+        TE_LOCAL(all.data(), n_states + n_extra + n_y, L, fmhip_polynomial_cross_moments(L, n_states, exponents, n_terms, L + n_states, n_extra, L + n_states + n_extra, n_y, sums_out));
+    }
+    return guarded([&] {
+        Engine& e = Engine::get();
+        e.xmom_poly_pass(states, n_states, exponents, n_terms, extra_x, n_extra, y, n_y, sums_out);
+        const size_t n_x = (size_t)n_terms + (size_t)n_extra;
+        comm_add_sums(e, sums_out, n_x * (n_x + 1) / 2 + n_x * (size_t)n_y);      // one gather, rank order: the sums of the global sample
+    });
+}
+int fmhip_polynomial_evaluate(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const double* coefficients, fmhip_vec* out) {
+    FRONT(polynomial_evaluate(states, n_states, exponents, n_terms, extra_x, n_extra, coefficients, out));
+    if (te::active()) {
+        const int rc = host_only([&] { fm::poly_check_evaluate(states, n_states, exponents, n_terms, extra_x, n_extra, coefficients, out); });
+        if (rc != FMHIP_OK) return rc;
+        const std::vector<fmhip_vec> all = te_poly_operands(states, n_states, extra_x, n_extra, nullptr, 0);
+        TE_LOCAL(all.data(), n_states + n_extra, L, fmhip_polynomial_evaluate(L, n_states, exponents, n_terms, L + n_states, n_extra, coefficients, out));
+    }
+    return guarded([&] { const fmhip_vec r = Engine::get().poly_eval(states, n_states, exponents, n_terms, extra_x, n_extra, coefficients, out); *out = r; });
+}
+
 // ---------------------------------------------------------------- localized regression (binned_engine.hpp)
 extern "C++" {
 namespace fm {

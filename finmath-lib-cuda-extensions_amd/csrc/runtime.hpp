@@ -383,6 +383,11 @@ public:
     void xmom_pass(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out);
     // the same for up to 64 vectors in all, on the matrix cores (xmom_wide_engine.hpp): same layout, same checks, its own bits
     void xmom_wide_pass(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out);
+    // polynomial regression in one pass (xmom_poly_engine.hpp): the wide pass's sums — and bits — for the list [monomials of the
+    // states (exponents[n_terms][n_states]), extra_x, y] with the monomials formed in registers; and the fitted polynomial as a new,
+    // materialised vector.  Arguments are checked before anything is flushed or launched.
+    void xmom_poly_pass(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const fmhip_vec* y, int n_y, double* sums_out);
+    fmhip_vec poly_eval(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const double* coefficients, const fmhip_vec* out_checked);
 
     // localized regression (binned_engine.hpp): per bin of `key` (bin(k) = #{ j : bounds[j] < k }) the count and the cross moments
     // of fmhip_cross_moments' layout, from ONE launch; and Σ_i x_i·(float)coefficients[bin·n_x + i] as a new, materialised vector.  Arguments are
@@ -738,5 +743,11 @@ void binned_check_moments(fmhip_vec key, const double* bounds, int n_bins, const
 void binned_check_evaluate(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const double* coefficients, const fmhip_vec* out);
 void binned_cross_moments_host(const float* key, int64_t n, const double* bounds, int n_bins, const float* const* x, int n_x, const float* const* y, int n_y, int64_t* counts_out, double* sums_out);
 void binned_evaluate_host(const float* key, int64_t n, const double* bounds, int n_bins, const float* const* x, int n_x, const double* coefficients, float* out);
+// the same for fmhip_polynomial_cross_moments / fmhip_polynomial_evaluate (xmom_poly_engine.hpp; the rules are fmhost::polynomialCheck*'s,
+// host/polynomial_regression.hpp), and the host definitions: all throw FMHIP_ERR_INVALID_ARGUMENT
+void poly_check_moments(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const fmhip_vec* y, int n_y, const double* sums_out);
+void poly_check_evaluate(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const double* coefficients, const fmhip_vec* out);
+void poly_cross_moments_host(const float* const* states, int64_t n, int n_states, const uint8_t* exponents, int n_terms, const float* const* extra_x, int n_extra, const float* const* y, int n_y, double* sums_out);
+void poly_evaluate_host(const float* const* states, int64_t n, int n_states, const uint8_t* exponents, int n_terms, const float* const* extra_x, int n_extra, const double* coefficients, float* out);
 
 } // namespace fm

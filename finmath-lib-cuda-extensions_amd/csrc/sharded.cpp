@@ -772,15 +772,16 @@ int count_not_above(fmhip_vec v, const double* bounds, int n_bounds, int64_t* co
     });
 }
 
-// Cross moments, narrow (12 + 4 vectors) and wide (64): the shards' sums add in shard order
+// Cross moments, narrow (12 + 4 vectors), wide (64) and polynomial: the shards' sums add in shard order.  n_reg: the regressors the sums are
+// laid out for — n_x, except where the vectors of x are not the regressors themselves (the polynomial pass: states and extra vectors)
 template <class Check, class Local>
-static int front_cross_moments(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out, const char* what, Check check, Local local) {
+static int front_cross_moments(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out, const char* what, Check check, Local local, int n_reg = -1) {
     return fronted([&](Shards& s) {
         check(x, n_x, y, n_y, sums_out);
         std::vector<fmhip_vec> all(x, x + n_x);
         all.insert(all.end(), y, y + n_y);
         const int64_t n = front_size(s, all.data(), n_x + n_y, what, true);
-        const size_t m = (size_t)n_x * (n_x + 1) / 2 + (size_t)n_x * n_y;
+        const size_t k = (size_t)(n_reg < 0 ? n_x : n_reg), m = k * (k + 1) / 2 + k * (size_t)n_y;
         std::vector<std::vector<double>> per((size_t)s.D(), std::vector<double>(m, 0.0));
         const std::vector<char> took = post_where_paths(s, n, [&](Worker& w) {
             const std::vector<fmhip_vec> l = localize(w, all.data(), n_x + n_y);
@@ -794,6 +795,42 @@ int cross_moments(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, doub
 }
 int cross_moments_wide(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out) {
     return front_cross_moments(x, n_x, y, n_y, sums_out, "wide cross moments", xmom_wide_check_counts, xmom_wide_local);
+}
+
+// Polynomial regression: the vectors of the call are the states and the extra regressors; the sums are those of n_terms + n_extra regressors
+static std::vector<fmhip_vec> poly_all(const fmhip_vec* states, int n_states, const fmhip_vec* extra_x, int n_extra) {      // states…, extra…
+    std::vector<fmhip_vec> all(states, states + n_states);
+    all.insert(all.end(), extra_x, extra_x + n_extra);
+    return all;
+}
+int polynomial_cross_moments(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const fmhip_vec* y, int n_y, double* sums_out) {
+    // (the check runs before the lists are looked at; until it has, none is put together)
+    { const int rc = fronted([&](Shards&) { poly_check_moments(states, n_states, exponents, n_terms, extra_x, n_extra, y, n_y, sums_out); }); if (rc != FMHIP_OK) return rc; }
+    const std::vector<fmhip_vec> x = poly_all(states, n_states, extra_x, n_extra);
+    return front_cross_moments(x.data(), n_states + n_extra, y, n_y, sums_out, "polynomial cross moments",
+        [](const fmhip_vec*, int, const fmhip_vec*, int, const double*) {},
+        [&](const fmhip_vec* lx, int, const fmhip_vec* ly, int, double* sums) { return xmom_poly_local(lx, n_states, exponents, n_terms, lx + n_states, n_extra, ly, n_y, sums); },
+        n_terms + n_extra);
+}
+int polynomial_evaluate(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const double* coefficients, fmhip_vec* out) {
+    return fronted([&](Shards& s) {
+        poly_check_evaluate(states, n_states, exponents, n_terms, extra_x, n_extra, coefficients, out);
+        auto all = std::make_shared<std::vector<fmhip_vec>>(poly_all(states, n_states, extra_x, n_extra));
+        const int64_t n = front_size(s, all->data(), n_states + n_extra, "polynomial evaluation", true);
+        auto ex = std::make_shared<std::vector<uint8_t>>(exponents, exponents + (size_t)n_terms * n_states);
+        auto co = std::make_shared<std::vector<double>>(coefficients, coefficients + (size_t)(n_terms + n_extra));
+        const fmhip_vec id = s.fresh(n);
+        s.post([=](Worker& w) {
+            int64_t off, cnt; shard_range(n, w.shards, w.shard, &off, &cnt);
+            fmhip_vec h = 0;
+            if (cnt <= 0) { if (w.ok(fmhip_vec_create_uninitialized(0, &h))) w.bind(id, h); return; }
+            const std::vector<fmhip_vec> l = localize(w, all->data(), n_states + n_extra);
+            if (w.ok(fmhip_polynomial_evaluate(l.data(), n_states, ex->data(), n_terms, l.data() + n_states, n_extra, co->data(), &h))) w.bind(id, h);
+        });
+        // eager, like the call on one engine: a shard's refusal (no kernel, a value that was given up) is THIS call's status
+        try { s.wait(); } catch (...) { s.post([=](Worker& w) { if (const fmhip_vec h = w.at(id)) { (void)fmhip_vec_release(h); w.local.erase(id); } }); s.meta.erase(id); throw; }
+        *out = id;
+    });
 }
 
 // Localized regression.  The evaluation is per shard: a new vector whose blocks are the shards' results.

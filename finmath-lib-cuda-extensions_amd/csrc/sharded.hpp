@@ -35,6 +35,7 @@ int os_local_count(fmhip_vec v, const double* ascending, int m, uint64_t* counts
 // the cross moments of the calling thread's engine (abi.cpp; a shard's worker calls it)
 int xmom_local(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums);
 int xmom_wide_local(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums);
+int xmom_poly_local(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const fmhip_vec* y, int n_y, double* sums);
 // the binned cross moments of the calling thread's engine (abi.cpp; a shard's worker calls it)
 int binned_xmom_local(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, int64_t* counts, double* sums);
 void os_counts_from_passes(const double* bounds, int n_bounds, int64_t* counts_out, const std::function<void(const double*, int, uint64_t*)>& pass);
@@ -69,6 +70,8 @@ int cross_moments(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, doub
 int cross_moments_wide(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, double* sums_out);
 int binned_cross_moments(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, int64_t* counts_out, double* sums_out);
 int binned_evaluate(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const double* coefficients, fmhip_vec* out);
+int polynomial_cross_moments(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const fmhip_vec* y, int n_y, double* sums_out);
+int polynomial_evaluate(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const double* coefficients, fmhip_vec* out);
 int program_create(const fmhip_prog_op* ops, int n_ops, int n_inputs, const int32_t* out_values, int n_outputs, const int32_t* reduce_values, int n_reduce, fmhip_program* out);
 int program_release(fmhip_program p);
 int program_shape(fmhip_program p, int* n_inputs, int* n_outputs, int* n_reduce);

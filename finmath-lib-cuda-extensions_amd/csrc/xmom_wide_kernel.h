@@ -33,6 +33,9 @@ constexpr int FM_XMOMW_MAX_GRID = 256;             // one workgroup per CU
 
 // what a slot of the list holds instead of an address (no vector lives at either)
 constexpr uint64_t FM_XMOMW_PAD = 0, FM_XMOMW_ONE = 1;
+// … and, for fm_xmom_poly_kernel only (xmom_poly_kernel.h), a monomial the lane forms itself: this tag (no address has bit 63) beside the
+// exponents of up to 8 state vectors, 3 bits each, state s at bits 3s … 3s + 2
+constexpr uint64_t FM_XMOMW_TERM = uint64_t(1) << 63;
 
 struct DevXmomWideArgs {
     uint32_t* counter;         // one arrival counter; zero before and after

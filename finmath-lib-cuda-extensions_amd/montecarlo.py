@@ -261,15 +261,18 @@ def monomial_exponents(n_assets, order):
     return out
 
 
-def bermudan_max_call_mc(brownian_motion, initial_values, risk_free_rate, dividend_yield, volatility, exercise_dates, strike, basis_order=2):
+def bermudan_max_call_mc(brownian_motion, initial_values, risk_free_rate, dividend_yield, volatility, exercise_dates, strike, basis_order=2, one_pass_basis=False):
     """Value of a Bermudan call on max_i S_i under Black–Scholes by Longstaff–Schwartz backward induction: independent assets, asset i driven
     by factor i of `brownian_motion` (log-Euler, exact for ln S), drift r − δ − σ²/2, all with one dividend yield and one volatility.  States
     are kept at the exercise dates (points of the time discretisation).  The value starts as the last date's discounted payoff; at each
     earlier date it is regressed over ALL paths on all monomials of total degree <= basis_order in the assets, scaled by the strike —
     C(A + basis_order, basis_order) basis functions, the constant among them as a deterministic random variable — and paths on which
     exercise − continuation estimate >= 0 take the discounted exercise value.  One regression, that is one pass over the data on the device, per
-    exercise date but the last.  Returns (value, standard error).  With one exercise date this is the European max-call on the same paths."""
-    from .regression import MonteCarloConditionalExpectationRegression
+    exercise date but the last.  Returns (value, standard error).  With one exercise date this is the European max-call on the same paths.
+    one_pass_basis=True: the monomials are not built at all — MonteCarloConditionalExpectationPolynomialRegression forms them in registers
+    from the scaled states.  The value is then the default's to the last bit wherever the default takes the wide pass
+    (more than 12 basis functions); with 12 or fewer the default's narrow pass adds in another order and the two agree to rounding only."""
+    from .regression import MonteCarloConditionalExpectationPolynomialRegression, MonteCarloConditionalExpectationRegression
     dates = sorted(float(d) for d in exercise_dates)
     if not dates: raise ValueError("no exercise date")
     assets = len(initial_values)
@@ -297,6 +300,11 @@ def bermudan_max_call_mc(brownian_motion, initial_values, risk_free_rate, divide
     exponents = monomial_exponents(assets, basis_order)
     for k in range(len(dates) - 2, -1, -1):
         scaled = [s.div(strike) for s in states[k]]
+        if one_pass_basis:
+            continuation = MonteCarloConditionalExpectationPolynomialRegression(scaled, exponents=exponents, one=one).getConditionalExpectation(value)
+            exercise = exercise_value(states[k], dates[k])
+            value = exercise.sub(continuation).choose(exercise, value)
+            continue
         powers = [[one, u] for u in scaled]
         for p in powers:
             for _ in range(2, basis_order + 1): p.append(p[-1].mult(p[1]))

@@ -18,7 +18,13 @@ returns the cross moments PER BIN of a key vector from one launch (fmhip_binned_
 fit that is local in the key —, quantile_bounds the bounds of bins of equal count, binned_evaluate the piecewise estimate as a new vector,
 and MonteCarloConditionalExpectationLocalizedRegression the estimator on top of them (finmath-lib: BermudanOption's binning basis, the
 …LocalizedOnDependentRegression factories).  FMHIP_DEVICE_BINNED_MOMENTS=0 or any other RandomVariable class: indicators by choose and
-averages pair by pair."""
+averages pair by pair.
+
+Polynomial regression in one pass: a polynomial basis need not exist in memory.  polynomial_cross_moments returns the
+sums — and the bits — the wide pass returns for the materialised monomials, from the state vectors and an exponent table
+(fmhip_polynomial_cross_moments: the monomials are formed in registers), polynomial_evaluate the fitted polynomial as a new vector, and
+MonteCarloConditionalExpectationPolynomialRegression the estimator on top of them.  FMHIP_DEVICE_POLYNOMIAL_MOMENTS=0: the monomials are
+materialised by mult chains and MonteCarloConditionalExpectationRegression does the rest, as before the pass existed."""
 from __future__ import annotations
 
 import ctypes as C
@@ -34,6 +40,7 @@ MAX_X, MAX_Y = 12, 4                     # fmhip_cross_moments' limits
 WIDE_MAX = 64                            # fmhip_cross_moments_wide's limit: x and y together
 WIDE_MAX_BASIS = 60                      # the estimator's one-pass path: at least four dependents per call
 BINNED_MAX_X, BINNED_MAX_Y, MAX_BINS = 3, 4, 64      # fmhip_binned_cross_moments' limits
+POLY_MAX_STATES, POLY_MAX_EXPONENT = 8, 6            # fmhip_polynomial_cross_moments' limits
 PIVOT_TOLERANCE = 1e-12                  # a basis function whose remaining pivot is <= this x the largest diagonal entry is dropped
 
 
@@ -421,3 +428,136 @@ class MonteCarloConditionalExpectationLocalizedRegression:
         beta = self.getLinearRegressionParameters(dependents)
         if beta.ndim == 2: return self._evaluate(beta)
         return [self._evaluate(beta[:, :, m]) for m in range(beta.shape[2])]
+
+
+# ------------------------------------------------------------------ polynomial regression in one pass
+def device_polynomial_moments() -> bool:
+    """FMHIP_DEVICE_POLYNOMIAL_MOMENTS=0: the polynomial estimator materialises its monomials by mult chains and hands them to
+    MonteCarloConditionalExpectationRegression (the A/B switch and the fallback: exactly the code path there was before); anything else:
+    fmhip_polynomial_cross_moments and fmhip_polynomial_evaluate on the state vectors.  Read per call."""
+    return os.environ.get("FMHIP_DEVICE_POLYNOMIAL_MOMENTS", "1") != "0"
+
+
+def _exponent_table(exponents, n_states):
+    e = np.ascontiguousarray(exponents, dtype=np.int64).reshape(-1, n_states)
+    if e.size == 0: raise ValueError("a polynomial basis has at least one term")
+    if e.min() < 0 or e.max() > 255: raise ValueError("exponents are 0 … 6")
+    e = np.ascontiguousarray(e, dtype=np.uint8)
+    return e, e.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+def polynomial_cross_moments(states, exponents, extra=(), ys=()):
+    """(S, T) of cross_moments for the regressors [monomials of `states` by the rows of `exponents`…, extra…] and the dependents ys, from
+    the STATE vectors: the monomials are formed in registers (fmhip_polynomial_cross_moments), never stored.  The sums are, bit for bit, the
+    wide pass's for the same list with the monomials materialised by monomial_basis' mult chains.  At most 8 states, exponents 0 … 6 (a
+    row of zeros: the constant 1), len(exponents) + len(extra) + len(ys) <= 64; an extra may be None or 1.0 for the constant 1."""
+    states, extra, ys = list(states), list(extra), list(ys)
+    e, pe = _exponent_table(exponents, len(states))
+    nt, ne, ny = e.shape[0], len(extra), len(ys)
+    nx = nt + ne
+    hs = (C.c_int64 * max(len(states), 1))(*[_handle(v, False) for v in states])
+    hx = (C.c_int64 * max(ne, 1))(*[_handle(v, True) for v in extra])
+    hy = (C.c_int64 * max(ny, 1))(*[_handle(v, False) for v in ys])
+    out = np.empty(nx * (nx + 1) // 2 + nx * ny, dtype=np.float64)
+    N.check(N.lib().fmhip_polynomial_cross_moments(hs, len(states), pe, nt, hx if ne else None, ne, hy if ny else None, ny, out.ctypes.data_as(C.POINTER(C.c_double))))
+    S = np.empty((nx, nx), dtype=np.float64)
+    iu = np.triu_indices(nx)
+    S[iu] = out[:iu[0].size]
+    S.T[iu] = out[:iu[0].size]
+    return S, out[iu[0].size:].reshape(nx, ny).copy()
+
+
+def polynomial_evaluate(states, exponents, coefficients, extra=()) -> DeviceVector:
+    """The fitted polynomial as a new device vector: ((t_0·c_0) + t_1·c_1) + … over the monomials, then the extras, c = (float)coefficients,
+    every fp32 operation rounded on its own (fmhip_polynomial_evaluate) — the bits of basis[0].mult(c0).addProduct(basis[1], c1)… on the
+    materialised basis."""
+    states, extra = list(states), list(extra)
+    e, pe = _exponent_table(exponents, len(states))
+    c = np.ascontiguousarray(coefficients, dtype=np.float64).ravel()
+    if c.size != e.shape[0] + len(extra): raise ValueError("one coefficient per term and per extra vector")
+    hs = (C.c_int64 * max(len(states), 1))(*[_handle(v, False) for v in states])
+    hx = (C.c_int64 * max(len(extra), 1))(*[_handle(v, True) for v in extra])
+    out = C.c_int64(0)
+    N.check(N.lib().fmhip_polynomial_evaluate(hs, len(states), pe, e.shape[0], hx if extra else None, len(extra), c.ctypes.data_as(C.POINTER(C.c_double)), C.byref(out)))
+    first = states[0].realizations if isinstance(states[0], RandomVariableHip) else states[0]
+    return DeviceVector(out.value, first.n)
+
+
+def monomial_basis(states, exponents, one=None):
+    """The monomials of `states` as random variables, by the chain that is the contract of the one-pass path: powers u, u·u, (u·u)·u … by
+    mult, a monomial the product of its non-trivial powers in ascending state index, left to right.  A row of zeros is `one` (default: the
+    deterministic 1 of the first state's class, built as cls(time, value))."""
+    states = list(states)
+    rows = [tuple(int(x) for x in row) for row in np.asarray(exponents, dtype=np.int64).reshape(-1, len(states))]
+    top = max((max(r) for r in rows), default=0)
+    if one is None: one = type(states[0])(-math.inf, 1.0)
+    powers = [[one, u] for u in states]
+    for p in powers:
+        for _ in range(2, top + 1): p.append(p[-1].mult(p[1]))
+    basis = []
+    for row in rows:
+        f = None
+        for a, ea in enumerate(row):
+            if ea: f = powers[a][ea] if f is None else f.mult(powers[a][ea])
+        basis.append(one if f is None else f)
+    return basis
+
+
+class MonteCarloConditionalExpectationPolynomialRegression:
+    """E[ · | polynomial in the states] by least squares, the basis given as an exponent table instead of vectors: every monomial of total
+    degree <= `order` in `states` (montecarlo.monomial_exponents; or the rows of `exponents`), then `extra_basis` (ordinary regressors: an
+    exercise value, a spline).  Semantics of MonteCarloConditionalExpectationRegression with estimator = predictor.  The one-pass path —
+    fmhip_polynomial_cross_moments per 64 − K dependents, one fmhip_polynomial_evaluate per estimate: no monomial is ever stored — is taken
+    when every state, extra and dependent is a non-deterministic RandomVariableHip, K <= 60 and FMHIP_DEVICE_POLYNOMIAL_MOMENTS is not 0;
+    otherwise the monomials are materialised by monomial_basis and MonteCarloConditionalExpectationRegression does the rest.  Both paths
+    agree to the last bit wherever that estimator takes the wide pass (K > 12)."""
+
+    def __init__(self, states, order=None, exponents=None, extra_basis=(), one=None):
+        """one: the constant 1 of the materialised basis, as a random variable of the states' class (default: cls(−inf, 1.0))."""
+        self.states, self.one = list(states), one
+        if not self.states: raise ValueError("a polynomial regression needs at least one state")
+        if exponents is None:
+            if order is None: raise ValueError("give the order of the polynomial or its exponents")
+            from .montecarlo import monomial_exponents
+            exponents = monomial_exponents(len(self.states), int(order))
+        self.exponents = np.ascontiguousarray(exponents, dtype=np.int64).reshape(-1, len(self.states))
+        if self.exponents.shape[0] < 1 or self.exponents.min() < 0: raise ValueError("a polynomial basis has at least one term and no negative exponent")
+        self.extra_basis = list(extra_basis)
+        self._materialised = None
+
+    def _one_pass(self, dependents) -> bool:
+        K = self.exponents.shape[0] + len(self.extra_basis)
+        if not device_polynomial_moments() or K > WIDE_MAX_BASIS or len(self.states) > POLY_MAX_STATES or self.exponents.max() > POLY_MAX_EXPONENT: return False
+        return all(isinstance(v, RandomVariableHip) and not v.isDeterministic() for v in self.states + self.extra_basis + list(dependents))
+
+    def _generic(self):
+        if self._materialised is None:
+            self._materialised = MonteCarloConditionalExpectationRegression(monomial_basis(self.states, self.exponents, self.one) + self.extra_basis)
+        return self._materialised
+
+    def getLinearRegressionParameters(self, dependents) -> np.ndarray:
+        """β (K) for one dependent, K × M for a sequence of M dependents (one pass per 64 − K of them)."""
+        one = not isinstance(dependents, (list, tuple))
+        ys = [dependents] if one else list(dependents)
+        if not ys or not self._one_pass(ys): return self._generic().getLinearRegressionParameters(dependents)
+        K = self.exponents.shape[0] + len(self.extra_basis)
+        n = float(self.states[0]._sample_size())
+        A, cols = None, []
+        step = WIDE_MAX - K
+        for m0 in range(0, len(ys), step):
+            S, T = polynomial_cross_moments(self.states, self.exponents, self.extra_basis, ys[m0:m0 + step])
+            A = S
+            cols.append(T)
+        scale = np.ones(K)                   # (the arithmetic of the materialised estimator, factor for factor)
+        beta = solve_normal_equations(A * np.outer(scale, scale) / n, np.hstack(cols) * scale[:, None] / n)
+        return beta[:, 0] if one else beta
+
+    def getConditionalExpectation(self, dependents):
+        """The fitted polynomial on the states, in the fp32 arithmetic of basis[0].mult(β0).addProduct(basis[i], βi)."""
+        one = not isinstance(dependents, (list, tuple))
+        ys = [dependents] if one else list(dependents)
+        if not ys or not self._one_pass(ys): return self._generic().getConditionalExpectation(dependents)
+        beta = self.getLinearRegressionParameters(ys)
+        time = max(v.getFiltrationTime() for v in self.states + self.extra_basis)
+        out = [RandomVariableHip(time, polynomial_evaluate(self.states, self.exponents, beta[:, m], self.extra_basis)) for m in range(beta.shape[1])]
+        return out[0] if one else out

@@ -398,6 +398,39 @@ int fmhip_binned_evaluate(fmhip_vec key, const double* bounds, int n_bins, const
 int fmhip_binned_evaluate_host(const float* key, int64_t n, const double* bounds, int n_bins, const float* const* x, int n_x,
                                const double* coefficients, float* out);
 
+/* Polynomial regression in one pass: the normal equations of a regression on a POLYNOMIAL basis — the Longstaff-Schwartz
+ * basis of a product on several underlyings — from the state vectors alone, and the fitted polynomial as a new vector.  The monomials are
+ * never in memory: the moments kernel forms them in registers as the operands of fmhip_cross_moments_wide's pass.
+ * states: n_states vectors (1 ... 8), all of one size n > 0.  exponents[n_terms][n_states], each entry 0 ... 6: term i is the monomial
+ *   prod_s states[s]^exponents[i*n_states + s].  extra_x: n_extra >= 0 ordinary vectors among the regressors (an exercise value, a spline); a
+ *   handle of 0 there is the constant 1, as in the wide call.  y: n_y >= 0 dependents.  n_terms >= 1; n_terms + n_extra + n_y <= 64 for the
+ *   moments, n_terms + n_extra <= 60 for the evaluation.  The regressor list is: the terms in the order given, then extra_x (then y).
+ * How a term is computed — the contract: u^e is u followed by e - 1 multiplications by u, each rounded to fp32: ((u*u)*u)...; the term is
+ *   the product of the powers with e > 0 in ascending state index, left to right, each product rounded to fp32, nothing contracted.  A state
+ *   with exponent 0 does not take part (it is not multiplied by 1, so inf^0 is no NaN).  The all-zero tuple is the constant 1.0f: it is not
+ *   loaded and behaves as a handle of 0 does in fmhip_cross_moments.
+ * fmhip_polynomial_cross_moments: sums_out has exactly the layout of fmhip_cross_moments with n_x = n_terms + n_extra.  The sums are, bit
+ *   for bit, those fmhip_cross_moments_wide returns for the same list with the terms materialised by the chain above: the same tree (chunks
+ *   of 64 paths, the waves in order, the workgroups in order; its bits depend on n and the pair's values only).  ONE launch.
+ * fmhip_polynomial_evaluate: *out = a new, materialised vector r = ((t_0*c_0) + t_1*c_1) + ... over the terms, then the extra vectors, with
+ *   c_i = (float)coefficients[i]: every product and every sum rounded to fp32 — what basis[0].mult(c0).addProduct(basis[1], c1)... computes on
+ *   the materialised basis.  Eager: pending operands are computed in one flush, one launch follows.
+ * The _host functions are the DEFINITION over host float arrays (a NULL among extra_x is the constant 1) and need no device; they add in
+ *   path order.  The device's sums agree with them to (xmom_wide_chain(n) + 1)*2^-53*sum|a*b| per entry (csrc/xmom_wide_kernel.h).
+ * Everything is checked on the host before anything is flushed or launched, by one function for the device and the host entry point:
+ * counts out of range, an exponent above 6, a NULL pointer, a 0 among states or y, n == 0 -> FMHIP_ERR_INVALID_ARGUMENT; vectors of
+ * different sizes -> FMHIP_ERR_SIZE_MISMATCH; FMHIP_ERR_INVALID_HANDLE.  A vector whose values were given up is the error a read of it is.
+ * A build without the kernels answers FMHIP_ERR_UNSUPPORTED; it never falls back.  With a device list the sums add in shard order and the
+ * evaluation is per shard; with an expectation communicator the sums are those of the GLOBAL sample (one gather, added in rank order). */
+int fmhip_polynomial_cross_moments(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms,
+                                   const fmhip_vec* extra_x, int n_extra, const fmhip_vec* y, int n_y, double* sums_out);
+int fmhip_polynomial_evaluate(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms,
+                              const fmhip_vec* extra_x, int n_extra, const double* coefficients, fmhip_vec* out);
+int fmhip_polynomial_cross_moments_host(const float* const* states, int64_t n, int n_states, const uint8_t* exponents, int n_terms,
+                                        const float* const* extra_x, int n_extra, const float* const* y, int n_y, double* sums_out);
+int fmhip_polynomial_evaluate_host(const float* const* states, int64_t n, int n_states, const uint8_t* exponents, int n_terms,
+                                   const float* const* extra_x, int n_extra, const double* coefficients, float* out);
+
 /* Expectation communicator: Monte-Carlo paths sharded over processes (one GPU each) behind an UNCHANGED caller.
  * Every vector of this process holds the paths [rank·n, (rank+1)·n) of a global vector of world·n paths; all element-wise
  * work is local; the one thing that couples paths is an expectation.  With a communicator set, fmhip_reduce_moments and

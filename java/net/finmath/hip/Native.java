@@ -90,6 +90,15 @@ final class Native {
 	static native int binnedEvaluate(long key, double[] bounds, long[] x, double[] coefficients, long[] out);
 	/** The definition of binnedEvaluate over host arrays (columns as in binnedCrossMomentsHost). */
 	static native int binnedEvaluateHost(float[] key, double[] bounds, float[] xColumns, int nX, int onesMask, double[] coefficients, float[] out);
+	// ---- polynomial regression in one pass: the normal equations of a polynomial basis from the state vectors, the monomials formed in registers
+	/** crossMomentsWide for the regressors [monomials of states..., extraX...] and the dependents y; exponents holds states.length ints (0 ... 6) per monomial, a row of zeros is the constant 1; a handle of 0 in extraX is the constant 1.  Bit for bit the sums of crossMomentsWide on the materialised monomials. */
+	static native int polynomialCrossMoments(long[] states, int[] exponents, long[] extraX, long[] y, double[] sumsOut);
+	/** out[0] = a new vector: ((t_0*c_0) + t_1*c_1) + ... over the monomials, then extraX, c = (float) coefficients[i], every fp32 operation rounded on its own. */
+	static native int polynomialEvaluate(long[] states, int[] exponents, long[] extraX, double[] coefficients, long[] out);
+	/** The definition of polynomialCrossMoments over host arrays: stateColumns (extraColumns, yColumns) holds nStates (nExtra, nY) columns of equal length; bit i of onesMask makes extra i the constant 1. */
+	static native int polynomialCrossMomentsHost(float[] stateColumns, int nStates, int[] exponents, float[] extraColumns, int nExtra, int onesMask, float[] yColumns, int nY, double[] sumsOut);
+	/** The definition of polynomialEvaluate over host arrays (columns as in polynomialCrossMomentsHost). */
+	static native int polynomialEvaluateHost(float[] stateColumns, int nStates, int[] exponents, float[] extraColumns, int nExtra, int onesMask, double[] coefficients, float[] out);
 	/** With a device list: one device buffer per listed device (0 = not wanted there), each receives the moments of the whole vectors. */
 	static native int reduceMomentsBatchDevices(long[] vectors, double[] shiftsOrNull, long[] deviceOutPerDevice);
 	static native int getStreamOf(int shard, long[] stream);

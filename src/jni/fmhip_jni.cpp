@@ -245,6 +245,67 @@ FMJ(jint, binnedEvaluateHost)(JNIEnv* env, jclass, jfloatArray key, jdoubleArray
     if ((int64_t)pc.length() < nb * nX || (int64_t)po.length() < n) return FMHIP_ERR_INVALID_ARGUMENT;
     return fmhip_binned_evaluate_host(pk.p, n, pb.p, (int)nb, xs.data(), nX, pc.p, po.p);
 }
+// ---------------------------------------------------------------- polynomial regression in one pass: the monomials of the states are formed in registers
+// exponents: states.length (nStates) entries per term, each 0 … 6, as ints; anything outside a byte is refused here, the rest by the library
+static bool poly_exponents(const jint* e, int64_t count, std::vector<uint8_t>& out) {
+    if (!e || count < 0) return false;
+    out.resize((size_t)count);
+    for (int64_t i = 0; i < count; ++i) { if (e[i] < 0 || e[i] > 255) return false; out[(size_t)i] = (uint8_t)e[i]; }
+    return true;
+}
+FMJ(jint, polynomialCrossMoments)(JNIEnv* env, jclass, jlongArray states, jintArray exponents, jlongArray extraX, jlongArray y, jdoubleArray sumsOut) {
+    Pin<jlong> ps(env, states, JNI_ABORT); Pin<jint> pe(env, exponents, JNI_ABORT); Pin<jlong> px(env, extraX, JNI_ABORT); Pin<jlong> py(env, y, JNI_ABORT); Pin<jdouble> po(env, sumsOut);
+    if (!ps.p || !pe.p || !po.p || ps.length() < 1 || pe.length() % ps.length() != 0) return FMHIP_ERR_INVALID_ARGUMENT;
+    std::vector<uint8_t> ex;
+    if (!poly_exponents(pe.p, pe.length(), ex)) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int64_t nt = pe.length() / ps.length(), ne = px.p ? px.length() : 0, ny = py.p ? py.length() : 0, nx = nt + ne;
+    if ((int64_t)po.length() < nx * (nx + 1) / 2 + nx * ny) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_polynomial_cross_moments((const fmhip_vec*)ps.p, ps.length(), ex.data(), (int)nt, ne ? (const fmhip_vec*)px.p : nullptr, (int)ne, ny ? (const fmhip_vec*)py.p : nullptr, (int)ny, po.p);
+}
+FMJ(jint, polynomialEvaluate)(JNIEnv* env, jclass, jlongArray states, jintArray exponents, jlongArray extraX, jdoubleArray coefficients, jlongArray out) {
+    Pin<jlong> ps(env, states, JNI_ABORT); Pin<jint> pe(env, exponents, JNI_ABORT); Pin<jlong> px(env, extraX, JNI_ABORT); Pin<jdouble> pc(env, coefficients, JNI_ABORT);
+    if (!ps.p || !pe.p || !pc.p || ps.length() < 1 || pe.length() % ps.length() != 0) return FMHIP_ERR_INVALID_ARGUMENT;
+    std::vector<uint8_t> ex;
+    if (!poly_exponents(pe.p, pe.length(), ex)) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int64_t nt = pe.length() / ps.length(), ne = px.p ? px.length() : 0;
+    if ((int64_t)pc.length() < nt + ne) return FMHIP_ERR_INVALID_ARGUMENT;
+    fmhip_vec h = 0;
+    const int st = fmhip_polynomial_evaluate((const fmhip_vec*)ps.p, ps.length(), ex.data(), (int)nt, ne ? (const fmhip_vec*)px.p : nullptr, (int)ne, pc.p, &h);
+    if (st == FMHIP_OK) set1(env, out, (jlong)h);
+    return st;
+}
+// columns as in binnedCrossMomentsHost: nStates (nExtra, nY) columns of n floats each, one after the other; bit i of onesMask: extra i is the constant 1
+static bool poly_columns(const jfloat* flat, int64_t flatLength, int64_t n, int count, int onesMask, std::vector<const float*>& out) {
+    if (count < 0 || count > 64) return false;
+    for (int i = 0; i < count; ++i) {
+        if (i < 31 && ((onesMask >> i) & 1)) { out.push_back(nullptr); continue; }
+        if (!flat || flatLength < (int64_t)(i + 1) * n) return false;
+        out.push_back(flat + (int64_t)i * n);
+    }
+    return true;
+}
+FMJ(jint, polynomialCrossMomentsHost)(JNIEnv* env, jclass, jfloatArray stateColumns, jint nStates, jintArray exponents, jfloatArray extraColumns, jint nExtra, jint onesMask, jfloatArray yColumns, jint nY, jdoubleArray sumsOut) {
+    Pin<jfloat> ps(env, stateColumns, JNI_ABORT); Pin<jint> pe(env, exponents, JNI_ABORT); Pin<jfloat> px(env, extraColumns, JNI_ABORT); Pin<jfloat> py(env, yColumns, JNI_ABORT); Pin<jdouble> po(env, sumsOut);
+    if (!ps.p || !pe.p || !po.p || nStates < 1 || nStates > 8 || ps.length() % nStates != 0 || pe.length() % nStates != 0) return FMHIP_ERR_INVALID_ARGUMENT;
+    std::vector<uint8_t> ex;
+    if (!poly_exponents(pe.p, pe.length(), ex)) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int64_t n = ps.length() / nStates, nt = pe.length() / nStates, nx = nt + nExtra;
+    std::vector<const float*> ss, xs, ys;
+    if (!poly_columns(ps.p, ps.length(), n, nStates, 0, ss) || !poly_columns(px.p, px.p ? px.length() : 0, n, nExtra, onesMask, xs) || !poly_columns(py.p, py.p ? py.length() : 0, n, nY, 0, ys)) return FMHIP_ERR_INVALID_ARGUMENT;
+    if ((int64_t)po.length() < nx * (nx + 1) / 2 + nx * nY) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_polynomial_cross_moments_host(ss.data(), n, nStates, ex.data(), (int)nt, nExtra ? xs.data() : nullptr, nExtra, nY ? ys.data() : nullptr, nY, po.p);
+}
+FMJ(jint, polynomialEvaluateHost)(JNIEnv* env, jclass, jfloatArray stateColumns, jint nStates, jintArray exponents, jfloatArray extraColumns, jint nExtra, jint onesMask, jdoubleArray coefficients, jfloatArray out) {
+    Pin<jfloat> ps(env, stateColumns, JNI_ABORT); Pin<jint> pe(env, exponents, JNI_ABORT); Pin<jfloat> px(env, extraColumns, JNI_ABORT); Pin<jdouble> pc(env, coefficients, JNI_ABORT); Pin<jfloat> po(env, out);
+    if (!ps.p || !pe.p || !pc.p || !po.p || nStates < 1 || nStates > 8 || ps.length() % nStates != 0 || pe.length() % nStates != 0) return FMHIP_ERR_INVALID_ARGUMENT;
+    std::vector<uint8_t> ex;
+    if (!poly_exponents(pe.p, pe.length(), ex)) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int64_t n = ps.length() / nStates, nt = pe.length() / nStates;
+    std::vector<const float*> ss, xs;
+    if (!poly_columns(ps.p, ps.length(), n, nStates, 0, ss) || !poly_columns(px.p, px.p ? px.length() : 0, n, nExtra, onesMask, xs)) return FMHIP_ERR_INVALID_ARGUMENT;
+    if ((int64_t)pc.length() < nt + nExtra || (int64_t)po.length() < n) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_polynomial_evaluate_host(ss.data(), n, nStates, ex.data(), (int)nt, nExtra ? xs.data() : nullptr, nExtra, pc.p, po.p);
+}
 FMJ(jint, reduceMomentsBatchDevice)(JNIEnv* env, jclass, jlongArray vectors, jdoubleArray shifts, jlong deviceOut) {
     Pin<jlong> pv(env, vectors, JNI_ABORT); Pin<jdouble> ps(env, shifts, JNI_ABORT);
     if (!pv.p || (ps.p && ps.length() < pv.length())) return FMHIP_ERR_INVALID_ARGUMENT;
