@@ -23,6 +23,7 @@ from .program import Program
 from .regression import MonteCarloConditionalExpectationRegression, covariance_matrix, cross_moments, solve_normal_equations
 from .regression import MonteCarloConditionalExpectationLocalizedRegression, binned_cross_moments, binned_evaluate, quantile_bounds
 from .regression import MonteCarloConditionalExpectationPolynomialRegression, polynomial_cross_moments, polynomial_evaluate
+from .sorting import argsort, rank_scores, read_elements, sort_by_key, sorted_quantiles, spearman_matrix
 from .differentiable import RandomVariableDifferentiableAAD, RandomVariableDifferentiableAADFactory
 
 

@@ -822,6 +822,39 @@ int fmhip_binned_evaluate(fmhip_vec key, const double* bounds, int n_bins, const
     return guarded([&] { const fmhip_vec r = Engine::get().binned_eval(key, bounds, n_bins, x, n_x, coefficients, out); *out = r; });
 }
 
+// ---------------------------------------------------------------- the device sort (sort_engine.hpp)
+int fmhip_argsort_host(const float* key, int64_t n, int64_t* permutation_out) {
+    return host_only([&] { fm::sort_argsort_host_checked(key, n, permutation_out); });
+}
+int fmhip_sort_by_key(fmhip_vec key, const fmhip_vec* values, int n_values, fmhip_vec* sorted_key_out, fmhip_vec* sorted_values_out) {
+    FRONT(sort_by_key(key, values, n_values, sorted_key_out, sorted_values_out));
+    if (te::active()) {
+        const int rc = host_only([&] { fm::sort_check_by_key(key, values, n_values, sorted_key_out, sorted_values_out); });
+        if (rc != FMHIP_OK) return rc;
+        const std::vector<fmhip_vec> all = te_operands(key, values, n_values, nullptr, 0);
+        TE_LOCAL(all.data(), 1 + n_values, L, fmhip_sort_by_key(L[0], L + 1, n_values, sorted_key_out, sorted_values_out));
+    }
+    return guarded([&] { Engine::get().sort_by_key(key, values, n_values, sorted_key_out, sorted_values_out); });
+}
+int fmhip_argsort(fmhip_vec key, int64_t* permutation_out) {
+    FRONT(argsort(key, permutation_out));
+    TE_OWNER(key, fmhip_argsort(key, permutation_out));
+    return guarded([&] { Engine::get().argsort(key, permutation_out); });
+}
+int fmhip_rank_scores(fmhip_vec key, fmhip_vec* out) {
+    FRONT(rank_scores(key, out));
+    if (te::active()) {
+        if (!out) { g_last_error = "null pointer: out"; return FMHIP_ERR_INVALID_ARGUMENT; }
+        TE_LOCAL(&key, 1, L, fmhip_rank_scores(L[0], out));
+    }
+    return guarded([&] { const fmhip_vec r = Engine::get().rank_scores(key, out); *out = r; });
+}
+int fmhip_vec_read_elements(fmhip_vec v, const int64_t* positions, int count, double* out) {
+    FRONT(vec_read_elements(v, positions, count, out));
+    TE_OWNER(v, fmhip_vec_read_elements(v, positions, count, out));
+    return guarded([&] { Engine::get().read_elements(v, positions, count, out); });
+}
+
 // The one call of a caller that values product after product: the engine lock is held for the bookkeeping (graph → launch → commit),
 // NOT while the device computes — other threads record and launch meanwhile.  The moments arrive in a slot of pinned memory of their
 // own; this thread polls its flag, then takes the lock again to copy them out and give the launch's buffers back.

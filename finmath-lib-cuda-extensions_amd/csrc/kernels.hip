@@ -24,6 +24,7 @@
 #include "fm_kernel_parts.hpp"
 #include "fm_normal_table.hpp"
 #include "kernels.h"
+#include "os_device.hpp"
 
 namespace fm {
 
@@ -376,34 +377,6 @@ __global__ void __launch_bounds__(64) fm_combine_moments_kernel(const double* __
 // All counts are integers (LDS atomics per workgroup, one agent-scope integer add per NON-EMPTY bin per workgroup); the one fp64 sum is
 // added in an order that depends on n alone.  No float atomics: results are the same from run to run by construction.
 // ---------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ uint32_t os_key(float x)
-{
-    const uint32_t u = __float_as_uint(x);
-    const uint32_t k = (u >> 31) ? ~u : (u | 0x80000000u);
-    return ((u & 0x7fffffffu) > 0x7f800000u) ? 0xffffffffu : k;     // NaNs of either sign and any payload: one key, the last
-}
-
-// h[bin] += 1 for every lane with `valid`.  Monte-Carlo data is clustered — the leading digit of values in [0.5, 2) is ONE bin, a floored
-// payoff is half exact zeros in every pass — and same-address LDS atomics serialise: the most frequent digits of the wave are peeled off
-// first, one add of a population count each (at most three rounds, given up as soon as a round finds fewer than eight equal lanes: digits
-// that are spread out gain nothing from it); what is left adds lane by lane.
-__device__ __forceinline__ void os_lds_add(uint32_t* h, const uint32_t bin, bool valid)
-{
-    uint64_t pending = __ballot(valid);
-#pragma unroll 1
-    for (int round = 0; round < 3 && pending != 0ull; ++round) {
-        const int leader = __ffsll((long long)pending) - 1;
-        const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)bin, leader);
-        const uint64_t same = __ballot(valid && bin == b0);
-        const uint32_t c = (uint32_t)__popcll(same);
-        if ((int)(threadIdx.x & 63u) == leader) atomicAdd(h + b0, c);
-        valid = valid && bin != b0;
-        pending &= ~same;
-        if (c < 8u) break;
-    }
-    if (valid) atomicAdd(h + bin, 1u);
-}
 
 // Arrival counting at `counter` (zero before the launch, zero again after the last arrival): true, for the whole workgroup, in the LAST of
 // `members` workgroups.  Whatever the others wrote before they arrived is visible to it: every thread's writes are released at agent scope

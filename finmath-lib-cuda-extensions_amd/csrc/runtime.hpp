@@ -395,6 +395,15 @@ public:
     void binned_xmom_pass(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, int64_t* counts_out, double* sums_out);
     fmhip_vec binned_eval(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const double* coefficients, const fmhip_vec* out_checked);
 
+    // the device sort (sort_engine.hpp): a stable radix sort of (key, path index) pairs by the key of §4.7 — equal keys in
+    // ascending path order —, and what is made of its permutation: the key and up to 8 companions gathered as new, materialised vectors; the
+    // permutation itself on the host; the rank scores (rank + 0.5) / n per path as a new vector.  read_elements: (double)v[positions[j]] of a
+    // few positions.  Arguments are checked before anything is flushed or launched; one engine's sample only (UNSUPPORTED with a communicator).
+    void sort_by_key(fmhip_vec key, const fmhip_vec* values, int n_values, fmhip_vec* sorted_key_out, fmhip_vec* sorted_values_out);
+    void argsort(fmhip_vec key, int64_t* permutation_out);
+    fmhip_vec rank_scores(fmhip_vec key, const fmhip_vec* out_checked);
+    void read_elements(fmhip_vec v, const int64_t* positions, int count, double* out);
+
     // programs
     fmhip_program program_create(const fmhip_prog_op* ops, int n_ops, int n_in, const int32_t* outs, int n_out,
                                  const int32_t* reds, int n_red);
@@ -486,6 +495,9 @@ private:
     // histograms; the kernels leave it so), scratch that need not be (tables, partial sums), the sequence number the completion flag
     // receives.  `what` names the pass in the frame's messages.
     struct PassHold;
+    struct SortBuffers;
+    int64_t sort_size(const fmhip_vec* hs, int count, const char* what);
+    hipError_t sort_enqueue(uint64_t key_ptr, int64_t n, const SortBuffers& s);
     void pass_prepare(const fmhip_vec* hs, int count, PassHold& hold, const char* what);
     void pass_scratch(size_t zero_bytes, size_t other_bytes);
     template <class Launch> void pass_launch(volatile uint64_t* flag, uint64_t*& done_flag, uint64_t& done_value, const char* what, Launch launch);
@@ -737,6 +749,11 @@ void increments_host(int32_t seed, int n_steps, int n_factors, int64_t n_paths, 
 void sobol_check(int randomize, int construction, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, const fmhip_vec* out);
 void sobol_increments_host(int32_t seed, int randomize, int construction, int n_steps, int n_factors, int64_t n_paths, int64_t path_offset, const double* dt, double* host_out);
 void sobol_points_host(int n_dims, int64_t first_index, int64_t count, int32_t seed, int randomize, double* u_out);
+// what can be said about the arguments of fmhip_sort_by_key / fmhip_vec_read_elements without looking at a vector, and the definition of the
+// order (sort_engine.hpp, sort_host.hpp): all throw FMHIP_ERR_INVALID_ARGUMENT
+void sort_check_by_key(fmhip_vec key, const fmhip_vec* values, int n_values, const fmhip_vec* sorted_key_out, const fmhip_vec* sorted_values_out);
+void sort_check_read_elements(fmhip_vec v, const int64_t* positions, int count, const double* out);
+void sort_argsort_host_checked(const float* key, int64_t n, int64_t* permutation_out);
 // what can be said about the arguments of fmhip_binned_cross_moments / fmhip_binned_evaluate without looking at a vector (binned_engine.hpp; the
 // rules are fmhost::binnedCheck*'s, host/binned_regression.hpp), and the host definitions: all throw FMHIP_ERR_INVALID_ARGUMENT
 void binned_check_moments(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, const int64_t* counts_out, const double* sums_out);

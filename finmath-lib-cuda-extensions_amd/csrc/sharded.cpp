@@ -877,6 +877,66 @@ int binned_evaluate(fmhip_vec key, const double* bounds, int n_bins, const fmhip
     });
 }
 
+// The device sort (sort_engine.hpp).  The order of a sample that is spread over several shards needs an exchange of elements between them,
+// which nothing does: a list of more than one shard answers FMHIP_ERR_UNSUPPORTED, never the order of a part.  A list of ONE shard is that
+// shard's call.
+static void sort_one_shard(Shards& s, const char* what) {
+    if (s.D() > 1) throw Error(FMHIP_ERR_UNSUPPORTED, std::string(what) + " with a device list of " + std::to_string(s.D()) + " shards: a global order needs an exchange of elements between the shards");
+}
+int sort_by_key(fmhip_vec key, const fmhip_vec* values, int n_values, fmhip_vec* sorted_key_out, fmhip_vec* sorted_values_out) {
+    return fronted([&](Shards& s) {
+        sort_check_by_key(key, values, n_values, sorted_key_out, sorted_values_out);
+        std::vector<fmhip_vec> all(1, key);
+        all.insert(all.end(), values, values + n_values);
+        const int64_t n = front_size(s, all.data(), 1 + n_values, "sort by key", false);
+        sort_one_shard(s, "sort by key");
+        const bool want_key = sorted_key_out != nullptr;
+        std::vector<fmhip_vec> ids;
+        for (int i = want_key ? 0 : 1; i < 1 + n_values; ++i) ids.push_back(s.fresh(n));
+        s.post([&](Worker& w) {
+            const std::vector<fmhip_vec> l = localize(w, all.data(), 1 + n_values);
+            fmhip_vec k = 0; std::vector<fmhip_vec> v((size_t)n_values + 1, 0);
+            if (!w.ok(fmhip_sort_by_key(l[0], l.data() + 1, n_values, want_key ? &k : nullptr, v.data()))) return;
+            size_t at = 0;
+            if (want_key) w.bind(ids[at++], k);
+            for (int i = 0; i < n_values; ++i) w.bind(ids[at++], v[(size_t)i]);
+        });
+        try { s.wait(); } catch (...) { for (fmhip_vec id : ids) s.meta.erase(id); throw; }
+        size_t at = 0;
+        if (want_key) *sorted_key_out = ids[at++];
+        for (int i = 0; i < n_values; ++i) sorted_values_out[i] = ids[at++];
+    });
+}
+int argsort(fmhip_vec key, int64_t* permutation_out) {
+    return fronted([&](Shards& s) {
+        need(permutation_out, "permutation_out");
+        front_size(s, &key, 1, "argsort", false);
+        sort_one_shard(s, "argsort");
+        s.post([&](Worker& w) { w.ok(fmhip_argsort(w.at(key), permutation_out)); });
+        s.wait();
+    });
+}
+int rank_scores(fmhip_vec key, fmhip_vec* out) {
+    return fronted([&](Shards& s) {
+        need(out, "out");
+        const int64_t n = front_size(s, &key, 1, "rank scores", false);
+        sort_one_shard(s, "rank scores");
+        const fmhip_vec id = s.fresh(n);
+        s.post([&](Worker& w) { fmhip_vec h = 0; if (w.ok(fmhip_rank_scores(w.at(key), &h))) w.bind(id, h); });
+        try { s.wait(); } catch (...) { s.meta.erase(id); throw; }
+        *out = id;
+    });
+}
+int vec_read_elements(fmhip_vec v, const int64_t* positions, int count, double* out) {
+    return fronted([&](Shards& s) {
+        sort_check_read_elements(v, positions, count, out);
+        front_size(s, &v, 1, "read elements", false);
+        sort_one_shard(s, "read elements");
+        s.post([&](Worker& w) { w.ok(fmhip_vec_read_elements(w.at(v), positions, count, out)); });
+        s.wait();
+    });
+}
+
 int vec_give_up_values(const fmhip_vec* vectors, int count) {
     return fronted([&](Shards& s) {
         need(vectors, "vectors");

@@ -398,6 +398,35 @@ int fmhip_binned_evaluate(fmhip_vec key, const double* bounds, int n_bins, const
 int fmhip_binned_evaluate_host(const float* key, int64_t n, const double* bounds, int n_bins, const float* const* x, int n_x,
                                const double* coefficients, float* out);
 
+/* Sort on the device: the whole ordered sample, the permutation and the ranks per path without the vector leaving the
+ * device — what the reference downloads and sorts for.  A stable radix sort of (key, path index) pairs.
+ * Order: ascending in the 32-bit key of the order statistics — the order of java.util.Arrays.sort(float[]):
+ *   -inf < ... < -0.0 < +0.0 < ... < +inf < NaN, every NaN (either sign, any payload) one key.  TIES ARE BROKEN BY PATH INDEX: equal keys
+ *   keep ascending path order, NaNs among them.  Midranks (average ranks for ties) and descending order are not offered.
+ * fmhip_sort_by_key: the key vector and n_values (0 ... 8) companion vectors of its size n (1 ... 2^31 - 1), reordered by the key's
+ *   permutation: *sorted_key_out and sorted_values_out[i] are new, materialised vectors with out[r] = in[permutation[r]], copied BIT FOR BIT
+ *   from the inputs (a NaN keeps its payload, a zero its sign).  sorted_key_out may be NULL when n_values > 0 (only the companions are
+ *   wanted); the key may be among the companions.  The inputs are unchanged.
+ * fmhip_argsort: permutation_out[n] on the host: permutation_out[r] = the path at position r of the ascending sample.
+ * fmhip_argsort_host: the DEFINITION over a host float array; needs no device.
+ * fmhip_rank_scores: *out = a new, materialised vector with out[p] = (float)((rank(p) + 0.5) / n), the quotient in fp64, rank(p) the ORDINAL
+ *   rank of path p (the position of p in the permutation: ties by path index) — empirical-CDF scores strictly inside (0, 1).
+ * fmhip_vec_read_elements: out[j] = (double)v[positions[j]] for count >= 1 positions in [0, n), in any order, repeats allowed: a few
+ *   elements of a vector (the quantiles of a sorted one) without reading the vector.
+ * Everything is checked on the host before anything is flushed or launched, with the status codes of the other passes: n_values outside
+ * 0 ... 8, a NULL pointer, a handle of 0, nothing asked for, a position outside [0, n), n == 0 or n > 2^31 - 1 -> FMHIP_ERR_INVALID_ARGUMENT;
+ * vectors of different sizes -> FMHIP_ERR_SIZE_MISMATCH; FMHIP_ERR_INVALID_HANDLE.  A vector whose values were given up is the error a read
+ * of it is.  A build without the kernels answers FMHIP_ERR_UNSUPPORTED; it never falls back.
+ * ONE sample on ONE device: a global order needs an exchange of elements between devices, which is not done.  With a device list of more
+ * than one shard, and with an expectation communicator of more than one rank, the three sorting calls answer FMHIP_ERR_UNSUPPORTED (never
+ * the order of a part); fmhip_vec_read_elements answers FMHIP_ERR_UNSUPPORTED with a device list of more than one shard and reads this
+ * rank's vector under a communicator. */
+int fmhip_sort_by_key(fmhip_vec key, const fmhip_vec* values, int n_values, fmhip_vec* sorted_key_out, fmhip_vec* sorted_values_out);
+int fmhip_argsort(fmhip_vec key, int64_t* permutation_out);
+int fmhip_argsort_host(const float* key, int64_t n, int64_t* permutation_out);
+int fmhip_rank_scores(fmhip_vec key, fmhip_vec* out);
+int fmhip_vec_read_elements(fmhip_vec v, const int64_t* positions, int count, double* out);
+
 /* Polynomial regression in one pass: the normal equations of a regression on a POLYNOMIAL basis — the Longstaff-Schwartz
  * basis of a product on several underlyings — from the state vectors alone, and the fitted polynomial as a new vector.  The monomials are
  * never in memory: the moments kernel forms them in registers as the operands of fmhip_cross_moments_wide's pass.

@@ -90,6 +90,17 @@ final class Native {
 	static native int binnedEvaluate(long key, double[] bounds, long[] x, double[] coefficients, long[] out);
 	/** The definition of binnedEvaluate over host arrays (columns as in binnedCrossMomentsHost). */
 	static native int binnedEvaluateHost(float[] key, double[] bounds, float[] xColumns, int nX, int onesMask, double[] coefficients, float[] out);
+	// ---- sort on the device: a stable radix sort of (key, path index) pairs by the key of the order statistics; ties keep path order, NaNs last
+	/** sortedKeyOut[0] (may be null when values.length > 0) and sortedValuesOut[i] = new vectors out[r] = in[permutation[r]], copied bit for bit; values.length <= 8. */
+	static native int sortByKey(long key, long[] values, long[] sortedKeyOut, long[] sortedValuesOut);
+	/** permutationOut[r] = the path at position r of the ascending sample; permutationOut.length = the vector's size. */
+	static native int argsort(long key, long[] permutationOut);
+	/** The definition of argsort over a host array. */
+	static native int argsortHost(float[] key, long[] permutationOut);
+	/** out[0] = a new vector: (float) ((rank(p) + 0.5) / n) per path, ordinal ranks (ties by path index). */
+	static native int rankScores(long key, long[] out);
+	/** out[j] = (double) v[positions[j]]; every position in [0, size). */
+	static native int vecReadElements(long v, long[] positions, double[] out);
 	// ---- polynomial regression in one pass: the normal equations of a polynomial basis from the state vectors, the monomials formed in registers
 	/** crossMomentsWide for the regressors [monomials of states..., extraX...] and the dependents y; exponents holds states.length ints (0 ... 6) per monomial, a row of zeros is the constant 1; a handle of 0 in extraX is the constant 1.  Bit for bit the sums of crossMomentsWide on the materialised monomials. */
 	static native int polynomialCrossMoments(long[] states, int[] exponents, long[] extraX, long[] y, double[] sumsOut);

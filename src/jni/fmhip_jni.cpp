@@ -245,6 +245,43 @@ FMJ(jint, binnedEvaluateHost)(JNIEnv* env, jclass, jfloatArray key, jdoubleArray
     if ((int64_t)pc.length() < nb * nX || (int64_t)po.length() < n) return FMHIP_ERR_INVALID_ARGUMENT;
     return fmhip_binned_evaluate_host(pk.p, n, pb.p, (int)nb, xs.data(), nX, pc.p, po.p);
 }
+// ---------------------------------------------------------------- sort on the device
+FMJ(jint, sortByKey)(JNIEnv* env, jclass, jlong key, jlongArray values, jlongArray sortedKeyOut, jlongArray sortedValuesOut) {
+    Pin<jlong> pv(env, values, JNI_ABORT);
+    const int64_t nv = pv.p ? pv.length() : 0;
+    if (nv > 8 || (nv > 0 && (!sortedValuesOut || env->GetArrayLength(sortedValuesOut) < nv)) || (sortedKeyOut && env->GetArrayLength(sortedKeyOut) < 1)) return FMHIP_ERR_INVALID_ARGUMENT;
+    fmhip_vec k = 0, out[8] = { 0 };
+    const int st = fmhip_sort_by_key(key, (const fmhip_vec*)pv.p, (int)nv, sortedKeyOut ? &k : nullptr, out);
+    if (st == FMHIP_OK) {
+        set1(env, sortedKeyOut, (jlong)k);
+        if (nv > 0) { jlong o[8]; for (int i = 0; i < nv; ++i) o[i] = (jlong)out[i]; env->SetLongArrayRegion(sortedValuesOut, 0, (jsize)nv, o); }
+    }
+    return st;
+}
+FMJ(jint, argsort)(JNIEnv* env, jclass, jlong key, jlongArray permutationOut) {
+    int64_t n = 0;
+    const int sz = fmhip_vec_size(key, &n);
+    if (sz != FMHIP_OK) return sz;
+    Pin<jlong> po(env, permutationOut);
+    if (!po.p || (int64_t)po.length() < n) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_argsort(key, (int64_t*)po.p);
+}
+FMJ(jint, argsortHost)(JNIEnv* env, jclass, jfloatArray key, jlongArray permutationOut) {
+    Pin<jfloat> pk(env, key, JNI_ABORT); Pin<jlong> po(env, permutationOut);
+    if (!pk.p || !po.p || po.length() < pk.length()) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_argsort_host(pk.p, pk.length(), (int64_t*)po.p);
+}
+FMJ(jint, rankScores)(JNIEnv* env, jclass, jlong key, jlongArray out) {
+    fmhip_vec h = 0;
+    const int st = fmhip_rank_scores(key, &h);
+    if (st == FMHIP_OK) set1(env, out, (jlong)h);
+    return st;
+}
+FMJ(jint, vecReadElements)(JNIEnv* env, jclass, jlong v, jlongArray positions, jdoubleArray out) {
+    Pin<jlong> pp(env, positions, JNI_ABORT); Pin<jdouble> po(env, out);
+    if (!pp.p || !po.p || po.length() < pp.length()) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_vec_read_elements(v, (const int64_t*)pp.p, (int)pp.length(), po.p);
+}
 // ---------------------------------------------------------------- polynomial regression in one pass: the monomials of the states are formed in registers
 // exponents: states.length (nStates) entries per term, each 0 … 6, as ints; anything outside a byte is refused here, the rest by the library
 static bool poly_exponents(const jint* e, int64_t count, std::vector<uint8_t>& out) {
