@@ -143,7 +143,7 @@ void Engine::argsort(fmhip_vec key, int64_t* permutation_out) {
     });
     // the permutation comes down as read() brings a vector down: through the pinned block, widened on the way
     const uint32_t* perm = reinterpret_cast<const uint32_t*>(s.b[3]->ptr);
-    const int64_t chunk = int64_t(16) << 20;
+    const int64_t chunk = FM_SORT_READBACK_CHUNK;
     for (int64_t off = 0; off < n; off += chunk) {
         const int64_t m = std::min(chunk, n - off);
         uint32_t* st = (uint32_t*)ensure_stage((size_t)m * 4);

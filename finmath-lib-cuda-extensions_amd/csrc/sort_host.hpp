@@ -19,6 +19,8 @@ constexpr int FM_SORT_BINS = 256;                  // 8-bit digits: four passes 
 constexpr int FM_SORT_PASSES = 4;
 constexpr int FM_SORT_MIN_CHUNK_TILES = 2;         // a workgroup's chunk is at least two tiles: half the rows in the table, and the running offsets from tile to tile are not a large-n path
 constexpr int FM_SORT_MAX_BLOCKS = 1024;           // rows of the count table: four workgroups per CU
+constexpr int FM_SORT_STREAM_MAX_BLOCKS = 8192;   // grid cap of the gather and the scores kernel (256 lanes, a quad each): above 4 · 256 · 8192 elements a lane takes a second quad
+constexpr int FM_SORT_READBACK_CHUNK = 16 << 20;   // elements of the permutation per D2H copy of fmhip_argsort (64 MiB of pinned stage)
 constexpr int FM_SORT_MAX_VALUES = 8;              // companion vectors of one fmhip_sort_by_key call
 constexpr int64_t FM_SORT_MAX_N = 0x7fffffffLL;    // positions are uint32 and every position + one tile stays below 2^32
 

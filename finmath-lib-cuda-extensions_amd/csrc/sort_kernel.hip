@@ -257,7 +257,7 @@ __global__ void __launch_bounds__(64) fm_sort_done_kernel(uint64_t* done_flag, c
 static uint32_t st_stream_blocks(uint64_t quads)
 {
     const uint64_t b = (quads + 255u) / 256u;
-    return (uint32_t)(b < 1u ? 1u : b > 8192u ? 8192u : b);
+    return (uint32_t)(b < 1u ? 1u : b > (uint64_t)FM_SORT_STREAM_MAX_BLOCKS ? (uint64_t)FM_SORT_STREAM_MAX_BLOCKS : b);
 }
 
 hipError_t launch_sort_pass(const DevSortPassArgs& a, hipStream_t st)

@@ -19,6 +19,7 @@ constexpr int FM_POLY_MAX_STATES = 8;
 constexpr int FM_POLY_MAX_EXPONENT = 6;
 constexpr int FM_POLY_MAX_EVAL = 60;               // terms and extra vectors of one evaluation: the estimator's limit
 constexpr int FM_POLY_EVAL_BLOCK = 256;
+constexpr int FM_POLY_EVAL_MAX_BLOCKS = 4096;      // the evaluation's grid stops growing here: above 4 · 256 · 4096 elements a lane takes a second quad
 
 // the slot of a term: state s has exponent (slot >> 3s) & 7
 inline uint64_t xmom_poly_term_slot(const uint8_t* exponents, int n_states)

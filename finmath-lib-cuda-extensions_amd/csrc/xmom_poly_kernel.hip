@@ -159,7 +159,7 @@ hipError_t launch_poly_eval(const DevPolyEvalArgs& a, hipStream_t st)
 {
     if (!poly_eval_shape_ok(a)) return hipErrorInvalidValue;
     int64_t blocks = (a.n + 4 * FM_POLY_EVAL_BLOCK - 1) / (4 * FM_POLY_EVAL_BLOCK);
-    if (blocks > 4096) blocks = 4096;
+    if (blocks > FM_POLY_EVAL_MAX_BLOCKS) blocks = FM_POLY_EVAL_MAX_BLOCKS;
     hipLaunchKernelGGL(fm_poly_eval_kernel, dim3((uint32_t)blocks), dim3(FM_POLY_EVAL_BLOCK), 0, st, a);
     return hipGetLastError();
 }

@@ -1,7 +1,10 @@
 """The device sort without a GPU (include/fmhip.h: fmhip_argsort_host; csrc/sort_host.hpp): the DEFINITION of the order —
-ascending in the 32-bit key of the order statistics, ties in path order — against numpy's stable argsort of the same keys, and the host
+ascending in the 32-bit key of the order statistics, ties in path order — against numpy's stable argsort of the same keys; the host
 half of the kernels (chunk arithmetic, offsets, a model of a pass) in a stand-alone program under AddressSanitizer / UBSan
-(tests/cpp/test_sort_host.cpp).  Nothing sanitized is loaded into this process."""
+(tests/cpp/test_sort_host.cpp); and the engine's side of the four calls (csrc/sort_engine.hpp, the fronts of csrc/sharded.cpp and
+csrc/abi.cpp) on the test-only null device under AddressSanitizer + UBSan and ThreadSanitizer (tests/nulldev/sort.mk: drive_sort.cpp with
+the stand-in launchers of null_sort.cpp, drive_sort_absent.cpp without them).  Stand-alone programs only: nothing sanitized is loaded
+into this process."""
 import ctypes as C
 import os
 import shutil
@@ -11,6 +14,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NULLDEV = os.path.join(ROOT, "tests", "nulldev")
 
 
 def keys(a):
@@ -117,3 +121,60 @@ def test_the_kernels_are_in_the_library(fm):
     blob = open(fm._native.LIB_PATH, "rb").read()
     for kernel in (b"fm_sort_count_kernel", b"fm_sort_offsets_kernel", b"fm_sort_scatter_kernel", b"fm_sort_gather_kernel", b"fm_sort_scores_kernel", b"fm_sort_read_elements_kernel"):
         assert kernel in blob, kernel
+
+
+# ---------------------------------------------------------------- the engine's side on the null device
+@pytest.fixture(scope="module")
+def built():
+    if not shutil.which("g++") or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"):
+        pytest.skip("needs g++ and the HIP headers")
+    r = subprocess.run(["make", "-C", NULLDEV, "-f", "sort.mk", "-j8", "sort_asan", "sort_tsan", "sort_absent_asan"], capture_output=True, text=True, timeout=1200)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    return os.path.join(NULLDEV, "build")
+
+
+def _env(tmp_path, env):
+    return dict(os.environ, FMHIP_JIT_CACHE_DIR=str(tmp_path / "code_objects"), FMHIP_JIT_PACK_DIR="off", FMHIP_RING_BYTES="16384", FMHIP_ARENA_BYTES="4096",
+                ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1", TSAN_OPTIONS="halt_on_error=1", **env)
+
+
+@pytest.mark.parametrize("env", [{}, {"FMNULL_DEVICES": "2"}, {"FMNULL_DEVICES": "3"}, {"FMNULL_THREAD_ENGINES": "1"}])
+def test_engine_pass_is_clean_under_the_sanitizers(built, tmp_path, env):
+    """drive_sort: the four calls on vectors of real data at n = 1 … 300 007 and small again, checked against the definition; 0, 1 and 8
+    companions, pending operands, a second thread releasing the inputs of pending operands during the call, every argument error — on one
+    engine and behind a device list of one shard, behind 2 and 3 shards (FMHIP_ERR_UNSUPPORTED, nothing left behind), with thread engines
+    (a caller that owns none of the vectors, owners mixed in one call)."""
+    full = _env(tmp_path, env)
+    a = subprocess.run([os.path.join(built, "drive_sort_asan")], capture_output=True, text=True, timeout=600, env=full)
+    assert a.returncode == 0 and "Sanitizer" not in a.stderr and "runtime error" not in a.stderr, a.stdout[-500:] + a.stderr[-6000:]
+    assert a.stdout.count("sort done") == 2 and a.stderr == ""
+    assert ("a device list of one shard: checked" in a.stdout) == (not env)
+    t = subprocess.run([os.path.join(built, "drive_sort_tsan")], capture_output=True, text=True, timeout=600, env=full)
+    assert t.returncode == 0 and "ThreadSanitizer" not in t.stderr, t.stdout[-500:] + t.stderr[-6000:]
+    assert t.stdout.count("sort done") == 2 and t.stderr == ""
+
+
+def test_a_failing_allocation_inside_a_sort_leaves_nothing_behind(built, tmp_path):
+    """One fmhip_sort_by_key with 8 companions takes 13 buffers from the pool: the 4 ping-pong buffers, then the 9 outputs.  The hook
+    FMHIP_TEST_FAIL_ALLOC_AT is swept over them (positions from a counting run), and once set where nothing reaches it: the call answers FMHIP_OK or
+    FMHIP_ERR_OUT_OF_MEMORY, a result it gives is right, live vectors and bytes in use are what they were, the same call succeeds
+    afterwards (the driver checks all of it), and the process ends without a leak."""
+    import re
+    exe = os.path.join(built, "drive_sort_asan")
+    counting = subprocess.run([exe, "failure"], capture_output=True, text=True, timeout=600, env=_env(tmp_path, {}))
+    assert counting.returncode == 0 and "Sanitizer" not in counting.stderr, counting.stdout[-500:] + counting.stderr[-6000:]
+    before, inside, status = map(int, re.search(r"failure: (\d+) allocations before the call, (\d+) in it, status (-?\d+)", counting.stdout).groups())
+    assert inside == 13 and status == 0
+    for at in list(range(before + 1, before + inside + 1)) + [10**9]:
+        r = subprocess.run([exe, "failure"], capture_output=True, text=True, timeout=600, env=_env(tmp_path, {"FMHIP_TEST_FAIL_ALLOC_AT": str(at)}))
+        assert r.returncode == 0 and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr and r.stderr == "", (at, r.stdout[-500:] + r.stderr[-6000:])
+        assert "failure done" in r.stdout
+        failed = int(re.search(r"status (-?\d+)", r.stdout).group(1)) != 0
+        assert failed == (at <= before + inside), (at, r.stdout)      # every one of the 13 is THIS call's allocation: it fails, and says so
+
+
+@pytest.mark.parametrize("env", [{}, {"FMNULL_DEVICES": "2"}, {"FMNULL_THREAD_ENGINES": "1"}])
+def test_a_build_without_the_kernel_answers_unsupported(built, tmp_path, env):
+    a = subprocess.run([os.path.join(built, "drive_sort_absent_asan")], capture_output=True, text=True, timeout=600, env=_env(tmp_path, env))
+    assert a.returncode == 0 and "Sanitizer" not in a.stderr and "runtime error" not in a.stderr, a.stdout[-500:] + a.stderr[-6000:]
+    assert a.stdout.count("sort absent done") == 2
