@@ -4169,6 +4169,7 @@ void Engine::engine_stats(fmhip_engine_stats_t* out) {
     out->peak_bytes_reserved = pool_.peak_reserved;
     out->late_releases_while_waiting = n_late_waiting_; out->late_releases_at_once = n_late_at_once_; out->late_release_nanoseconds = late_ns_;
     out->merged_launches = n_merged_launches_; out->merged_chains = n_merged_chains_; out->common_rows = n_common_rows_;
+    out->rolled_launches = n_rolled_launches_;
 }
 
 void Engine::pool_stats(fmhip_pool_stats_t* out) {

@@ -666,6 +666,8 @@ typedef struct fmhip_engine_stats_t {
     /* rows of batched launches that were not computed because an earlier row of the same launch read the same vectors with the same
      * scalars (the parameter sets of a finite-difference batch before their bumped parameter matters): they share its vectors */
     int64_t common_rows;
+    /* launches of a loop kernel: the rolled stretch of a component, its peeled form (head, loop and tail), a merged family */
+    int64_t rolled_launches;
 } fmhip_engine_stats_t;
 int fmhip_engine_stats(fmhip_engine_stats_t* out);
 int fmhip_profile_read(double* kernel_ms_total, int64_t* n_launches);

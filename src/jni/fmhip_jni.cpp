@@ -537,11 +537,11 @@ FMJ(jint, trafficStats)(JNIEnv* env, jclass, jlongArray algorithmicBytesAndSpeci
     if (st == FMHIP_OK && algorithmicBytesAndSpecialisedLaunches && env->GetArrayLength(algorithmicBytesAndSpecialisedLaunches) >= 2) { const jlong v[2] = { (jlong)bytes, (jlong)launches }; env->SetLongArrayRegion(algorithmicBytesAndSpecialisedLaunches, 0, 2, v); }
     return st;
 }
-FMJ(jint, engineStats)(JNIEnv* env, jclass, jlongArray stats17) {
+FMJ(jint, engineStats)(JNIEnv* env, jclass, jlongArray stats18) {
     fmhip_engine_stats_t s;
     const int st = fmhip_engine_stats(&s);
-    static_assert(sizeof(fmhip_engine_stats_t) == 17 * sizeof(int64_t), "engine statistics travel as 17 longs");
-    if (st == FMHIP_OK && stats17) { const jsize len = env->GetArrayLength(stats17); env->SetLongArrayRegion(stats17, 0, len < 17 ? len : 17, (const jlong*)&s); }
+    static_assert(sizeof(fmhip_engine_stats_t) == 18 * sizeof(int64_t), "engine statistics travel as 18 longs");
+    if (st == FMHIP_OK && stats18) { const jsize len = env->GetArrayLength(stats18); env->SetLongArrayRegion(stats18, 0, len < 18 ? len : 18, (const jlong*)&s); }
     return st;
 }
 FMJ(jint, profileRead)(JNIEnv* env, jclass, jdoubleArray kernelMsTotal, jlongArray launches) {
