@@ -58,7 +58,7 @@ std::string jit_generate_source(const DevProgramArgs& proto);
 std::string jit_describe(const DevProgramArgs& proto);
 bool jit_parse_description(const std::string& line, DevProgramArgs& proto);
 
-// Body of a rolled loop (runtime.cpp: detect_loop): everything the source of its kernel depends on.  Operand names: v<q> = value of
+// Body of a rolled loop (loop_engine.hpp: detect_loop): everything the source of its kernel depends on.  Operand names: v<q> = value of
 // position q of this iteration, c<k> = k-th value carried over from the previous iteration, g<k> = k-th loop-invariant input vector,
 // l<m> = m-th input vector of this iteration.  Iteration count, pointers and scalar operands are run-time arguments (fm_program.h).
 struct RolledBody {
@@ -67,7 +67,7 @@ struct RolledBody {
     std::vector<uint32_t> carried, final_pos, out_pos;                 // positions whose value is carried / stored once behind the loop / stored every iteration
     struct Op { uint32_t uop; std::string x0, x1, x2; bool scalar; };  // x1 / x2 empty: the micro-op does not read them
     std::vector<Op> ops;
-    // PEELED form: the operations in front of the loop and behind it run in the SAME launch (runtime.cpp: plan_peel) — a component
+    // PEELED form: the operations in front of the loop and behind it run in the SAME launch (loop_engine.hpp: plan_peel) — a component
     // that is a short head, a periodic stretch and a short tail (a swaption's backward induction with its payoff) is ONE launch
     // instead of three, and the values between the parts stay in registers.  Further operand names: p<i> = result of operation i
     // in front of the loop, q<i> = of operation i behind it, x<k> = k-th extra input vector (the first extra_pre of them are loaded
@@ -85,7 +85,7 @@ struct RolledBody {
         // tree (fm_kernel_parts.hpp), so the moments are those of the stand-alone reduction to the last bit.
         std::string reduce;
     } peel;
-    // MERGED form (chains >= 2; runtime.cpp: merge_families): ONE launch serves `chains` components of this very shape whose inputs —
+    // MERGED form (chains >= 2; merged_chains_engine.hpp: merge_families): ONE launch serves `chains` components of this very shape whose inputs —
     // the head's own vectors, then the loop's, one per step — are the same vectors, the shorter components reading a SUFFIX of the longest
     // one's sequence (the swaptions of one exercise date, tenor by tenor: each reads the forward rates from its last period back to the
     // exercise date).  A step loads its vector once and every chain that has started takes its turn on it: the head's operations in the
@@ -113,7 +113,7 @@ public:
     void quiesce();                                            // joins the worker only (process exit: no HIP calls)
     // Returns the (shared) slot of this program; compiles synchronously when `sync`, else queues it for the worker.
     std::shared_ptr<JitSlot> request(const DevProgramArgs& proto, bool sync);
-    // The same for a kernel pair given as source text (rolled loops, runtime.cpp): `elems` = elements per lane and pass.
+    // The same for a kernel pair given as source text (rolled loops, loop_engine.hpp): `elems` = elements per lane and pass.
     std::shared_ptr<JitSlot> request_source(std::string source, int elems, bool sync, bool cached_only = false);
     // The slot of a program only if its kernel exists already (loaded in this process, in the user's cache or in the pack): looked up
     // on the calling thread at a lazily built program's FIRST launch; nullptr = it stays on the interpreter until it has earned a compilation.

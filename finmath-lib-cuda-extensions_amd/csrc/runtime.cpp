@@ -42,6 +42,10 @@ void hip_check(hipError_t e, const char* what) {
     throw Error(code, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// Environment knobs: a switch that is on unless it is set to "0…", a size with a default.  Read once where they are used (static const).
+static bool knob_on(const char* name) { const char* e = std::getenv(name); return !(e && e[0] == '0'); }
+static size_t knob_size(const char* name, size_t dflt) { const char* e = std::getenv(name); return e ? (size_t)std::atoll(e) : dflt; }
+
 // ---------------------------------------------------------------- opcode table
 
 struct OpInfo { int n_vec; bool scalar; };
@@ -88,7 +92,7 @@ void* Pool::alloc(size_t bytes, size_t* cap_out) {
     // one — grows the pool until something fails.  With less than the headroom left a miss counts as out of memory (purge, then the error
     // the caller answers with a collection: RandomVariableCuda.java:311-335 does the same below a free-memory percentage).  Asked on a miss
     // only: a slab allocation costs ≈ 100 µs, the query a few.
-    static const size_t HEADROOM = [] { const char* e = std::getenv("FMHIP_POOL_HEADROOM_BYTES"); return e ? (size_t)std::atoll(e) : (size_t(2) << 30); }();
+    static const size_t HEADROOM = knob_size("FMHIP_POOL_HEADROOM_BYTES", (size_t(2) << 30));
     auto room_for = [&](size_t bytes) { size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); return true; } return fr >= bytes + HEADROOM; };
     hipError_t e = hipErrorOutOfMemory;
     if (blocks > 1 && !room_for(blocks * cap)) blocks = 1;
@@ -481,7 +485,7 @@ void Engine::node_maybe_free(Node* nd) {
     if (nd->refs_ext > 0 || nd->refs_int > 0) return;
     if (nd->buf) buffer_unref(nd->buf);
     else { pend_erase(nd); drop_expression(nd); }
-    static const size_t NODE_POOL_CAP = [] { const char* e = std::getenv("FMHIP_NODE_POOL_CAP"); return e ? (size_t)std::atoll(e) : (size_t)65536; }();      // (measured under a lagging collector: recycling ALL the nodes a burst of releases frees — random addresses — is no faster than fresh, consecutive ones)
+    static const size_t NODE_POOL_CAP = knob_size("FMHIP_NODE_POOL_CAP", (size_t)65536);      // (measured under a lagging collector: recycling ALL the nodes a burst of releases frees — random addresses — is no faster than fresh, consecutive ones)
     if (node_pool_.size() < NODE_POOL_CAP) node_pool_.push_back(nd); else delete nd;      // (a collector's burst frees hundreds of thousands at once: they are the next ones handed out, most recently touched first)
 }
 
@@ -510,7 +514,7 @@ void Engine::drain_late(size_t at_most) {
     // The nodes of handles that died a while ago are COLD, and performing a release touches several lines of several nodes: the node's
     // own three, its neighbours on the deferred list (unlinked), its operands (their counts drop; whatever only the recipe kept alive goes
     // with it).  Two stages of prefetching ahead of the work: the node itself 16 handles ahead, what it points to 8 ahead (by then it is there).
-    static const size_t AHEAD = [] { const char* e = std::getenv("FMHIP_DRAIN_PREFETCH"); return e ? (size_t)std::atoll(e) : (size_t)8; }();
+    static const size_t AHEAD = knob_size("FMHIP_DRAIN_PREFETCH", (size_t)8);
     std::vector<Node*> nds(batch.size());
     for (size_t i = 0; i < batch.size(); ++i) nds[i] = owner_of(batch[i]) == index_ ? nodes_.get(batch[i]) : nullptr;     // (a handle that is not one: nobody is left to tell)
     auto fetch = [](const void* p) { __builtin_prefetch(p, 1, 1); };
@@ -673,6 +677,13 @@ static bool variant_for(int opcode, int a_pos, UVariant* out) {
     return false;
 }
 
+// … and the micro-op that runs: FMHIP_MATH_FAST takes the fast forms of exp and log (the interpreter's programs and the loop kernels alike)
+static bool micro_op_for(int opcode, int a_pos, int math_mode, UVariant* out) {
+    if (!variant_for(opcode, a_pos, out)) return false;
+    if (math_mode == FMHIP_MATH_FAST) { if (out->uop == U_EXP) out->uop = U_EXP_FAST; else if (out->uop == U_LOG) out->uop = U_LOG_FAST; }
+    return true;
+}
+
 // Position (0..2) at which value `v` can be consumed from the accumulator by `op`, or -1.
 static int acc_position(const SsaOp& op, int n_vec, int v) {
     if (v < 0) return -1;
@@ -765,7 +776,7 @@ Program* Engine::compile_variant(const std::vector<SsaOp>& ops, int n_in, const 
             ap = 0;
         }
         UVariant uv{};
-        if (!variant_for(ops[i].opcode, ap, &uv)) { delete p; throw Error(FMHIP_ERR_INVALID_ARGUMENT, "internal: no accumulator form"); }
+        if (!micro_op_for(ops[i].opcode, ap, math_mode, &uv)) { delete p; throw Error(FMHIP_ERR_INVALID_ARGUMENT, "internal: no accumulator form"); }
         const unsigned r1 = uv.r1_pos >= 0 ? (unsigned)reg_of[v[uv.r1_pos]] : 0u;
         const unsigned r2 = uv.r2_pos >= 0 ? (unsigned)reg_of[v[uv.r2_pos]] : 0u;
         for (int q = 0; q < n_vec[i]; ++q) {        // values whose last read from R is this op free their register first
@@ -782,7 +793,6 @@ Program* Engine::compile_variant(const std::vector<SsaOp>& ops, int n_in, const 
         }
         unsigned slot = 0;
         uint32_t uop = uv.uop;
-        if (math_mode == FMHIP_MATH_FAST) { if (uop == U_EXP) uop = U_EXP_FAST; else if (uop == U_LOG) uop = U_LOG_FAST; }
         if (uop == U_LOG) p->proto.flags |= FM_ARGS_LOG_TABLE;
         if (op_info(ops[i].opcode).scalar) {
             if ((int)scal.size() >= FM_MAX_SCAL) { delete p; throw Error(FMHIP_ERR_PROGRAM_LIMIT, "too many scalar operands for one launch"); }
@@ -1079,7 +1089,7 @@ void Engine::red_begin(RedLaunch& red, int batch, int n_red, size_t blocks_per_r
     red.dev_moments = dev_moments;
     red.on_host = host_moments && !dev_moments;
     red.partials = pool_.alloc((size_t)batch * n_red * (blocks_per_row + 8) * 32, &red.partials_cap);       // + FM_COMBINE_GROUP_SLOTS group partials per row
-    static const bool POLL = [] { const char* e = std::getenv("FMHIP_POLL"); return !(e && e[0] == '0'); }();
+    static const bool POLL = knob_on("FMHIP_POLL");
     try {
         if (dev_moments) red.results = dev_moments;
         else if (red.on_host && POLL && batch == 1 && n_red <= 2 && !free_slots_.empty()) {       // a slot of its own: results [0, 64), flag at 64
@@ -1157,17 +1167,17 @@ static int FUSION_MAX_WEIGHT = 40;    // pending ops below one node before it is
                                        // recording of the next methods, and that path is host-bound
 
 void fusion_max_weight_override(int v) { FUSION_MAX_WEIGHT = v; }
-static const size_t SPECULATE_PENDING = [] { const char* e = std::getenv("FMHIP_SPECULATE_PENDING"); return e ? (size_t)std::atoll(e) : (size_t)2000; }();   // operations recorded since the last time step; 0 = off.  5000 until the second half of round 5, when the device was what the hint-free calibration waited for; with the
+static const size_t SPECULATE_PENDING = knob_size("FMHIP_SPECULATE_PENDING", (size_t)2000);   // operations recorded since the last time step; 0 = off.  5000 until the second half of round 5, when the device was what the hint-free calibration waited for; with the
                                                          // swaptions of an exercise date merged (merge_families) it is the host, and what counts is how little is left to run when the caller asks for its first expectation: 1500 / 2000 / 2500 / 3000 / 4000 / 5000
                                                          // methods: 3.48 / 3.37–3.45 / 3.46–3.55 / 3.56 / 3.63 / 3.66–3.70 s on one box (profiles/round05b_merged_chains.txt)
-static const size_t SPECULATE_IDLE_MIN = [] { const char* e = std::getenv("FMHIP_SPECULATE_IDLE_MIN"); return e ? (size_t)std::atoll(e) : (size_t)0; }();   // 0 (default) = the device's idleness is not looked at.  Measured, lmm_hip --finmath-like at 1 M paths on one box: off 4.68 s; 512 / 1024 / 2048 / 4096: 5.26 / 4.89 / 4.96 / 4.90 s —
+static const size_t SPECULATE_IDLE_MIN = knob_size("FMHIP_SPECULATE_IDLE_MIN", (size_t)0);   // 0 (default) = the device's idleness is not looked at.  Measured, lmm_hip --finmath-like at 1 M paths on one box: off 4.68 s; 512 / 1024 / 2048 / 4096: 5.26 / 4.89 / 4.96 / 4.90 s —
                                                          // chains cut wherever the device happens to run dry are shapes that never repeat (70 kernels compiled instead of 38, 4–12 k launches on the interpreter)
 static const size_t FUSION_SOFT_CAP = 32768;     // pending operations at which a SOFT hold (fmhip_fusion_hold(2)) executes everything
 // Experiment knob (off): execute everything once this many operations are pending anywhere, instead of the per-handle weight rule.
 // On the hint-free LMM calibration (lmm_hip --finmath-like) 1000 … 16000 gave 15-18 ms per evaluation against 22.8 with the
 // weight rule and 12.5 with BrownianMotionHip's time-step grouping: cut points that do not coincide with time steps give graph
 // shapes that never repeat, so every flush plans from scratch and nothing rolls.
-static size_t FUSION_MAX_PENDING = [] { const char* e = std::getenv("FMHIP_FUSION_MAX_PENDING"); return e ? (size_t)std::atoll(e) : (size_t)0; }();   // 0 = off
+static size_t FUSION_MAX_PENDING = knob_size("FMHIP_FUSION_MAX_PENDING", (size_t)0);   // 0 = off
 
 fmhip_vec Engine::call(int opcode, int n_in, const fmhip_vec* in, double scalar, bool has_scalar) {
     HostTimer timer(HostProfile::CALL);
@@ -1322,7 +1332,7 @@ static void clone_nodes_impl(std::vector<Node*>& graph, uint64_t ep_graph, uint6
     }
 }
 
-static const bool REPLICAS = [] { const char* e = std::getenv("FMHIP_REPLICAS"); return !(e && e[0] == '0'); }();     // =0: copies are always made of nodes (A/B measurement)
+static const bool REPLICAS = knob_on("FMHIP_REPLICAS");     // =0: copies are always made of nodes (A/B measurement)
 
 void Engine::graph_clone(const fmhip_vec* roots, int n_roots, int n_copies, const fmhip_vec* leaf_from, const fmhip_vec* leaf_to, int n_map,
                          const double* scalars, int n_scalars, fmhip_vec* out) {
@@ -1535,7 +1545,7 @@ void Engine::expand_replicas_below(const std::vector<Node*>& targets) {
 
 // ---------------------------------------------------------------- escape policy (runtime.hpp: policy_state_)
 
-static const bool ESCAPE_POLICY = [] { const char* e = std::getenv("FMHIP_ESCAPE_POLICY"); return !(e && e[0] == '0'); }();     // =0: whatever has a handle is stored (rounds 1–4; A/B measurement)
+static const bool ESCAPE_POLICY = knob_on("FMHIP_ESCAPE_POLICY");     // =0: whatever has a handle is stored (rounds 1–4; A/B measurement)
 
 void Engine::policy_reset() { policy_state_.clear(); ++policy_gen_; }       // (shapes bind again, lazily: their generation no longer matches)
 
@@ -1589,6 +1599,8 @@ void Engine::materialize_deferred() {
         if (nd && nd->id == id && !nd->buf && nd->deferred && !nd->discarded) materialize({ nd });
     }
 }
+
+static void set_moments(Node* r, const fmhip_moments& m) { r->moments[0] = m.sum; r->moments[1] = m.sumsq; r->moments[2] = m.min; r->moments[3] = m.max; r->has_moments = true; }
 
 struct Engine::Dag {
     std::vector<Node*> roots;       // the values asked for
@@ -1747,14 +1759,14 @@ bool Engine::run_dags(std::vector<Dag>& dags, const double* reduce_shift, fmhip_
         }
         program_cache_[key] = prog;
     }
-    std::vector<std::vector<Buffer*>> out_bufs(dags.size());
+    std::vector<Stored> stored;
     std::vector<RowSpec> rows(dags.size());
     try {
         for (size_t i = 0; i < dags.size(); ++i) {
             for (Node* l : dags[i].leaves) rows[i].in.push_back(l->buf->ptr);
             for (size_t k = 0; k < dags[i].outs.size() && !moments_only; ++k) {
                 Buffer* b = new_buffer(n);
-                out_bufs[i].push_back(b);
+                stored.push_back({ nullptr, 0, dags[i].outs[k], b });
                 rows[i].out.push_back(b->ptr);
             }
             rows[i].scalars = dags[i].scalars.data();
@@ -1762,26 +1774,16 @@ bool Engine::run_dags(std::vector<Dag>& dags, const double* reduce_shift, fmhip_
         }
         launch(prog, n, rows, host_moments, dev_moments);
     } catch (...) {
-        for (auto& v : out_bufs) for (Buffer* b : v) buffer_unref(b);
+        for (Stored& o : stored) buffer_unref(o.buf);
         throw;
     }
     if (async_slots) for (size_t i = 0; i < dags.size(); ++i) arena_assign(dags[i].outs[0], async_slots + i * 4);
-    for (size_t i = 0; i < all.size(); ++i) {
-        Node* r = dags[i].outs[0];
-        r->moments[0] = all[i].sum; r->moments[1] = all[i].sumsq; r->moments[2] = all[i].min; r->moments[3] = all[i].max; r->has_moments = true;
-    }
+    for (size_t i = 0; i < all.size(); ++i) set_moments(dags[i].outs[0], all[i]);
     if (moments_only) {         // nothing was stored: the roots keep their moments, give their expressions up and are no roots of later flushes
-        for (size_t i = 0; i < dags.size(); ++i) { Node* r = dags[i].outs[0]; r->discarded = true; r->refs_int++; drop_expression(r); r->refs_int--; }
+        for (size_t i = 0; i < dags.size(); ++i) give_up_value(dags[i].outs[0]);
         return true;
     }
-    // commit: outputs become materialised leaves; their expressions (and unreferenced intermediates) go away
-    for (size_t i = 0; i < dags.size(); ++i)
-        for (size_t k = 0; k < dags[i].outs.size(); ++k) commit_node(dags[i].outs[k], out_bufs[i][k]);
-    // (all outputs are kept alive until every expression has been dismantled: one that nobody holds — stored for the sake of a launch shape
-    // whose kernel exists, build_big — goes away with its last consumer)
-    for (size_t i = 0; i < dags.size(); ++i) for (Node* nd : dags[i].outs) nd->refs_int++;
-    for (size_t i = 0; i < dags.size(); ++i) for (Node* nd : dags[i].outs) drop_expression(nd);
-    for (size_t i = 0; i < dags.size(); ++i) for (Node* nd : dags[i].outs) { nd->refs_int--; node_maybe_free(nd); }
+    commit_stored(stored);
     return true;
 }
 
@@ -1997,7 +1999,7 @@ bool Engine::build_big(const std::vector<Node*>& roots, BigDag& big) {
             schedule_cache_bytes_ += vs[at].sig.size() + m;
         }
         size_t use = at;
-        static const bool HYSTERESIS = [] { const char* e = std::getenv("FMHIP_VARIANT_HYSTERESIS"); return !(e && e[0] == '0'); }();
+        static const bool HYSTERESIS = knob_on("FMHIP_VARIANT_HYSTERESIS");
         if (HYSTERESIS && ESCAPE_POLICY && vs.size() > 1 && jit_mode == FMHIP_JIT_AUTO) {
             auto plan_of = [&](const ScheduleMemo::Variant& v) -> BigPlan* { auto it = plan_cache_.find(v.hash); return it != plan_cache_.end() && it->second.sig == v.sig ? &it->second : nullptr; };
             auto kernel_there = [&](const BigPlan& p) {
@@ -2108,14 +2110,33 @@ void Engine::commit_described(BigDag& big, size_t pos, Buffer* b) {
     commit_node(c, b);
 }
 
+// Commit: what a launch has stored becomes materialised vectors; their expressions (and unreferenced intermediates) go away.  All
+// outputs are kept alive until every expression has been dismantled: one that nobody holds — stored for the sake of a launch shape whose
+// kernel exists (build_big), a position a loop stores in every iteration for the sake of one — goes away with its last consumer.
+void Engine::commit_stored(const std::vector<Stored>& outs) {
+    std::vector<Node*> done;
+    done.reserve(outs.size());
+    for (const Stored& o : outs) {
+        if (o.big && o.big->described()) { commit_described(*o.big, o.pos, o.buf); continue; }
+        Node* nd = o.big ? o.big->order[o.pos] : o.node;
+        commit_node(nd, o.buf);
+        done.push_back(nd);
+    }
+    for (Node* nd : done) nd->refs_int++;
+    for (Node* nd : done) drop_expression(nd);
+    for (Node* nd : done) { nd->refs_int--; node_maybe_free(nd); }
+}
+
+void Engine::give_up_value(Node* r) { r->discarded = true; r->refs_int++; drop_expression(r); r->refs_int--; }
+
 // One segment of a planned component for every member of a group: gather the row blocks by index, launch, commit.
 void Engine::run_planned_segment(const BigPlan::Seg& seg, std::vector<BigDag>& group, size_t first, size_t count, ReduceRequest* rr, Program* prog_red) {
     const int64_t n = group[first].n;
     const size_t n_scal = seg.scal.empty() ? 1 : seg.scal.size();
     std::vector<RowSpec> rows(count);
     std::vector<float> scalars(count * n_scal, 0.0f);
-    std::vector<Buffer*> out_bufs;
-    out_bufs.reserve(count * seg.out.size());
+    std::vector<Stored> stored;
+    stored.reserve(count * seg.out.size());
     try {
         for (size_t c = 0; c < count; ++c) {
             BigDag& big = group[first + c];
@@ -2126,528 +2147,49 @@ void Engine::run_planned_segment(const BigPlan::Seg& seg, std::vector<BigDag>& g
                 if (!b) throw Error(FMHIP_ERR_PROGRAM_LIMIT, "planned segment reads a value that has not been computed");
                 r.in.push_back(b->ptr);
             }
-            for (size_t k = 0; k < seg.out.size(); ++k) { Buffer* b = new_buffer(n); out_bufs.push_back(b); r.out.push_back(b->ptr); }
+            for (size_t k = 0; k < seg.out.size(); ++k) { Buffer* b = new_buffer(n); stored.push_back({ &big, (size_t)seg.out[k], nullptr, b }); r.out.push_back(b->ptr); }
             float* sc = scalars.data() + c * n_scal;
             for (size_t k = 0; k < seg.scal.size(); ++k) sc[k] = big.scalar_at((size_t)seg.scal[k]);
             r.scalars = sc; r.shifts = rr ? &rr->shift : nullptr;
         }
         if (rr) { launch(prog_red, n, rows, rr->host_out, rr->dev_out); rr->done = true; }
         else launch(seg.prog, n, rows, nullptr, nullptr);
-    } catch (...) { for (Buffer* b : out_bufs) buffer_unref(b); throw; }
-    // commit (as run_dags): outputs become materialised leaves; their expressions (and unreferenced intermediates) go away
-    for (size_t c = 0; c < count; ++c) {
-        BigDag& big = group[first + c];
-        for (size_t k = 0; k < seg.out.size(); ++k) {
-            Buffer* b = out_bufs[c * seg.out.size() + k];
-            if (big.described()) commit_described(big, (size_t)seg.out[k], b);
-            else commit_node(big.order[(size_t)seg.out[k]], b);
-        }
-    }
-    std::vector<Node*> done;
-    for (size_t c = 0; c < count; ++c) {
-        BigDag& big = group[first + c];
-        if (big.described()) continue;
-        for (size_t k = 0; k < seg.out.size(); ++k) done.push_back(big.order[(size_t)seg.out[k]]);
-    }
-    for (Node* nd : done) nd->refs_int++;       // keep alive while the expressions are dismantled
-    for (Node* nd : done) drop_expression(nd);
-    for (Node* nd : done) { nd->refs_int--; node_maybe_free(nd); }
+    } catch (...) { for (Stored& o : stored) buffer_unref(o.buf); throw; }
+    commit_stored(stored);
 }
 
-// ---------------------------------------------------------------- rolled loops
-//
-// The scheduled order of a large component is often PERIODIC: the same few operations over one vector after another, each
-// iteration feeding the next through a value or two — the running factor sum over the LIBOR components of an Euler step, a
-// swap's backward induction over its periods.  Cut into launches of ≤ 12 inputs / 8 outputs such a stretch moves ≈ 1.5 vectors
-// per iteration and step and costs a launch every six iterations.  Rolled up it is ONE launch: the body of one iteration is
-// compiled (hiprtc) into a kernel that loops over the iterations, keeps the carried values in registers, loads each iteration's
-// inputs while it computes the previous one and stores each result the moment it is final; iteration count, vector pointers and
-// scalar operands come from the row table, so one kernel serves every component count.  Every operation is evaluated by the
-// same ueval<> functions in the same order per element as in the segmented launches: results are bit-identical, and until the
-// kernel is compiled (or with FMHIP_JIT=off / FMHIP_ROLL=0) the segmented launches run.
+static const bool MERGE_CHAINS = knob_on("FMHIP_MERGE_CHAINS");          // =0: off (merged_chains_engine.hpp)
 
-static bool MERGE_CHAINS_ON() { static const bool v = [] { const char* e = std::getenv("FMHIP_MERGE_CHAINS"); return !(e && e[0] == '0'); }(); return v; }
-static inline uint64_t mix64(uint64_t h, uint64_t v) { h ^= v + 0x9e3779b97f4a7c15ull + (h << 6) + (h >> 2); return h * 0xff51afd7ed558ccdull; }
-
-#define ROLL_TRACE(...) do { if (roll_trace) std::fprintf(stderr, __VA_ARGS__); } while (0)
-bool Engine::detect_loop(const BigDag& g, const std::vector<std::array<int32_t, 3>>& operand, BigPlan::Rolled& ro, std::string* source, int* elems_out, RolledBody* body_out)
-{
-    static const bool roll_trace = std::getenv("FMHIP_ROLL_TRACE") != nullptr;
-    const size_t n = g.order.size();
-    ROLL_TRACE("[fmhip roll] component of %zu nodes, %zu leaves\n", n, g.leaves.size());
-    const int MAX_PERIOD = 128, MIN_ITERATIONS = 5, GLOBAL_SPAN = MAX_PERIOD;      // an input of ONE iteration has all its uses less than a period apart
-    if (n < 48) return false;
-    std::vector<int32_t> first_use(g.leaves.size(), -1), last_leaf_use(g.leaves.size(), -1);
-    std::vector<uint32_t> last_use(n, 0);                       // largest consumer index; n = needed outside the component
-    for (size_t i = 0; i < n; ++i) {
-        if (g.escapes[i]) last_use[i] = (uint32_t)n;
-        for (int k = 0; k < g.order[i]->n_in; ++k) {
-            const int32_t o = operand[i][(size_t)k];
-            if (o < 0) { const size_t l = (size_t)(-1 - o); if (first_use[l] < 0) first_use[l] = (int32_t)i; last_leaf_use[l] = (int32_t)i; }
-            else if (last_use[(size_t)o] < (uint32_t)i) last_use[(size_t)o] = (uint32_t)i;
-        }
+// A kernel of the specialised tier on demand: asked for when its slot is empty — with FMHIP_JIT=sync also while it still waits for the
+// worker: the caller compiles it now —; true when it is there.
+template <class Source> bool Engine::kernel_ready(std::shared_ptr<JitSlot>& slot, Source&& source, int elems) {
+    const bool sync = jit_mode == FMHIP_JIT_SYNC;
+    if (!slot || (sync && slot->state.load(std::memory_order_acquire) == JitSlot::QUEUED)) {
+        std::string text = source();
+        if (text.empty()) return false;
+        slot = jit().request_source(std::move(text), elems, sync);
     }
-    auto is_global = [&](size_t l) { return last_leaf_use[l] - first_use[l] >= GLOBAL_SPAN; };
-    // position-independent signature of every node: what it does and how far back its operands are.  NOT whether it is stored: an
-    // iteration that stores a value the others only pass on (a state one product reads, a handle the escape policy keeps for one
-    // component and not for the next) is the same iteration — the loop stores that position in EVERY iteration (out_needed below is the
-    // union over the iterations): a few vectors more written, against a stretch that would not roll at all.
-    std::vector<uint64_t> sig(n);
-    for (size_t i = 0; i < n; ++i) {
-        const Node* nd = g.order[i];
-        uint64_t h = mix64(0x1234, (uint64_t)nd->opcode * 8 + (uint64_t)nd->n_in * 2);
-        for (int k = 0; k < nd->n_in; ++k) {
-            const int32_t o = operand[i][(size_t)k];
-            if (o >= 0) h = mix64(h, 0x100000000ull + (uint64_t)((int64_t)i - o));
-            else { const size_t l = (size_t)(-1 - o); h = is_global(l) ? mix64(h, 0x200000000ull + l) : mix64(h, 0x300000000ull + (uint64_t)((int64_t)i - first_use[l])); }
-        }
-        sig[i] = h;
-    }
-    // the periodic stretch that covers the most nodes
-    size_t best_start = 0, best_cover = 0; int best_period = 0;
-    for (int P = 3; P <= MAX_PERIOD && (size_t)P * MIN_ITERATIONS <= n; ++P) {
-        size_t run_start = 0, run = 0;
-        for (size_t i = 0; i + (size_t)P <= n; ++i) {
-            const bool match = i + (size_t)P < n && sig[i] == sig[i + (size_t)P];
-            if (match) { if (run == 0) run_start = i; ++run; }
-            if (!match || i + (size_t)P + 1 >= n) {
-                if (run > 0) { const size_t cover = (run + (size_t)P) / (size_t)P * (size_t)P; if (cover > best_cover) { best_cover = cover; best_start = run_start; best_period = P; } }
-                run = 0;
-            }
-        }
-    }
-    ROLL_TRACE("[fmhip roll]   best period %d, start %zu, cover %zu\n", best_period, best_start, best_cover);
-    if (best_period == 0 || best_cover / (size_t)best_period < (size_t)MIN_ITERATIONS) return false;
-    const uint32_t P = (uint32_t)best_period;
-    // phase: any rotation of the period is periodic too; take the one with the fewest values crossing the iteration boundary
-    uint32_t best_phase = 0; size_t best_carried = SIZE_MAX;
-    for (uint32_t phase = 0; phase < P; ++phase) {
-        const size_t b = best_start + P + phase;                // second detected iteration: its predecessors exist
-        if (b + P > best_start + best_cover) break;
-        std::unordered_set<int32_t> crossing;
-        bool ok = true;
-        for (uint32_t q = 0; q < P && ok; ++q)
-            for (int k = 0; k < g.order[b + q]->n_in; ++k) {
-                const int32_t o = operand[b + q][(size_t)k];
-                if (o < 0) {                                    // an input of one iteration must not straddle the boundary either
-                    const size_t l = (size_t)(-1 - o);
-                    if (!is_global(l) && ((size_t)first_use[l] < b || (size_t)last_leaf_use[l] >= b + P)) { ok = false; break; }
-                    continue;
-                }
-                const int64_t d = (int64_t)(b + q) - o;
-                if (d > (int64_t)q) { if (d > (int64_t)q + P) { ok = false; break; } crossing.insert(o); }
-            }
-        if (ok && crossing.size() < best_carried) { best_carried = crossing.size(); best_phase = phase; }
-    }
-    ROLL_TRACE("[fmhip roll]   phase %u, %zu values cross the iteration boundary\n", best_phase, best_carried == SIZE_MAX ? (size_t)0 : best_carried);
-    if (best_carried == SIZE_MAX) return false;
-    const size_t begin = best_start + P + best_phase;
-    const size_t R = (best_start + best_cover - begin) / P;
-    if (R < (size_t)MIN_ITERATIONS - 1) return false;
-    const size_t end = begin + R * P;
-    // validate every iteration; collect the body's interface from the first one
-    std::vector<char> out_needed(P, 0), final_needed(P, 0);
-    for (size_t r = 0; r < R; ++r)
-        for (uint32_t q = 0; q < P; ++q) {
-            const size_t i = begin + r * P + q;
-            if (sig[i] != sig[begin + q]) { ROLL_TRACE("[fmhip roll]   aperiodic at iteration %zu position %u\n", r, q); return false; }
-            for (int k = 0; k < g.order[i]->n_in; ++k) {
-                const int32_t o = operand[i][(size_t)k];
-                if (o >= 0) { const int64_t d = (int64_t)i - o; if (d > (int64_t)q + P) { ROLL_TRACE("[fmhip roll]   operand further back than one iteration (iteration %zu position %u)\n", r, q); return false; } }
-                else {
-                    const size_t l = (size_t)(-1 - o);
-                    if (!is_global(l) && ((size_t)first_use[l] < begin + r * P || (size_t)last_leaf_use[l] >= begin + (r + 1) * P)) {   // an input of exactly one iteration
-                        ROLL_TRACE("[fmhip roll]   input used by more than one iteration (iteration %zu position %u, span %d)\n", r, q, last_leaf_use[l] - first_use[l]); return false; }
-                }
-            }
-            // consumers in the same and in the next iteration are served from registers; anybody later (or outside) needs the vector
-            const size_t reach = r + 1 < R ? begin + (r + 2) * P : end;
-            if (last_use[i] >= reach) { if (r + 1 == R && !g.escapes[i]) final_needed[q] = 1; else out_needed[q] = 1; }     // last iteration only: stored once, behind the loop
-        }
-    ro = BigPlan::Rolled();
-    ro.begin = (uint32_t)begin; ro.period = P; ro.iterations = (uint32_t)R;
-    std::vector<int> carried_index(P, -1), global_index(g.leaves.size(), -1);
-    std::vector<std::array<std::string, 3>> name(P);              // operand names of the body
-    bool library_math = false, uses_log = false;
-    int n_local_leaf = 0;
-    std::unordered_map<size_t, int> local_leaf;                      // leaf -> per-iteration input number (first iteration's leaves)
-    for (uint32_t q = 0; q < P; ++q) {
-        const size_t i = begin + q;
-        const Node* nd = g.order[i];
-        library_math |= nd->opcode == FMHIP_OP_POW_S || nd->opcode == FMHIP_OP_SIN || nd->opcode == FMHIP_OP_COS || nd->opcode == FMHIP_OP_EXP || nd->opcode == FMHIP_OP_LOG;
-        uses_log |= nd->opcode == FMHIP_OP_LOG && math_mode != FMHIP_MATH_FAST;
-        if (op_info(nd->opcode).scalar) ro.scal_pos.push_back(q);
-        if (out_needed[q]) ro.out_pos.push_back(q);
-        else if (final_needed[q]) ro.final_pos.push_back(q);
-        for (int k = 0; k < nd->n_in; ++k) {
-            const int32_t o = operand[i][(size_t)k];
-            if (o >= 0) {
-                const int64_t d = (int64_t)i - o;
-                if (d <= (int64_t)q) name[q][(size_t)k] = "v" + std::to_string(q - (uint32_t)d);
-                else {
-                    const uint32_t src = q + P - (uint32_t)d;
-                    if (carried_index[src] < 0) { carried_index[src] = (int)ro.carried.size(); ro.carried.push_back(src); }
-                    name[q][(size_t)k] = "c" + std::to_string(carried_index[src]);
-                }
-            } else {
-                const size_t l = (size_t)(-1 - o);
-                if (is_global(l)) {
-                    if (global_index[l] < 0) { global_index[l] = (int)ro.global_leaf.size(); ro.global_leaf.push_back((int32_t)l); }
-                    name[q][(size_t)k] = "g" + std::to_string(global_index[l]);
-                } else {
-                    auto it = local_leaf.find(l);
-                    if (it == local_leaf.end()) { it = local_leaf.emplace(l, n_local_leaf++).first; ro.leaf_in.push_back({ q, (uint32_t)k }); }
-                    name[q][(size_t)k] = "l" + std::to_string(it->second);
-                }
-            }
-        }
-    }
-    const size_t G = ro.global_leaf.size(), CI = ro.carried.size(), CO = ro.final_pos.size(), LI = ro.leaf_in.size(), LO = ro.out_pos.size(), LS = ro.scal_pos.size();
-    ROLL_TRACE("[fmhip roll]   begin %zu, %zu iterations of %u: %zu global, %zu carried, %zu in, %zu out, %zu scalars\n", begin, R, P, G, CI, LI, LO, LS);
-    if (G > 8 || CI > 12 || CO > 12 || LI > 12 || LO > 12 || LO + CO == 0 || LS > 48) return false;
-    ro.row_words = (uint32_t)(G + CI + CO + R * (LI + LO) + (R * LS + 1) / 2);
-    ro.iter_leaf.resize(R * LI);
-    for (size_t r = 0; r < R; ++r)
-        for (size_t m2 = 0; m2 < LI; ++m2) ro.iter_leaf[r * LI + m2] = -1 - operand[begin + r * P + ro.leaf_in[m2].first][(size_t)ro.leaf_in[m2].second];
-    // ---- the kernel
-    // elements per lane: 8 keeps more bytes in flight per wave, 4 halves the registers (more waves per SIMD to overlap the loop's
-    // load → compute → store with each other) — which loops with library mathematics need
-    const int E = library_math ? 4 : 8;
-    *elems_out = E;
-    RolledBody body;
-    body.elems = E; body.uses_log = uses_log; body.globals = (uint32_t)G; body.inputs = (uint32_t)LI;
-    body.carried = ro.carried; body.final_pos = ro.final_pos; body.out_pos = ro.out_pos;
-    for (uint32_t q = 0; q < P; ++q) {
-        const Node* nd = g.order[begin + q];
-        UVariant uv{};
-        if (!variant_for(nd->opcode, 0, &uv)) return false;
-        uint32_t uop = uv.uop;
-        if (math_mode == FMHIP_MATH_FAST) { if (uop == U_EXP) uop = U_EXP_FAST; else if (uop == U_LOG) uop = U_LOG_FAST; }
-        body.ops.push_back({ uop, name[q][0], uv.r1_pos >= 0 ? name[q][(size_t)uv.r1_pos] : std::string(), uv.r2_pos >= 0 ? name[q][(size_t)uv.r2_pos] : std::string(),
-                             op_info(nd->opcode).scalar });
-    }
-    jit().record(jit_describe(body));
-    *source = jit_generate_rolled_source(body);
-    if (body_out) *body_out = body;
-    return true;
+    return slot && slot->state.load(std::memory_order_acquire) == JitSlot::READY;
 }
 
-// The PEELED form of a component with a rolled loop: everything in front of the loop and behind it in the same launch (jit.hpp:
-// RolledBody::Peel).  Possible when both parts are short, read few vectors of their own, and the part behind the loop reads nothing
-// of the loop but final values of its last iteration.
-bool Engine::plan_peel(const BigDag& g, const std::vector<std::array<int32_t, 3>>& operand, BigPlan::Rolled& ro, const RolledBody& loop_body)
-{
-    static const bool PEEL = [] { const char* e = std::getenv("FMHIP_PEEL"); return !(e && e[0] == '0'); }();
-    if (!PEEL) return false;
-    const size_t n = g.order.size(), P = ro.period, R = ro.iterations, begin = ro.begin, end = begin + P * R;
-    static const size_t MAX_OPS = [] { const char* e = std::getenv("FMHIP_PEEL_MAX_OPS"); return e ? (size_t)std::atoll(e) : (size_t)192; }();
-    const size_t MAX_EXTRA = 16;
-    if (begin > MAX_OPS || n - end > MAX_OPS || begin == 0) return false;
-    RolledBody body = loop_body;
-    RolledBody::Peel& pl = body.peel;
-    BigPlan::Rolled::Peeled pe;
-    pl.present = true;
-    std::vector<int> global_of(g.leaves.size(), -1), extra_of(g.leaves.size(), -1);
-    for (size_t k = 0; k < ro.global_leaf.size(); ++k) global_of[(size_t)ro.global_leaf[k]] = (int)k;
-    auto leaf_name = [&](size_t l) {
-        if (global_of[l] >= 0) return "g" + std::to_string(global_of[l]);
-        if (extra_of[l] < 0) { extra_of[l] = (int)pe.extra_leaf.size(); pe.extra_leaf.push_back((int32_t)l); }
-        return "x" + std::to_string(extra_of[l]);
-    };
-    std::vector<int> final_of(P, -1);
-    for (size_t k = 0; k < ro.final_pos.size(); ++k) final_of[ro.final_pos[k]] = (int)k;
-    auto make_op = [&](size_t i, bool behind, RolledBody::Op& out) {
-        const Node* nd = g.order[i];
-        UVariant uv{};
-        if (!variant_for(nd->opcode, 0, &uv)) return false;
-        if (nd->opcode == FMHIP_OP_POW_S || nd->opcode == FMHIP_OP_SIN || nd->opcode == FMHIP_OP_COS) return false;     // out-of-line library code: not in these kernels
-        uint32_t uop = uv.uop;
-        if (math_mode == FMHIP_MATH_FAST) { if (uop == U_EXP) uop = U_EXP_FAST; else if (uop == U_LOG) uop = U_LOG_FAST; }
-        body.uses_log |= uop == U_LOG;
-        std::string name[3];
-        for (int k = 0; k < nd->n_in; ++k) {
-            const int32_t o = operand[i][(size_t)k];
-            if (o < 0) name[k] = leaf_name((size_t)(-1 - o));
-            else if ((size_t)o < begin) name[k] = "p" + std::to_string(o);
-            else if ((size_t)o >= end) { if (!behind) return false; name[k] = "q" + std::to_string((size_t)o - end); }
-            else {                                                   // a value of the loop: only a final value of its LAST iteration, only from behind it
-                const size_t it = ((size_t)o - begin) / P, q = ((size_t)o - begin) % P;
-                if (!behind || it != R - 1 || final_of[q] < 0) return false;
-                name[k] = "F" + std::to_string(final_of[q]);
-            }
-        }
-        out = { uop, name[0], uv.r1_pos >= 0 ? name[(size_t)uv.r1_pos] : std::string(), uv.r2_pos >= 0 ? name[(size_t)uv.r2_pos] : std::string(), op_info(nd->opcode).scalar };
-        return true;
-    };
-    for (size_t i = 0; i < begin; ++i) {
-        RolledBody::Op op;
-        if (!make_op(i, false, op)) return false;
-        pl.pre.push_back(op);
-        if (op.scalar) pe.pre_scal.push_back((uint32_t)i);
-        if (g.escapes[i]) { pl.pre_out.push_back((uint32_t)i); pe.pre_out.push_back((uint32_t)i); }
-    }
-    pl.extra_pre = (uint32_t)pe.extra_leaf.size();
-    for (size_t k = 0; k < ro.carried.size(); ++k) pl.carried_init.push_back("p" + std::to_string(begin - P + ro.carried[k]));
-    for (size_t i = end; i < n; ++i) {
-        RolledBody::Op op;
-        if (!make_op(i, true, op)) return false;
-        pl.post.push_back(op);
-        if (op.scalar) pe.post_scal.push_back((uint32_t)i);
-        if (g.escapes[i]) { pl.post_out.push_back((uint32_t)(i - end)); pe.post_out.push_back((uint32_t)i); }
-    }
-    pl.extra_post = (uint32_t)pe.extra_leaf.size() - pl.extra_pre;
-    if (pe.extra_leaf.size() > MAX_EXTRA) return false;
-    // a value of the loop that a later launch used to read (stored every iteration) must not be one the tail needed from an earlier
-    // iteration: make_op has rejected those.  Final values are stored only where somebody outside the component reads them.
-    for (size_t k = 0; k < ro.final_pos.size(); ++k) { const bool esc = g.escapes[begin + (R - 1) * P + ro.final_pos[k]] != 0; pl.final_store.push_back(esc ? 1u : 0u); pe.final_store.push_back(esc ? 1 : 0); }
-    pe.n_pre_scal = (uint32_t)pe.pre_scal.size(); pe.n_post_scal = (uint32_t)pe.post_scal.size(); pe.n_ops = (uint32_t)n;
-    const size_t NX = pe.extra_leaf.size(), G = ro.global_leaf.size(), CO = ro.final_pos.size(), NXO = pe.pre_out.size() + pe.post_out.size(), LI = ro.leaf_in.size(), LO = ro.out_pos.size(), LS = ro.scal_pos.size();
-    pe.row_words = (uint32_t)(NX + G + CO + NXO + R * (LI + LO) + (pe.n_pre_scal + R * LS + pe.n_post_scal + 1) / 2);
-    jit().record(jit_describe(body));
-    pe.source = jit_generate_rolled_source(body);
-    pe.elems = body.elems;
-    pe.present = true;
-    // the variant that also takes the moments of the component's root (its last operation), for `chain.getAverage()`
-    if (body.elems == 8) {
-        if (n > end) pl.reduce = "q" + std::to_string(n - 1 - end);
-        else if (final_of[(n - 1 - begin) % P] >= 0) pl.reduce = "F" + std::to_string(final_of[(n - 1 - begin) % P]);
-        if (!pl.reduce.empty()) { pe.desc_red = jit_describe(body); jit().record(pe.desc_red); pe.source_red = jit_generate_rolled_source(body);
-                                  if (MERGE_CHAINS_ON()) pe.mergeable = merge_shape_index(pe.desc_red) >= 0 ? 1 : 0; }
-    }
-    ro.peeled = std::move(pe);
-    return true;
-}
+struct Engine::TempGuard {
+    Engine* e; std::vector<BigDag>& g;
+    static void drop(Engine* e, BigDag& b) { if (b.described()) for (Buffer*& t : b.temp) if (t) { e->buffer_unref(t); t = nullptr; } }
+    ~TempGuard() { for (BigDag& b : g) drop(e, b); }
+};
 
-// One launch for the rolled stretch of every member of a group: row tables by index, launch, commit.
-void Engine::run_rolled(const BigPlan::Rolled& ro, std::vector<BigDag>& group, size_t first, size_t count)
-{
-    const size_t G = ro.global_leaf.size(), CI = ro.carried.size(), CO = ro.final_pos.size(), LI = ro.leaf_in.size(), LO = ro.out_pos.size(), LS = ro.scal_pos.size();
-    const size_t R = ro.iterations, P = ro.period, rw = ro.row_words;
-    const int64_t n = group[first].n;
-    std::vector<uint64_t> table(count * rw, 0);
-    std::vector<Buffer*> out_bufs;
-    out_bufs.reserve(count * (R * LO + CO));
-    auto ptr_of = [](const Buffer* b) -> uint64_t {
-        if (!b) throw Error(FMHIP_ERR_PROGRAM_LIMIT, "rolled loop reads a value that has not been computed");
-        return (uint64_t)(uintptr_t)b->ptr;
-    };
-    try {
-        for (size_t c = 0; c < count; ++c) {
-            BigDag& big = group[first + c];
-            uint64_t* row = table.data() + c * rw;
-            for (size_t k = 0; k < G; ++k) row[k] = ptr_of(big.leaves[(size_t)ro.global_leaf[k]]->buf);
-            for (size_t k = 0; k < CI; ++k) row[G + k] = ptr_of(big.value(ro.begin - P + ro.carried[k]));       // the iteration before the loop ran as ordinary launches
-            float* sc = reinterpret_cast<float*>(row + G + CI + CO + R * (LI + LO));
-            for (size_t r = 0; r < R; ++r) {
-                uint64_t* ip = row + G + CI + CO + r * (LI + LO);
-                const size_t base = ro.begin + r * P;
-                for (size_t m = 0; m < LI; ++m) ip[m] = ptr_of(big.leaves[(size_t)ro.iter_leaf[r * LI + m]]->buf);
-                for (size_t m = 0; m < LO; ++m) { Buffer* b = new_buffer(n); out_bufs.push_back(b); ip[LI + m] = (uint64_t)(uintptr_t)b->ptr; }
-                for (size_t m = 0; m < LS; ++m) sc[r * LS + m] = big.scalar_at(base + ro.scal_pos[m]);
-            }
-            for (size_t k = 0; k < CO; ++k) { Buffer* b = new_buffer(n); out_bufs.push_back(b); row[G + CI + k] = (uint64_t)(uintptr_t)b->ptr; }    // after the per-iteration outputs, in this order
-        }
-        if (n > 0) {
-            const int64_t elems_per_pass = (int64_t)FM_BLOCK * ro.jit->elems;
-            const int64_t tiles = (n + elems_per_pass - 1) / elems_per_pass;
-            DevRolledArgs args{};
-            args.n = n; args.tiles_per_row = (uint32_t)tiles; args.row_words = (uint32_t)rw; args.iterations = (uint32_t)R;
-            args.dump = (uint64_t)(uintptr_t)dump_dev_;
-            const size_t table_bytes = table.size() * 8;
-            const size_t ring_off = ring_reserve(table_bytes);
-            std::memcpy((char*)ring_host_ + ring_off, table.data(), table_bytes);
-            hip_check(hipMemcpyAsync((char*)ring_dev_ + ring_off, (char*)ring_host_ + ring_off, table_bytes, hipMemcpyHostToDevice, stream_), "rolled row table H2D");
-            const uint64_t* rows_arg = (const uint64_t*)((char*)ring_dev_ + ring_off);
-            hipEvent_t ev0 = nullptr, ev1 = nullptr;
-            if (profiling_) { hip_check(hipEventCreate(&ev0), "hipEventCreate"); hip_check(hipEventCreate(&ev1), "hipEventCreate"); hip_check(hipEventRecord(ev0, stream_), "hipEventRecord"); }
-            void* params[] = { &args, &rows_arg };
-            hip_check(hipModuleLaunchKernel(ro.jit->fn_table, (unsigned)tiles, (unsigned)count, 1, FM_BLOCK, 1, 1, 0, stream_, params, nullptr), "launch rolled kernel");
-            if (profiling_) { hip_check(hipEventRecord(ev1, stream_), "hipEventRecord"); profile_events_.push_back({ ev0, ev1 });
-                              profile_tags_.push_back({ (int)(R * P), (int)(G + CI + R * LI), (int)(R * LO + CO), 0, (int)count, 2, n }); }
-            n_launches_++; n_jit_launches_++; n_rolled_launches_++;
-            n_ops_executed_ += (int64_t)(R * P) * (int64_t)count;
-            algorithmic_bytes_ += 4 * n * (int64_t)(G + CI + CO + R * (LI + LO)) * (int64_t)count;
-            bytes_written_ += 4 * n * (int64_t)(CO + R * LO) * (int64_t)count;
-        }
-    } catch (...) { for (Buffer* b : out_bufs) buffer_unref(b); throw; }
-    // commit (as run_dags): outputs become materialised vectors; their expressions (and the inner values) go away
-    size_t k = 0;
-    std::vector<Node*> outs;
-    outs.reserve(out_bufs.size());
-    for (size_t c = 0; c < count; ++c) {
-        BigDag& big = group[first + c];
-        auto commit = [&](size_t pos) {
-            Buffer* b = out_bufs[k++];
-            if (big.described()) commit_described(big, pos, b);
-            else { Node* nd = big.order[pos]; commit_node(nd, b); outs.push_back(nd); }
-        };
-        for (size_t r = 0; r < R; ++r)
-            for (size_t m = 0; m < LO; ++m) commit(ro.begin + r * P + ro.out_pos[m]);
-        for (size_t m = 0; m < CO; ++m) commit(ro.begin + (R - 1) * P + ro.final_pos[m]);
+struct Engine::OperandTable {
+    std::unordered_map<const Node*, int32_t> index_of;          // position in the order; a leaf: -1 - its number
+    std::vector<std::array<int32_t, 3>> operand;                 // per operation
+    explicit OperandTable(const BigDag& g) : operand(g.order.size()) {
+        index_of.reserve(g.order.size() + g.leaves.size());
+        for (size_t i = 0; i < g.order.size(); ++i) index_of[g.order[i]] = (int32_t)i;
+        for (size_t i = 0; i < g.leaves.size(); ++i) index_of[g.leaves[i]] = -1 - (int32_t)i;
+        for (size_t i = 0; i < g.order.size(); ++i)
+            for (int k = 0; k < g.order[i]->n_in; ++k) operand[i][(size_t)k] = index_of.at(g.order[i]->in[k]);
     }
-    // (a stored value nobody holds — a position the loop stores in every iteration for the sake of one — goes away with its last consumer:
-    // all of them are kept alive until every expression has been dismantled)
-    for (Node* nd : outs) nd->refs_int++;
-    for (Node* nd : outs) drop_expression(nd);
-    for (Node* nd : outs) { nd->refs_int--; node_maybe_free(nd); }
-}
+};
 
-// The whole component of every member of a group as ONE launch of its peeled kernel (plan_peel): row tables by index, launch, commit.
-static const bool COMMON_ROWS = [] { const char* e = std::getenv("FMHIP_COMMON_ROWS"); return !(e && e[0] == '0'); }();     // =0: identical rows of a launch are all computed (A/B)
-
-void Engine::run_peeled(const BigPlan::Rolled& ro, std::vector<BigDag>& group, size_t first, size_t count, ReduceRequest* rr, std::vector<uint32_t>* row_of_out)
-{
-    const BigPlan::Rolled::Peeled& pe = ro.peeled;
-    const size_t NX = pe.extra_leaf.size(), G = ro.global_leaf.size(), CO = ro.final_pos.size(), NXO = pe.pre_out.size() + pe.post_out.size();
-    const size_t LI = ro.leaf_in.size(), LO = ro.out_pos.size(), LS = ro.scal_pos.size(), NS0 = pe.n_pre_scal, NS2 = pe.n_post_scal;
-    const size_t R = ro.iterations, P = ro.period, rw = pe.row_words;
-    const size_t oG = NX, oCO = oG + G, oXO = oCO + CO, oIT = oXO + NXO;
-    const int64_t n = group[first].n;
-    std::vector<uint64_t> table(count * rw, 0);
-    struct Out { size_t member, pos; Buffer* buf; };
-    std::vector<Out> outs;
-    outs.reserve(count * (R * LO + CO + NXO));
-    auto ptr_of = [](const Buffer* b) -> uint64_t {
-        if (!b) throw Error(FMHIP_ERR_PROGRAM_LIMIT, "peeled loop reads a value that has not been computed");
-        return (uint64_t)(uintptr_t)b->ptr;
-    };
-    // COMMON ROWS.  What a row computes is a function of the vectors it reads and of its scalars: members whose rows agree in both —
-    // the parameter sets of a Jacobian batch up to the time step at which their bumped parameter is first used, which read the very same
-    // vectors because THEIR predecessors were common rows too — are computed once; the others' values are the same vectors (shared
-    // storage, copied if anybody writes into one in place: make_private).  A row's inputs and scalars are written first (output slots
-    // zero), compared with the rows before it, and only a row that is new gets output vectors.
-    std::vector<uint32_t> row_of(count);
-    std::vector<size_t> member_of_row;                          // launch row → the member (offset from `first`) that it computes
-    const bool dedup = COMMON_ROWS && count > 1 && (!rr || row_of_out);
-    std::unordered_multimap<uint64_t, uint32_t> seen;
-    std::vector<uint64_t> keys;                                 // the rows as they were compared: inputs and scalars, output slots still zero
-    try {
-        for (size_t c = 0; c < count; ++c) {
-            BigDag& big = group[first + c];
-            const size_t r_new = member_of_row.size();
-            uint64_t* row = table.data() + r_new * rw;
-            std::fill(row, row + rw, (uint64_t)0);
-            for (size_t k = 0; k < NX; ++k) row[k] = ptr_of(big.leaves[(size_t)pe.extra_leaf[k]]->buf);
-            for (size_t k = 0; k < G; ++k) row[oG + k] = ptr_of(big.leaves[(size_t)ro.global_leaf[k]]->buf);
-            float* sc = reinterpret_cast<float*>(row + oIT + R * (LI + LO));
-            for (size_t k = 0; k < NS0; ++k) sc[k] = big.scalar_at(pe.pre_scal[k]);
-            for (size_t r = 0; r < R; ++r) {
-                uint64_t* ip = row + oIT + r * (LI + LO);
-                const size_t base = ro.begin + r * P;
-                for (size_t m = 0; m < LI; ++m) ip[m] = ptr_of(big.leaves[(size_t)ro.iter_leaf[r * LI + m]]->buf);
-                for (size_t m = 0; m < LS; ++m) sc[NS0 + r * LS + m] = big.scalar_at(base + ro.scal_pos[m]);
-            }
-            for (size_t k = 0; k < NS2; ++k) sc[NS0 + R * LS + k] = big.scalar_at(pe.post_scal[k]);
-            if (dedup) {
-                uint64_t h = 0x9e3779b97f4a7c15ull;
-                for (size_t w = 0; w < rw; ++w) { h = (h ^ row[w]) * 0xff51afd7ed558ccdull; h ^= h >> 31; }
-                bool common = false;
-                auto range = seen.equal_range(h);
-                for (auto it = range.first; it != range.second && !common; ++it)
-                    if (std::memcmp(keys.data() + (size_t)it->second * rw, row, rw * 8) == 0) { row_of[c] = it->second; common = true; }
-                if (common) { ++n_common_rows_; continue; }
-                seen.emplace(h, (uint32_t)r_new);
-                keys.insert(keys.end(), row, row + rw);
-            }
-            row_of[c] = (uint32_t)r_new;
-            member_of_row.push_back(c);
-            auto fresh = [&](size_t pos) { Buffer* b = new_buffer(n); outs.push_back({ first + c, pos, b }); return (uint64_t)(uintptr_t)b->ptr; };
-            for (size_t k = 0; k < CO; ++k) if (pe.final_store[k]) row[oCO + k] = fresh(ro.begin + (R - 1) * P + ro.final_pos[k]);
-            for (size_t k = 0; k < pe.pre_out.size(); ++k) row[oXO + k] = fresh(pe.pre_out[k]);
-            for (size_t k = 0; k < pe.post_out.size(); ++k) row[oXO + pe.pre_out.size() + k] = fresh(pe.post_out[k]);
-            for (size_t r = 0; r < R; ++r) {
-                uint64_t* ip = row + oIT + r * (LI + LO);
-                for (size_t m = 0; m < LO; ++m) ip[LI + m] = fresh(ro.begin + r * P + ro.out_pos[m]);
-            }
-        }
-        const size_t rows = member_of_row.size();
-        table.resize(rows * rw);
-        if (n > 0) {
-            const int64_t elems_per_pass = (int64_t)FM_BLOCK * pe.jit->elems;
-            const int64_t tiles = (n + elems_per_pass - 1) / elems_per_pass;
-            DevRolledArgs args{};
-            args.n = n; args.tiles_per_row = (uint32_t)tiles; args.row_words = (uint32_t)rw; args.iterations = (uint32_t)R;
-            args.dump = (uint64_t)(uintptr_t)dump_dev_;
-            const size_t table_bytes = table.size() * 8;
-            const bool inline_rows = table.size() <= (size_t)FM_INLINE_WORDS;      // few rows: the table travels in the kernel arguments
-            const uint64_t* rows_arg = nullptr;
-            if (inline_rows) std::memcpy(args.inline_row, table.data(), table_bytes);
-            else {
-                const size_t ring_off = ring_reserve(table_bytes);
-                std::memcpy((char*)ring_host_ + ring_off, table.data(), table_bytes);
-                hip_check(hipMemcpyAsync((char*)ring_dev_ + ring_off, (char*)ring_host_ + ring_off, table_bytes, hipMemcpyHostToDevice, stream_), "peeled row table H2D");
-                rows_arg = (const uint64_t*)((char*)ring_dev_ + ring_off);
-            }
-            hipEvent_t ev0 = nullptr, ev1 = nullptr;
-            if (profiling_) { hip_check(hipEventCreate(&ev0), "hipEventCreate"); hip_check(hipEventCreate(&ev1), "hipEventCreate"); hip_check(hipEventRecord(ev0, stream_), "hipEventRecord"); }
-            void* params[] = { &args, &rows_arg };
-            // Tiles per workgroup: ONE.  Measured against 2 and 4 (profiles/round04_peel_tiles_per_workgroup.txt): a workgroup
-            // that walks two or four tiles one after the other — a quarter of the partials, arrival counts and lingering keeper waves of a
-            // launch that takes the moments of its roots — is SLOWER on every kind of launch (valuation chains 5607 → 5527 → 5424 GB/s,
-            // simulation components −2 % and −4 %): these kernels live on the number of independent tiles in flight.  Same moments either
-            // way (the reduction tree is defined on the vector, fm_kernel_parts.hpp).
-            const int64_t grid_x = tiles;                                          // (the kernel derives its stretch from the grid)
-            RedLaunch red;
-            std::vector<fmhip_moments> by_row;                                     // host moments arrive per ROW; the caller's array is per member
-            if (rr) {                           // the kernel with the fused reduction of the root (rr->host_out: one entry per member; rr->dev_out: one slot per row)
-                fmhip_moments* host_rows = rr->host_out;
-                if (rr->host_out && rows != count) { by_row.resize(rows); host_rows = by_row.data(); }
-                red_begin(red, (int)rows, 1, (size_t)tiles, host_rows, rr->dev_out);
-                args.shift = rr->shift; args.partials = (double*)red.partials; args.results = (double*)red.results; args.counters = counters_dev_;
-                args.done_flag = const_cast<uint64_t*>(red.poll_flag); args.done_value = red.done_value;
-            }
-            try {
-                const JitSlot& slot = rr ? *pe.jit_red : *pe.jit;
-                hip_check(hipModuleLaunchKernel(inline_rows ? slot.fn_inline : slot.fn_table, (unsigned)grid_x, (unsigned)rows, 1, FM_BLOCK, 1, 1, 0, stream_, params, nullptr), "launch peeled kernel");
-                const size_t stored = R * LO + NXO + (size_t)std::count(pe.final_store.begin(), pe.final_store.end(), (char)1);
-                if (profiling_) { hip_check(hipEventRecord(ev1, stream_), "hipEventRecord"); profile_events_.push_back({ ev0, ev1 });
-                                  profile_tags_.push_back({ (int)pe.n_ops, (int)(NX + G + R * LI), (int)stored, rr ? 1 : 0, (int)rows, 2, n }); }
-                n_launches_++; n_jit_launches_++; n_rolled_launches_++;
-                n_ops_executed_ += (int64_t)pe.n_ops * (int64_t)rows;
-                algorithmic_bytes_ += 4 * n * (int64_t)(NX + G + R * LI + stored) * (int64_t)rows;
-                bytes_written_ += 4 * n * (int64_t)stored * (int64_t)rows;
-                if (rr) {
-                    rr->done = true;
-                    if (count == 1 && defer_red_ && !defer_red_->pending && rr->host_out && red.on_host) {
-                        red.pending = true; red.batch = 1; red.n_red = 1; red.host = rr->host_out;
-                        *defer_red_ = red; red = RedLaunch();      // reduce() waits and releases
-                    } else {
-                        red_wait(red, (int)rows, 1, by_row.empty() ? rr->host_out : by_row.data());
-                        if (!by_row.empty()) for (size_t c = 0; c < count; ++c) rr->host_out[c] = by_row[row_of[c]];
-                    }
-                }
-            } catch (...) { red_release(red); throw; }
-            red_release(red);
-        } else if (rr) rr = nullptr;
-    } catch (...) { for (Out& o : outs) buffer_unref(o.buf); throw; }
-    if (row_of_out) *row_of_out = row_of;
-    // the members of a common row receive the vectors its first member stored (one more reference each)
-    if (member_of_row.size() != count) {
-        std::vector<std::pair<size_t, size_t>> span(member_of_row.size(), { 0, 0 });   // per row: its outs [begin, end)
-        { size_t k = 0;
-          for (size_t r = 0; r < member_of_row.size(); ++r) { const size_t b = k; while (k < outs.size() && outs[k].member == first + member_of_row[r]) ++k; span[r] = { b, k }; } }
-        const size_t n_first = outs.size();
-        for (size_t c = 0; c < count; ++c) {
-            const size_t r = row_of[c];
-            if (member_of_row[r] == c) continue;
-            for (size_t k = span[r].first; k < span[r].second && k < n_first; ++k) { Buffer* b = outs[k].buf; b->refs++; outs.push_back({ first + c, outs[k].pos, b }); }
-        }
-    }
-    // commit: every stored value becomes a materialised vector; the rest of the component goes away with their expressions
-    std::vector<Node*> done;
-    done.reserve(outs.size());
-    for (Out& o : outs) {
-        BigDag& big = group[o.member];
-        if (big.described()) commit_described(big, o.pos, o.buf);
-        else { Node* nd = big.order[o.pos]; commit_node(nd, o.buf); done.push_back(nd); }
-    }
-    for (Node* nd : done) nd->refs_int++;
-    for (Node* nd : done) drop_expression(nd);
-    for (Node* nd : done) { nd->refs_int--; node_maybe_free(nd); }
-}
-
-// A component shape with a plan, for every member of a group: segment by segment (the rolled stretch as one launch once its kernel
-// exists), ≤ 1024 members per launch.
 // The root of a component that has exactly one, as its LAST operation — its node (for a copy that exists as a description: the copy's
 // root node) or nullptr.  g0 = the member that carries the order.
 Node* Engine::single_root(const BigDag& b, const BigDag& g0)
@@ -2661,13 +2203,13 @@ Node* Engine::single_root(const BigDag& b, const BigDag& g0)
     return g->copy_roots[(size_t)b.copy * g->n_roots + (size_t)rep_root[n - 1]];
 }
 
+// A component shape with a plan, for every member of a group: segment by segment (the rolled stretch as one launch once its kernel
+// exists), ≤ 1024 members per launch.
 void Engine::run_plan(BigPlan& plan, std::vector<BigDag>& group, ReduceRequest* rr) {
     const size_t max_batch = 1024;
     { static const bool batch_trace = std::getenv("FMHIP_BATCH_TRACE") != nullptr;
       if (batch_trace && want_root_moments_) std::fprintf(stderr, "[fmhip batch] plan for a group of %zu, %zu nodes, %zu roots: rolled %d peeled %d segs %zu\n", group.size(), group[0].order.size(), group[0].roots.size(), plan.rolled.present ? 1 : 0, plan.rolled.peeled.present ? 1 : 0, plan.segs.size()); }
-    if (plan.rolled.present && jit_mode != FMHIP_JIT_OFF && (!plan.rolled.jit || (jit_mode == FMHIP_JIT_SYNC && plan.rolled.jit->state.load(std::memory_order_acquire) == JitSlot::QUEUED)))
-        plan.rolled.jit = jit().request_source(plan.rolled.source, plan.rolled.elems, jit_mode == FMHIP_JIT_SYNC);
-    bool rolled = plan.rolled.present && jit_mode != FMHIP_JIT_OFF && plan.rolled.jit && plan.rolled.jit->state.load(std::memory_order_acquire) == JitSlot::READY;
+    bool rolled = plan.rolled.present && jit_mode != FMHIP_JIT_OFF && kernel_ready(plan.rolled.jit, [&] { return plan.rolled.source; }, plan.rolled.elems);
     // The rolled launch carries one row table for all its members through the pinned ring (≈ 5 KB per row for the LMM step, but
     // iterations x (inputs + outputs) words in general): as many members per launch as fit; a single row that does not fit leaves the
     // stretch to its segments.
@@ -2682,23 +2224,18 @@ void Engine::run_plan(BigPlan& plan, std::vector<BigDag>& group, ReduceRequest* 
     // kernel time with the head and the tail limited to 128 operations each).  FMHIP_PEEL_MAX_WORKGROUPS limits it to small launches.
     {
         BigPlan::Rolled::Peeled& pe = plan.rolled.peeled;
-        if (pe.present && jit_mode != FMHIP_JIT_OFF && (!pe.jit || (jit_mode == FMHIP_JIT_SYNC && pe.jit->state.load(std::memory_order_acquire) == JitSlot::QUEUED)))
-            pe.jit = jit().request_source(pe.source, pe.elems, jit_mode == FMHIP_JIT_SYNC);
-        if (pe.present && jit_mode != FMHIP_JIT_OFF && pe.jit && pe.jit->state.load(std::memory_order_acquire) == JitSlot::READY && group[0].n > 0) {
-            static const size_t PEEL_MAX_WORKGROUPS = [] { const char* e = std::getenv("FMHIP_PEEL_MAX_WORKGROUPS"); return e ? (size_t)std::atoll(e) : ~(size_t)0; }();
+        auto red_ready = [&] { return kernel_ready(pe.jit_red, [&] { return pe.source_red; }, pe.elems); };
+        if (pe.present && jit_mode != FMHIP_JIT_OFF && kernel_ready(pe.jit, [&] { return pe.source; }, pe.elems) && group[0].n > 0) {
+            static const size_t PEEL_MAX_WORKGROUPS = knob_size("FMHIP_PEEL_MAX_WORKGROUPS", ~(size_t)0);
             const size_t tiles = (size_t)((group[0].n + (int64_t)FM_BLOCK * pe.jit->elems - 1) / ((int64_t)FM_BLOCK * pe.jit->elems));
             const size_t rows_fit = ring_cap_ / ((size_t)pe.row_words * 8 + 256);
             if (group.size() * tiles <= PEEL_MAX_WORKGROUPS && rows_fit >= group.size()) {
-                struct TempGuard2 { Engine* e; std::vector<BigDag>& g; ~TempGuard2() { for (BigDag& b : g) if (b.described()) for (Buffer*& t : b.temp) if (t) { e->buffer_unref(t); t = nullptr; } } } guard2{ this, group };
+                TempGuard guard{ this, group };
                 // `chain.getAverage()` on the component's root: the same launch takes the moments (a workgroup's tile is one unit of the
                 // reduction tree) — a product of a caller that values one after the other is ONE launch, and its value is not read again
                 ReduceRequest* fused = nullptr;
                 if (rr && group.size() == 1 && !group[0].described() && !pe.source_red.empty() && group[0].order.back() == group[0].roots[0] &&
-                    tiles <= (size_t)FM_SPAN_UNITS * 65536) {
-                    if (!pe.jit_red || (jit_mode == FMHIP_JIT_SYNC && pe.jit_red->state.load(std::memory_order_acquire) == JitSlot::QUEUED))
-                        pe.jit_red = jit().request_source(pe.source_red, pe.elems, jit_mode == FMHIP_JIT_SYNC);
-                    if (pe.jit_red->state.load(std::memory_order_acquire) == JitSlot::READY) fused = rr;
-                }
+                    tiles <= (size_t)FM_SPAN_UNITS * 65536 && red_ready()) fused = rr;
                 // … and with a flush that collects the moments of all pending roots (Engine::reduce): of every member, as rows of this launch
                 std::vector<fmhip_moments> all;
                 ReduceRequest every{ 0.0, nullptr, nullptr, false };
@@ -2707,13 +2244,9 @@ void Engine::run_plan(BigPlan& plan, std::vector<BigDag>& group, ReduceRequest* 
                 if (!fused && want_root_moments_ && !rr && !pe.source_red.empty() && tiles <= (size_t)FM_SPAN_UNITS * 65536) {
                     bool roots_only = true;
                     for (const BigDag& b : group) { Node* r = single_root(b, group[0]); roots_only &= r != nullptr && !r->moments_blocked && (!plan.discards_root || r->discard); }
-                    if (roots_only) {
-                        if (!pe.jit_red || (jit_mode == FMHIP_JIT_SYNC && pe.jit_red->state.load(std::memory_order_acquire) == JitSlot::QUEUED))
-                            pe.jit_red = jit().request_source(pe.source_red, pe.elems, jit_mode == FMHIP_JIT_SYNC);
-                        if (pe.jit_red->state.load(std::memory_order_acquire) == JitSlot::READY) {
-                            if (async_moments_) { every.dev_out = arena_alloc(group.size()); if (every.dev_out) fused = &every; }
-                            else { all.resize(group.size()); every.host_out = all.data(); fused = &every; }
-                        }
+                    if (roots_only && red_ready()) {
+                        if (async_moments_) { every.dev_out = arena_alloc(group.size()); if (every.dev_out) fused = &every; }
+                        else { all.resize(group.size()); every.host_out = all.data(); fused = &every; }
                     }
                 }
                 // A plan whose root is wanted for its moments only has peeled kernels that do not store it: usable only when this launch
@@ -2726,12 +2259,9 @@ void Engine::run_plan(BigPlan& plan, std::vector<BigDag>& group, ReduceRequest* 
                 if (fused == &every && every.done && every.dev_out)
                     for (size_t i = 0; i < root_nodes.size(); ++i) arena_assign(root_nodes[i], (double*)every.dev_out + (size_t)row_of[i] * 4);      // (members of a common row: the same slot)
                 else if (fused == &every && every.done)
-                    for (size_t i = 0; i < root_nodes.size(); ++i) {
-                        Node* r = root_nodes[i];
-                        r->moments[0] = all[i].sum; r->moments[1] = all[i].sumsq; r->moments[2] = all[i].min; r->moments[3] = all[i].max; r->has_moments = true;
-                    }
+                    for (size_t i = 0; i < root_nodes.size(); ++i) set_moments(root_nodes[i], all[i]);
                 if (plan.discards_root && every.done)       // moments taken, value not stored: not a root of later flushes; what it was computed from is let go
-                    for (Node* r : root_nodes) if (!r->buf) { r->discarded = true; r->refs_int++; drop_expression(r); r->refs_int--; }
+                    for (Node* r : root_nodes) if (!r->buf) give_up_value(r);
                 return;
                 }
             }
@@ -2757,10 +2287,7 @@ void Engine::run_plan(BigPlan& plan, std::vector<BigDag>& group, ReduceRequest* 
             for (int32_t pos : positions) if (Buffer* t = b.temp[(size_t)pos]) { b.temp[(size_t)pos] = nullptr; buffer_unref(t); }
         }
     };
-    struct TempGuard {              // whatever happens, the values held for members without nodes go back to the pool
-        Engine* e; std::vector<BigDag>& g;
-        ~TempGuard() { for (BigDag& b : g) if (b.described()) for (Buffer*& t : b.temp) if (t) { e->buffer_unref(t); t = nullptr; } }
-    } guard{ this, group };
+    TempGuard guard{ this, group };
     // The variant of the last segment that also reduces the component's root, for `chain.getAverage()` on a single large expression: one
     // launch and one read of the root less than a stand-alone reduction behind the segment.  Only when that variant accumulates like
     // the stand-alone reduction program does (8 elements per lane: the sums are then the same to the last bit).
@@ -2803,13 +2330,11 @@ void Engine::plan_segments(BigPlan& plan, std::vector<BigDag>& group) {
     const size_t n_ops = group[0].order.size();
     const size_t max_batch = 1024;
     // Node -> index in group[0] for the plan (segment_dag reuses the nodes' scratch fields)
-    std::unordered_map<const Node*, int32_t> index_of;
-    index_of.reserve(n_ops + group[0].leaves.size());
-    for (size_t i = 0; i < n_ops; ++i) index_of[group[0].order[i]] = (int32_t)i;
-    for (size_t i = 0; i < group[0].leaves.size(); ++i) index_of[group[0].leaves[i]] = -1 - (int32_t)i;
+    const OperandTable table(group[0]);
+    const std::unordered_map<const Node*, int32_t>& index_of = table.index_of;
     std::vector<int32_t> uses(n_ops, 0);                    // consumers inside the component, per position (before anything runs)
     for (size_t i = 0; i < n_ops; ++i)
-        for (int k = 0; k < group[0].order[i]->n_in; ++k) { const int32_t o = index_of.at(group[0].order[i]->in[k]); if (o >= 0) uses[(size_t)o]++; }
+        for (int k = 0; k < group[0].order[i]->n_in; ++k) { const int32_t o = table.operand[i][(size_t)k]; if (o >= 0) uses[(size_t)o]++; }
     size_t zone_begin = n_ops, zone_end = n_ops;
     if (plan.rolled.present) { zone_begin = plan.rolled.begin; zone_end = zone_begin + (size_t)plan.rolled.period * plan.rolled.iterations; }
     size_t s = 0;
@@ -2863,534 +2388,7 @@ void Engine::plan_segments(BigPlan& plan, std::vector<BigDag>& group) {
     }
 }
 
-// The loop of a component shape (detect_loop) and its peeled form (plan_peel), their kernels asked of the specialised tier; nothing runs.
-void Engine::plan_loop(BigPlan& plan, const BigDag& g) {
-    static const bool ROLL = [] { const char* e = std::getenv("FMHIP_ROLL"); return !(e && e[0] == '0'); }();
-    if (!ROLL) return;
-    const size_t n_ops = g.order.size();
-    std::vector<std::array<int32_t, 3>> operand(n_ops);      // (build_big left every node's position, resp. -1 - leaf number, in tmp_id)
-    std::unordered_map<const Node*, int32_t> index_of;
-    index_of.reserve(n_ops + g.leaves.size());
-    for (size_t i = 0; i < n_ops; ++i) index_of[g.order[i]] = (int32_t)i;
-    for (size_t i = 0; i < g.leaves.size(); ++i) index_of[g.leaves[i]] = -1 - (int32_t)i;
-    for (size_t i = 0; i < n_ops; ++i)
-        for (int k = 0; k < g.order[i]->n_in; ++k) operand[i][(size_t)k] = index_of.at(g.order[i]->in[k]);
-    std::string source; int elems = 0;
-    RolledBody body;
-    if (!detect_loop(g, operand, plan.rolled, &source, &elems, &body)) return;
-    if (plan_peel(g, operand, plan.rolled, body) && jit_mode != FMHIP_JIT_OFF)
-        plan.rolled.peeled.jit = jit().request_source(plan.rolled.peeled.source, plan.rolled.peeled.elems, jit_mode == FMHIP_JIT_SYNC);
-    if (const char* dump = std::getenv("FMHIP_ROLL_DUMP")) { if (FILE* f = std::fopen(dump, "a")) { std::fputs(source.c_str(), f); std::fputs("\n// ----\n", f); std::fclose(f); } }
-    plan.rolled.present = true;
-    plan.rolled.source = source; plan.rolled.elems = elems;
-    if (jit_mode != FMHIP_JIT_OFF) plan.rolled.jit = jit().request_source(std::move(source), elems, jit_mode == FMHIP_JIT_SYNC);
-}
-
-// ---------------------------------------------------------------- merged chains (runtime.hpp: merge_families; jit.hpp: RolledBody::chains)
-//
-// The 14 swaptions of one exercise date are 14 components of the same loop shape and different length — 14 launches by shape (each with the
-// other exercise dates' swaptions of that tenor as its rows), every one of which reads the forward rates of its tenor: L_e[e] 14 times,
-// L_e[e + 19] five times, 304 vector reads per exercise date where 61 vectors exist.  A FAMILY is a set of such components, found by
-// their vectors: same shape of head, body and tail, the same tail inputs, and the head + loop inputs of each a suffix of the longest
-// one's.  One launch per (shape, family size): a row per family, a step per vector of the longest chain, every chain joining at its own
-// first step; per chain the same operations on the same operands in the same order as in its own launch, and its moments by the same
-// tree — bit-identical results, a fifth of the bytes.  Nothing is assumed about the caller: the family is read off the pending graph.
-static const bool MERGE_CHAINS = MERGE_CHAINS_ON();         // FMHIP_MERGE_CHAINS=0: off
-static const bool MERGE_SMALL = [] { const char* e = std::getenv("FMHIP_MERGE_SMALL"); return !(e && e[0] == '0'); }();      // =0: components that fit one launch never join a family
-
 struct Engine::SmallGroup { std::vector<Dag> members; Dag proto; const SmallMatch* match = nullptr; std::vector<std::pair<ReplicaGroup*, std::vector<int>>> done; };
-
-// Is this single-launch component, position by position, head + R iterations of the body + tail of a mergeable loop shape?  (The walk
-// that lists its operations — depth first from the root, operands in order — and the schedule of the large components of the same shape
-// list a chain the same way; where they do not, the answer is no and the component runs on its own as before.)
-const Engine::SmallMatch* Engine::match_small(const Dag& d)
-{
-    if (!MERGE_SMALL || merge_shapes_.empty()) return nullptr;
-    auto known = small_match_.find(d.sig);
-    if (known != small_match_.end()) {
-        if (known->second.ok) return &known->second;
-        if (known->second.shape == (int)merge_shapes_.size()) return nullptr;      // (no, with every shape known today)
-    }
-    if (small_match_.size() > 4096) small_match_.clear();
-    SmallMatch& out = small_match_[d.sig];
-    out = SmallMatch();
-    out.shape = (int)merge_shapes_.size();                      // (looked at with these shapes known: asked again when another one appears)
-    const size_t m = d.order.size(), n_in = d.leaves.size();
-    if (d.roots.size() != 1 || d.outs.size() != 1 || m == 0 || d.order.back() != d.roots[0] || d.ops.size() != m) return nullptr;
-    for (size_t si = 0; si < merge_shapes_.size() && !out.ok; ++si) {
-        const RolledBody& B = merge_shape_bodies_[si];
-        const RolledBody::Peel& PL = B.peel;
-        const size_t n_pre = PL.pre.size(), n_post = PL.post.size(), P = B.ops.size(), NXa = PL.extra_pre, NXP = PL.extra_post;
-        if (m < n_pre + n_post || (m - n_pre - n_post) % P != 0) continue;
-        // the tail stores nothing but the component's root, or nothing at all
-        if (!(PL.post_out.empty() || (PL.post_out.size() == 1 && PL.post_out[0] + 1 == n_post)) || PL.reduce != "q" + std::to_string(n_post - 1)) continue;
-        const size_t R = (m - n_pre - n_post) / P;
-        std::vector<int> seq(NXa + R, -1), post(NXP, -1);
-        bool ok = true;
-        // an operand by name → what it must be here: position of an operation (>= 0), or a sequence / tail vector (checked against the leaf)
-        auto check = [&](const RolledBody::Op& op, size_t i, auto&& resolve) {
-            const SsaOp& a = d.ops[i];
-            UVariant uv{};
-            if (!variant_for(a.opcode, 0, &uv)) return false;
-            uint32_t uop = uv.uop;
-            if (math_mode == FMHIP_MATH_FAST) { if (uop == U_EXP) uop = U_EXP_FAST; else if (uop == U_LOG) uop = U_LOG_FAST; }
-            if (uop != op.uop || op_info(a.opcode).scalar != op.scalar) return false;
-            const int ids[3] = { a.a, a.b, a.c };
-            const std::string* names[3] = { &op.x0, &op.x1, &op.x2 };
-            const int pos[3] = { 0, uv.r1_pos, uv.r2_pos };
-            for (int k = 0; k < 3; ++k) {
-                if (names[k]->empty()) { if (k > 0 && pos[k] >= 0) return false; continue; }
-                if (pos[k] < 0 || ids[pos[k]] < 0) return false;
-                if (!resolve(*names[k], ids[pos[k]])) return false;
-            }
-            return true;
-        };
-        auto is_op = [&](int id, size_t position) { return id >= (int)n_in && (size_t)(id - (int)n_in) == position; };
-        auto is_leaf = [&](int id, int& slot) { if (id < 0 || id >= (int)n_in) return false; if (slot < 0) slot = id; return slot == id; };
-        for (size_t i = 0; i < n_pre && ok; ++i)
-            ok = check(PL.pre[i], i, [&](const std::string& nm, int id) {
-                const size_t idx = (size_t)std::atoi(nm.c_str() + 1);
-                if (nm[0] == 'x') return idx < NXa && is_leaf(id, seq[idx]);
-                if (nm[0] == 'p') return idx < i && is_op(id, idx);
-                return false; });
-        for (size_t r = 0; r < R && ok; ++r)
-            for (size_t q = 0; q < P && ok; ++q) {
-                const size_t base = n_pre + r * P;
-                ok = check(B.ops[q], base + q, [&](const std::string& nm, int id) {
-                    const size_t idx = (size_t)std::atoi(nm.c_str() + 1);
-                    if (nm[0] == 'v') return idx < q && is_op(id, base + idx);
-                    if (nm[0] == 'c') {
-                        if (idx >= B.carried.size()) return false;
-                        if (r > 0) return is_op(id, base - P + B.carried[idx]);
-                        const std::string& init = PL.carried_init[idx];
-                        return init[0] == 'p' && is_op(id, (size_t)std::atoi(init.c_str() + 1)); }
-                    if (nm == "l0") return is_leaf(id, seq[NXa + r]);
-                    return false; });
-            }
-        for (size_t i = 0; i < n_post && ok; ++i) {
-            const size_t base = n_pre + R * P;
-            ok = check(PL.post[i], base + i, [&](const std::string& nm, int id) {
-                const size_t idx = (size_t)std::atoi(nm.c_str() + 1);
-                if (nm[0] == 'q') return idx < i && is_op(id, base + idx);
-                if (nm[0] == 'x') return idx >= NXa && idx < NXa + NXP && is_leaf(id, post[idx - NXa]);
-                if (nm[0] == 'F') {
-                    if (idx >= B.final_pos.size()) return false;
-                    if (R > 0) return is_op(id, base - P + B.final_pos[idx]);
-                    for (size_t c = 0; c < B.carried.size(); ++c)
-                        if (B.carried[c] == B.final_pos[idx]) { const std::string& init = PL.carried_init[c]; return init[0] == 'p' && is_op(id, (size_t)std::atoi(init.c_str() + 1)); }
-                    return false; }
-                return false; });
-        }
-        // every vector of the sequence is a vector of its own step (the kernel loads one per step), every leaf is accounted for
-        for (int v : seq) ok = ok && v >= 0;
-        for (int v : post) ok = ok && v >= 0;
-        if (ok) { std::vector<int> all(seq); all.insert(all.end(), post.begin(), post.end()); std::sort(all.begin(), all.end()); ok = all.size() == n_in && std::adjacent_find(all.begin(), all.end()) == all.end(); }
-        if (!ok) continue;
-        out.ok = true; out.shape = (int)si; out.R = (uint32_t)R;
-        out.seq_leaf.assign(seq.begin(), seq.end()); out.post_leaf.assign(post.begin(), post.end());
-    }
-    if (!out.ok) { out.shape = (int)merge_shapes_.size(); return nullptr; }
-    return &out;
-}
-
-// The number of a mergeable loop shape (by its description), registered at its first sight — when its plan is made (plan_peel), so that
-// single-launch components of the flush after can be recognised as its chains; -1: the shape has no merged form.
-int Engine::merge_shape_index(const std::string& desc)
-{
-    if (desc.empty()) return -1;
-    for (size_t i = 0; i < merge_shapes_.size(); ++i) if (merge_shapes_[i] == desc) return (int)i;
-    RolledBody body;
-    if (!jit_parse_description(desc, body)) return -1;
-    RolledBody probe = body; probe.chains = 2; probe.shared_den = true;
-    if (jit_generate_rolled_source(probe).empty()) return -1;
-    merge_shapes_.push_back(desc); merge_shape_bodies_.push_back(std::move(body));
-    return (int)merge_shapes_.size() - 1;
-}
-
-void Engine::merge_families(std::vector<std::vector<BigDag>>& groups, std::vector<SmallGroup>& small)
-{
-    if (!MERGE_CHAINS || !want_root_moments_ || jit_mode == FMHIP_JIT_OFF) return;
-    // a chain: a large component (group, member: its plan says where its vectors and scalars are) or a small one (sgroup, smember: its match does)
-    struct Chain { size_t group, member; BigPlan* plan; int shape; Node* root; uint32_t steps, R; const float* last; bool small; };
-    std::vector<Chain> chains;
-    auto shape_index = [&](BigPlan::Rolled::Peeled& pe) -> int { return merge_shape_index(pe.desc_red); };
-    std::vector<BigPlan*> plan_of_shape;                         // a plan of every shape met in this flush (what its large chains are described by)
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
-        std::vector<BigDag>& g = groups[gi];
-        if (g.empty() || g[0].described() || g[0].n <= 0) continue;
-        auto planned = plan_cache_.find(g[0].hash);
-        if (planned == plan_cache_.end() || planned->second.sig != g[0].sig) continue;
-        BigPlan& plan = planned->second;
-        BigPlan::Rolled& ro = plan.rolled;
-        BigPlan::Rolled::Peeled& pe = ro.peeled;
-        if (!ro.present || !pe.present || pe.desc_red.empty() || pe.elems != 8) continue;
-        if (pe.mergeable < 0) pe.mergeable = shape_index(pe) >= 0 ? 1 : 0;
-        if (!pe.mergeable) continue;
-        const int shape = shape_index(pe);
-        if (shape < 0) continue;
-        if ((size_t)((g[0].n + FM_UNIT_ELEMS - 1) / FM_UNIT_ELEMS) > (size_t)FM_SPAN_UNITS * 65536) continue;
-        if (plan_of_shape.size() <= (size_t)shape) plan_of_shape.resize((size_t)shape + 1, nullptr);
-        if (!plan_of_shape[(size_t)shape]) plan_of_shape[(size_t)shape] = &plan;
-        const uint32_t steps = (uint32_t)(merge_shape_bodies_[(size_t)shape].peel.extra_pre + ro.iterations);
-        for (size_t mi = 0; mi < g.size(); ++mi) {
-            const BigDag& b = g[mi];
-            Node* r = single_root(b, g[0]);
-            if (!r || r->moments_blocked || (plan.discards_root && !r->discard) || r->buf) continue;
-            const int32_t last_leaf = ro.iter_leaf[(size_t)(ro.iterations - 1) * ro.leaf_in.size()];
-            const Buffer* lb = b.leaves[(size_t)last_leaf]->buf;
-            if (!lb) continue;
-            chains.push_back({ gi, mi, &plan, shape, r, steps, ro.iterations, lb->ptr, false });
-        }
-    }
-    for (size_t gi = 0; gi < small.size(); ++gi) {
-        SmallGroup& sg = small[gi];
-        if (!sg.match || sg.members.empty()) continue;
-        const int shape = sg.match->shape;
-        if ((size_t)shape >= plan_of_shape.size() || !plan_of_shape[(size_t)shape]) continue;      // no large chain of this shape in this flush: nobody to join
-        const RolledBody& body = merge_shape_bodies_[(size_t)shape];
-        const bool stores_root = !body.peel.post_out.empty();
-        const uint32_t steps = (uint32_t)(body.peel.extra_pre + sg.match->R);
-        for (size_t mi = 0; mi < sg.members.size(); ++mi) {
-            const Dag& d = sg.members[mi];
-            if (d.outs.size() != 1 || d.leaves.size() != sg.proto.leaves.size() || d.outs[0]->n <= 0) continue;
-            Node* r = d.outs[0];
-            // (as run_dags: a root that is held; given up — and held by nobody else, a copy's root but by its group — exactly when the shape stores nothing)
-            const bool given_up = r->discard && r->refs_int == ((r->rep_id && r->rep_copy && replica_of(r)) ? 1 : 0);
-            if (r->moments_blocked || r->buf || r->refs_ext <= 0 || (stores_root ? r->discard : !given_up)) continue;
-            const Buffer* lb = d.leaves[(size_t)sg.match->seq_leaf.back()]->buf;
-            if (!lb) continue;
-            chains.push_back({ gi, mi, plan_of_shape[(size_t)shape], shape, r, steps, sg.match->R, lb->ptr, true });
-        }
-    }
-    if (chains.size() < 2) return;
-    struct Shape { const RolledBody* body = nullptr; size_t NXa = 0, NXP = 0, NS0 = 0, NS2 = 0, LS = 0, NXO = 0, P = 0; std::vector<uint32_t> shared_pre, shared_body; };
-    std::unordered_map<int, Shape> shapes;
-    auto shape_of = [&](int shape) -> Shape& {
-        auto it = shapes.find(shape);
-        if (it != shapes.end()) return it->second;
-        Shape& sh = shapes[shape];
-        sh.body = &merge_shape_bodies_[(size_t)shape];
-        sh.NXa = sh.body->peel.extra_pre; sh.NXP = sh.body->peel.extra_post; sh.NXO = sh.body->peel.post_out.size(); sh.P = sh.body->ops.size();
-        for (const RolledBody::Op& op : sh.body->peel.pre) sh.NS0 += op.scalar ? 1 : 0;
-        for (const RolledBody::Op& op : sh.body->peel.post) sh.NS2 += op.scalar ? 1 : 0;
-        for (const RolledBody::Op& op : sh.body->ops) sh.LS += op.scalar ? 1 : 0;
-        jit_merged_shared_scalars(*sh.body, sh.shared_pre, sh.shared_body);
-        return sh;
-    };
-    auto vec_ptr = [](const Node* leaf) -> const float* { return leaf->buf ? leaf->buf->ptr : nullptr; };
-    auto chain_n = [&](const Chain& c) -> int64_t { return c.small ? small[c.group].members[c.member].outs[0]->n : groups[c.group][c.member].n; };
-    // the vector a chain reads at step i of its own sequence (head inputs first, then one per iteration); the vectors of its tail
-    auto seq_ptr = [&](const Chain& c, const Shape& sh, size_t i) -> const float* {
-        if (c.small) { const SmallGroup& sg = small[c.group]; return vec_ptr(sg.members[c.member].leaves[(size_t)sg.match->seq_leaf[i]]); }
-        const BigDag& b = groups[c.group][c.member];
-        const BigPlan::Rolled& ro = c.plan->rolled;
-        return vec_ptr(b.leaves[(size_t)(i < sh.NXa ? ro.peeled.extra_leaf[i] : ro.iter_leaf[(i - sh.NXa) * ro.leaf_in.size()])]);
-    };
-    auto post_ptr = [&](const Chain& c, const Shape& sh, size_t x) -> const float* {
-        if (c.small) { const SmallGroup& sg = small[c.group]; return vec_ptr(sg.members[c.member].leaves[(size_t)sg.match->post_leaf[x]]); }
-        return vec_ptr(groups[c.group][c.member].leaves[(size_t)c.plan->rolled.peeled.extra_leaf[sh.NXa + x]]);
-    };
-    // scalar number i of the chain's head / of iteration `it` / of its tail, in the order of the operations
-    auto pre_scalar = [&](const Chain& c, const Shape&, size_t i) -> float {
-        if (c.small) return small[c.group].members[c.member].scalars[i];
-        return groups[c.group][c.member].scalar_at(c.plan->rolled.peeled.pre_scal[i]);
-    };
-    auto body_scalar = [&](const Chain& c, const Shape& sh, size_t it, size_t i) -> float {
-        if (c.small) return small[c.group].members[c.member].scalars[sh.NS0 + it * sh.LS + i];
-        const BigPlan::Rolled& ro = c.plan->rolled;
-        return groups[c.group][c.member].scalar_at(ro.begin + it * ro.period + ro.scal_pos[i]);
-    };
-    auto post_scalar = [&](const Chain& c, const Shape& sh, size_t i) -> float {
-        if (c.small) return small[c.group].members[c.member].scalars[sh.NS0 + (size_t)c.R * sh.LS + i];
-        return groups[c.group][c.member].scalar_at(c.plan->rolled.peeled.post_scal[i]);
-    };
-    // candidates by (shape, last vector): longest first
-    std::sort(chains.begin(), chains.end(), [&](const Chain& a, const Chain& b) {
-        if (a.shape != b.shape) return a.shape < b.shape;
-        if (a.last != b.last) return a.last < b.last;
-        if (a.steps != b.steps) return a.steps > b.steps;
-        if (a.small != b.small) return !a.small;
-        if (a.group != b.group) return a.group < b.group;
-        return a.member < b.member;
-    });
-    struct Family { std::vector<size_t> chain; };          // indices into `chains`, longest first
-    std::vector<Family> families;
-    for (size_t i = 0; i < chains.size();) {
-        size_t j = i + 1;
-        while (j < chains.size() && chains[j].last == chains[i].last && chains[j].shape == chains[i].shape) ++j;
-        // [i, j): same shape, same last vector.  Those whose whole sequence is a suffix of the longest one's and whose tail inputs and
-        // shared scalars agree with it form families of at most 16 (a family of small components only has nobody to carry it: skipped).
-        // Chains of the SAME length that end in the same vector — the same product valued for several parameter sets whose simulations
-        // were common rows up to this exercise date (run_peeled) — belong to different families: the m-th chain of every length forms
-        // layer m; the layers are rows of one launch (and, reading the same vectors with the same scalars, one common row of it).
-        std::vector<std::vector<size_t>> layers;
-        { size_t occurrence = 0;
-          for (size_t q = i; q < j; ++q) {
-              occurrence = (q > i && chains[q].steps == chains[q - 1].steps) ? occurrence + 1 : 0;
-              if (layers.size() <= occurrence) layers.resize(occurrence + 1);
-              layers[occurrence].push_back(q);
-          } }
-        for (const std::vector<size_t>& layer : layers) {
-        const Chain& lead = chains[layer[0]];
-        const Shape& sh = shape_of(lead.shape);
-        const bool any_shared = !(sh.shared_pre.empty() && sh.shared_body.empty());
-        float s_star = 0.f;
-        if (!sh.shared_pre.empty()) s_star = pre_scalar(lead, sh, sh.shared_pre[0]);
-        else if (!sh.shared_body.empty() && lead.R > 0) s_star = body_scalar(lead, sh, 0, sh.shared_body[0]);
-        uint32_t want; std::memcpy(&want, &s_star, 4);
-        auto same = [&](float v) { uint32_t u; std::memcpy(&u, &v, 4); return u == want; };
-        Family fam;
-        for (size_t q : layer) {
-            if (lead.small) break;
-            const Chain& c = chains[q];
-            bool ok = chain_n(c) == chain_n(lead);
-            for (size_t x = 0; ok && x < sh.NXP; ++x) { const float* p = post_ptr(c, sh, x); ok = p != nullptr && p == post_ptr(lead, sh, x); }
-            const size_t shift = lead.steps - c.steps;
-            for (size_t t = 0; ok && t < c.steps; ++t) { const float* p = seq_ptr(c, sh, t); ok = p != nullptr && p == seq_ptr(lead, sh, shift + t); }
-            if (ok && any_shared) {              // every scalar the shared denominators stand for carries the same bits
-                for (uint32_t sl : sh.shared_pre) ok = ok && same(pre_scalar(c, sh, sl));
-                for (size_t r = 0; ok && r < c.R; ++r) for (uint32_t sl : sh.shared_body) ok = ok && same(body_scalar(c, sh, r, sl));
-            }
-            if (!ok) continue;
-            fam.chain.push_back(q);
-            if (fam.chain.size() == 16) { families.push_back(std::move(fam)); fam = Family(); }
-        }
-        if (fam.chain.size() >= 2) families.push_back(std::move(fam));
-        }
-        i = j;
-    }
-    // (after a split at 16 the later part is a family of its own: its first chain is its longest, the others suffixes of it)
-    families.erase(std::remove_if(families.begin(), families.end(), [&](const Family& f) { return f.chain.size() < 2 || chains[f.chain[0]].small; }), families.end());
-    if (families.empty()) return;
-    // kernels: one per (shape, family size); a family whose kernel does not exist yet runs as before
-    struct Launch { std::shared_ptr<JitSlot> slot; std::vector<size_t> rows; };
-    std::vector<Launch> launches;
-    std::unordered_map<uint64_t, size_t> launch_of;
-    for (size_t f = 0; f < families.size(); ++f) {
-        const Chain& lead = chains[families[f].chain[0]];
-        const size_t K = families[f].chain.size();
-        const uint64_t lkey = ((uint64_t)lead.shape << 8) | K;
-        auto known = launch_of.find(lkey);
-        if (known == launch_of.end()) {
-            const std::string key = merge_shapes_[(size_t)lead.shape] + " chains " + std::to_string(K) + " sden 1";
-            std::shared_ptr<JitSlot>& slot = merged_kernels_[key];
-            if (!slot || (jit_mode == FMHIP_JIT_SYNC && slot->state.load(std::memory_order_acquire) == JitSlot::QUEUED)) {
-                RolledBody body = merge_shape_bodies_[(size_t)lead.shape];
-                body.chains = (uint32_t)K; body.shared_den = true;
-                std::string source = jit_generate_rolled_source(body);
-                if (source.empty()) continue;
-                jit().record(jit_describe(body));
-                slot = jit().request_source(std::move(source), 8, jit_mode == FMHIP_JIT_SYNC);
-            }
-            known = launch_of.emplace(lkey, launches.size()).first;
-            launches.push_back({ slot, {} });
-        }
-        launches[known->second].rows.push_back(f);
-    }
-    // the original of a replicated component and its copies go together or not at all: a copy left behind would have nobody to carry its
-    // order (run_plan, run_dags) — if any set is split, nothing is merged in this flush
-    std::vector<std::vector<char>> taken(groups.size()), staken(small.size());
-    for (size_t gi = 0; gi < groups.size(); ++gi) taken[gi].assign(groups[gi].size(), 0);
-    for (size_t gi = 0; gi < small.size(); ++gi) staken[gi].assign(small[gi].members.size(), 0);
-    auto mark = [&](const Chain& c) -> char& { return c.small ? staken[c.group][c.member] : taken[c.group][c.member]; };
-    for (const Launch& l : launches) {
-        if (!l.slot || l.slot->state.load(std::memory_order_acquire) != JitSlot::READY) continue;
-        for (size_t f : l.rows) for (size_t q : families[f].chain) mark(chains[q]) = 1;
-    }
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
-        const std::vector<BigDag>& g = groups[gi];
-        for (size_t mi = 0; mi < g.size(); ++mi) {
-            if (g[mi].described()) continue;
-            size_t e = mi + 1;
-            while (e < g.size() && g[e].described()) ++e;
-            for (size_t q = mi + 1; q < e; ++q) if (taken[gi][q] != taken[gi][mi]) return;
-        }
-    }
-    for (size_t gi = 0; gi < small.size(); ++gi) {
-        const std::vector<Dag>& g = small[gi].members;
-        for (size_t mi = 0; mi < g.size(); ++mi) {
-            if (g[mi].order.empty()) continue;                           // (a copy that exists as a description: vectors, outputs and scalars only)
-            size_t e = mi + 1;
-            while (e < g.size() && g[e].order.empty()) ++e;
-            for (size_t q = mi + 1; q < e; ++q) if (staken[gi][q] != staken[gi][mi]) return;
-        }
-    }
-    for (Launch& l : launches) {
-        if (!l.slot || l.slot->state.load(std::memory_order_acquire) != JitSlot::READY || l.rows.empty()) continue;
-        const Shape& sh = shape_of(chains[families[l.rows[0]].chain[0]].shape);
-        const size_t K = families[l.rows[0]].chain.size();
-        const int64_t n = chain_n(chains[families[l.rows[0]].chain[0]]);
-        auto section_words = [&](const Chain& c) { return sh.NXO + (sh.NS0 + (size_t)c.R * sh.LS + sh.NS2 + 1) / 2; };
-        size_t rw = 0;
-        for (size_t f : l.rows) {
-            size_t w = 1 + K + chains[families[f].chain[0]].steps + sh.NXP + 1;
-            for (size_t q : families[f].chain) w += section_words(chains[q]);
-            rw = std::max(rw, w);
-        }
-        const size_t max_rows = std::min((size_t)1024, ring_cap_ / (rw * 8 + 256));
-        if (max_rows == 0) continue;
-        // (rows of one launch have vectors of one length: families are looked for within a flush, whose components of a shape and length
-        // share a group; a launch over rows of another length would be a different grid)
-        std::vector<size_t> rows_n;
-        for (size_t f : l.rows) if (chain_n(chains[families[f].chain[0]]) == n) rows_n.push_back(f);
-        for (size_t off = 0; off < rows_n.size(); off += max_rows) {
-            const size_t count = std::min(max_rows, rows_n.size() - off);
-            std::vector<uint64_t> table(count * rw, 0);
-            struct Out { size_t chain; Buffer* buf; };
-            std::vector<Out> outs;
-            size_t n_ops = 0, n_vec_in = 0;
-            std::vector<fmhip_moments> all;
-            ReduceRequest every{ 0.0, nullptr, nullptr, false };
-            RedLaunch red;
-            // common rows (as run_peeled): families that read the same vectors with the same scalars — the parameter sets of a Jacobian
-            // batch at an exercise date before their bumped parameter matters — are ONE row; their chains share moments and stored values
-            std::vector<uint32_t> row_of(count);
-            std::vector<size_t> family_of_row;                           // launch row → index into rows_n (offset from `off`)
-            std::unordered_multimap<uint64_t, uint32_t> seen;
-            std::vector<uint64_t> keys;
-            std::vector<std::pair<size_t, size_t>> out_span;             // per launch row: its outs [begin, end)
-            try {
-                for (size_t r = 0; r < count; ++r) {
-                    const Family& fam = families[rows_n[off + r]];
-                    const Chain& lead = chains[fam.chain[0]];
-                    const size_t r_new = family_of_row.size();
-                    uint64_t* row = table.data() + r_new * rw;
-                    std::fill(row, row + rw, (uint64_t)0);
-                    const size_t T = lead.steps;
-                    row[0] = (uint64_t)T;
-                    for (size_t t = 0; t < T; ++t) row[1 + K + t] = (uint64_t)(uintptr_t)seq_ptr(lead, sh, t);
-                    for (size_t x = 0; x < sh.NXP; ++x) row[1 + K + T + x] = (uint64_t)(uintptr_t)post_ptr(lead, sh, x);
-                    { float s_star = 0.f; bool any = false;
-                      if (!sh.shared_pre.empty()) { any = true; s_star = pre_scalar(lead, sh, sh.shared_pre[0]); }
-                      else if (!sh.shared_body.empty() && lead.R > 0) { any = true; s_star = body_scalar(lead, sh, 0, sh.shared_body[0]); }
-                      uint32_t bits = 0; if (any) std::memcpy(&bits, &s_star, 4);
-                      row[1 + K + T + sh.NXP] = bits; }
-                    size_t at = 1 + K + T + sh.NXP + 1;
-                    for (size_t k = 0; k < K; ++k) {
-                        const Chain& c = chains[fam.chain[k]];
-                        row[1 + k] = (uint64_t)(T - c.steps) | ((uint64_t)at << 32);
-                        uint64_t* sec = row + at;
-                        float* sc = reinterpret_cast<float*>(sec + sh.NXO);
-                        for (size_t i = 0; i < sh.NS0; ++i) sc[i] = pre_scalar(c, sh, i);
-                        for (size_t it = 0; it < c.R; ++it)
-                            for (size_t m = 0; m < sh.LS; ++m) sc[sh.NS0 + it * sh.LS + m] = body_scalar(c, sh, it, m);
-                        for (size_t i = 0; i < sh.NS2; ++i) sc[sh.NS0 + (size_t)c.R * sh.LS + i] = post_scalar(c, sh, i);
-                        at += section_words(c);
-                    }
-                    if (COMMON_ROWS && count > 1) {
-                        uint64_t h = 0x9e3779b97f4a7c15ull;
-                        for (size_t w = 0; w < rw; ++w) { h = (h ^ row[w]) * 0xff51afd7ed558ccdull; h ^= h >> 31; }
-                        bool common = false;
-                        auto range = seen.equal_range(h);
-                        for (auto it = range.first; it != range.second && !common; ++it)
-                            if (std::memcmp(keys.data() + (size_t)it->second * rw, row, rw * 8) == 0) { row_of[r] = it->second; common = true; }
-                        if (common) { ++n_common_rows_; continue; }
-                        seen.emplace(h, (uint32_t)r_new);
-                        keys.insert(keys.end(), row, row + rw);
-                    }
-                    row_of[r] = (uint32_t)r_new;
-                    family_of_row.push_back(r);
-                    n_vec_in += T + sh.NXP;
-                    const size_t out_begin = outs.size();
-                    for (size_t k = 0; k < K; ++k) {
-                        const Chain& c = chains[fam.chain[k]];
-                        uint64_t* sec = row + (size_t)(row[1 + k] >> 32);
-                        for (size_t m = 0; m < sh.NXO; ++m) { Buffer* nb = new_buffer(n); outs.push_back({ fam.chain[k], nb }); sec[m] = (uint64_t)(uintptr_t)nb->ptr; }
-                        n_ops += sh.body->peel.pre.size() + (size_t)c.R * sh.P + sh.body->peel.post.size();
-                    }
-                    out_span.push_back({ out_begin, outs.size() });
-                }
-                const size_t launch_rows = family_of_row.size();
-                table.resize(launch_rows * rw);
-                const int64_t tiles = (n + FM_UNIT_ELEMS - 1) / FM_UNIT_ELEMS;
-                if (async_moments_) { every.dev_out = arena_alloc(launch_rows * K); if (!every.dev_out) { for (Out& o : outs) buffer_unref(o.buf); continue; } }
-                else { all.resize(launch_rows * K); every.host_out = all.data(); }
-                DevRolledArgs args{};
-                args.n = n; args.tiles_per_row = (uint32_t)tiles; args.row_words = (uint32_t)rw; args.iterations = 0; args.pad = (uint32_t)K;
-                args.dump = (uint64_t)(uintptr_t)dump_dev_;
-                const size_t table_bytes = table.size() * 8;
-                const size_t ring_off = ring_reserve(table_bytes);
-                std::memcpy((char*)ring_host_ + ring_off, table.data(), table_bytes);
-                hip_check(hipMemcpyAsync((char*)ring_dev_ + ring_off, (char*)ring_host_ + ring_off, table_bytes, hipMemcpyHostToDevice, stream_), "merged row table H2D");
-                const uint64_t* rows_arg = (const uint64_t*)((char*)ring_dev_ + ring_off);
-                hipEvent_t ev0 = nullptr, ev1 = nullptr;
-                if (profiling_) { hip_check(hipEventCreate(&ev0), "hipEventCreate"); hip_check(hipEventCreate(&ev1), "hipEventCreate"); hip_check(hipEventRecord(ev0, stream_), "hipEventRecord"); }
-                void* params[] = { &args, &rows_arg };
-                red_begin(red, (int)launch_rows, (int)K, (size_t)tiles, every.host_out, every.dev_out);
-                args.shift = 0.0; args.partials = (double*)red.partials; args.results = (double*)red.results; args.counters = counters_dev_;
-                args.done_flag = const_cast<uint64_t*>(red.poll_flag); args.done_value = red.done_value;
-                hip_check(hipModuleLaunchKernel(l.slot->fn_table, (unsigned)tiles, (unsigned)launch_rows, 1, FM_BLOCK, 1, 1, 0, stream_, params, nullptr), "launch merged kernel");
-                if (profiling_) { hip_check(hipEventRecord(ev1, stream_), "hipEventRecord"); profile_events_.push_back({ ev0, ev1 });
-                                  profile_tags_.push_back({ (int)(n_ops / launch_rows), (int)(n_vec_in / launch_rows), (int)(K * sh.NXO), (int)K, (int)launch_rows, 4, n }); }
-                n_launches_++; n_jit_launches_++; n_rolled_launches_++; n_merged_launches_++; n_merged_chains_ += (int64_t)(count * K);
-                n_ops_executed_ += (int64_t)n_ops;
-                algorithmic_bytes_ += 4 * n * (int64_t)(n_vec_in + outs.size());
-                bytes_written_ += 4 * n * (int64_t)outs.size();
-                every.done = true;
-                red_wait(red, (int)launch_rows, (int)K, every.host_out);
-            } catch (...) { red_release(red); for (Out& o : outs) buffer_unref(o.buf); throw; }
-            red_release(red);
-            // the chains of a family that was a common row receive the vectors its first family stored (one more reference each)
-            if (family_of_row.size() != count) {
-                const size_t n_first = outs.size();
-                for (size_t r = 0; r < count; ++r) {
-                    const size_t lr = row_of[r];
-                    if (family_of_row[lr] == r) continue;
-                    const Family& fam = families[rows_n[off + r]];
-                    size_t k = 0;
-                    for (size_t o = out_span[lr].first; o < out_span[lr].second && o < n_first; ++o, ++k) { Buffer* b = outs[o].buf; b->refs++; outs.push_back({ fam.chain[k / std::max<size_t>(1, sh.NXO)], b }); }
-                }
-            }
-            // the moments go to the chains' roots; stored values become vectors; expressions are dismantled
-            for (size_t r = 0; r < count; ++r) {
-                const Family& fam = families[rows_n[off + r]];
-                for (size_t k = 0; k < K; ++k) {
-                    Node* root = chains[fam.chain[k]].root;
-                    if (every.dev_out) arena_assign(root, (double*)every.dev_out + ((size_t)row_of[r] * K + k) * 4);
-                    else { const fmhip_moments& m = all[(size_t)row_of[r] * K + k]; root->moments[0] = m.sum; root->moments[1] = m.sumsq; root->moments[2] = m.min; root->moments[3] = m.max; root->has_moments = true; }
-                }
-            }
-            std::vector<Node*> done;
-            for (Out& o : outs) {                                       // (the one value a chain stores is its root)
-                const Chain& c = chains[o.chain];
-                if (c.small) { commit_node(c.root, o.buf); done.push_back(c.root); continue; }
-                BigDag& b = groups[c.group][c.member];
-                const size_t pos = c.plan->rolled.peeled.post_out[0];
-                if (b.described()) commit_described(b, pos, o.buf);
-                else { Node* nd = b.order[pos]; commit_node(nd, o.buf); done.push_back(nd); }
-            }
-            for (Node* nd : done) nd->refs_int++;
-            for (Node* nd : done) drop_expression(nd);
-            for (Node* nd : done) { nd->refs_int--; node_maybe_free(nd); }
-            for (size_t r = 0; r < count; ++r)
-                for (size_t q : families[rows_n[off + r]].chain) {
-                    const Chain& c = chains[q];
-                    if (sh.NXO == 0 && !c.root->buf) { c.root->discarded = true; c.root->refs_int++; drop_expression(c.root); c.root->refs_int--; }
-                    if (!c.small) { BigDag& b = groups[c.group][c.member]; if (b.described()) for (Buffer*& t : b.temp) if (t) { buffer_unref(t); t = nullptr; } }
-                    mark(c) = 2;                                        // has run
-                }
-        }
-    }
-    // what has run leaves its group (the others keep their order: the first member of a group carries the order for its copies)
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
-        std::vector<BigDag>& g = groups[gi];
-        bool any = false;
-        for (char t : taken[gi]) any |= t == 2;
-        if (!any) continue;
-        std::vector<BigDag> rest;
-        for (size_t mi = 0; mi < g.size(); ++mi) if (taken[gi][mi] != 2) rest.push_back(std::move(g[mi]));
-        g.swap(rest);
-    }
-    for (size_t gi = 0; gi < small.size(); ++gi) {
-        std::vector<Dag>& g = small[gi].members;
-        bool any = false;
-        for (char t : staken[gi]) any |= t == 2;
-        if (!any) continue;
-        std::vector<Dag> rest;
-        for (size_t mi = 0; mi < g.size(); ++mi) if (staken[gi][mi] != 2) rest.push_back(std::move(g[mi]));
-        g.swap(rest);
-    }
-}
 
 void Engine::run_big_group(std::vector<BigDag>& group, ReduceRequest* rr) {
     HostTimer timer(HostProfile::RUN_BIG);
@@ -3694,7 +2692,7 @@ void Engine::reduce(fmhip_vec h, double shift, fmhip_moments* host_out, void* de
     // components of equal shape as rows of the same launches, and those launches take the moments of their roots along.  The other
     // products' getAverage() calls are answered from what is left with their nodes; the moments are those of the stand-alone
     // reduction to the last bit (one reduction tree per vector: fm_kernel_parts.hpp).
-    static const size_t BATCH_PENDING = [] { const char* e = std::getenv("FMHIP_BATCH_EXPECTATIONS"); return e ? (size_t)std::atoll(e) : (size_t)256; }();   // 0 = off
+    static const size_t BATCH_PENDING = knob_size("FMHIP_BATCH_EXPECTATIONS", (size_t)256);   // 0 = off
     if (BATCH_PENDING && fusion && fusion_hold != 1 && !nd->buf && shift == 0.0 && host_out && !dev_out && n_pending_ >= BATCH_PENDING && n_pending_ >= 4 * (size_t)std::max(1, nd->weight)) {
         struct Want { bool& w; ~Want() { w = false; } } want{ want_root_moments_ };
         want_root_moments_ = true;
@@ -3753,7 +2751,7 @@ int64_t Engine::reduce_batch_begin(const fmhip_vec* hs, int count, const double*
     // anyway, results into slots of the pinned arena) — no reduction launch, the vectors are not read again.  The ticket remembers the
     // slots; ending it waits for them.  (Vectors computed already, shifts, or a component whose launches cannot take moments: the
     // reduction launch below.)
-    static const bool FROM_LAUNCHES = [] { const char* e = std::getenv("FMHIP_MOMENTS_FROM_LAUNCHES"); return !(e && e[0] == '0'); }();
+    static const bool FROM_LAUNCHES = knob_on("FMHIP_MOMENTS_FROM_LAUNCHES");
     bool unshifted = true;
     for (int i = 0; shifts && i < count; ++i) unshifted &= shifts[i] == 0.0;
     if (FROM_LAUNCHES && fusion && unshifted && hs) return reduce_batch_begin_from_launches(hs, count);
@@ -3786,7 +2784,7 @@ int64_t Engine::reduce_batch_begin(const fmhip_vec* hs, int count, const double*
 void Engine::give_up_values(const fmhip_vec* hs, int count) {
     require_init();
     if (count <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "count must be positive");
-    static const bool DISCARD = [] { const char* e = std::getenv("FMHIP_DISCARD_VALUES"); return !(e && e[0] == '0'); }();      // =0: every value is stored (A/B measurement)
+    static const bool DISCARD = knob_on("FMHIP_DISCARD_VALUES");      // =0: every value is stored (A/B measurement)
     std::vector<Node*> nds((size_t)count);
     for (int i = 0; i < count; ++i) nds[(size_t)i] = node(hs[i]);
     if (!DISCARD) return;
@@ -3893,7 +2891,7 @@ void Engine::reduce_batch_device_from_launches(const fmhip_vec* hs, int count, v
 void Engine::reduce_batch_device(const fmhip_vec* hs, int count, const double* shifts, void* dev_out) {
     require_init();
     if (count <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "count must be positive");
-    static const bool FROM_LAUNCHES = [] { const char* e = std::getenv("FMHIP_MOMENTS_FROM_LAUNCHES"); return !(e && e[0] == '0'); }();
+    static const bool FROM_LAUNCHES = knob_on("FMHIP_MOMENTS_FROM_LAUNCHES");
     bool unshifted = true;
     for (int i = 0; shifts && i < count; ++i) unshifted &= shifts[i] == 0.0;
     bool worth = false;                                          // something is pending, given up, or has its moments already
@@ -4231,6 +3229,8 @@ void Engine::profile_read(double* ms_total, int64_t* n) {
 
 } // namespace fm
 
+#include "loop_engine.hpp"             // Engine::detect_loop, plan_peel, plan_loop, run_rolled, run_peeled: the periodic stretch of a component as one launch
+#include "merged_chains_engine.hpp"    // Engine::match_small, merge_shape_index, merge_families: components of one loop shape over the same vectors as one launch
 #include "side_pass_engine.hpp"        // Engine::pass_*: the frame the reducing passes below stand in
 #include "order_stats_engine.hpp"      // Engine::os_*: the order-statistics passes
 #include "cross_moments_engine.hpp"    // Engine::xmom_pass: the cross moments of a regression in one launch

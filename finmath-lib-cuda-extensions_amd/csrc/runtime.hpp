@@ -547,7 +547,7 @@ private:
         bool segs_missing = false;  // the shape has only run as ONE launch of its peeled kernel so far: `segs` is cut when that launch is not available (run_plan)
         bool discards_root = false; // the component's root is wanted for its moments only (Node::discard): the peeled kernels of this plan do not store it
         // A periodic stretch of the scheduled order — the same few operations over one component after another, each iteration
-        // feeding the next (a running sum) — as ONE launch of a kernel that loops over the iterations (runtime.cpp: rolled loops).
+        // feeding the next (a running sum) — as ONE launch of a kernel that loops over the iterations (loop_engine.hpp).
         // Positions are offsets inside one iteration; the loop covers order[begin + r·period + q], r < iterations.
         struct Rolled {
             bool present = false;
@@ -662,6 +662,22 @@ private:
     void run_plan(BigPlan& plan, std::vector<BigDag>& group, ReduceRequest* rr = nullptr);
     Node* single_root(const BigDag& b, const BigDag& g0);
     void commit_described(BigDag& big, size_t pos, Buffer* b);
+    // What a launch has stored: position `pos` of a member's order (a member without nodes keeps it as a description's value), or, big ==
+    // nullptr, the value of `node`.  commit_stored: all of them become materialised vectors, then their expressions (and whatever only
+    // those held) are dismantled, every output kept alive until the last one has been.
+    struct Stored { BigDag* big; size_t pos; Node* node; Buffer* buf; };
+    void commit_stored(const std::vector<Stored>& outs);
+    void give_up_value(Node* r);                                  // moments taken, value not stored: no root of later flushes, its expression is let go
+    struct TempGuard;                                             // whatever happens, the values held for members without nodes go back to the pool
+    struct OperandTable;                                          // of a component: node → position, and every operation's operands by position
+    // a kernel of the specialised tier on demand (source(): its text, made only when it is asked for; empty: there is none): is it there?
+    template <class Source> bool kernel_ready(std::shared_ptr<JitSlot>& slot, Source&& source, int elems);
+    // the launches of the loop kernels (loop_engine.hpp): one row-table launch, the rows that are computed once, who else receives what they store
+    struct RowLaunch;
+    void launch_row_table(const RowLaunch& l, const std::vector<uint64_t>& table);
+    struct CommonRows;
+    template <class Retarget> static void share_common_rows(std::vector<Stored>& outs, const std::vector<std::pair<size_t, size_t>>& span, const std::vector<uint32_t>& row_of,
+                                                            const std::vector<size_t>& first_of_row, Retarget&& retarget);
     bool detect_loop(const BigDag& g, const std::vector<std::array<int32_t, 3>>& operand, BigPlan::Rolled& out, std::string* source, int* elems, RolledBody* body_out = nullptr);
     void run_rolled(const BigPlan::Rolled& ro, std::vector<BigDag>& group, size_t first, size_t count);
     bool plan_peel(const BigDag& g, const std::vector<std::array<int32_t, 3>>& operand, BigPlan::Rolled& ro, const RolledBody& body);
@@ -682,6 +698,15 @@ private:
     struct SmallMatch { bool ok = false; int shape = -1; uint32_t R = 0; std::vector<uint16_t> seq_leaf, post_leaf; };
     struct SmallGroup;
     void merge_families(std::vector<std::vector<BigDag>>& groups, std::vector<SmallGroup>& small);
+    struct MergeContext;                                          // what the parts of merge_families share (merged_chains_engine.hpp)
+    void merge_collect_large(MergeContext& mc);
+    void merge_collect_small(MergeContext& mc);
+    void merge_form_families(MergeContext& mc);
+    void merge_request_kernels(MergeContext& mc);
+    bool merge_mark_whole_sets(MergeContext& mc);
+    void merge_run_launch(MergeContext& mc, size_t launch);
+    void merge_run_batch(MergeContext& mc, size_t launch, const std::vector<size_t>& batch, size_t rw);
+    void merge_remove_run(MergeContext& mc);
     const SmallMatch* match_small(const Dag& d);
     int merge_shape_index(const std::string& desc);
     std::vector<std::string> merge_shapes_;                                          // descriptions (desc_red) of the mergeable loop shapes met so far …

@@ -1,13 +1,13 @@
 """Catalogue of loop shapes, shared by tests/test_gpu_loop_shapes.py: recurrences whose pending graph is periodic, each chosen to
 drive one path of the loop-kernel generator (csrc/jit.cpp: jit_generate_rolled_source, jit_generate_merged_source) or one condition of
-the detector (csrc/runtime.cpp: Engine::detect_loop, plan_peel, merge_families).
+the detector (csrc/loop_engine.hpp: Engine::detect_loop, plan_peel; csrc/merged_chains_engine.hpp: merge_families).
 
 A shape is a PAIR of functions over the same data — `device(d)` records the recurrence on DeviceVectors with v1s0 … v3s0, `oracle(o, d)`
 restates it with oracle.f_v* — and, next to them, the description the engine is meant to make of it (`expect`): what one line of
 FMHIP_JIT_RECORD says (jit.cpp: jit_describe).  Both functions return {name: vector} of everything that keeps a handle; whatever else
 they compute is dropped, as a caller drops its temporaries — which values keep a handle decides what a loop stores.
 
-What the detector does with handles (runtime.cpp, detect_loop: out_needed / final_needed), since the shapes are built around it:
+What the detector does with handles (loop_engine.hpp, detect_loop: out_needed / final_needed), since the shapes are built around it:
   * a value with a handle, or read later than the next iteration, is an OUTPUT of its position: stored in every iteration;
   * a FINAL value is one of the last iteration that only the operations BEHIND the loop read; with a handle of its own it would be an
     output — so the engine never asks a peeled kernel to store a final value (Peel::final_store is 0 in every description it makes);
@@ -432,7 +432,7 @@ _scal48, _scal49 = _long_body(47, 0), _long_body(48, 0)          # (+ the FLOOR_
 _per128, _per129 = _long_body(40, 86), _long_body(40, 87)        # (+ ADD and FLOOR_S: periods 128 and 129)
 _per12 = _long_body(5, 5)                                        # period 12
 
-# runtime.cpp, detect_loop: `if (G > 8 || CI > 12 || CO > 12 || LI > 12 || LO > 12 || LO + CO == 0 || LS > 48) return false;`, MAX_PERIOD = 128,
+# loop_engine.hpp, detect_loop: `if (G > 8 || CI > 12 || CO > 12 || LI > 12 || LO > 12 || LO + CO == 0 || LS > 48) return false;`, MAX_PERIOD = 128,
 # `if (n < 48) return false;`, MIN_ITERATIONS = 5 (`R < MIN_ITERATIONS - 1`: the loop itself starts at the SECOND periodic iteration).
 # For the period-12 body none of these decides: with one stored value an iteration a component of up to 8 iterations (96 operations, 9 input
 # and 8 output vectors) still fits ONE ordinary launch (fm_program.h: FM_MAX_OPS = 128, FM_MAX_OUT = 8) and is never handed to the detector;
@@ -454,7 +454,7 @@ LIMITS_OUTSIDE = [
 ]
 
 # ------------------------------------------------------------------------------------------------ merged families
-# (runtime.cpp: merge_families) products of ONE exercise date: each reads a suffix of the date's vectors.  `kind`:
+# (merged_chains_engine.hpp: merge_families) products of ONE exercise date: each reads a suffix of the date's vectors.  `kind`:
 #   "swaption"     test_gpu_merged_chains.py: swaption / swaption_oracle, every DISCOUNT with that module's PERIOD;
 #   "other_period" the same induction discounting with another period — its shared scalar differs from the family's: left out of it;
 #   "no_discount"  value = (value + payoff)·L[p]: a shape without shared scalars.

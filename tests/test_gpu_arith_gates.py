@@ -314,7 +314,7 @@ def test_peeled_loop_with_planted_elements(gpu):
 def test_merged_chains_with_a_shared_denominator(gpu, oracle):
     """tests/test_gpu_merged_chains.py's swaptions of one exercise date: the chains of a merged launch discount by the same rate, so the
     denominator is prepared once (div_prepare_discount / ueval_div_prepared: every merged launch is generated with the shared denominator,
-    runtime.cpp: merge_families, and tests/test_jit_source_cpu.py pins that such a source divides through ueval_div_prepared).  A numerator that leaves the range in ONE chain only (its
+    merged_chains_engine.hpp: merge_families, and tests/test_jit_source_cpu.py pins that such a source divides through ueval_div_prepared).  A numerator that leaves the range in ONE chain only (its
     first payoff is zero), denominators that leave it for all chains (zero, 2^49)."""
     n, dates, tenors = 8197, (60, 60), (60, 40, 30, 20, 14, 12)
     prods = [(d, periods, 0.01 + 0.002 * k + 0.0005 * d) for d in range(len(dates)) for k, periods in enumerate(tenors)]

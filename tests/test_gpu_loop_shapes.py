@@ -1,4 +1,4 @@
-"""The rolled, peeled and merged loop kernels (runtime.cpp: detect_loop, plan_peel, merge_families; jit.cpp: jit_generate_rolled_source,
+"""The rolled, peeled and merged loop kernels (loop_engine.hpp: detect_loop, plan_peel; merged_chains_engine.hpp: merge_families; jit.cpp: jit_generate_rolled_source,
 jit_generate_merged_source) over the catalogue of tests/loop_shapes.py: every operand form and limit of the generator, bit for bit
 against the oracle, in the three modes the other loop tests use — the segmented launches of the interpreter tier, the run that meets the
 shape with the specialised tier on, and the run after it — with the engine's own counter as the proof of which kernel ran, and the

@@ -1,4 +1,4 @@
-"""Merged chains (runtime.cpp: merge_families; jit.cpp: jit_generate_merged_source): components of ONE loop shape whose vectors are the
+"""Merged chains (merged_chains_engine.hpp: merge_families; jit.cpp: jit_generate_merged_source): components of ONE loop shape whose vectors are the
 same sequence — the shorter ones reading a suffix of the longest one's, as the swaptions of one exercise date read the forward rates of
 their tenor (SwaptionSimple's backward induction: LIBORMarketModelCalibrationATMTest.java:475-520 builds 14 tenors per exercise date) —
 run as ONE launch that loads every vector once.  Per chain it is the same operations on the same operands in the same order and the
@@ -138,7 +138,7 @@ def test_chains_that_do_not_share_their_vectors_are_left_alone(gpu, oracle):
 def test_common_rows_are_computed_once_and_share_their_vectors(gpu, oracle, with_moments):
     """Rows of a batched launch that read the SAME vectors with the SAME scalars — the bumped parameter sets of a finite-difference
     Jacobian before the time step at which their bump first matters (LIBORMarketModelCalibrationATMTest.java:314-340: one re-simulation
-    per parameter) — are computed once (runtime.cpp: run_peeled / merge_families, common rows); the other members receive the same
+    per parameter) — are computed once (loop_engine.hpp: run_peeled; merged_chains_engine.hpp: merge_families, common rows); the other members receive the same
     vectors.  Storage that is shared is copied before anybody writes into it in place (make_private): the two doors through which a
     vector can be written, fmhip_program_run_into and a raw device pointer, leave the other holders' values alone."""
     n = 20011

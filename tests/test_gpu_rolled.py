@@ -1,4 +1,4 @@
-"""Rolled loops (runtime.cpp): a periodic stretch of a large pending graph — the same operations over one vector after
+"""Rolled loops (loop_engine.hpp): a periodic stretch of a large pending graph — the same operations over one vector after
 another, each iteration feeding the next — runs as ONE launch of a kernel that loops over the iterations, once that kernel is
 compiled; until then (and with the JIT tier off) the segmented launches run.  Both forms must give the same bits, which must
 be the oracle's."""
@@ -128,7 +128,7 @@ def swaption_like_chain(x_of, periods, numeraire, strike, delta):
 
 
 def test_head_loop_and_tail_in_one_launch(gpu, oracle):
-    """The PEELED form of a rolled component (runtime.cpp: plan_peel; jit.hpp: RolledBody::Peel): when the operations in front of the
+    """The PEELED form of a rolled component (loop_engine.hpp: plan_peel; jit.hpp: RolledBody::Peel): when the operations in front of the
     loop and behind it are few, a launch of few workgroups runs the whole component — head, loop, tail — as ONE kernel; the values
     between the parts stay in registers.  Same bits as the segmented launches (interpreter tier) and as the oracle."""
     n, periods = 50_021, 40
