@@ -24,6 +24,8 @@ from .regression import MonteCarloConditionalExpectationRegression, covariance_m
 from .regression import MonteCarloConditionalExpectationLocalizedRegression, binned_cross_moments, binned_evaluate, quantile_bounds
 from .regression import MonteCarloConditionalExpectationPolynomialRegression, polynomial_cross_moments, polynomial_evaluate
 from .sorting import argsort, rank_scores, read_elements, sort_by_key, sorted_quantiles, spearman_matrix
+from .prefix import cumulative_sums, expected_shortfall_curve, prefix_search, prefix_sums_at, prefix_sums_host, running_average
+from .prefix import weighted_expected_shortfall, weighted_quantiles
 from .differentiable import RandomVariableDifferentiableAAD, RandomVariableDifferentiableAADFactory
 
 

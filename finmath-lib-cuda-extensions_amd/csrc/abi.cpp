@@ -855,6 +855,30 @@ int fmhip_vec_read_elements(fmhip_vec v, const int64_t* positions, int count, do
     return guarded([&] { Engine::get().read_elements(v, positions, count, out); });
 }
 
+// ---------------------------------------------------------------- prefix sums (prefix_engine.hpp)
+int fmhip_prefix_sums_host(const float* v, int64_t n, double* prefix_out) {
+    return host_only([&] { fm::prefix_sums_host_checked(v, n, prefix_out); });
+}
+int fmhip_prefix_sums(fmhip_vec v, int mode, fmhip_vec* out, double* total_out) {
+    FRONT(prefix_sums(v, mode, out, total_out));
+    if (te::active()) {
+        const int rc = host_only([&] { fm::prefix_check_sums(v, mode, out); });
+        if (rc != FMHIP_OK) return rc;
+        TE_LOCAL(&v, 1, L, fmhip_prefix_sums(L[0], mode, out, total_out));
+    }
+    return guarded([&] { const fmhip_vec r = Engine::get().prefix_sums(v, mode, out, total_out); *out = r; });
+}
+int fmhip_prefix_sums_at(fmhip_vec v, const int64_t* positions, int count, double* sums_out) {
+    FRONT(prefix_sums_at(v, positions, count, sums_out));
+    TE_OWNER(v, fmhip_prefix_sums_at(v, positions, count, sums_out));
+    return guarded([&] { Engine::get().prefix_sums_at(v, positions, count, sums_out); });
+}
+int fmhip_prefix_search(fmhip_vec v, const double* thresholds, int count, int relative, int64_t* positions_out, double* sums_out, double* total_out) {
+    FRONT(prefix_search(v, thresholds, count, relative, positions_out, sums_out, total_out));
+    TE_OWNER(v, fmhip_prefix_search(v, thresholds, count, relative, positions_out, sums_out, total_out));
+    return guarded([&] { Engine::get().prefix_search(v, thresholds, count, relative, positions_out, sums_out, total_out); });
+}
+
 // The one call of a caller that values product after product: the engine lock is held for the bookkeeping (graph → launch → commit),
 // NOT while the device computes — other threads record and launch meanwhile.  The moments arrive in a slot of pinned memory of their
 // own; this thread polls its flag, then takes the lock again to copy them out and give the launch's buffers back.

@@ -3240,3 +3240,4 @@ void Engine::profile_read(double* ms_total, int64_t* n) {
 #include "xmom_wide_engine.hpp"        // Engine::xmom_wide_pass: the cross moments of up to 64 vectors in one launch on the matrix cores
 #include "xmom_poly_engine.hpp"        // Engine::xmom_poly_pass, poly_eval: the same for a polynomial basis formed in registers, the fitted polynomial
 #include "sort_engine.hpp"             // Engine::sort_by_key, argsort, rank_scores, read_elements: a stable radix sort of (key, path) pairs and what is made of its permutation
+#include "prefix_engine.hpp"           // Engine::prefix_sums, prefix_sums_at, prefix_search: fp64 prefix sums in a tree that is a function of n alone

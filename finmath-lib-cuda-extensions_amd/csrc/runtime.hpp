@@ -404,6 +404,14 @@ public:
     fmhip_vec rank_scores(fmhip_vec key, const fmhip_vec* out_checked);
     void read_elements(fmhip_vec v, const int64_t* positions, int count, double* out);
 
+    // prefix sums (prefix_engine.hpp): P[r] = the fp64 sum of (double)v[0..r] in the nested tree of prefix_host.hpp, a function
+    // of n and r alone — every prefix (or every running mean) rounded to fp32 as a new, materialised vector; the prefixes at a few positions;
+    // the first position whose prefix reaches a threshold.  Arguments are checked before anything is flushed or launched; one engine's sample
+    // only (UNSUPPORTED with a communicator).
+    fmhip_vec prefix_sums(fmhip_vec v, int mode, const fmhip_vec* out_checked, double* total_out);
+    void prefix_sums_at(fmhip_vec v, const int64_t* positions, int count, double* sums_out);
+    void prefix_search(fmhip_vec v, const double* thresholds, int count, int relative, int64_t* positions_out, double* sums_out, double* total_out);
+
     // programs
     fmhip_program program_create(const fmhip_prog_op* ops, int n_ops, int n_in, const int32_t* outs, int n_out,
                                  const int32_t* reds, int n_red);
@@ -498,6 +506,8 @@ private:
     struct SortBuffers;
     int64_t sort_size(const fmhip_vec* hs, int count, const char* what);
     hipError_t sort_enqueue(uint64_t key_ptr, int64_t n, const SortBuffers& s);
+    int64_t prefix_size(fmhip_vec v, const char* what);
+    void prefix_query_pass(fmhip_vec v, const int64_t* positions, const double* thresholds, int count, int relative, int64_t* positions_out, double* sums_out, double* total_out, const char* what);
     void pass_prepare(const fmhip_vec* hs, int count, PassHold& hold, const char* what);
     void pass_scratch(size_t zero_bytes, size_t other_bytes);
     template <class Launch> void pass_launch(volatile uint64_t* flag, uint64_t*& done_flag, uint64_t& done_value, const char* what, Launch launch);
@@ -779,6 +789,11 @@ void sobol_points_host(int n_dims, int64_t first_index, int64_t count, int32_t s
 void sort_check_by_key(fmhip_vec key, const fmhip_vec* values, int n_values, const fmhip_vec* sorted_key_out, const fmhip_vec* sorted_values_out);
 void sort_check_read_elements(fmhip_vec v, const int64_t* positions, int count, const double* out);
 void sort_argsort_host_checked(const float* key, int64_t n, int64_t* permutation_out);
+// the same for fmhip_prefix_sums / fmhip_prefix_sums_at / fmhip_prefix_search, and the definition of the prefix sums (prefix_engine.hpp,
+// prefix_host.hpp): all throw FMHIP_ERR_INVALID_ARGUMENT
+void prefix_check_sums(fmhip_vec v, int mode, const fmhip_vec* out);
+void prefix_check_queries(fmhip_vec v, const void* queries, int count, const void* sums_out, const char* what);
+void prefix_sums_host_checked(const float* v, int64_t n, double* prefix_out);
 // what can be said about the arguments of fmhip_binned_cross_moments / fmhip_binned_evaluate without looking at a vector (binned_engine.hpp; the
 // rules are fmhost::binnedCheck*'s, host/binned_regression.hpp), and the host definitions: all throw FMHIP_ERR_INVALID_ARGUMENT
 void binned_check_moments(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, const int64_t* counts_out, const double* sums_out);

@@ -937,6 +937,43 @@ int vec_read_elements(fmhip_vec v, const int64_t* positions, int count, double* 
     });
 }
 
+// Prefix sums (prefix_engine.hpp).  The prefixes of a sample that is spread over several shards need a carry between them, which is not
+// built: a list of more than one shard answers FMHIP_ERR_UNSUPPORTED, never the prefix sums of a part.  A list of ONE shard is that
+// shard's call.
+static void prefix_one_shard(Shards& s, const char* what) {
+    if (s.D() > 1) throw Error(FMHIP_ERR_UNSUPPORTED, std::string(what) + " with a device list of " + std::to_string(s.D()) + " shards: a carry between the shards is not built");
+}
+int prefix_sums(fmhip_vec v, int mode, fmhip_vec* out, double* total_out) {
+    return fronted([&](Shards& s) {
+        prefix_check_sums(v, mode, out);
+        const int64_t n = front_size(s, &v, 1, "prefix sums", false);
+        prefix_one_shard(s, "prefix sums");
+        const fmhip_vec id = s.fresh(n);
+        s.post([&](Worker& w) { fmhip_vec h = 0; if (w.ok(fmhip_prefix_sums(w.at(v), mode, &h, total_out))) w.bind(id, h); });
+        try { s.wait(); } catch (...) { s.meta.erase(id); throw; }
+        *out = id;
+    });
+}
+int prefix_sums_at(fmhip_vec v, const int64_t* positions, int count, double* sums_out) {
+    return fronted([&](Shards& s) {
+        prefix_check_queries(v, positions, count, sums_out, "prefix sums at");
+        front_size(s, &v, 1, "prefix sums at", false);
+        prefix_one_shard(s, "prefix sums at");
+        s.post([&](Worker& w) { w.ok(fmhip_prefix_sums_at(w.at(v), positions, count, sums_out)); });
+        s.wait();
+    });
+}
+int prefix_search(fmhip_vec v, const double* thresholds, int count, int relative, int64_t* positions_out, double* sums_out, double* total_out) {
+    return fronted([&](Shards& s) {
+        prefix_check_queries(v, thresholds, count, sums_out, "prefix search");
+        need(positions_out, "positions_out");
+        front_size(s, &v, 1, "prefix search", false);
+        prefix_one_shard(s, "prefix search");
+        s.post([&](Worker& w) { w.ok(fmhip_prefix_search(w.at(v), thresholds, count, relative, positions_out, sums_out, total_out)); });
+        s.wait();
+    });
+}
+
 int vec_give_up_values(const fmhip_vec* vectors, int count) {
     return fronted([&](Shards& s) {
         need(vectors, "vectors");

@@ -427,6 +427,38 @@ int fmhip_argsort_host(const float* key, int64_t n, int64_t* permutation_out);
 int fmhip_rank_scores(fmhip_vec key, fmhip_vec* out);
 int fmhip_vec_read_elements(fmhip_vec v, const int64_t* positions, int count, double* out);
 
+/* Prefix sums on the device: the running sum along the sample without the vector leaving the device — the cumulative
+ * weight behind a weighted quantile or a weighted expected shortfall, the expected-shortfall curve of a sorted loss vector, the running
+ * average of an estimator against the number of paths.
+ * P[r] is the fp64 sum of (double)v[0..r] in ONE association, a function of n and r alone (csrc/prefix_host.hpp): nested units — a lane's 8
+ *   elements, the 8 lanes of a group, the 8 groups of a wave, the 4 waves of a tile, the tiles of a chunk, the chunks — in each of which the
+ *   first subunit takes no base (it is not added to 0: a leading -0.0 stays -0.0) and every prefix of subunit j is fl(base + prefix inside),
+ *   the base being the last prefix of subunit j - 1.  The device's P[r] EQUALS fmhip_prefix_sums_host's bit for bit in all three calls (of a
+ *   NaN only that it is one).  For input without negative elements or NaNs P is non-decreasing.
+ *   |P[r] - exact| <= (prefix_chain(n) + 1) * 2^-53 * sum_{i<=r} |v[i]|.
+ * fmhip_prefix_sums: *out = a new, materialised vector of v's size n (1 ... 2^31 - 1): out[r] = (float)P[r], or with FMHIP_PREFIX_MEAN
+ *   (float)(P[r] / (double)(r + 1)), the quotient the correctly rounded fp64 one.  total_out may be NULL and receives P[n-1].
+ * fmhip_prefix_sums_at: sums_out[j] = P[positions[j]] in fp64 for count = 1 ... 4096 positions in [0, n), in any order, repeats allowed.  The
+ *   vector is read once (and one chunk of it again per position); no output vector is written.
+ * fmhip_prefix_search: positions_out[j] = the smallest r with P[r] >= t_j and sums_out[j] = that P[r]; if no r qualifies, n and P[n-1].
+ *   t_j = thresholds[j], or fl(thresholds[j] * P[n-1]) in fp64 when relative != 0; count = 1 ... 4096.  A NaN prefix never qualifies and a NaN
+ *   threshold finds nothing.  Defined for signed input too (P need not be monotone: the FIRST crossing is found).  total_out may be NULL
+ *   and receives P[n-1].
+ * fmhip_prefix_sums_host: the DEFINITION over a host float array: prefix_out[r] = P[r]; needs no device.
+ * Everything is checked on the host before anything is flushed or launched, with the status codes of the other passes: a mode that is
+ * neither, count outside 1 ... 4096, a NULL pointer, a handle of 0, a position outside [0, n), n == 0 or n > 2^31 - 1 ->
+ * FMHIP_ERR_INVALID_ARGUMENT; FMHIP_ERR_SIZE_MISMATCH; FMHIP_ERR_INVALID_HANDLE.  A vector whose values were given up is the error a read of
+ * it is.  A build without the kernels answers FMHIP_ERR_UNSUPPORTED; it never falls back.
+ * ONE sample on ONE device: a carry between devices is not built.  With a device list of more than one shard, and with an expectation
+ * communicator of more than one rank, the three device calls answer FMHIP_ERR_UNSUPPORTED (never the prefix sums of a part). */
+#define FMHIP_PREFIX_SUM  0   /* out[r] = (float)P[r]                         */
+#define FMHIP_PREFIX_MEAN 1   /* out[r] = (float)(P[r] / (double)(r + 1))     */
+int fmhip_prefix_sums(fmhip_vec v, int mode, fmhip_vec* out, double* total_out);
+int fmhip_prefix_sums_at(fmhip_vec v, const int64_t* positions, int count, double* sums_out);
+int fmhip_prefix_search(fmhip_vec v, const double* thresholds, int count, int relative,
+                        int64_t* positions_out, double* sums_out, double* total_out);
+int fmhip_prefix_sums_host(const float* v, int64_t n, double* prefix_out);   /* the DEFINITION */
+
 /* Polynomial regression in one pass: the normal equations of a regression on a POLYNOMIAL basis — the Longstaff-Schwartz
  * basis of a product on several underlyings — from the state vectors alone, and the fitted polynomial as a new vector.  The monomials are
  * never in memory: the moments kernel forms them in registers as the operands of fmhip_cross_moments_wide's pass.

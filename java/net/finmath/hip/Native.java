@@ -101,6 +101,15 @@ final class Native {
 	static native int rankScores(long key, long[] out);
 	/** out[j] = (double) v[positions[j]]; every position in [0, size). */
 	static native int vecReadElements(long v, long[] positions, double[] out);
+	// ---- prefix sums on the device: P[r] = the fp64 sum of v[0..r] in a tree that is a function of the size alone; non-decreasing for input without negative elements
+	/** out[0] = a new vector: (float) P[r], or with mode 1 (float) (P[r] / (r + 1)); totalOutOrNull[0] = P[size - 1]. */
+	static native int prefixSums(long v, int mode, long[] out, double[] totalOutOrNull);
+	/** sumsOut[j] = P[positions[j]]; 1 ... 4096 positions in [0, size). */
+	static native int prefixSumsAt(long v, long[] positions, double[] sumsOut);
+	/** positionsOut[j] = the smallest r with P[r] >= thresholds[j] (times P[size - 1] when relative), sumsOut[j] = that P[r]; size and P[size - 1] if there is none. */
+	static native int prefixSearch(long v, double[] thresholds, boolean relative, long[] positionsOut, double[] sumsOut, double[] totalOutOrNull);
+	/** The definition of the prefix sums over a host array. */
+	static native int prefixSumsHost(float[] v, double[] prefixOut);
 	// ---- polynomial regression in one pass: the normal equations of a polynomial basis from the state vectors, the monomials formed in registers
 	/** crossMomentsWide for the regressors [monomials of states..., extraX...] and the dependents y; exponents holds states.length ints (0 ... 6) per monomial, a row of zeros is the constant 1; a handle of 0 in extraX is the constant 1.  Bit for bit the sums of crossMomentsWide on the materialised monomials. */
 	static native int polynomialCrossMoments(long[] states, int[] exponents, long[] extraX, long[] y, double[] sumsOut);

@@ -282,6 +282,36 @@ FMJ(jint, vecReadElements)(JNIEnv* env, jclass, jlong v, jlongArray positions, j
     if (!pp.p || !po.p || po.length() < pp.length()) return FMHIP_ERR_INVALID_ARGUMENT;
     return fmhip_vec_read_elements(v, (const int64_t*)pp.p, (int)pp.length(), po.p);
 }
+// ---------------------------------------------------------------- prefix sums on the device
+FMJ(jint, prefixSums)(JNIEnv* env, jclass, jlong v, jint mode, jlongArray out, jdoubleArray totalOutOrNull) {
+    if (!out || env->GetArrayLength(out) < 1 || (totalOutOrNull && env->GetArrayLength(totalOutOrNull) < 1)) return FMHIP_ERR_INVALID_ARGUMENT;
+    fmhip_vec h = 0; double total = 0.0;
+    const int st = fmhip_prefix_sums(v, (int)mode, &h, &total);
+    if (st == FMHIP_OK) { set1(env, out, (jlong)h); if (totalOutOrNull) env->SetDoubleArrayRegion(totalOutOrNull, 0, 1, &total); }
+    return st;
+}
+FMJ(jint, prefixSumsAt)(JNIEnv* env, jclass, jlong v, jlongArray positions, jdoubleArray sumsOut) {
+    Pin<jlong> pp(env, positions, JNI_ABORT); Pin<jdouble> po(env, sumsOut);
+    if (!pp.p || !po.p || po.length() < pp.length()) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_prefix_sums_at(v, (const int64_t*)pp.p, (int)pp.length(), po.p);
+}
+FMJ(jint, prefixSearch)(JNIEnv* env, jclass, jlong v, jdoubleArray thresholds, jboolean relative, jlongArray positionsOut, jdoubleArray sumsOut, jdoubleArray totalOutOrNull) {
+    if (totalOutOrNull && env->GetArrayLength(totalOutOrNull) < 1) return FMHIP_ERR_INVALID_ARGUMENT;
+    double total = 0.0;
+    int st;
+    {
+        Pin<jdouble> pt(env, thresholds, JNI_ABORT); Pin<jlong> pp(env, positionsOut); Pin<jdouble> ps(env, sumsOut);
+        if (!pt.p || !pp.p || !ps.p || pp.length() < pt.length() || ps.length() < pt.length()) return FMHIP_ERR_INVALID_ARGUMENT;
+        st = fmhip_prefix_search(v, pt.p, (int)pt.length(), relative ? 1 : 0, (int64_t*)pp.p, ps.p, &total);
+    }
+    if (st == FMHIP_OK && totalOutOrNull) env->SetDoubleArrayRegion(totalOutOrNull, 0, 1, &total);
+    return st;
+}
+FMJ(jint, prefixSumsHost)(JNIEnv* env, jclass, jfloatArray v, jdoubleArray prefixOut) {
+    Pin<jfloat> pv(env, v, JNI_ABORT); Pin<jdouble> po(env, prefixOut);
+    if (!pv.p || !po.p || po.length() < pv.length()) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_prefix_sums_host(pv.p, pv.length(), po.p);
+}
 // ---------------------------------------------------------------- polynomial regression in one pass: the monomials of the states are formed in registers
 // exponents: states.length (nStates) entries per term, each 0 … 6, as ints; anything outside a byte is refused here, the rest by the library
 static bool poly_exponents(const jint* e, int64_t count, std::vector<uint8_t>& out) {
