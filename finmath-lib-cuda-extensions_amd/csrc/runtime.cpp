@@ -982,54 +982,6 @@ void Engine::launch(Program* p, int64_t n, const std::vector<RowSpec>& rows, fmh
     red_release(red);
 }
 
-// The buffers a launch with fused reductions needs, and where its moments go.  Results wanted on the host only: the last workgroup of
-// a row stores its 32 bytes straight into the pinned staging buffer (host memory is mapped into the device's address space) — no
-// device-to-host copy command between the kernel and the wait (a `chain.getAverage()` through the C++ mirror at 100 / 5 000 paths:
-// 19.6 → 17.7 / 22.9 → 21.2 µs, benchmarks/small_n_latency.cpp).  One row, results wanted on the host: the kernel raises a flag in
-// pinned memory behind the results and the host POLLS it instead of synchronising the stream.  A caller that values one product after
-// the other (finmath-lib's calibration: 144 getAverage() per objective evaluation) pays the wake-up of hipStreamSynchronize and,
-// measured, a launch that takes 20–25 µs instead of 5 right after it, once per product.
-double* Engine::arena_alloc(size_t count)
-{
-    const size_t need = count * 32;
-    if (need > ARENA_BYTES) return nullptr;
-    if (arena_off_ + need > ARENA_BYTES) {                     // full: everything written so far is collected, then it starts again
-        wait_for_stream("hipStreamSynchronize(moments arena)");
-        arena_collect();
-        arena_off_ = 0;
-    }
-    volatile uint64_t* p = reinterpret_cast<volatile uint64_t*>(moments_arena_ + arena_off_);
-    for (size_t i = 0; i < count * 4; ++i) p[i] = MOMENTS_SENTINEL;
-    arena_off_ += need;
-    return reinterpret_cast<double*>(const_cast<uint64_t*>(p));
-}
-
-void Engine::arena_assign(Node* nd, double* slot)
-{
-    nd->has_moments = false;
-    nd->moments_slot = reinterpret_cast<volatile uint64_t*>(slot);
-    arena_outstanding_.push_back({ nd->id, nd->moments_slot });
-}
-
-void Engine::arena_collect()
-{
-    for (const auto& o : arena_outstanding_) {
-        Node* nd = nodes_.get(o.first);
-        if (!nd || nd->moments_slot != o.second) continue;       // gone, asked for already, or written into since
-        bool arrived = true;
-        uint64_t v[4];
-        for (int c = 0; c < 4; ++c) { v[c] = o.second[c]; arrived &= v[c] != MOMENTS_SENTINEL; }
-        nd->moments_slot = nullptr;
-        if (arrived) { std::memcpy(nd->moments, v, 32); nd->has_moments = true; }
-    }
-    arena_outstanding_.clear();
-    for (auto& kv : tickets_) {                                   // tickets that wait for slots: what they wait for has arrived
-        MomentsTicket& t = kv.second;
-        for (size_t i = 0; i < t.slots.size(); ++i)
-            if (volatile uint64_t* slot = t.slots[i]) { uint64_t v[4] = { slot[0], slot[1], slot[2], slot[3] }; std::memcpy(&t.ready[i], v, 32); t.slots[i] = nullptr; }
-    }
-}
-
 // Waits for everything queued on the stream — and, while it waits, performs releases that other threads have queued (drain_late): the
 // device is asked whether it is done between portions instead of being slept on.
 void Engine::wait_for_stream(const char* what)
@@ -1047,33 +999,6 @@ void Engine::wait_for_stream(const char* what)
     hip_check(hipStreamSynchronize(stream_), what);
 }
 
-bool Engine::slot_wait(Node* nd)
-{
-    volatile uint64_t* slot = nd->moments_slot;
-    if (!slot) return false;
-    auto complete = [&]() { return slot[0] != MOMENTS_SENTINEL && slot[1] != MOMENTS_SENTINEL && slot[2] != MOMENTS_SENTINEL && slot[3] != MOMENTS_SENTINEL; };
-    const auto t0 = std::chrono::steady_clock::now();
-    bool arrived = complete();
-    for (uint32_t spins = 1; !arrived; ++spins) {
-        if (has_late()) drain_late(late_portion());           // the device is being waited for: queued releases are performed meanwhile, a few per look
-        else {
-#if defined(__x86_64__)
-            _mm_pause();
-#endif
-        }
-        arrived = complete();
-        if (!arrived && (spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-    }
-    if (!arrived) { wait_for_stream("moments sync"); arrived = complete(); }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    nd->moments_slot = nullptr;
-    if (!arrived) return false;                                  // (the launch never took them: a failed launch)
-    uint64_t v[4] = { slot[0], slot[1], slot[2], slot[3] };
-    std::memcpy(nd->moments, v, 32);
-    nd->has_moments = true;
-    return true;
-}
-
 // A launch with fused reductions over `batch` rows of n elements gives every workgroup one unit of the reduction tree (instead of a span
 // of four) when it has few spans in all: such a launch has as many workgroups as one without reductions, so a chain over many vectors
 // need not fear it.
@@ -1081,82 +1006,6 @@ bool Engine::unit_launch(int64_t n, int64_t batch) const
 {
     const int64_t units = (n + FM_UNIT_ELEMS - 1) / FM_UNIT_ELEMS, spans = (units + FM_SPAN_UNITS - 1) / FM_SPAN_UNITS;
     return spans <= 65536 && spans * batch <= unit_workgroups_;
-}
-
-void Engine::red_begin(RedLaunch& red, int batch, int n_red, size_t blocks_per_row, fmhip_moments* host_moments, void* dev_moments)
-{
-    red = RedLaunch();
-    red.dev_moments = dev_moments;
-    red.on_host = host_moments && !dev_moments;
-    red.partials = pool_.alloc((size_t)batch * n_red * (blocks_per_row + 8) * 32, &red.partials_cap);       // + FM_COMBINE_GROUP_SLOTS group partials per row
-    static const bool POLL = knob_on("FMHIP_POLL");
-    try {
-        if (dev_moments) red.results = dev_moments;
-        else if (red.on_host && POLL && batch == 1 && n_red <= 2 && !free_slots_.empty()) {       // a slot of its own: results [0, 64), flag at 64
-            red.slot = free_slots_.back(); free_slots_.pop_back();
-            red.results = result_slots_ + (size_t)red.slot * 128;
-        }
-        else if (red.on_host) red.results = ensure_stage((size_t)batch * n_red * 32);
-        else red.results = pool_.alloc((size_t)batch * n_red * 32, &red.results_cap);
-    } catch (...) { pool_.release(red.partials, red.partials_cap); red.partials = nullptr; throw; }
-    if (red.slot >= 0) {
-        red.poll_flag = reinterpret_cast<volatile uint64_t*>((char*)red.results + 64);
-        *red.poll_flag = 0;
-        red.done_value = ++poll_sequence_;
-    }
-}
-
-bool Engine::red_poll(const RedLaunch& red)
-{
-    if (!red.poll_flag) return false;
-    const auto t0 = std::chrono::steady_clock::now();
-    bool arrived = false;
-    for (uint32_t spins = 1; !(arrived = *red.poll_flag == red.done_value); ++spins) {
-#if defined(__x86_64__)
-        _mm_pause();
-#endif
-        if ((spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;      // a long kernel: wait the ordinary way
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return arrived;
-}
-
-void Engine::red_complete(RedLaunch& red, bool arrived)
-{
-    if (!red.pending) return;
-    red.pending = false;
-    try {
-        if (!arrived) wait_for_stream("moments sync");
-        std::memcpy(red.host, red.results, (size_t)red.batch * red.n_red * 32);
-    } catch (...) { red_release(red); throw; }
-    red_release(red);
-}
-
-void Engine::red_wait(RedLaunch& red, int batch, int n_red, fmhip_moments* host_moments)
-{
-    if (!host_moments) return;
-    const size_t bytes = (size_t)batch * n_red * 32;
-    void* src = red.results;
-    if (!red.on_host) { src = ensure_stage(bytes); hip_check(hipMemcpyAsync(src, red.results, bytes, hipMemcpyDeviceToHost, stream_), "moments D2H"); }
-    bool arrived = false;
-    if (red.poll_flag && has_late()) {                      // (as red_poll, with queued releases performed between the looks)
-        const auto t0 = std::chrono::steady_clock::now();
-        for (uint32_t spins = 1; !(arrived = *red.poll_flag == red.done_value); ++spins) {
-            if (has_late()) drain_late(late_portion());
-            if ((spins & 63u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-    }
-    if (!arrived && !red_poll(red)) wait_for_stream("moments sync");
-    std::memcpy(host_moments, src, bytes);
-}
-
-void Engine::red_release(RedLaunch& red)
-{
-    if (red.partials) pool_.release(red.partials, red.partials_cap);
-    if (red.results && !red.dev_moments && !red.on_host) pool_.release(red.results, red.results_cap);
-    if (red.slot >= 0) { free_slots_.push_back(red.slot); red.slot = -1; }
-    red.partials = nullptr; red.results = nullptr; red.poll_flag = nullptr;
 }
 
 // ---------------------------------------------------------------- lazy front-end
@@ -1225,8 +1074,7 @@ fmhip_vec Engine::call(int opcode, int n_in, const fmhip_vec* in, double scalar,
         // (Engine::reduce), the device has been at work while the caller was recording.
         const fmhip_vec id = nd->id;
         ops_since_boundary_ = 0;
-        struct Mode { Engine* e; ~Mode() { e->want_root_moments_ = false; e->async_moments_ = false; } } mode{ this };
-        want_root_moments_ = true; async_moments_ = true;
+        MomentsAlong along(this, true);
         try { flush_all(); }
         catch (...) {
             if (nodes_.get(id) == nd) { nd->refs_ext = 0; nodes_.erase(id); node_maybe_free(nd); }
@@ -1601,6 +1449,7 @@ void Engine::materialize_deferred() {
 }
 
 static void set_moments(Node* r, const fmhip_moments& m) { r->moments[0] = m.sum; r->moments[1] = m.sumsq; r->moments[2] = m.min; r->moments[3] = m.max; r->has_moments = true; }
+static fmhip_moments moments_of(const Node* r) { return { r->moments[0], r->moments[1], r->moments[2], r->moments[3] }; }
 
 struct Engine::Dag {
     std::vector<Node*> roots;       // the values asked for
@@ -2662,320 +2511,6 @@ Engine::Dag Engine::replica_dag(const Dag& d, ReplicaGroup* g, int copy) {
     return r;
 }
 
-// ---------------------------------------------------------------- reductions
-
-// The stand-alone reduction is the empty program with one fused reduction of its input (compiled once).
-Program* Engine::reduce_program() {
-    static const char* key = "__reduce1";
-    auto it = program_cache_.find(key);
-    if (it != program_cache_.end()) return it->second;
-    Program* prog = compile({}, 1, {}, { 0 }, nullptr, true);
-    if (jit_mode != FMHIP_JIT_OFF) prog->jit = jit().request(prog->proto, jit_mode == FMHIP_JIT_SYNC);      // every getAverage() runs it: specialised from the start (it is in the kernel pack)
-    program_cache_[key] = prog;
-    return prog;
-}
-
-void Engine::reduce(fmhip_vec h, double shift, fmhip_moments* host_out, void* dev_out, RedLaunch* hand_over) {
-    require_init();
-    end_step_group();
-    Node* nd = node(h);
-    auto cached = [&]() {
-        if (!(nd->has_moments && shift == 0.0 && host_out && !dev_out)) return false;
-        host_out->sum = nd->moments[0]; host_out->sumsq = nd->moments[1]; host_out->min = nd->moments[2]; host_out->max = nd->moments[3];
-        return true;
-    };
-    if (cached()) return;
-    if (nd->moments_slot && shift == 0.0 && host_out && !dev_out && slot_wait(nd) && cached()) return;
-    ++flush_seq_;
-    // One expectation is asked for while much else is pending (a caller that records the payoffs of all its products and then takes
-    // their averages one by one — 144 per objective evaluation of the LIBOR market model calibration): everything pending runs NOW,
-    // components of equal shape as rows of the same launches, and those launches take the moments of their roots along.  The other
-    // products' getAverage() calls are answered from what is left with their nodes; the moments are those of the stand-alone
-    // reduction to the last bit (one reduction tree per vector: fm_kernel_parts.hpp).
-    static const size_t BATCH_PENDING = knob_size("FMHIP_BATCH_EXPECTATIONS", (size_t)256);   // 0 = off
-    if (BATCH_PENDING && fusion && fusion_hold != 1 && !nd->buf && shift == 0.0 && host_out && !dev_out && n_pending_ >= BATCH_PENDING && n_pending_ >= 4 * (size_t)std::max(1, nd->weight)) {
-        struct Want { bool& w; ~Want() { w = false; } } want{ want_root_moments_ };
-        want_root_moments_ = true;
-        flush_all();
-    }
-    if (cached()) return;
-    if (nd->moments_slot && shift == 0.0 && host_out && !dev_out && slot_wait(nd) && cached()) return;
-    touch(nd);
-    RedLaunch deferred;
-    struct Defer {                      // the launch that takes the moments hands its wait to this scope (RedLaunch::pending)
-        Engine* e; RedLaunch* r; RedLaunch* hand_over;
-        Defer(Engine* e_, RedLaunch* r_, RedLaunch* h_) : e(e_), r(r_), hand_over(h_) { e->defer_red_ = r; }
-        ~Defer() { e->defer_red_ = nullptr; if (r->pending) { r->pending = false; (void)hipStreamSynchronize(e->stream_); e->red_release(*r); } }      // (an error behind the launch: its buffers go back when it has finished)
-        // the moments: waited for here, or — results in a slot of their own, a caller that can wait without the engine lock — by the caller
-        void finish() {
-            e->defer_red_ = nullptr;
-            if (!r->pending) return;
-            if (hand_over && r->slot >= 0) { *hand_over = *r; r->pending = false; return; }
-            e->red_wait(*r, r->batch, r->n_red, r->host); r->pending = false; e->red_release(*r);
-        }
-    } defer(this, &deferred, hand_over);
-    if (!nd->buf) {
-        // `chain.getAverage()`: the expectation of a pending expression that fits one launch is taken in THAT launch (the kernel's
-        // fused reduction) instead of a second launch that reads the vector again — one launch and 4 B per path less.  A launch with a
-        // fused reduction of a large row has one workgroup per 8192 elements (fine for a chain over two vectors, a starved launch for one
-        // over eleven) unless it is small enough to take one UNIT of the reduction tree per workgroup (unit_launch).
-        expand_replicas_below({ nd });
-        std::vector<Dag> one(1);
-        if (fusion && nd->weight <= 4 * FM_MAX_OPS && build_dag({ nd }, one[0]) && (nd->n * (int64_t)one[0].leaves.size() <= (int64_t(1) << 21) || unit_launch(nd->n, 1)) && run_dags(one, &shift, host_out, dev_out)) { defer.finish(); return; }
-        // … and of one that takes several launches, in the LAST of them (when its plan exists: from the second time a shape is seen)
-        if (fusion && !nd->buf && nd->n > 0) {
-            std::vector<BigDag> big(1);
-            if (build_big({ nd }, big[0])) {
-                ReduceRequest rr{ shift, host_out, dev_out, false };
-                run_big_group(big, &rr);
-                if (rr.done) { defer.finish(); return; }
-            }
-        }
-        defer.finish();
-        defer_red_ = &deferred;
-        if (!nd->buf) materialize({ nd });
-    }
-    Program* prog = reduce_program();
-    std::vector<RowSpec> rows(1);
-    rows[0].in.push_back(nd->buf->ptr);
-    rows[0].scalars = nullptr;
-    rows[0].shifts = &shift;
-    launch(prog, nd->n, rows, host_out, dev_out);
-    defer.finish();
-}
-
-int64_t Engine::reduce_batch_begin(const fmhip_vec* hs, int count, const double* shifts) {
-    require_init();
-    if (count <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "count must be positive");
-    // Vectors that are still pending: the flush that computes them takes their moments along (rows of the launches that compute them
-    // anyway, results into slots of the pinned arena) — no reduction launch, the vectors are not read again.  The ticket remembers the
-    // slots; ending it waits for them.  (Vectors computed already, shifts, or a component whose launches cannot take moments: the
-    // reduction launch below.)
-    static const bool FROM_LAUNCHES = knob_on("FMHIP_MOMENTS_FROM_LAUNCHES");
-    bool unshifted = true;
-    for (int i = 0; shifts && i < count; ++i) unshifted &= shifts[i] == 0.0;
-    if (FROM_LAUNCHES && fusion && unshifted && hs) return reduce_batch_begin_from_launches(hs, count);
-    const size_t bytes = (size_t)count * 32;
-    MomentsTicket t;
-    for (size_t i = 0; i < free_tickets_.size(); ++i)
-        if (free_tickets_[i].cap >= bytes) { t = free_tickets_[i]; free_tickets_[i] = free_tickets_.back(); free_tickets_.pop_back(); break; }
-    try {
-        if (!t.host) {
-            t.cap = std::max(bytes, size_t(8192));
-            hip_check(hipHostMalloc(&t.host, t.cap, hipHostMallocDefault), "hipHostMalloc(moments ticket)");
-            hip_check(hipEventCreateWithFlags(&t.event, hipEventDisableTiming), "hipEventCreate(moments ticket)");
-        }
-        t.count = count;
-        reduce_batch(hs, count, shifts, nullptr, t.host);     // the last workgroup of every row stores its moments straight into the block
-        hip_check(hipEventRecord(t.event, stream_), "hipEventRecord(moments ticket)");
-    } catch (...) { if (t.host) free_tickets_.push_back(t); throw; }
-    const int64_t id = next_ticket_++;
-    tickets_[id] = t;
-    return id;
-}
-
-// fmhip_vec_give_up_values: the caller wants the EXPECTATIONS of these vectors and will never read their values.  A vector that is
-// still pending and that nobody but the caller references is marked (Node::discard); a flush that takes the moments of its roots along
-// (reduce_batch_begin, reduce) then computes it in a launch that takes its moments and does NOT store it (run_plan: a peeled component
-// whose root is 'm' in the signature).  One 8 KB store per workgroup at the end of a read-only chain costs such a launch 8-10 % of its
-// rate (benchmarks/read_pattern.hip: 6486 → 5893 GB/s; the valuation kernel in isolation 6145 → 6617): the memory system pays for
-// turning a stream of reads around for a trickle of writes.  A marked vector that runs through a launch which cannot take its moments
-// is stored like any other.
-void Engine::give_up_values(const fmhip_vec* hs, int count) {
-    require_init();
-    if (count <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "count must be positive");
-    static const bool DISCARD = knob_on("FMHIP_DISCARD_VALUES");      // =0: every value is stored (A/B measurement)
-    std::vector<Node*> nds((size_t)count);
-    for (int i = 0; i < count; ++i) nds[(size_t)i] = node(hs[i]);
-    if (!DISCARD) return;
-    // nobody but the caller references it — not counting the holds of a live replica description (fmhip_graph_clone) on the roots it
-    // replicates (one external reference on the original's root) and on the roots of its copies (one internal reference each)
-    auto sole_owner = [&](const Node* nd) {
-        int ext = nd->refs_ext, in = nd->refs_int;
-        if (nd->rep_id && replica_of(nd)) { if (nd->rep_copy) in -= 1; else if (nd->rep_root >= 0) ext -= 1; }
-        return ext == 1 && in == 0;
-    };
-    for (Node* nd : nds) if (!nd->buf && !nd->moments_blocked && sole_owner(nd)) nd->discard = true;
-}
-
-// The expectations of vectors that may still be pending, every one through a slot of the pinned arena (or at hand already): the flush
-// that computes the pending ones takes their moments along; what has none afterwards (computed earlier, a launch that could not take
-// them along, a vector somebody writes into) is reduced by ONE launch of the reduction program into arena slots.
-int64_t Engine::reduce_batch_begin_from_launches(const fmhip_vec* hs, int count) {
-    end_step_group();
-    std::vector<Node*> nds((size_t)count);
-    for (int i = 0; i < count; ++i) nds[(size_t)i] = node(hs[i]);
-    for (int i = 1; i < count; ++i)
-        if (nds[(size_t)i]->n != nds[0]->n) throw Error(FMHIP_ERR_SIZE_MISMATCH, "batched reduction over vectors of different size");
-    bool pending = false;
-    for (Node* nd : nds) pending |= !nd->buf && !nd->discarded;
-    if (pending) {
-        struct Mode { Engine* e; ~Mode() { e->want_root_moments_ = false; e->async_moments_ = false; } } mode{ this };
-        want_root_moments_ = true; async_moments_ = true;
-        flush_all();
-    }
-    std::vector<fmhip_vec> rest;
-    std::vector<size_t> rest_index;
-    for (int i = 0; i < count; ++i) {
-        Node* nd = nds[(size_t)i];
-        if (nd->has_moments || nd->moments_slot) continue;
-        rest.push_back(hs[i]); rest_index.push_back((size_t)i);
-    }
-    MomentsTicket t;
-    t.count = count; t.slots.resize((size_t)count, nullptr); t.ready.resize((size_t)count);
-    if (!rest.empty()) {
-        double* slots = arena_alloc(rest.size());
-        if (!slots) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "too many expectations for one ticket");
-        reduce_batch(rest.data(), (int)rest.size(), nullptr, nullptr, slots);
-        for (size_t k = 0; k < rest.size(); ++k) t.slots[rest_index[k]] = reinterpret_cast<volatile uint64_t*>(slots + k * 4);
-    }
-    for (int i = 0; i < count; ++i) {
-        Node* nd = nds[(size_t)i];
-        if (t.slots[(size_t)i]) continue;
-        if (nd->has_moments) t.ready[(size_t)i] = { nd->moments[0], nd->moments[1], nd->moments[2], nd->moments[3] };
-        else t.slots[(size_t)i] = nd->moments_slot;
-    }
-    const int64_t id = next_ticket_++;
-    tickets_[id] = std::move(t);
-    return id;
-}
-
-// fmhip_reduce_moments_batch_device on vectors that may still be pending: as reduce_batch_begin_from_launches — the flush that computes them
-// takes their moments along (values that were given up are not stored at all) — but the caller wants the 32-byte blocks in ONE device
-// buffer, in the order asked (the send buffer of its RCCL exchange), not on the host: a one-wave kernel behind the launches collects them
-// from their slots of the pinned arena, which the device reads through the same mapping it wrote them through.  Until round 4 a caller
-// with a communicator of its own (lmm_hip --world N) had to flush first and pay a reduction launch that read every value again.
-void Engine::reduce_batch_device_from_launches(const fmhip_vec* hs, int count, void* dev_out) {
-    end_step_group();
-    std::vector<Node*> nds((size_t)count);
-    for (int i = 0; i < count; ++i) nds[(size_t)i] = node(hs[i]);
-    for (int i = 1; i < count; ++i)
-        if (nds[(size_t)i]->n != nds[0]->n) throw Error(FMHIP_ERR_SIZE_MISMATCH, "batched reduction over vectors of different size");
-    bool pending = false;
-    for (Node* nd : nds) pending |= !nd->buf && !nd->discarded;
-    if (pending) {
-        struct Mode { Engine* e; ~Mode() { e->want_root_moments_ = false; e->async_moments_ = false; } } mode{ this };
-        want_root_moments_ = true; async_moments_ = true;
-        flush_all();
-    }
-    // one block of the arena for whatever has no slot yet, taken BEFORE the vectors are sorted: if the arena wraps here, the slots written so
-    // far are collected into their nodes (has_moments) now and not between two looks at them
-    double* block = arena_alloc((size_t)count);
-    if (!block) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "too many expectations for one call");
-    std::vector<fmhip_vec> rest;
-    std::vector<uint64_t> src((size_t)count, 0);
-    size_t used = 0;
-    std::vector<size_t> rest_index;
-    for (int i = 0; i < count; ++i) {
-        Node* nd = nds[(size_t)i];
-        if (nd->moments_slot) src[(size_t)i] = (uint64_t)(uintptr_t)nd->moments_slot;
-        else if (nd->has_moments) { double* at = block + 4 * used++; std::memcpy(at, nd->moments, 32); src[(size_t)i] = (uint64_t)(uintptr_t)at; }
-        else { rest.push_back(hs[i]); rest_index.push_back((size_t)i); }
-    }
-    if (!rest.empty()) {           // computed earlier, or by a launch that could not take the moments along: one reduction launch, into the block
-        double* at = block + 4 * used;
-        reduce_batch(rest.data(), (int)rest.size(), nullptr, nullptr, at);
-        for (size_t k = 0; k < rest.size(); ++k) src[rest_index[k]] = (uint64_t)(uintptr_t)(at + 4 * k);
-        used += rest.size();
-    }
-    { volatile uint64_t* tail = reinterpret_cast<volatile uint64_t*>(block + 4 * used); for (size_t i = 0; i < ((size_t)count - used) * 4; ++i) tail[i] = 0; }    // (unused slots: no sentinels left behind)
-    for (int off = 0; off < count; off += FM_GATHER_MAX) {
-        DevGatherArgs a{};
-        a.count = (uint32_t)std::min(FM_GATHER_MAX, count - off);
-        std::memcpy(a.src, src.data() + off, (size_t)a.count * 8);
-        hip_check(launch_gather_moments(a, (double*)dev_out + (size_t)off * 4, stream_), "launch fm_gather_moments_kernel");
-        n_launches_++;
-    }
-}
-
-void Engine::reduce_batch_device(const fmhip_vec* hs, int count, const double* shifts, void* dev_out) {
-    require_init();
-    if (count <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "count must be positive");
-    static const bool FROM_LAUNCHES = knob_on("FMHIP_MOMENTS_FROM_LAUNCHES");
-    bool unshifted = true;
-    for (int i = 0; shifts && i < count; ++i) unshifted &= shifts[i] == 0.0;
-    bool worth = false;                                          // something is pending, given up, or has its moments already
-    if (FROM_LAUNCHES && fusion && unshifted) for (int i = 0; i < count && !worth; ++i) { const Node* nd = node(hs[i]); worth = !nd->buf || nd->has_moments || nd->moments_slot; }
-    if (worth) reduce_batch_device_from_launches(hs, count, dev_out);
-    else reduce_batch(hs, count, shifts, nullptr, dev_out);
-}
-
-Engine::MomentsTicket Engine::ticket_take(int64_t id) {
-    auto it = tickets_.find(id);
-    if (it == tickets_.end()) throw Error(FMHIP_ERR_INVALID_HANDLE, "unknown (or already ended) expectation ticket");
-    MomentsTicket t = std::move(it->second);
-    tickets_.erase(it);
-    for (size_t i = 0; i < t.slots.size(); ++i) {                 // moments taken by the launches that computed the vectors: wait for their slots
-        volatile uint64_t* slot = t.slots[i];
-        if (!slot) continue;
-        auto complete = [&]() { return slot[0] != MOMENTS_SENTINEL && slot[1] != MOMENTS_SENTINEL && slot[2] != MOMENTS_SENTINEL && slot[3] != MOMENTS_SENTINEL; };
-        const auto t0 = std::chrono::steady_clock::now();
-        bool arrived = complete();
-        for (uint32_t spins = 1; !arrived; ++spins) {
-            if (has_late()) drain_late(late_portion());
-            else {
-#if defined(__x86_64__)
-                _mm_pause();
-#endif
-            }
-            arrived = complete();
-            if (!arrived && (spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-        }
-        // Not there after 2 ms of spinning: the launch that writes it is far down the queue.  Keep watching THIS slot, asleep in between —
-        // never hipStreamSynchronize: that waits for everything queued behind as well (a driver that records batch b+1 before it asks
-        // for batch b's expectations lost its overlap at every second batch that way: the device drained, then idled 2 ms per batch
-        // while the host recorded the next one).  A stream that has run dry without the slot being written is an error.
-        for (uint32_t naps = 1; !arrived; ++naps) {
-            std::this_thread::sleep_for(std::chrono::microseconds(50));
-            arrived = complete();
-            if (!arrived && (naps & 63u) == 0) {
-                const hipError_t q = hipStreamQuery(stream_);
-                if (q == hipSuccess) { arrived = complete(); break; }
-                if (q != hipErrorNotReady) hip_check(q, "hipStreamQuery(moments)");
-            }
-        }
-        if (!arrived) throw Error(FMHIP_ERR_HIP, "the moments of a vector never arrived");
-        std::atomic_thread_fence(std::memory_order_acquire);
-        uint64_t v[4] = { slot[0], slot[1], slot[2], slot[3] };
-        std::memcpy(&t.ready[i], v, 32);
-        t.slots[i] = nullptr;
-    }
-    return t;
-}
-
-void Engine::ticket_retire(MomentsTicket& t) {
-    t.slots.clear(); t.ready.clear();
-    if (t.host) free_tickets_.push_back(t);
-    t = MomentsTicket();
-}
-
-void Engine::reduce_batch(const fmhip_vec* hs, int count, const double* shifts, fmhip_moments* host_out, void* dev_out) {
-    HostTimer timer(HostProfile::REDUCE);
-    require_init();
-    end_step_group();
-    if (count <= 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "count must be positive");
-    std::vector<Node*> nds((size_t)count);
-    for (int i = 0; i < count; ++i) nds[(size_t)i] = node(hs[i]);
-    for (int i = 1; i < count; ++i)
-        if (nds[(size_t)i]->n != nds[0]->n) throw Error(FMHIP_ERR_SIZE_MISMATCH, "batched reduction over vectors of different size");
-    bool pending = false;
-    for (Node* nd : nds) { touch(nd); pending |= !nd->buf; }
-    if (pending) flush_all();                                   // one batched flush instead of one launch per vector
-    for (Node* nd : nds) if (!nd->buf) materialize({ nd });
-    Program* prog = reduce_program();
-    const int max_rows = 1024;
-    for (int off = 0; off < count; off += max_rows) {
-        const int m = std::min(max_rows, count - off);
-        std::vector<RowSpec> rows((size_t)m);
-        for (int i = 0; i < m; ++i) {
-            rows[(size_t)i].in.push_back(nds[(size_t)(off + i)]->buf->ptr);
-            rows[(size_t)i].scalars = nullptr;
-            rows[(size_t)i].shifts = shifts ? &shifts[off + i] : nullptr;
-        }
-        launch(prog, nds[0]->n, rows, host_out ? host_out + off : nullptr, dev_out ? (char*)dev_out + (size_t)off * 32 : nullptr);
-    }
-}
-
 // ---------------------------------------------------------------- explicit programs
 
 fmhip_program Engine::program_create(const fmhip_prog_op* ops, int n_ops, int n_in, const int32_t* outs, int n_out,
@@ -3231,6 +2766,7 @@ void Engine::profile_read(double* ms_total, int64_t* n) {
 
 #include "loop_engine.hpp"             // Engine::detect_loop, plan_peel, plan_loop, run_rolled, run_peeled: the periodic stretch of a component as one launch
 #include "merged_chains_engine.hpp"    // Engine::match_small, merge_shape_index, merge_families: components of one loop shape over the same vectors as one launch
+#include "expectations_engine.hpp"     // Engine::red_*, arena_*, slot_wait, reduce, reduce_batch*, give_up_values, ticket_*: from a vector to its expectation
 #include "side_pass_engine.hpp"        // Engine::pass_*: the frame the reducing passes below stand in
 #include "order_stats_engine.hpp"      // Engine::os_*: the order-statistics passes
 #include "cross_moments_engine.hpp"    // Engine::xmom_pass: the cross moments of a regression in one launch

@@ -270,7 +270,7 @@ public:
     // lock at every other call and sleep on it (measured, lmm_hip --finmath-like --release-lag 100, 1 M paths: 14.1 s against 4.3 s with
     // the same launches).  They are queued (a tiny lock of their own; abi.cpp collects 256 per releasing thread first) and PERFORMED by the
     // driving thread — preferably while it has nothing else to do: in small portions while it waits for the device (the spin loops of
-    // slot_wait / ticket_take / red_wait), all of them before a flush looks for memory in vain (new_buffer), at the latest when LATE_EAGER
+    // slot_wait / ticket_take / red_wait: pinned_wait.hpp), all of them before a flush looks for memory in vain (new_buffer), at the latest when LATE_EAGER
     // wait.  A node that was released 100 ms after its creation is cold: performing 21 M of them between the recorded methods cost the
     // hint-free calibration 1.5 s; the device gives that time away for nothing while it is waited for.  The releasing thread performs the
     // queue itself only when no thread has entered the engine for 10 ms (the caller has gone quiet).
@@ -342,7 +342,7 @@ public:
     int graph_scalars(const fmhip_vec* roots, int n_roots, double* out, int capacity);
 
     // reductions
-    // what a launch with fused reductions holds while it runs (runtime.cpp: red_begin / red_wait / red_release)
+    // what a launch with fused reductions holds while it runs (expectations_engine.hpp: red_begin / red_wait / red_release)
     struct RedLaunch { void* partials = nullptr; size_t partials_cap = 0; void* results = nullptr; size_t results_cap = 0; void* dev_moments = nullptr;
                        bool on_host = false; volatile uint64_t* poll_flag = nullptr; uint64_t done_value = 0; int slot = -1;
                        bool pending = false; int batch = 0, n_red = 0; fmhip_moments* host = nullptr; };       // pending: launched, not yet waited for (defer_red_)
@@ -652,6 +652,11 @@ private:
     // no reduction produces (results are canonicalised); the arena is reused after a stream synchronisation that first collects what
     // is still outstanding.
     bool async_moments_ = false;
+    struct MomentsAlong {                                        // the scope of a flush that takes the moments of its roots along; async: without waiting, into arena slots
+        Engine* e;
+        MomentsAlong(Engine* e_, bool async) : e(e_) { e->want_root_moments_ = true; if (async) e->async_moments_ = true; }
+        ~MomentsAlong() { e->want_root_moments_ = false; e->async_moments_ = false; }
+    };
     size_t ops_since_boundary_ = 0;                              // methods recorded since the last time-step boundary (step_boundary)
     char* moments_arena_ = nullptr; size_t arena_off_ = 0;
     size_t ARENA_BYTES = size_t(16) << 20;                        // 512 k slots: a wrap waits for the stream, so it should be rare (a 1 M-path calibration uses 89 k); FMHIP_ARENA_BYTES: tests shrink it
@@ -661,7 +666,13 @@ private:
     void arena_collect();                                        // stream synchronised: every outstanding slot goes to its node (if it still exists)
     void arena_assign(Node* nd, double* slot);
     void wait_for_stream(const char* what);                      // hipStreamSynchronize, with queued releases performed meanwhile
+    static bool slot_arrived(const volatile uint64_t* slot);     // all four words of a slot are there
+    static void slot_take(const volatile uint64_t* slot, void* out32);
     bool slot_wait(Node* nd);                                    // the node's slot has arrived (or the stream is waited for): moments into the node
+    void drain_or_pause();                                       // between two looks at a slot: a few queued releases if there are any (the device is being waited for), else a pause
+    std::vector<Node*> batch_nodes(const fmhip_vec* hs, int count);       // the nodes of a batched reduction: one size, or FMHIP_ERR_SIZE_MISMATCH
+    bool from_launches_applies(int count, const double* shifts) const;    // the batched forms may leave the moments to the launches: the knob, fusion, every shift zero
+    void flush_for_moments(const std::vector<Node*>& nds);       // something pending and not given up: a flush that takes the moments along, without waiting
     void red_begin(RedLaunch& red, int batch, int n_red, size_t blocks_per_row, fmhip_moments* host_moments, void* dev_moments);
     void red_wait(RedLaunch& red, int batch, int n_red, fmhip_moments* host_moments);
     void red_release(RedLaunch& red);

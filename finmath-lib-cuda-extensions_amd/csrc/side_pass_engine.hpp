@@ -11,12 +11,10 @@
 // and its device scratch (pass_scratch), launches once and waits under the engine lock as read() does (pass_launch).  Shared storage (common
 // rows) is only read.  `what` names the pass in whatever the frame has to say.
 #include "runtime.hpp"
+#include "pinned_wait.hpp"
 
 #include <algorithm>
 #include <string>
-#if defined(__x86_64__)
-#include <immintrin.h>
-#endif
 
 namespace fm {
 
@@ -101,17 +99,8 @@ void Engine::pass_release() {
 }
 
 void Engine::pass_wait(volatile uint64_t* flag, uint64_t value, const char* what) {
-    const auto t0 = std::chrono::steady_clock::now();
-    bool arrived = *flag == value;
-    for (uint32_t spins = 1; !arrived; ++spins) {
-#if defined(__x86_64__)
-        _mm_pause();
-#endif
-        arrived = *flag == value;
-        if (!arrived && (spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-    }
-    if (!arrived) { hip_check(hipStreamSynchronize(stream_), "side pass sync"); arrived = *flag == value; }
-    std::atomic_thread_fence(std::memory_order_acquire);
+    bool arrived = spin_until([&] { return *flag == value; }, [] { pause(); });
+    if (!arrived) { hip_check(hipStreamSynchronize(stream_), "side pass sync"); arrived = *flag == value; std::atomic_thread_fence(std::memory_order_acquire); }
     if (!arrived) throw Error(FMHIP_ERR_HIP, std::string("the ") + what + " ended without delivering its results");
     pass_dirty_ = false;
 }

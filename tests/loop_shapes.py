@@ -489,7 +489,7 @@ class Family:
     """products: [(kind, periods, rate)] over `vectors` vectors drawn from `lo` … `hi`; merged: how many of them are chains of merged
     launches from the second round on; kernels: the family sizes whose merged kernels are recorded.  Shortest product first: the first
     `.moments()` runs everything pending with the moments taken along only when at least 256 methods are pending and four times as many
-    as below the vector asked for (runtime.cpp, Engine::reduce: BATCH_PENDING)."""
+    as below the vector asked for (expectations_engine.hpp, Engine::reduce: BATCH_PENDING)."""
 
     def __init__(self, name, vectors, products, merged, kernels, lo=-0.01, hi=0.05):
         self.name, self.vectors, self.products, self.merged, self.kernels, self.lo, self.hi = name, vectors, products, merged, kernels, lo, hi

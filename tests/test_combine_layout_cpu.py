@@ -35,7 +35,7 @@ def test_groups_partition_the_row():
 def test_constants_agree_between_host_and_device():
     parts = open(os.path.join(CSRC, "fm_kernel_parts.hpp")).read()
     prog = open(os.path.join(CSRC, "fm_program.h")).read()
-    runtime = open(os.path.join(CSRC, "runtime.cpp")).read()
+    runtime = open(os.path.join(CSRC, "expectations_engine.hpp")).read()           # red_begin
     slots = int(re.search(r"FM_COMBINE_GROUP_SLOTS\s*=\s*(\d+)", parts).group(1))
     planes = int(re.search(r"FM_COUNTER_PLANES\s*=\s*(\d+)", prog).group(1))
     assert slots >= 7 and planes >= 8                                  # 7 group counters + the second-level counter

@@ -213,7 +213,7 @@ def test_expectation_in_the_launch_of_the_peeled_chain(gpu, oracle, n):
 def test_one_expectation_asked_many_pending(gpu, oracle):
     """A caller records the payoffs of many products and then takes their averages one by one (what an optimiser over calibration products
     does).  At the first getAverage() the engine runs everything pending — components of equal shape as rows of the same launches — and
-    those launches take the moments of their roots along (runtime.cpp: Engine::reduce, want_root_moments_); the other averages are
+    those launches take the moments of their roots along (expectations_engine.hpp: Engine::reduce, want_root_moments_); the other averages are
     answered from what was left with the nodes: no further launch.  Same bits as asking one at a time; nothing of the kind under a
     caller's own hold; a vector that is written into afterwards forgets its moments."""
     n, periods, products = 40_009, 24, 12
@@ -281,7 +281,7 @@ def test_one_expectation_asked_many_pending(gpu, oracle):
 def test_expectations_taken_while_the_caller_is_still_recording(gpu, oracle):
     """Behind a simulation (the engine holds the methods of the time steps it is grouping) a caller records payoff after payoff without
     asking for anything: after 5000 methods without a new time step the engine runs what is pending WITHOUT waiting, and those launches
-    write the moments of their roots into slots of a pinned arena (runtime.cpp: call, arena_alloc, slot_wait).  Asked later, every
+    write the moments of their roots into slots of a pinned arena (runtime.cpp: call; expectations_engine.hpp: arena_alloc, slot_wait).  Asked later, every
     expectation has the bits of the stand-alone reduction — also when more roots were outstanding than the arena has slots (it is
     collected and reused), and for vectors released or overwritten in between."""
     n, count = 67, 530_000                               # (more payoffs than the arena has slots: 2^19)
@@ -421,6 +421,53 @@ def test_moments_into_a_device_buffer_come_from_the_launches_too(gpu, oracle):
             m = chains[2].moments()                                         # asked again on the host: from the node's slot
             assert np.array([m.sum, m.sumsq, m.min, m.max]).tobytes() == want[2].tobytes()
             del chains, asked, early, known
+        gpu.flush()
+    finally:
+        gpu.set_jit(prev_jit)
+        gpu.set_fusion(prev_fusion)
+
+
+def test_moments_into_a_device_buffer_past_one_gather_launch(gpu):
+    """ONE fmhip_reduce_moments_batch_device call over 400 vectors — more than the FM_GATHER_MAX = 384 sources of one gather launch — of
+    n = 2 049 (one unit of the reduction tree plus one element: the smallest size with two units), mixed in the order asked: every third
+    still pending (its moments come from the launch that computes it), every third computed earlier without moments (ONE reduction launch
+    for all of them), every third with its moments known.  Each 32-byte block is moments() of the same vector byte for byte — and, for a
+    pending one, the moments of the same expression stored first and reduced on its own."""
+    import ctypes as C
+    n, count = 2_049, 400
+    rng = np.random.default_rng(79)
+    prev_fusion, prev_jit = gpu.set_fusion(True), gpu.set_jit(gpu.JIT_SYNC)
+    try:
+        dev = [gpu.DeviceVector.from_host(rng.uniform(0.5, 1.5, n).astype(np.float32)) for _ in range(7)]
+
+        def block(m):
+            return np.array([m.sum, m.sumsq, m.min, m.max]).tobytes()
+
+        def expression(i):
+            return dev[i % 7].v1s1("MULT_S", 1.0 + 1e-3 * i)
+        stored = {}
+        for i in range(0, count, 3):                          # what the pending ones must give: stored, then reduced alone
+            v = expression(i); v.to_float32()
+            stored[i] = block(v.moments())
+            del v
+        asked = [None] * count
+        for i in range(1, count, 3):                          # computed earlier, no moments yet
+            asked[i] = expression(i); asked[i].to_float32()
+        for i in range(2, count, 3):                          # moments known already
+            asked[i] = expression(i); asked[i].moments()
+        soft = gpu.fusion_hold(2)
+        for i in range(0, count, 3):                          # still pending when the call comes
+            asked[i] = expression(i)
+        gpu.fusion_hold(soft)
+        handles = (C.c_int64 * count)(*[v.handle for v in asked])
+        out = gpu.DeviceVector.filled(8 * count, 0.0)
+        gpu._native.check(gpu.lib().fmhip_reduce_moments_batch_device(handles, count, None, C.c_void_p(out.device_ptr())))
+        raw = out.to_float32().view(np.float64).reshape(count, 4)
+        for i, v in enumerate(asked):
+            assert raw[i].tobytes() == block(v.moments()), i
+            assert i % 3 or raw[i].tobytes() == stored[i], i
+            assert np.isfinite(raw[i]).all() and raw[i][0] > 0.25 * n, i
+        del asked
         gpu.flush()
     finally:
         gpu.set_jit(prev_jit)

@@ -1,5 +1,5 @@
-"""The engine's host runtime (csrc/runtime.cpp, abi.cpp, jit.cpp: node pools, intrusive reference counts, replica descriptions, tickets, the
-pinned arena, plan caches) under AddressSanitizer + UndefinedBehaviorSanitizer and under ThreadSanitizer, on a TEST-ONLY null device
+"""The engine's host runtime (csrc/runtime.cpp, abi.cpp, jit.cpp: node pools, intrusive reference counts, replica descriptions, plan caches;
+csrc/expectations_engine.hpp: tickets, the pinned arena) under AddressSanitizer + UndefinedBehaviorSanitizer and under ThreadSanitizer, on a TEST-ONLY null device
 (tests/nulldev/null_hip.cpp: device memory = host memory, launches compute nothing) — no GPU needed; GPU sanitizers do not exist on this
 pool.  tests/nulldev/drive.cpp replays the graph shapes of the GPU tests (replicas in the ten orders of test_gpu_replicas.py, long
 chains through segments / rolled / peeled plans, expectations taken along, values given up, tickets out of order, the row-table ring
