@@ -26,6 +26,7 @@ from .regression import MonteCarloConditionalExpectationPolynomialRegression, po
 from .sorting import argsort, rank_scores, read_elements, sort_by_key, sorted_quantiles, spearman_matrix
 from .prefix import cumulative_sums, expected_shortfall_curve, prefix_search, prefix_sums_at, prefix_sums_host, running_average
 from .prefix import weighted_expected_shortfall, weighted_quantiles
+from .tabulated import TabulatedFunction, table_apply, table_apply_host
 from .differentiable import RandomVariableDifferentiableAAD, RandomVariableDifferentiableAADFactory
 
 

@@ -879,6 +879,23 @@ int fmhip_prefix_search(fmhip_vec v, const double* thresholds, int count, int re
     return guarded([&] { Engine::get().prefix_search(v, thresholds, count, relative, positions_out, sums_out, total_out); });
 }
 
+// ---------------------------------------------------------------- tabulated functions (table_engine.hpp)
+int fmhip_table_build(const double* knots, const double* values, int count, int interpolation, int extrapolation, int derivative, double* coefficients_out) {
+    return host_only([&] { fm::table_build_checked(knots, values, count, interpolation, extrapolation, derivative, coefficients_out); });
+}
+int fmhip_table_apply_host(const float* x, int64_t n, const double* knots, int count, const double* coefficients, int n_tables, float* const* out) {
+    return host_only([&] { fm::table_apply_host_checked(x, n, knots, count, coefficients, n_tables, out); });
+}
+int fmhip_table_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, fmhip_vec* out) {
+    FRONT(table_apply(x, knots, count, coefficients, n_tables, out));
+    if (te::active()) {
+        const int rc = host_only([&] { fm::table_check_apply(x, knots, count, coefficients, n_tables, out); });
+        if (rc != FMHIP_OK) return rc;
+        TE_LOCAL(&x, 1, L, fmhip_table_apply(L[0], knots, count, coefficients, n_tables, out));
+    }
+    return guarded([&] { Engine::get().table_apply(x, knots, count, coefficients, n_tables, out); });
+}
+
 // The one call of a caller that values product after product: the engine lock is held for the bookkeeping (graph → launch → commit),
 // NOT while the device computes — other threads record and launch meanwhile.  The moments arrive in a slot of pinned memory of their
 // own; this thread polls its flag, then takes the lock again to copy them out and give the launch's buffers back.

@@ -412,6 +412,11 @@ public:
     void prefix_sums_at(fmhip_vec v, const int64_t* positions, int count, double* sums_out);
     void prefix_search(fmhip_vec v, const double* thresholds, int count, int relative, int64_t* positions_out, double* sums_out, double* total_out);
 
+    // tabulated functions (table_engine.hpp): n_tables functions on the same knots (host/tabulated_function.hpp) applied to
+    // every element of x, out[0 … n_tables) new, materialised vectors from one launch that reads x once.  Arguments are checked before
+    // anything is flushed or launched; out is written only when the call succeeds.
+    void table_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, fmhip_vec* out);
+
     // programs
     fmhip_program program_create(const fmhip_prog_op* ops, int n_ops, int n_in, const int32_t* outs, int n_out,
                                  const int32_t* reds, int n_red);
@@ -805,6 +810,11 @@ void sort_argsort_host_checked(const float* key, int64_t n, int64_t* permutation
 void prefix_check_sums(fmhip_vec v, int mode, const fmhip_vec* out);
 void prefix_check_queries(fmhip_vec v, const void* queries, int count, const void* sums_out, const char* what);
 void prefix_sums_host_checked(const float* v, int64_t n, double* prefix_out);
+// the same for fmhip_table_apply, and the definitions behind fmhip_table_build / fmhip_table_apply_host (table_engine.hpp; the rules are
+// host/tabulated_function.hpp's): all throw FMHIP_ERR_INVALID_ARGUMENT
+void table_check_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, const fmhip_vec* out);
+void table_build_checked(const double* knots, const double* values, int count, int interpolation, int extrapolation, int derivative, double* coefficients_out);
+void table_apply_host_checked(const float* x, int64_t n, const double* knots, int count, const double* coefficients, int n_tables, float* const* out);
 // what can be said about the arguments of fmhip_binned_cross_moments / fmhip_binned_evaluate without looking at a vector (binned_engine.hpp; the
 // rules are fmhost::binnedCheck*'s, host/binned_regression.hpp), and the host definitions: all throw FMHIP_ERR_INVALID_ARGUMENT
 void binned_check_moments(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, const int64_t* counts_out, const double* sums_out);

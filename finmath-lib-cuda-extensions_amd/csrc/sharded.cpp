@@ -974,6 +974,32 @@ int prefix_search(fmhip_vec v, const double* thresholds, int count, int relative
     });
 }
 
+// Tabulated functions (table_engine.hpp).  Elementwise: every shard runs the call on its block; the new vectors' blocks are the shards' results.
+int table_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, fmhip_vec* out) {
+    return fronted([&](Shards& s) {
+        table_check_apply(x, knots, count, coefficients, n_tables, out);
+        const int64_t n = front_size(s, &x, 1, "tabulated function", false);
+        auto kn = std::make_shared<std::vector<double>>(knots, knots + count);
+        auto co = std::make_shared<std::vector<double>>(coefficients, coefficients + (size_t)n_tables * (size_t)(count + 1) * 4);
+        auto ids = std::make_shared<std::vector<fmhip_vec>>();
+        for (int f = 0; f < n_tables; ++f) ids->push_back(s.fresh(n));
+        s.post([=](Worker& w) {
+            int64_t off, cnt; shard_range(n, w.shards, w.shard, &off, &cnt);
+            fmhip_vec h[4] = { 0, 0, 0, 0 };
+            if (cnt <= 0) { for (int f = 0; f < n_tables; ++f) if (w.ok(fmhip_vec_create_uninitialized(0, &h[f]))) w.bind((*ids)[(size_t)f], h[f]); return; }
+            if (w.ok(fmhip_table_apply(w.at(x), kn->data(), count, co->data(), n_tables, h))) for (int f = 0; f < n_tables; ++f) w.bind((*ids)[(size_t)f], h[f]);
+        });
+        // eager, like the call on one engine: a shard's refusal (no kernel, a value that was given up) is THIS call's status
+        try { s.wait(); }
+        catch (...) {
+            s.post([=](Worker& w) { for (fmhip_vec id : *ids) if (const fmhip_vec h = w.at(id)) { (void)fmhip_vec_release(h); w.local.erase(id); } });
+            for (fmhip_vec id : *ids) s.meta.erase(id);
+            throw;
+        }
+        for (int f = 0; f < n_tables; ++f) out[f] = (*ids)[(size_t)f];
+    });
+}
+
 int vec_give_up_values(const fmhip_vec* vectors, int count) {
     return fronted([&](Shards& s) {
         need(vectors, "vectors");

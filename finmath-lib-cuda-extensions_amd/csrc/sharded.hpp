@@ -76,6 +76,7 @@ int rank_scores(fmhip_vec key, fmhip_vec* out);
 int vec_read_elements(fmhip_vec v, const int64_t* positions, int count, double* out);
 int prefix_sums(fmhip_vec v, int mode, fmhip_vec* out, double* total_out);                     // one shard; more: FMHIP_ERR_UNSUPPORTED
 int prefix_sums_at(fmhip_vec v, const int64_t* positions, int count, double* sums_out);
+int table_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, fmhip_vec* out);      // per shard
 int prefix_search(fmhip_vec v, const double* thresholds, int count, int relative, int64_t* positions_out, double* sums_out, double* total_out);
 int polynomial_cross_moments(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const fmhip_vec* y, int n_y, double* sums_out);
 int polynomial_evaluate(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const double* coefficients, fmhip_vec* out);

@@ -142,6 +142,25 @@ class RandomVariableDifferentiableAAD:
         return self._new("AVERAGE", self.values.average(), (self,))
 
     def apply(self, *a, **k):
+        """apply(TabulatedFunction): a curve has a derivative, the curve of its segments' derivatives.  Value and derivative come from ONE
+        table_apply of the pair (one read of x) where the inner value is a device vector; a constant is mapped in double; the values of any
+        other inner implementation go through the definition on the host (fmhip_table_apply_host) and back through the inner factory.
+        Anything else has no derivative."""
+        from .tabulated import TabulatedFunction, table_apply, table_apply_host
+        if len(a) == 1 and not k and isinstance(a[0], TabulatedFunction):
+            f, df = a[0], a[0].derivative()
+            x = self.values
+            realizations = getattr(x, "realizations", None)
+            if hasattr(x, "_sto"):                                       # RandomVariableHip
+                value, slope = (x._sto(v) for v in table_apply(realizations, [f, df])) if realizations is not None else (x.apply(f), x.apply(df))
+            elif self.factory is None:
+                raise NotImplementedError("apply(TabulatedFunction) on this inner implementation needs the factory that made the variable")
+            elif x.isDeterministic():
+                value, slope = (self.factory.inner.createRandomVariable(x.getFiltrationTime(), g(x.doubleValue())) for g in (f, df))
+            else:
+                columns = table_apply_host(np.asarray(x.getRealizations(), dtype=np.float32), [f, df])
+                value, slope = (self.factory.inner.createRandomVariable(x.getFiltrationTime(), c) for c in columns)
+            return RandomVariableDifferentiableAAD(value, _Node("APPLY_TABLE", (self.node,), (slope,), 0.0), self.factory)
         raise NotImplementedError("UnsupportedOperationException: apply(lambda) has no derivative")
 
     # ---- the adjoint sweep
@@ -254,6 +273,7 @@ def _partial_times(nd, k, d, const):
         if k == 0: return None
         return d.mult(X.choose(one, zero)) if k == 1 else d.mult(X.choose(zero, one))
     if op == "AVERAGE": return d.average()
+    if op == "APPLY_TABLE": return d.mult(X)                                # X holds f'(x): x.apply(f.derivative())
     raise NotImplementedError(op)
 
 

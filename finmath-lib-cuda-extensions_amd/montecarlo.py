@@ -5,6 +5,8 @@ a RandomVariableFactory by injection (LIBORMarketModelCalibrationATMTest.java:35
 
     black_scholes_call_mc   MonteCarloBlackScholesModelTest.java:62-85,125-157 (Euler scheme on the log state,
                             numeraire exp(r t), European call)
+    local_volatility_call_mc  the same scheme under a tabulated surface σ(t, S): the volatility of a step is a row of the surface applied
+                            to the state by RandomVariable.apply(TabulatedFunction) (tabulated.py)
     heston_call_mc          BASELINE.json configs[2]: Euler full-truncation Heston driven by BrownianMotionHip
     geometric_asian_call_mc a call on the geometric average over the points of the time discretisation — a path-dependent product with a
                             closed form (geometric_asian_call_analytic), where a Brownian bridge over Sobol' points (sobol.py) has
@@ -49,6 +51,33 @@ def black_scholes_call_analytic(initial_value, risk_free_rate, volatility, matur
     d2 = d1 - volatility * sqrt(maturity)
     cdf = lambda z: 0.5 * (1.0 + erf(z / sqrt(2.0)))
     return initial_value * cdf(d1) - strike * exp(-risk_free_rate * maturity) * cdf(d2)
+
+
+def local_volatility_call_mc(brownian_motion, initial_value, risk_free_rate, times, spots, vols, maturity, strike):
+    """Value and standard error of a European call under a LOCAL-VOLATILITY surface σ(t, S) by Monte-Carlo: the log-Euler scheme
+    X_{i+1} = X_i + (r − σ_i²/2) Δt_i + σ_i ΔW_i with σ_i = σ(t_i, S_i), S = exp(X); payoff max(S_T − K, 0) / exp(r T).
+    The surface is tabulated: vols[j][k] = σ(times[j], spots[k]), piecewise constant in time (step i takes the last row whose time is not
+    after t_i, the first row before that), linear in the spot with constant extrapolation.  σ_i is that row applied to S by
+    RandomVariable.apply (tabulated.py): the state never leaves the device.  `maturity` must be a point of the time discretisation."""
+    import numpy as np
+    from .tabulated import TabulatedFunction
+    times = np.asarray(times, dtype=np.float64).ravel()
+    vols = np.asarray(vols, dtype=np.float64).reshape(times.size, -1)
+    slices = {}
+    td = brownian_motion.getTimeDiscretization()
+    x = brownian_motion.getRandomVariableForConstant(math.log(initial_value))
+    t, i = td.getTime(0), 0
+    while t < maturity - 1e-12:
+        dt = td.getTimeStep(i)
+        dw = brownian_motion.getBrownianIncrement(i, 0)
+        row = max(int(np.searchsorted(times, t + 1e-12, side="right")) - 1, 0)
+        if row not in slices: slices[row] = TabulatedFunction(spots, vols[row], "linear", "constant")
+        sigma = x.exp().apply(slices[row])
+        x = x.add(sigma.squared().mult(-0.5 * dt).add(risk_free_rate * dt)).addProduct(sigma, dw)
+        i += 1
+        t = td.getTime(i)
+    value = x.exp().sub(strike).floor(0.0).div(math.exp(risk_free_rate * maturity))
+    return value.getAverage(), value.getStandardError()
 
 
 def geometric_asian_call_mc(brownian_motion, initial_value, risk_free_rate, volatility, maturity, strike):

@@ -459,6 +459,42 @@ int fmhip_prefix_search(fmhip_vec v, const double* thresholds, int count, int re
                         int64_t* positions_out, double* sums_out, double* total_out);
 int fmhip_prefix_sums_host(const float* v, int64_t n, double* prefix_out);   /* the DEFINITION */
 
+/* Tabulated functions on the device: RandomVariable.apply for a CURVE — a function tabulated on knots and interpolated: a
+ * local-volatility slice, a Markov-functional numeraire, a payoff profile, an exercise boundary, an inverse empirical CDF — without the
+ * vector leaving the device.  The definition is host/tabulated_function.hpp, one header for the host and the device.
+ * A table: count = m knots (1 ... FMHIP_TABLE_MAX_KNOTS), finite and strictly increasing, and per function m + 1 segments of four fp64
+ *   coefficients C[s][0..3].  For an element x (fp32): X = (double)x; s = the number of knots <= X (0 ... m: the last knot belongs to the
+ *   right end segment); a = knots[max(s - 1, 0)], t = X - a; the result is (float)(((C3*t + C2)*t + C1)*t + C0), every operation rounded on
+ *   its own in fp64, one final narrowing.  A segment with C1 = C2 = C3 = 0 yields (float)C0 for every x in it, the infinite ones included.
+ *   A NaN x, and a result that is a NaN, is the quiet NaN 0x7fc00000.  At a knot that is an fp32 number the result is (float)values[i].
+ * fmhip_table_build (host only): the coefficients of one function from its values at the knots, coefficients_out[(count + 1) * 4].
+ *   interpolation: FMHIP_TABLE_PIECEWISE_CONSTANT (the value of the knot at or below x), FMHIP_TABLE_LINEAR, FMHIP_TABLE_CUBIC_SPLINE (natural),
+ *   FMHIP_TABLE_MONOTONE_CUBIC (Fritsch-Carlson slopes: weighted harmonic mean, three-point end formula).  extrapolation: FMHIP_TABLE_CONSTANT
+ *   (the end knot's value) or FMHIP_TABLE_LINEAR_EXTRAPOLATION (value and slope of the adjacent segment at the end knot).  derivative: 0, or 1
+ *   for the coefficients of the derivative, (C1, 2*C2, 3*C3, 0).  With count = 1 every mode is the constant; the cubic modes need count >= 3
+ *   and are the linear mode below that.
+ * fmhip_table_apply: n_tables (1 ... 4, count * n_tables <= 1024) functions on the same knots, coefficients[n_tables][count + 1][4], applied
+ *   to every element of x in ONE launch that reads x once: out[0 ... n_tables) are new, materialised vectors of x's size.  The device's
+ *   bits EQUAL fmhip_table_apply_host's.  Elementwise: with a device list every shard runs the call on its block.
+ * fmhip_table_apply_host (host only): the DEFINITION over a host float array of n (1 ... 2^31) elements, out[f][p]; needs no device.
+ * Everything is checked on the host before anything is flushed or launched: counts out of range, a NULL pointer, a handle of 0, knots or
+ * values that are not finite, knots that are not strictly increasing, an unknown mode -> FMHIP_ERR_INVALID_ARGUMENT;
+ * FMHIP_ERR_INVALID_HANDLE.  A vector whose values were given up is the error a read of it is.  A build without the kernel answers
+ * FMHIP_ERR_UNSUPPORTED; it never falls back. */
+#define FMHIP_TABLE_MAX_KNOTS            1024
+#define FMHIP_TABLE_PIECEWISE_CONSTANT   0
+#define FMHIP_TABLE_LINEAR               1
+#define FMHIP_TABLE_CUBIC_SPLINE         2
+#define FMHIP_TABLE_MONOTONE_CUBIC       3
+#define FMHIP_TABLE_CONSTANT             0   /* extrapolation: the end knot's value                          */
+#define FMHIP_TABLE_LINEAR_EXTRAPOLATION 1   /* extrapolation: value and slope of the adjacent segment there */
+int fmhip_table_build(const double* knots, const double* values, int count, int interpolation, int extrapolation, int derivative,
+                      double* coefficients_out /* (count+1)*4 */);
+int fmhip_table_apply(fmhip_vec x, const double* knots, int count, const double* coefficients /* n_tables*(count+1)*4 */, int n_tables,
+                      fmhip_vec* out /* n_tables new, materialised vectors */);
+int fmhip_table_apply_host(const float* x, int64_t n, const double* knots, int count, const double* coefficients, int n_tables,
+                           float* const* out);
+
 /* Polynomial regression in one pass: the normal equations of a regression on a POLYNOMIAL basis — the Longstaff-Schwartz
  * basis of a product on several underlyings — from the state vectors alone, and the fitted polynomial as a new vector.  The monomials are
  * never in memory: the moments kernel forms them in registers as the operands of fmhip_cross_moments_wide's pass.

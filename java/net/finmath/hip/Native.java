@@ -110,6 +110,13 @@ final class Native {
 	static native int prefixSearch(long v, double[] thresholds, boolean relative, long[] positionsOut, double[] sumsOut, double[] totalOutOrNull);
 	/** The definition of the prefix sums over a host array. */
 	static native int prefixSumsHost(float[] v, double[] prefixOut);
+	// ---- tabulated functions on the device: RandomVariable.apply for a curve; the device's bits are those of tableApplyHost
+	/** coefficientsOut[(knots.length + 1) * 4]: the segments of one function from its values at the knots; interpolation 0 piecewise constant, 1 linear, 2 natural cubic spline, 3 monotone cubic; extrapolation 0 constant, 1 linear; derivative 0 or 1. */
+	static native int tableBuild(double[] knots, double[] values, int interpolation, int extrapolation, int derivative, double[] coefficientsOut);
+	/** out[f] = a new vector: function f of coefficients[nTables][knots.length + 1][4] at every element of x; 1 ... 4 functions on the same knots from one launch that reads x once. */
+	static native int tableApply(long x, double[] knots, double[] coefficients, int nTables, long[] out);
+	/** The definition of tableApply over a host array: outColumns holds nTables columns of x.length floats. */
+	static native int tableApplyHost(float[] x, double[] knots, double[] coefficients, int nTables, float[] outColumns);
 	// ---- polynomial regression in one pass: the normal equations of a polynomial basis from the state vectors, the monomials formed in registers
 	/** crossMomentsWide for the regressors [monomials of states..., extraX...] and the dependents y; exponents holds states.length ints (0 ... 6) per monomial, a row of zeros is the constant 1; a handle of 0 in extraX is the constant 1.  Bit for bit the sums of crossMomentsWide on the materialised monomials. */
 	static native int polynomialCrossMoments(long[] states, int[] exponents, long[] extraX, long[] y, double[] sumsOut);

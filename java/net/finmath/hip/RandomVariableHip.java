@@ -437,6 +437,12 @@ public class RandomVariableHip implements RandomVariable {
 		if(isDeterministic()) {
 			return constant(time, function.applyAsDouble(valueIfNonStochastic));
 		}
+		if(function instanceof TabulatedFunctionHip) {						// a curve runs on the device: one launch, the vector stays in HBM (fmhip_table_apply)
+			final TabulatedFunctionHip table = (TabulatedFunctionHip)function;
+			final long[] out = new long[1];
+			Native.check(Native.tableApply(deviceHandle(), table.getKnots(), table.getCoefficients(), 1, out));
+			return new RandomVariableHip(time, new DeviceVector(out[0], size()));
+		}
 		final double[] values = getRealizations();						// the twin maps on the host (twin:667-676); RandomVariableCuda throws (:1146-1159)
 		for(int i = 0; i < values.length; i++) {
 			values[i] = function.applyAsDouble(values[i]);

@@ -312,6 +312,30 @@ FMJ(jint, prefixSumsHost)(JNIEnv* env, jclass, jfloatArray v, jdoubleArray prefi
     if (!pv.p || !po.p || po.length() < pv.length()) return FMHIP_ERR_INVALID_ARGUMENT;
     return fmhip_prefix_sums_host(pv.p, pv.length(), po.p);
 }
+// ---------------------------------------------------------------- tabulated functions on the device
+FMJ(jint, tableBuild)(JNIEnv* env, jclass, jdoubleArray knots, jdoubleArray values, jint interpolation, jint extrapolation, jint derivative, jdoubleArray coefficientsOut) {
+    Pin<jdouble> pk(env, knots, JNI_ABORT); Pin<jdouble> pv(env, values, JNI_ABORT); Pin<jdouble> po(env, coefficientsOut);
+    if (!pk.p || !pv.p || !po.p || pv.length() < pk.length() || (int64_t)po.length() < ((int64_t)pk.length() + 1) * 4) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_table_build(pk.p, pv.p, (int)pk.length(), (int)interpolation, (int)extrapolation, (int)derivative, po.p);
+}
+FMJ(jint, tableApply)(JNIEnv* env, jclass, jlong x, jdoubleArray knots, jdoubleArray coefficients, jint nTables, jlongArray out) {
+    Pin<jdouble> pk(env, knots, JNI_ABORT); Pin<jdouble> pc(env, coefficients, JNI_ABORT);
+    if (!pk.p || !pc.p || !out || nTables < 1 || nTables > 4 || env->GetArrayLength(out) < nTables) return FMHIP_ERR_INVALID_ARGUMENT;
+    if ((int64_t)pc.length() < (int64_t)nTables * ((int64_t)pk.length() + 1) * 4) return FMHIP_ERR_INVALID_ARGUMENT;
+    fmhip_vec h[4] = { 0, 0, 0, 0 };
+    const int st = fmhip_table_apply(x, pk.p, (int)pk.length(), pc.p, (int)nTables, h);
+    if (st == FMHIP_OK) { jlong o[4]; for (int f = 0; f < nTables; ++f) o[f] = (jlong)h[f]; env->SetLongArrayRegion(out, 0, (jsize)nTables, o); }
+    return st;
+}
+FMJ(jint, tableApplyHost)(JNIEnv* env, jclass, jfloatArray x, jdoubleArray knots, jdoubleArray coefficients, jint nTables, jfloatArray outColumns) {
+    Pin<jfloat> px(env, x, JNI_ABORT); Pin<jdouble> pk(env, knots, JNI_ABORT); Pin<jdouble> pc(env, coefficients, JNI_ABORT); Pin<jfloat> po(env, outColumns);
+    if (!px.p || !pk.p || !pc.p || !po.p || nTables < 1 || nTables > 4) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int64_t n = px.length();
+    if ((int64_t)pc.length() < (int64_t)nTables * ((int64_t)pk.length() + 1) * 4 || (int64_t)po.length() < (int64_t)nTables * n) return FMHIP_ERR_INVALID_ARGUMENT;
+    float* columns[4] = { nullptr, nullptr, nullptr, nullptr };
+    for (int f = 0; f < nTables; ++f) columns[f] = po.p + (int64_t)f * n;
+    return fmhip_table_apply_host(px.p, n, pk.p, (int)pk.length(), pc.p, (int)nTables, columns);
+}
 // ---------------------------------------------------------------- polynomial regression in one pass: the monomials of the states are formed in registers
 // exponents: states.length (nStates) entries per term, each 0 … 6, as ints; anything outside a byte is refused here, the rest by the library
 static bool poly_exponents(const jint* e, int64_t count, std::vector<uint8_t>& out) {
