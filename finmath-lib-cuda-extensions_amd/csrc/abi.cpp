@@ -896,6 +896,32 @@ int fmhip_table_apply(fmhip_vec x, const double* knots, int count, const double*
     return guarded([&] { Engine::get().table_apply(x, knots, count, coefficients, n_tables, out); });
 }
 
+// ---------------------------------------------------------------- kernel regression (kreg_engine.hpp)
+extern "C++" {
+namespace fm {
+int kernel_moments_local(fmhip_vec key, const double* points, const double* bandwidths, int n_points, int kernel, int order, const fmhip_vec* y, int n_y, double* sums) {
+    return guarded([&] { Engine::get().kernel_moments_pass(key, points, bandwidths, n_points, kernel, order, y, n_y, sums); });
+}
+}
+}
+int fmhip_kernel_moments_host(const float* key, int64_t n, const double* points, const double* bandwidths, int n_points, int kernel, int order, const float* const* y, int n_y, double* sums_out) {
+    return host_only([&] { fm::kernel_moments_host_checked(key, n, points, bandwidths, n_points, kernel, order, y, n_y, sums_out); });
+}
+int fmhip_kernel_moments(fmhip_vec key, const double* points, const double* bandwidths, int n_points, int kernel, int order, const fmhip_vec* y, int n_y, double* sums_out) {
+    FRONT(kernel_moments(key, points, bandwidths, n_points, kernel, order, y, n_y, sums_out));
+    if (te::active()) {
+        const int rc = host_only([&] { fm::kernel_moments_check(key, points, bandwidths, n_points, kernel, order, y, n_y, sums_out); });
+        if (rc != FMHIP_OK) return rc;
+        const std::vector<fmhip_vec> all = te_operands(key, y, n_y, nullptr, 0);      // key and y as ONE list
+        TE_LOCAL(all.data(), 1 + n_y, L, fmhip_kernel_moments(L[0], points, bandwidths, n_points, kernel, order, L + 1, n_y, sums_out));
+    }
+    return guarded([&] {
+        Engine& e = Engine::get();
+        e.kernel_moments_pass(key, points, bandwidths, n_points, kernel, order, y, n_y, sums_out);
+        comm_add_sums(e, sums_out, (size_t)n_points * (size_t)(order == 0 ? 1 + n_y : 3 + 2 * n_y));      // ONE gather, rank order: the sums of the global sample
+    });
+}
+
 // The one call of a caller that values product after product: the engine lock is held for the bookkeeping (graph → launch → commit),
 // NOT while the device computes — other threads record and launch meanwhile.  The moments arrive in a slot of pinned memory of their
 // own; this thread polls its flag, then takes the lock again to copy them out and give the launch's buffers back.

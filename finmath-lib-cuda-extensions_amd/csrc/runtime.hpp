@@ -417,6 +417,11 @@ public:
     // anything is flushed or launched; out is written only when the call succeeds.
     void table_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, fmhip_vec* out);
 
+    // kernel regression (kreg_engine.hpp): the kernel-weighted local moments of n_y vectors at n_points points of `key`
+    // (host/kernel_regression.hpp), sums_out[n_points][order 0: 1 + n_y, order 1: 3 + 2 n_y], from ONE launch.  Arguments are checked before
+    // anything is flushed or launched.
+    void kernel_moments_pass(fmhip_vec key, const double* points, const double* bandwidths, int n_points, int kernel, int order, const fmhip_vec* y, int n_y, double* sums_out);
+
     // programs
     fmhip_program program_create(const fmhip_prog_op* ops, int n_ops, int n_in, const int32_t* outs, int n_out,
                                  const int32_t* reds, int n_red);
@@ -827,5 +832,9 @@ void poly_check_moments(const fmhip_vec* states, int n_states, const uint8_t* ex
 void poly_check_evaluate(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const double* coefficients, const fmhip_vec* out);
 void poly_cross_moments_host(const float* const* states, int64_t n, int n_states, const uint8_t* exponents, int n_terms, const float* const* extra_x, int n_extra, const float* const* y, int n_y, double* sums_out);
 void poly_evaluate_host(const float* const* states, int64_t n, int n_states, const uint8_t* exponents, int n_terms, const float* const* extra_x, int n_extra, const double* coefficients, float* out);
+// the same for fmhip_kernel_moments (kreg_engine.hpp; the rules are fmhost::kernelMomentsCheck's, host/kernel_regression.hpp), and the host
+// definition: both throw FMHIP_ERR_INVALID_ARGUMENT
+void kernel_moments_check(fmhip_vec key, const double* points, const double* bandwidths, int n_points, int kernel, int order, const fmhip_vec* y, int n_y, const double* sums_out);
+void kernel_moments_host_checked(const float* key, int64_t n, const double* points, const double* bandwidths, int n_points, int kernel, int order, const float* const* y, int n_y, double* sums_out);
 
 } // namespace fm

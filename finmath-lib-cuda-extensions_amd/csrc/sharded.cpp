@@ -877,6 +877,22 @@ int binned_evaluate(fmhip_vec key, const double* bounds, int n_bins, const fmhip
     });
 }
 
+// Kernel regression (kreg_engine.hpp): the shards' sums add in shard order.
+int kernel_moments(fmhip_vec key, const double* points, const double* bandwidths, int n_points, int kernel, int order, const fmhip_vec* y, int n_y, double* sums_out) {
+    return fronted([&](Shards& s) {
+        kernel_moments_check(key, points, bandwidths, n_points, kernel, order, y, n_y, sums_out);
+        const std::vector<fmhip_vec> all = binned_all(key, y, n_y, nullptr, 0);      // key, y…
+        const int64_t n = front_size(s, all.data(), (int)all.size(), "kernel moments", false);
+        const size_t m = (size_t)n_points * (size_t)(order == 0 ? 1 + n_y : 3 + 2 * n_y);
+        std::vector<std::vector<double>> per((size_t)s.D(), std::vector<double>(m, 0.0));
+        const std::vector<char> took = post_where_paths(s, n, [&](Worker& w) {
+            const std::vector<fmhip_vec> l = localize(w, all.data(), (int)all.size());
+            return kernel_moments_local(l[0], points, bandwidths, n_points, kernel, order, n_y ? l.data() + 1 : nullptr, n_y, per[(size_t)w.shard].data());
+        });
+        add_sums(per, m, sums_out, &took);
+    });
+}
+
 // The device sort (sort_engine.hpp).  The order of a sample that is spread over several shards needs an exchange of elements between them,
 // which nothing does: a list of more than one shard answers FMHIP_ERR_UNSUPPORTED, never the order of a part.  A list of ONE shard is that
 // shard's call.

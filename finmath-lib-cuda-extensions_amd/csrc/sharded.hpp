@@ -38,6 +38,8 @@ int xmom_wide_local(const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, do
 int xmom_poly_local(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const fmhip_vec* y, int n_y, double* sums);
 // the binned cross moments of the calling thread's engine (abi.cpp; a shard's worker calls it)
 int binned_xmom_local(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, int64_t* counts, double* sums);
+// the kernel moments of the calling thread's engine (abi.cpp; a shard's worker calls it)
+int kernel_moments_local(fmhip_vec key, const double* points, const double* bandwidths, int n_points, int kernel, int order, const fmhip_vec* y, int n_y, double* sums);
 void os_counts_from_passes(const double* bounds, int n_bounds, int64_t* counts_out, const std::function<void(const double*, int, uint64_t*)>& pass);
 namespace front {
 int init_devices(const int* devices, int count);
@@ -78,6 +80,7 @@ int prefix_sums(fmhip_vec v, int mode, fmhip_vec* out, double* total_out);      
 int prefix_sums_at(fmhip_vec v, const int64_t* positions, int count, double* sums_out);
 int table_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, fmhip_vec* out);      // per shard
 int prefix_search(fmhip_vec v, const double* thresholds, int count, int relative, int64_t* positions_out, double* sums_out, double* total_out);
+int kernel_moments(fmhip_vec key, const double* points, const double* bandwidths, int n_points, int kernel, int order, const fmhip_vec* y, int n_y, double* sums_out);      // sums add in shard order
 int polynomial_cross_moments(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const fmhip_vec* y, int n_y, double* sums_out);
 int polynomial_evaluate(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const double* coefficients, fmhip_vec* out);
 int program_create(const fmhip_prog_op* ops, int n_ops, int n_inputs, const int32_t* out_values, int n_outputs, const int32_t* reduce_values, int n_reduce, fmhip_program* out);

@@ -8,6 +8,9 @@ a RandomVariableFactory by injection (LIBORMarketModelCalibrationATMTest.java:35
     local_volatility_call_mc  the same scheme under a tabulated surface σ(t, S): the volatility of a step is a row of the surface applied
                             to the state by RandomVariable.apply(TabulatedFunction) (tabulated.py)
     heston_call_mc          BASELINE.json configs[2]: Euler full-truncation Heston driven by BrownianMotionHip
+    stochastic_local_volatility_call_mc  Heston's variance under a leverage function calibrated to a Dupire surface by the particle
+                            method: E[v | ln S] re-estimated at every step by kernel regression on the device (kernel_regression.py,
+                            DESIGN.md §4.19)
     geometric_asian_call_mc a call on the geometric average over the points of the time discretisation — a path-dependent product with a
                             closed form (geometric_asian_call_analytic), where a Brownian bridge over Sobol' points (sobol.py) has
                             something to show
@@ -234,6 +237,53 @@ def heston_call_mc(brownian_motion, initial_value, risk_free_rate, v0, kappa, th
     payoff = x.exp().sub(strike).floor(0.0)
     value = payoff.div(math.exp(risk_free_rate * maturity))
     return value.getAverage(), value
+
+
+def stochastic_local_volatility_call_mc(brownian_motion, initial_value, risk_free_rate, times, spots, dupire_vols, v0, kappa, theta, xi, rho, maturity, strike,
+                                        n_points=64, order=0):
+    """Value and standard error of a European call under a LOCAL-STOCHASTIC-VOLATILITY model calibrated on the fly by the particle method
+    (Guyon, Henry-Labordère): heston_call_mc's variance scheme (Euler, full truncation), local_volatility_call_mc's surface lookup, and the
+    leverage function L(t_i, S)² = σ_Dupire(t_i, S)² / max(E[v⁺_i | ln S_i], 1e-8), re-estimated at EVERY time step by kernel regression
+    on X = ln S (kernel_regression.py, DESIGN.md §4.19: Epanechnikov, n_points uniform points between the 0.1 % and 99.9 % quantiles of X,
+    bandwidth max(3 · Silverman, 1.5 · spacing), local constant or local linear fit, linear interpolation between the points):
+        a_i² = L_i² v⁺_i,   X_{i+1} = X_i + (r − a_i²/2) Δt + a_i ΔW¹,   v_{i+1} = v_i + κ(θ − v⁺_i) Δt + ξ sqrt(v⁺_i) (ρ ΔW¹ + sqrt(1−ρ²) ΔW²).
+    Step 0, where the state is a constant, uses σ²/v0.  A deterministic variance (ξ = 0) is its own conditional expectation: the model is
+    then the local-volatility model of the surface.  Written in RandomVariable methods, kernel_moments and apply only: per step nothing
+    leaves the device but two quantiles, a variance and the n_points sums.  Uses factors 0 and 1 of the Brownian motion; `maturity` must be
+    a point of the time discretisation."""
+    import numpy as np
+    from .kernel_regression import MonteCarloConditionalExpectationKernelRegression
+    from .tabulated import TabulatedFunction
+    times = np.asarray(times, dtype=np.float64).ravel()
+    vols = np.asarray(dupire_vols, dtype=np.float64).reshape(times.size, -1)
+    slices = {}
+    td = brownian_motion.getTimeDiscretization()
+    x = brownian_motion.getRandomVariableForConstant(math.log(initial_value))
+    v = brownian_motion.getRandomVariableForConstant(v0)
+    rho_c = math.sqrt(1.0 - rho * rho)
+    t, i = td.getTime(0), 0
+    while t < maturity - 1e-12:
+        dt = td.getTimeStep(i)
+        dw1 = brownian_motion.getBrownianIncrement(i, 0)
+        row = max(int(np.searchsorted(times, t + 1e-12, side="right")) - 1, 0)
+        if row not in slices: slices[row] = TabulatedFunction(spots, vols[row], "linear", "constant")
+        dupire_variance = x.exp().apply(slices[row]).squared()
+        vp = v.floor(0.0)
+        if vp.isDeterministic(): conditional = vp                  # E[v⁺ | X] of a constant (step 0: v0)
+        elif x.isDeterministic(): conditional = vp.average()
+        else: conditional = MonteCarloConditionalExpectationKernelRegression(x, n_points, None, "epanechnikov", order).getConditionalExpectation(vp)
+        variance = dupire_variance.mult(vp).div(conditional.floor(1e-8))      # a² = σ² v⁺ / max(E[v⁺ | X], 1e-8)
+        x = x.add(risk_free_rate * dt).addProduct(variance, -0.5 * dt).addProduct(variance.sqrt(), dw1)
+        if xi != 0.0:
+            dw2 = brownian_motion.getBrownianIncrement(i, 1)
+            dz = dw1.mult(rho).addProduct(dw2, rho_c)
+            v = v.addProduct(vp.bus(theta), kappa * dt).addProduct(vp.sqrt().mult(xi), dz)
+        else:
+            v = v.addProduct(vp.bus(theta), kappa * dt)
+        i += 1
+        t = td.getTime(i)
+    value = x.exp().sub(strike).floor(0.0).div(math.exp(risk_free_rate * maturity))
+    return value.getAverage(), value.getStandardError()
 
 
 def bermudan_option_mc(brownian_motion, initial_value, risk_free_rate, volatility, exercise_dates, strike, call=False, basis_order=3, bins=0):

@@ -495,6 +495,43 @@ int fmhip_table_apply(fmhip_vec x, const double* knots, int count, const double*
 int fmhip_table_apply_host(const float* x, int64_t n, const double* knots, int count, const double* coefficients, int n_tables,
                            float* const* out);
 
+/* Kernel regression on the device: kernel-weighted LOCAL MOMENTS of up to four vectors at a grid of points of a key vector
+ * in one pass — E[y | x = p_q] as a curve: the inner step of the particle method for local-stochastic-volatility calibration
+ * (E[v_t | S_t = S] at every time step), kernel density estimates, smooth exercise boundaries, exposure profiles — without the vectors
+ * leaving the device.  The definition is host/kernel_regression.hpp, one header for the host and the device.
+ * points[n_points]: finite, non-decreasing doubles, 1 <= n_points <= FMHIP_KERNEL_MAX_POINTS; bandwidths[n_points]: finite, > 0.  Per point,
+ *   one fp64 rounding each: lower_q = p_q - h_q, upper_q = p_q + h_q, rh_q = 1.0 / h_q.  BOTH lower and upper must be non-decreasing in q (one
+ *   bandwidth for all points always is; bandwidths that widen in the tails are when they widen slowly enough).
+ * Membership: with xd = (double)key[i], element i is a member of point q iff lower_q < xd && xd < upper_q.  A NaN or infinite key is a
+ *   member of no point.
+ * Weight of a member, in fp64, every operation rounded on its own: d = xd - p_q; u = d*rh_q; t = 1 - u*u; w = 1 (FMHIP_KERNEL_UNIFORM),
+ *   1 - |u| (TRIANGULAR), t (EPANECHNIKOV), t*t (QUARTIC), (t*t)*t (TRIWEIGHT); then w = w < 0 ? 0 : w.  No Gaussian: its support is not
+ *   compact.
+ * sums_out[n_points][entries], the fp64 SUMS over the members, yd_m = (double)y_m[i], n_y = 0 ... 4:
+ *   order 0: [w, w*yd_0, ...]                                         entries = 1 + n_y
+ *   order 1: [w, e1 = w*d, e1*d, w*yd_0, ..., e1*yd_0, ...]           entries = 3 + 2*n_y
+ *   Normalisation constants (3/4, 1/(n*h)) are the caller's.  No float atomics.  The bits of one (point, entry) sum are a function of n, of
+ *   which path positions are members and of the values there — not of the other points, n_y, or the position of a vector in y; w, w*d and
+ *   w*d*d are the same bits for both orders.  ONE launch.
+ * fmhip_kernel_moments_host: the DEFINITION over host float arrays; needs no device; a point's members are added in path order.  The
+ *   device's sums agree with any summation order's to 2*members*2^-53*sum|terms| per (point, entry).
+ * Everything is checked on the host before anything is flushed or launched, by one function for the device and the host entry point:
+ * counts out of range, an unknown kernel or order, a NULL pointer, points or bandwidths that are not finite, a bandwidth <= 0, points, lower
+ * or upper that decrease, a 0 among y or as the key, n == 0 -> FMHIP_ERR_INVALID_ARGUMENT; vectors of different sizes ->
+ * FMHIP_ERR_SIZE_MISMATCH; FMHIP_ERR_INVALID_HANDLE.  A vector whose values were given up is the error a read of it is.  A build without the
+ * kernel answers FMHIP_ERR_UNSUPPORTED; it never falls back.  With a device list the sums add in shard order; with an expectation
+ * communicator they are those of the GLOBAL sample (one gather, added in rank order). */
+#define FMHIP_KERNEL_MAX_POINTS   256
+#define FMHIP_KERNEL_UNIFORM      0
+#define FMHIP_KERNEL_TRIANGULAR   1
+#define FMHIP_KERNEL_EPANECHNIKOV 2
+#define FMHIP_KERNEL_QUARTIC      3
+#define FMHIP_KERNEL_TRIWEIGHT    4
+int fmhip_kernel_moments(fmhip_vec key, const double* points, const double* bandwidths, int n_points, int kernel, int order,
+                         const fmhip_vec* y, int n_y, double* sums_out);
+int fmhip_kernel_moments_host(const float* key, int64_t n, const double* points, const double* bandwidths, int n_points, int kernel, int order,
+                              const float* const* y, int n_y, double* sums_out);
+
 /* Polynomial regression in one pass: the normal equations of a regression on a POLYNOMIAL basis — the Longstaff-Schwartz
  * basis of a product on several underlyings — from the state vectors alone, and the fitted polynomial as a new vector.  The monomials are
  * never in memory: the moments kernel forms them in registers as the operands of fmhip_cross_moments_wide's pass.

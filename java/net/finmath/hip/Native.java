@@ -117,6 +117,11 @@ final class Native {
 	static native int tableApply(long x, double[] knots, double[] coefficients, int nTables, long[] out);
 	/** The definition of tableApply over a host array: outColumns holds nTables columns of x.length floats. */
 	static native int tableApplyHost(float[] x, double[] knots, double[] coefficients, int nTables, float[] outColumns);
+	// ---- kernel regression: kernel-weighted local moments of up to 4 vectors at up to 256 points of a key from one launch
+	/** sumsOut[points.length][order 0: 1 + y.length; order 1: 3 + 2 y.length]: per point the fp64 sums [w, w*y...] or [w, w*d, w*d*d, w*y..., w*d*y...] over its members (lower &lt; key &lt; upper); kernel 0 uniform, 1 triangular, 2 Epanechnikov, 3 quartic, 4 triweight. */
+	static native int kernelMoments(long key, double[] points, double[] bandwidths, int kernel, int order, long[] y, double[] sumsOut);
+	/** The definition of kernelMoments over host arrays: yColumns holds nY columns of key.length floats. */
+	static native int kernelMomentsHost(float[] key, double[] points, double[] bandwidths, int kernel, int order, float[] yColumns, int nY, double[] sumsOut);
 	// ---- polynomial regression in one pass: the normal equations of a polynomial basis from the state vectors, the monomials formed in registers
 	/** crossMomentsWide for the regressors [monomials of states..., extraX...] and the dependents y; exponents holds states.length ints (0 ... 6) per monomial, a row of zeros is the constant 1; a handle of 0 in extraX is the constant 1.  Bit for bit the sums of crossMomentsWide on the materialised monomials. */
 	static native int polynomialCrossMoments(long[] states, int[] exponents, long[] extraX, long[] y, double[] sumsOut);

@@ -336,6 +336,24 @@ FMJ(jint, tableApplyHost)(JNIEnv* env, jclass, jfloatArray x, jdoubleArray knots
     for (int f = 0; f < nTables; ++f) columns[f] = po.p + (int64_t)f * n;
     return fmhip_table_apply_host(px.p, n, pk.p, (int)pk.length(), pc.p, (int)nTables, columns);
 }
+// ---------------------------------------------------------------- kernel regression: kernel-weighted local moments at a grid of points of a key
+static int64_t kernel_entries(int order, int64_t ny) { return order == 0 ? 1 + ny : 3 + 2 * ny; }
+FMJ(jint, kernelMoments)(JNIEnv* env, jclass, jlong key, jdoubleArray points, jdoubleArray bandwidths, jint kernel, jint order, jlongArray y, jdoubleArray sumsOut) {
+    Pin<jdouble> pp(env, points, JNI_ABORT); Pin<jdouble> pb(env, bandwidths, JNI_ABORT); Pin<jlong> py(env, y, JNI_ABORT); Pin<jdouble> po(env, sumsOut);
+    if (!pp.p || !pb.p || !po.p || pb.length() < pp.length()) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int64_t q = pp.length(), ny = py.p ? py.length() : 0;
+    if (ny > 4 || (order != 0 && order != 1) || (int64_t)po.length() < q * kernel_entries(order, ny)) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_kernel_moments(key, pp.p, pb.p, (int)q, (int)kernel, (int)order, ny ? (const fmhip_vec*)py.p : nullptr, (int)ny, po.p);
+}
+FMJ(jint, kernelMomentsHost)(JNIEnv* env, jclass, jfloatArray key, jdoubleArray points, jdoubleArray bandwidths, jint kernel, jint order, jfloatArray yColumns, jint nY, jdoubleArray sumsOut) {
+    Pin<jfloat> pk(env, key, JNI_ABORT); Pin<jdouble> pp(env, points, JNI_ABORT); Pin<jdouble> pb(env, bandwidths, JNI_ABORT); Pin<jfloat> py(env, yColumns, JNI_ABORT); Pin<jdouble> po(env, sumsOut);
+    if (!pk.p || !pp.p || !pb.p || !po.p || pb.length() < pp.length() || nY < 0 || nY > 4 || (order != 0 && order != 1)) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int64_t n = pk.length(), q = pp.length();
+    std::vector<const float*> ys;
+    if (!binned_columns(py.p, py.p ? py.length() : 0, n, nY, 0, ys)) return FMHIP_ERR_INVALID_ARGUMENT;
+    if ((int64_t)po.length() < q * kernel_entries(order, nY)) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_kernel_moments_host(pk.p, n, pp.p, pb.p, (int)q, (int)kernel, (int)order, nY ? ys.data() : nullptr, nY, po.p);
+}
 // ---------------------------------------------------------------- polynomial regression in one pass: the monomials of the states are formed in registers
 // exponents: states.length (nStates) entries per term, each 0 … 6, as ints; anything outside a byte is refused here, the rest by the library
 static bool poly_exponents(const jint* e, int64_t count, std::vector<uint8_t>& out) {
