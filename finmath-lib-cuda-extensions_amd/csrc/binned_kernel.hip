@@ -14,62 +14,21 @@
 //
 // Order of the additions of one (bin, product): a lane adds its elements tile by tile, element by element (an element of another bin, or past
 // n, adds nothing — which equals adding +0.0: a running sum that starts at +0.0 is never -0.0); the 64 lanes of a wave by the plain butterfly
-// (bit 5 of the lane first); the four waves in order; the workgroups' partials lane-strided by the last workgroup of the slice to arrive,
-// then the butterfly.  The grid along x is binned_blocks(n) and the element a lane holds is a function of n alone: the bits of a sum depend on
+// (bit 5 of the lane first); the tail — the waves, the workgroups of a slice, the arrivals, the host's flag — is side_pass_device.hpp's.
+// The grid along x is binned_blocks(n) and the element a lane holds is a function of n alone: the bits of a sum depend on
 // n, on which positions fall into the bin and on the two vectors' values there — not on the other vectors, roles, positions in the lists,
 // the slicing, or the bounds of other bins.
 // The kernels trust their arguments: the launchers refuse what binned_*_shape_ok refuse.  No register array is indexed at run time: no scratch.
 #include <hip/hip_runtime.h>
 
 #include "binned_kernel.h"
+#include "os_device.hpp"
+#include "side_pass_device.hpp"
 
 namespace fm {
 
 typedef float bn_f32x4 __attribute__((ext_vector_type(4)));
 typedef bn_f32x4 __attribute__((address_space(1))) bn_gfloat4;
-
-__device__ __forceinline__ double bn_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// true, for the whole workgroup, in the LAST of `members` workgroups to arrive at `counter` (zero before the launch, zero again after the
-// last arrival); what the others wrote before they arrived is visible to it (fm_xmom_kernel's protocol: release, agent-scope add, acquire)
-__device__ __forceinline__ bool bn_arrive_last(uint32_t* counter, const uint32_t members, uint32_t* last)
-{
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-        const uint32_t arrived = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        *last = (arrived == members - 1u) ? 1u : 0u;
-        if (*last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    const bool r = *last != 0u;
-    if (r) __threadfence();
-    return r;
-}
-
-// c[bin] += 1 for every lane with `valid` — integers, so the order does not matter.  The most frequent bins of the wave go first, one add of
-// a population count each (same-address LDS atomics serialise); what is left adds lane by lane.
-__device__ __forceinline__ void bn_count(uint32_t* c, const uint32_t bin, bool valid)
-{
-    uint64_t pending = __ballot(valid);
-#pragma unroll 1
-    for (int round = 0; round < 3 && pending != 0ull; ++round) {
-        const int leader = __ffsll((long long)pending) - 1;
-        const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)bin, leader);
-        const uint64_t same = __ballot(valid && bin == b0);
-        const uint32_t k = (uint32_t)__popcll(same);
-        if ((int)(threadIdx.x & 63u) == leader) atomicAdd(c + b0, k);
-        valid = valid && bin != b0;
-        pending &= ~same;
-        if (k < 8u) break;
-    }
-    if (valid) atomicAdd(c + bin, 1u);
-}
 
 // bounds below kd among the 63 padded ones: six levels, the last index read is 62
 __device__ __forceinline__ uint32_t bn_bin_of(const double* b, const double kd)
@@ -94,7 +53,6 @@ __global__ void __launch_bounds__(FM_BINNED_BLOCK) fm_binned_xmom_kernel(const D
     __shared__ double wave_part[FM_BINNED_BLOCK / 64][FM_BINNED_ENTRIES];
     __shared__ double b[64];
     __shared__ uint32_t cnt[FM_BINNED_MAX_BINS];
-    __shared__ uint32_t last;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t slice = blockIdx.y;
     const uint32_t qe = A.entries_per_bin;
@@ -130,7 +88,7 @@ __global__ void __launch_bounds__(FM_BINNED_BLOCK) fm_binned_xmom_kernel(const D
             const float k = kv[j];
             const bool valid = (int64_t)i4 * 4 + j < n && k == k;
             const uint32_t bin = bn_bin_of(b, (double)k);
-            if (counting) bn_count(cnt, bin, valid);
+            if (counting) os_lds_add(cnt, bin, valid);                  // integers: the order does not matter
             const uint32_t local = bin - b_lo;
             if (valid && local < nb) {
                 double* a = acc + (size_t)(local * qe) * FM_BINNED_BLOCK + tid;
@@ -163,26 +121,20 @@ __global__ void __launch_bounds__(FM_BINNED_BLOCK) fm_binned_xmom_kernel(const D
         if (c) __hip_atomic_fetch_add(A.counts_dev + tid, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     for (uint32_t e = 0; e < used; ++e) {
-        const double v = bn_wave_sum(acc[e * FM_BINNED_BLOCK + tid]);
+        const double v = pass_wave_sum(acc[e * FM_BINNED_BLOCK + tid]);
         if (lane == 0u) wave_part[wave][e] = v;
     }
     __syncthreads();
-    double* part = A.partials + (size_t)slice * FM_BINNED_ENTRIES * gridDim.x;
-    if (tid < used) part[(size_t)tid * gridDim.x + blockIdx.x] = ((wave_part[0][tid] + wave_part[1][tid]) + wave_part[2][tid]) + wave_part[3][tid];
-    if (!bn_arrive_last(A.counters + slice, gridDim.x, &last)) return;
-    for (uint32_t e = wave; e < used; e += FM_BINNED_BLOCK / 64) {
-        double s = 0.0;
-        for (uint32_t w = lane; w < gridDim.x; w += 64u) s += part[(size_t)e * gridDim.x + w];
-        s = bn_wave_sum(s);
-        if (lane == 0u) A.out_host[(size_t)b_lo * qe + e] = s;
-    }
-    if (counting && tid < A.n_bins) {
-        A.counts_host[tid] = __hip_atomic_load(A.counts_dev + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(A.counts_dev + tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __threadfence_system();
-    if (!bn_arrive_last(A.counters + FM_BINNED_MAX_SLICES, gridDim.y, &last)) return;
-    if (tid == 0u) __hip_atomic_store(A.done_flag, A.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    // the counts go to pinned memory with the sums of slice 0; the device array is zero again behind them
+    const auto publish_counts = [&] {
+        if (counting && tid < A.n_bins) {
+            A.counts_host[tid] = __hip_atomic_load(A.counts_dev + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(A.counts_dev + tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    };
+    pass_combine_partials<FM_BINNED_BLOCK>(&wave_part[0][0], FM_BINNED_ENTRIES, used, A.partials + (size_t)slice * FM_BINNED_ENTRIES * gridDim.x,
+                                           A.out_host + (size_t)b_lo * qe, A.counters + slice, A.counters + FM_BINNED_MAX_SLICES, A.done_flag, A.done_value,
+                                           publish_counts);
 }
 
 // out[p] = ((x_0[p]·c_0) + x_1[p]·c_1) + x_2[p]·c_2 with the coefficients of bin(key[p]): fp32 products and sums that round one by one

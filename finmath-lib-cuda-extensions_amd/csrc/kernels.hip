@@ -25,6 +25,7 @@
 #include "fm_normal_table.hpp"
 #include "kernels.h"
 #include "os_device.hpp"
+#include "side_pass_device.hpp"
 
 namespace fm {
 
@@ -378,40 +379,21 @@ __global__ void __launch_bounds__(64) fm_combine_moments_kernel(const double* __
 // added in an order that depends on n alone.  No float atomics: results are the same from run to run by construction.
 // ---------------------------------------------------------------------------------------------
 
-// Arrival counting at `counter` (zero before the launch, zero again after the last arrival): true, for the whole workgroup, in the LAST of
-// `members` workgroups.  Whatever the others wrote before they arrived is visible to it: every thread's writes are released at agent scope
-// before the barrier, the count is an agent-scope acquire-release add, and the last arriver's threads fence again behind the barrier.
-__device__ __forceinline__ bool os_arrive_last(uint32_t* counter, const uint32_t members)
-{
-    __shared__ uint32_t last;
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-        const uint32_t arrived = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        last = (arrived == members - 1u) ? 1u : 0u;
-        if (last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    const bool r = last != 0u;
-    if (r) __threadfence();
-    return r;
-}
-
 // Integers counted in LDS → the device array (adds of the non-empty bins) → by the last workgroup of the vector into pinned host memory
-// (the device array is zero again behind it) → the last vector's last workgroup raises the flag.
+// (the device array is zero again behind it) → the last vector's last workgroup raises the flag.  The arrivals are side_pass_device.hpp's.
 __device__ __forceinline__ void os_publish_counts(const uint32_t* lds, const uint32_t count, uint32_t* dev, uint32_t* host, const DevOsCommon& C)
 {
     for (uint32_t i = threadIdx.x; i < count; i += FM_BLOCK) {
         const uint32_t c = lds[i];
         if (c) __hip_atomic_fetch_add(dev + i, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (!os_arrive_last(C.counters + blockIdx.y, gridDim.x)) return;
+    if (!pass_arrive_last(C.counters + blockIdx.y, gridDim.x)) return;
     for (uint32_t i = threadIdx.x; i < count; i += FM_BLOCK) {
         host[i] = __hip_atomic_load(dev + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(dev + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __threadfence_system();
-    if (!os_arrive_last(C.counters + gridDim.y, gridDim.y)) return;
+    if (!pass_arrive_last(C.counters + gridDim.y, gridDim.y)) return;
     if (threadIdx.x == 0u) __hip_atomic_store(C.done_flag, C.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
@@ -461,14 +443,8 @@ __global__ void __launch_bounds__(FM_BLOCK) fm_os_hist_kernel(const DevSelectArg
 }
 
 // Σ (double)x over the elements with key_lo < key < key_hi.  Order of the additions: a lane adds its elements tile by tile, the lanes of a
-// wave and the waves of a workgroup are added in a fixed tree, the last workgroup of the vector adds the workgroups' partials — lane-strided,
-// then the same tree.  The grid is a function of n alone (os_sum_blocks), so the bits depend on the data and on nothing else.
-__device__ __forceinline__ double os_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
+// wave by the plain butterfly; the tail is side_pass_device.hpp's, with one entry per workgroup.  The grid is a function of n alone
+// (os_sum_blocks), so the bits depend on the data and on nothing else.
 __global__ void __launch_bounds__(FM_BLOCK) fm_os_sum_kernel(const DevRankSumArgs A, const uint64_t* __restrict__ vecs, const uint32_t* __restrict__ keys)
 {
     __shared__ double wave_part[FM_BLOCK / 64];
@@ -483,21 +459,11 @@ __global__ void __launch_bounds__(FM_BLOCK) fm_os_sum_kernel(const DevRankSumArg
             if (in_range && key > lo && key < hi) acc += (double)x;
         })
     }
-    acc = os_wave_sum(acc);
+    acc = pass_wave_sum(acc);
     if ((threadIdx.x & 63u) == 0u) wave_part[threadIdx.x >> 6] = acc;
     __syncthreads();
-    double* part = A.partials + (size_t)k * gridDim.x;
-    if (threadIdx.x == 0u) part[blockIdx.x] = ((wave_part[0] + wave_part[1]) + wave_part[2]) + wave_part[3];
-    if (!os_arrive_last(A.c.counters + k, gridDim.x)) return;
-    if (threadIdx.x < 64u) {
-        double s = 0.0;
-        for (uint32_t b = threadIdx.x; b < gridDim.x; b += 64u) s += part[b];
-        s = os_wave_sum(s);
-        if (threadIdx.x == 0u) A.out_host[k] = s;
-    }
-    __threadfence_system();
-    if (!os_arrive_last(A.c.counters + gridDim.y, gridDim.y)) return;
-    if (threadIdx.x == 0u) __hip_atomic_store(A.c.done_flag, A.c.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    pass_combine_partials<FM_BLOCK>(wave_part, 1u, 1u, A.partials + (size_t)k * gridDim.x, A.out_host + k,
+                                    A.c.counters + k, A.c.counters + gridDim.y, A.c.done_flag, A.c.done_value);
 }
 
 // counts[i] = number of elements x, not NaN, with exactly i of the m ascending bounds strictly below (double)x — i.e. x lies in
@@ -538,8 +504,8 @@ __global__ void __launch_bounds__(FM_BLOCK) fm_os_count_kernel(const DevCountArg
 //
 // Order of the additions of one pair: a lane adds its elements tile by tile (elements past n add +0.0, which changes no sum: a running sum
 // that starts at +0.0 is never -0.0); the 64 lanes of a wave are added by a butterfly (bit 5 of the lane first) that leaves the total of pair
-// q in lane q — 63 exchanges for all 64 pairs —; the four waves in order; the last workgroup of the block adds the workgroups' partials
-// lane-strided, then the plain butterfly.  The grid along x is xmom_blocks(n): the bits depend on the data and on n, on nothing else.
+// q in lane q — 63 exchanges for all 64 pairs —; the tail is side_pass_device.hpp's, with 64 entries per workgroup.  The grid along x is
+// xmom_blocks(n): the bits depend on the data and on n, on nothing else.
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(FM_BLOCK) fm_xmom_kernel(const DevXmomArgs A)
 {
@@ -601,19 +567,8 @@ __global__ void __launch_bounds__(FM_BLOCK) fm_xmom_kernel(const DevXmomArgs A)
     }
     wave_part[threadIdx.x >> 6][lane] = v[0];
     __syncthreads();
-    double* part = A.partials + (size_t)by * FM_XMOM_PAIRS * gridDim.x;
-    if (threadIdx.x < (uint32_t)FM_XMOM_PAIRS)
-        part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = ((wave_part[0][threadIdx.x] + wave_part[1][threadIdx.x]) + wave_part[2][threadIdx.x]) + wave_part[3][threadIdx.x];
-    if (!os_arrive_last(A.counters + by, gridDim.x)) return;
-    for (uint32_t q = threadIdx.x >> 6; q < (uint32_t)FM_XMOM_PAIRS; q += FM_BLOCK / 64) {
-        double s = 0.0;
-        for (uint32_t b = lane; b < gridDim.x; b += 64u) s += part[(size_t)q * gridDim.x + b];
-        s = os_wave_sum(s);
-        if (lane == 0u) A.out_host[by * FM_XMOM_PAIRS + q] = s;
-    }
-    __threadfence_system();
-    if (!os_arrive_last(A.counters + FM_XMOM_MAX_BLOCKS, gridDim.y)) return;
-    if (threadIdx.x == 0u) __hip_atomic_store(A.done_flag, A.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    pass_combine_partials<FM_BLOCK>(&wave_part[0][0], FM_XMOM_PAIRS, FM_XMOM_PAIRS, A.partials + (size_t)by * FM_XMOM_PAIRS * gridDim.x,
+                                    A.out_host + by * FM_XMOM_PAIRS, A.counters + by, A.counters + FM_XMOM_MAX_BLOCKS, A.done_flag, A.done_value);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -2,7 +2,7 @@
 // points of a key vector in one pass — E[y | x = p_q] as a curve, the inner step of the particle method for local-stochastic volatility.
 // DESIGN.md §4.19; contract: include/fmhip.h; definition: host/kernel_regression.hpp (the weight and the terms are ITS functions, compiled
 // here for the device); engine side: kreg_engine.hpp.  A close relative of fm_binned_xmom_kernel (binned_kernel.hip) with soft, overlapping
-// bins: the accumulator layout, the reduction tree and the arrival protocol are that kernel's.
+// bins: the accumulator layout is that kernel's, and the tail is side_pass_device.hpp's.
 //
 // Points.  lower, upper (padded with +inf to the power of two above Q), points and rh sit in LDS.  The members of xd = (double)key[i] are the
 // points q ∈ [a, b), a = #{ q : upper_q <= xd }, b = #{ q : lower_q < xd }: two branch-free lower bounds by binary lifting, clamped to Q.  A NaN
@@ -17,43 +17,20 @@
 //
 // Order of the additions of one (point, term): a lane adds its elements tile by tile, element by element (a non-member adds nothing — which
 // equals adding +0.0: a running sum that starts at +0.0 is never −0.0); the 64 lanes of a wave by the plain butterfly
-// (bit 5 of the lane first); the four waves in order; the workgroups' partials lane-strided by the last workgroup of the slice to arrive,
-// then the butterfly.  The grid along x is binned_blocks(n): the bits of a sum depend on n, on which positions are members and on the values
+// (bit 5 of the lane first); the waves and the workgroups of a slice as pass_combine_partials adds them.  The grid along x is
+// binned_blocks(n): the bits of a sum depend on n, on which positions are members and on the values
 // there — not on the other points, the slicing, n_y, or the slot of a vector.
 // The kernel trusts its arguments: the launcher refuses what kernel_moments_shape_ok refuses.  No register array is indexed at run time: no scratch.
 #include <hip/hip_runtime.h>
 
 #include "kreg_kernel.h"
+#include "side_pass_device.hpp"
 #include "../host/kernel_regression.hpp"
 
 namespace fm {
 
 typedef float kr_f32x4 __attribute__((ext_vector_type(4)));
 typedef kr_f32x4 __attribute__((address_space(1))) kr_gfloat4;
-
-__device__ __forceinline__ double kr_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// true, for the whole workgroup, in the LAST of `members` workgroups to arrive at `counter` (zero before the launch, zero again after the
-// last arrival); what the others wrote before they arrived is visible to it (fm_binned_xmom_kernel's protocol)
-__device__ __forceinline__ bool kr_arrive_last(uint32_t* counter, const uint32_t members, uint32_t* last)
-{
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-        const uint32_t arrived = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        *last = (arrived == members - 1u) ? 1u : 0u;
-        if (*last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    const bool r = *last != 0u;
-    if (r) __threadfence();
-    return r;
-}
 
 // #{ j : t[j] < xd } (STRICT) or #{ j : t[j] <= xd } among the 2·half − 1 padded entries: the last index read is 2·half − 2
 template <bool STRICT>
@@ -75,7 +52,6 @@ __global__ void __launch_bounds__(FM_KREG_BLOCK) fm_kernel_moments_kernel(const 
     __shared__ double wave_part[FM_KREG_BLOCK / 64][FM_KREG_ENTRIES];
     __shared__ double lower[FM_KREG_PAD], upper[FM_KREG_PAD];
     __shared__ double pts[FM_KREG_MAX_POINTS], rhs[FM_KREG_MAX_POINTS];
-    __shared__ uint32_t last;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t slice = blockIdx.y;
     const uint32_t Q = A.n_points, qe = A.entries_per_point, ny = A.n_y;
@@ -150,22 +126,12 @@ __global__ void __launch_bounds__(FM_KREG_BLOCK) fm_kernel_moments_kernel(const 
     }
     __syncthreads();
     for (uint32_t e = 0; e < used; ++e) {
-        const double v = kr_wave_sum(acc[e * FM_KREG_BLOCK + tid]);
+        const double v = pass_wave_sum(acc[e * FM_KREG_BLOCK + tid]);
         if (lane == 0u) wave_part[wave][e] = v;
     }
     __syncthreads();
-    double* part = A.partials + (size_t)slice * FM_KREG_ENTRIES * gridDim.x;
-    if (tid < used) part[(size_t)tid * gridDim.x + blockIdx.x] = ((wave_part[0][tid] + wave_part[1][tid]) + wave_part[2][tid]) + wave_part[3][tid];
-    if (!kr_arrive_last(A.counters + slice, gridDim.x, &last)) return;
-    for (uint32_t e = wave; e < used; e += FM_KREG_BLOCK / 64) {
-        double s = 0.0;
-        for (uint32_t w = lane; w < gridDim.x; w += 64u) s += part[(size_t)e * gridDim.x + w];
-        s = kr_wave_sum(s);
-        if (lane == 0u) A.out_host[(size_t)s_lo * qe + e] = s;
-    }
-    __threadfence_system();
-    if (!kr_arrive_last(A.counters + FM_KREG_MAX_SLICES, gridDim.y, &last)) return;
-    if (tid == 0u) __hip_atomic_store(A.done_flag, A.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    pass_combine_partials<FM_KREG_BLOCK>(&wave_part[0][0], FM_KREG_ENTRIES, used, A.partials + (size_t)slice * FM_KREG_ENTRIES * gridDim.x,
+                                         A.out_host + (size_t)s_lo * qe, A.counters + slice, A.counters + FM_KREG_MAX_SLICES, A.done_flag, A.done_value);
 }
 
 hipError_t launch_kernel_moments(const DevKernelMomentsArgs& a, hipStream_t st)

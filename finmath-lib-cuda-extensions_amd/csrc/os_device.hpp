@@ -1,6 +1,6 @@
 // os_device.hpp — the two device functions that every kernel ordering or counting by the 32-bit key of DESIGN.md §4.7 shares: the key itself
 // and the wave-peeled LDS count.  Included by kernels.hip (radix select, counting) and sort_kernel.hip (radix sort): one definition of the
-// order, not two.
+// order, not two; binned_kernel.hip counts its bins with os_lds_add.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

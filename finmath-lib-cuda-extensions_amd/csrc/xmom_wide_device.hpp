@@ -1,6 +1,6 @@
 // xmom_wide_device.hpp — the device code fm_xmom_wide_kernel (xmom_wide_kernel.hip) and fm_xmom_poly_kernel
-// (xmom_poly_kernel.hip, §4.15) share: the tile map, the arrival protocol, the MFMA step, the additions of the waves and of the workgroups —
-// the TREE of xmom_wide_kernel.h, once.  What differs between the two kernels is how a round's operands are obtained, and that is a policy:
+// (xmom_poly_kernel.hip, §4.15) share: the tile map, the MFMA step, the additions of the waves and of the workgroups —
+// the TREE of xmom_wide_kernel.h, once; the arrival of the workgroups is side_pass_device.hpp's.  What differs between the two kernels is how a round's operands are obtained, and that is a policy:
 //
 //   struct Policy {
 //       struct Raw;                                                     what a round's loads leave in registers
@@ -13,6 +13,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "side_pass_device.hpp"
 #include "xmom_wide_kernel.h"
 
 namespace fm {
@@ -20,23 +21,6 @@ namespace fm {
 typedef float xw_f32x4 __attribute__((ext_vector_type(4)));
 typedef double xw_f64x4 __attribute__((ext_vector_type(4)));
 typedef xw_f32x4 __attribute__((address_space(1))) xw_gfloat4;
-
-// true, for the whole workgroup, in the LAST of `members` workgroups to arrive at `counter` (zero before the launch, zero again after the
-// last arrival); what the others wrote before they arrived is visible to it (fm_xmom_kernel's protocol: release, agent-scope add, acquire)
-__device__ __forceinline__ bool xw_arrive_last(uint32_t* counter, const uint32_t members, uint32_t* last)
-{
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-        const uint32_t arrived = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        *last = (arrived == members - 1u) ? 1u : 0u;
-        if (*last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    const bool r = *last != 0u;
-    if (r) __threadfence();
-    return r;
-}
 
 // tile (g, h), g <= h, in the layout of four groups (xmom_wide_entry)
 __device__ __forceinline__ constexpr int xw_tile(int g, int h) { return g * (2 * FM_XMOMW_MAX_GROUPS - 1 - g) / 2 + h; }
@@ -82,7 +66,6 @@ __device__ __forceinline__ void xw_pass(const DevXmomWideArgs& A, Policy& P)
 {
     constexpr int NT = NG * (NG + 1) / 2;
     __shared__ double wave_part[FM_XMOMW_WAVES][FM_XMOMW_TILE_ENTRIES];
-    __shared__ uint32_t last;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t sub = lane >> 4;                                 // the k of this lane's operand
 
@@ -133,7 +116,7 @@ __device__ __forceinline__ void xw_pass(const DevXmomWideArgs& A, Policy& P)
                 __syncthreads();
             }
     }
-    if (!xw_arrive_last(A.counter, gridDim.x, &last)) return;
+    if (!pass_arrive_last(A.counter, gridDim.x)) return;
 
     // the workgroups, in order: the two halves of the last workgroup take the tiles alternately, a thread one entry of each of its tiles
     {
