@@ -922,6 +922,40 @@ int fmhip_kernel_moments(fmhip_vec key, const double* points, const double* band
     });
 }
 
+// ---------------------------------------------------------------- named functions and option formulas per path (analytic_engine.hpp)
+int fmhip_function_apply_host(const float* x, int64_t n, const int* kinds, int n_functions, float* const* out) {
+    return host_only([&] { fm::function_apply_host_checked(x, n, kinds, n_functions, out); });
+}
+int fmhip_option_formula_host(int model, const float* forward, double forward_scalar, const float* volatility, double volatility_scalar, const float* payoff_unit,
+                              double payoff_unit_scalar, int64_t n, double maturity, double strike, int outputs, float* const* out) {
+    return host_only([&] { fm::option_formula_host_checked(model, forward, forward_scalar, volatility, volatility_scalar, payoff_unit, payoff_unit_scalar, n, maturity, strike, outputs, out); });
+}
+int fmhip_function_apply(fmhip_vec x, const int* kinds, int n_functions, fmhip_vec* out) {
+    FRONT(function_apply(x, kinds, n_functions, out));
+    if (te::active()) {
+        const int rc = host_only([&] { fm::analytic_check_function(x, kinds, n_functions, out); });
+        if (rc != FMHIP_OK) return rc;
+        TE_LOCAL(&x, 1, L, fmhip_function_apply(L[0], kinds, n_functions, out));
+    }
+    return guarded([&] { Engine::get().function_apply(x, kinds, n_functions, out); });
+}
+int fmhip_option_formula(int model, fmhip_vec forward, double forward_scalar, fmhip_vec volatility, double volatility_scalar, fmhip_vec payoff_unit,
+                         double payoff_unit_scalar, double maturity, double strike, int outputs, fmhip_vec* out) {
+    FRONT(option_formula(model, forward, forward_scalar, volatility, volatility_scalar, payoff_unit, payoff_unit_scalar, maturity, strike, outputs, out));
+    if (te::active()) {
+        const int rc = host_only([&] { fm::analytic_check_formula(model, forward, volatility, payoff_unit, maturity, strike, outputs, out); });
+        if (rc != FMHIP_OK) return rc;
+        // the vector operands as ONE list, so that foreign ones are imported by one call; a handle of 0 stays the scalar
+        fmhip_vec all[3]; int count = 0;
+        const int at_f = forward ? count : -1; if (forward) all[count++] = forward;
+        const int at_v = volatility ? count : -1; if (volatility) all[count++] = volatility;
+        const int at_n = payoff_unit ? count : -1; if (payoff_unit) all[count++] = payoff_unit;
+        TE_LOCAL(all, count, L, fmhip_option_formula(model, at_f < 0 ? 0 : L[at_f], forward_scalar, at_v < 0 ? 0 : L[at_v], volatility_scalar, at_n < 0 ? 0 : L[at_n],
+                                                     payoff_unit_scalar, maturity, strike, outputs, out));
+    }
+    return guarded([&] { Engine::get().option_formula(model, forward, forward_scalar, volatility, volatility_scalar, payoff_unit, payoff_unit_scalar, maturity, strike, outputs, out); });
+}
+
 // The one call of a caller that values product after product: the engine lock is held for the bookkeeping (graph → launch → commit),
 // NOT while the device computes — other threads record and launch meanwhile.  The moments arrive in a slot of pinned memory of their
 // own; this thread polls its flag, then takes the lock again to copy them out and give the launch's buffers back.

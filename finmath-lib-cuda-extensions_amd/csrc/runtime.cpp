@@ -2778,4 +2778,5 @@ void Engine::profile_read(double* ms_total, int64_t* n) {
 #include "sort_engine.hpp"             // Engine::sort_by_key, argsort, rank_scores, read_elements: a stable radix sort of (key, path) pairs and what is made of its permutation
 #include "prefix_engine.hpp"           // Engine::prefix_sums, prefix_sums_at, prefix_search: fp64 prefix sums in a tree that is a function of n alone
 #include "table_engine.hpp"            // Engine::table_apply: tabulated functions of a vector's elements, a new vector each from one launch
+#include "analytic_engine.hpp"         // Engine::function_apply, option_formula: Φ, φ, Φ⁻¹ and the Black–Scholes / Bachelier formulas per path
 #include "kreg_engine.hpp"             // Engine::kernel_moments_pass: kernel-weighted local moments at a grid of points of a key in one launch

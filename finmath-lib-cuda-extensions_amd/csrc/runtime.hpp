@@ -417,6 +417,14 @@ public:
     // anything is flushed or launched; out is written only when the call succeeds.
     void table_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, fmhip_vec* out);
 
+    // named functions and option formulas per path (analytic_engine.hpp): n_functions of Φ, φ, Φ⁻¹ (host/normal_functions.hpp)
+    // applied to every element of x, resp. value / delta / vega (a mask) of a Black–Scholes or Bachelier call whose forward, volatility and
+    // payoff unit are a vector or — handle 0 — the scalar beside it; out: new, materialised vectors from one launch.  Arguments are checked
+    // before anything is flushed or launched; out is written only when the call succeeds.
+    void function_apply(fmhip_vec x, const int* kinds, int n_functions, fmhip_vec* out);
+    void option_formula(int model, fmhip_vec forward, double forward_scalar, fmhip_vec volatility, double volatility_scalar, fmhip_vec payoff_unit,
+                        double payoff_unit_scalar, double maturity, double strike, int outputs, fmhip_vec* out);
+
     // kernel regression (kreg_engine.hpp): the kernel-weighted local moments of n_y vectors at n_points points of `key`
     // (host/kernel_regression.hpp), sums_out[n_points][order 0: 1 + n_y, order 1: 3 + 2 n_y], from ONE launch.  Arguments are checked before
     // anything is flushed or launched.
@@ -820,6 +828,13 @@ void prefix_sums_host_checked(const float* v, int64_t n, double* prefix_out);
 void table_check_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, const fmhip_vec* out);
 void table_build_checked(const double* knots, const double* values, int count, int interpolation, int extrapolation, int derivative, double* coefficients_out);
 void table_apply_host_checked(const float* x, int64_t n, const double* knots, int count, const double* coefficients, int n_tables, float* const* out);
+// the same for fmhip_function_apply / fmhip_option_formula, and the definitions behind their _host twins (analytic_engine.hpp; the rules are
+// host/normal_functions.hpp's): all throw FMHIP_ERR_INVALID_ARGUMENT
+void analytic_check_function(fmhip_vec x, const int* kinds, int n_functions, const fmhip_vec* out);
+void analytic_check_formula(int model, fmhip_vec forward, fmhip_vec volatility, fmhip_vec payoff_unit, double maturity, double strike, int outputs, const fmhip_vec* out);
+void function_apply_host_checked(const float* x, int64_t n, const int* kinds, int n_functions, float* const* out);
+void option_formula_host_checked(int model, const float* forward, double forward_scalar, const float* volatility, double volatility_scalar, const float* payoff_unit,
+                                 double payoff_unit_scalar, int64_t n, double maturity, double strike, int outputs, float* const* out);
 // what can be said about the arguments of fmhip_binned_cross_moments / fmhip_binned_evaluate without looking at a vector (binned_engine.hpp; the
 // rules are fmhost::binnedCheck*'s, host/binned_regression.hpp), and the host definitions: all throw FMHIP_ERR_INVALID_ARGUMENT
 void binned_check_moments(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, const int64_t* counts_out, const double* sums_out);

@@ -1016,6 +1016,52 @@ int table_apply(fmhip_vec x, const double* knots, int count, const double* coeff
     });
 }
 
+// Named functions and option formulas per path (analytic_engine.hpp).  Elementwise: every shard runs the call on its block; the new vectors'
+// blocks are the shards' results.  `call`: the shard's call, given the shard's handles of `operands` (0 stays 0: the scalar) and n_out slots.
+template <class Call> static void analytic_per_shard(Shards& s, int64_t n, const std::vector<fmhip_vec>& operands, int n_out, fmhip_vec* out, Call call) {
+    auto ids = std::make_shared<std::vector<fmhip_vec>>();
+    for (int f = 0; f < n_out; ++f) ids->push_back(s.fresh(n));
+    s.post([=](Worker& w) {
+        int64_t off, cnt; shard_range(n, w.shards, w.shard, &off, &cnt);
+        fmhip_vec h[4] = { 0, 0, 0, 0 };
+        if (cnt <= 0) { for (int f = 0; f < n_out; ++f) if (w.ok(fmhip_vec_create_uninitialized(0, &h[f]))) w.bind((*ids)[(size_t)f], h[f]); return; }
+        fmhip_vec mine[3] = { 0, 0, 0 };
+        for (size_t k = 0; k < operands.size(); ++k) mine[k] = operands[k] ? w.at(operands[k]) : 0;
+        if (w.ok(call(mine, h))) for (int f = 0; f < n_out; ++f) w.bind((*ids)[(size_t)f], h[f]);
+    });
+    // eager, like the call on one engine: a shard's refusal (no kernel, a value that was given up) is THIS call's status
+    try { s.wait(); }
+    catch (...) {
+        s.post([=](Worker& w) { for (fmhip_vec id : *ids) if (const fmhip_vec h = w.at(id)) { (void)fmhip_vec_release(h); w.local.erase(id); } });
+        for (fmhip_vec id : *ids) s.meta.erase(id);
+        throw;
+    }
+    for (int f = 0; f < n_out; ++f) out[f] = (*ids)[(size_t)f];
+}
+
+int function_apply(fmhip_vec x, const int* kinds, int n_functions, fmhip_vec* out) {
+    return fronted([&](Shards& s) {
+        analytic_check_function(x, kinds, n_functions, out);
+        const int64_t n = front_size(s, &x, 1, "named functions", false);
+        auto kd = std::make_shared<std::vector<int>>(kinds, kinds + n_functions);
+        analytic_per_shard(s, n, { x }, n_functions, out, [=](const fmhip_vec* mine, fmhip_vec* h) { return fmhip_function_apply(mine[0], kd->data(), n_functions, h); });
+    });
+}
+
+int option_formula(int model, fmhip_vec forward, double forward_scalar, fmhip_vec volatility, double volatility_scalar, fmhip_vec payoff_unit,
+                   double payoff_unit_scalar, double maturity, double strike, int outputs, fmhip_vec* out) {
+    return fronted([&](Shards& s) {
+        analytic_check_formula(model, forward, volatility, payoff_unit, maturity, strike, outputs, out);
+        std::vector<fmhip_vec> vectors;
+        for (fmhip_vec h : { forward, volatility, payoff_unit }) if (h) vectors.push_back(h);
+        const int64_t n = front_size(s, vectors.data(), (int)vectors.size(), "option formula", false);
+        const int n_out = (outputs & 1) + ((outputs >> 1) & 1) + ((outputs >> 2) & 1);      // one new vector per set bit of the mask
+        analytic_per_shard(s, n, { forward, volatility, payoff_unit }, n_out, out, [=](const fmhip_vec* mine, fmhip_vec* h) {
+            return fmhip_option_formula(model, mine[0], forward_scalar, mine[1], volatility_scalar, mine[2], payoff_unit_scalar, maturity, strike, outputs, h);
+        });
+    });
+}
+
 int vec_give_up_values(const fmhip_vec* vectors, int count) {
     return fronted([&](Shards& s) {
         need(vectors, "vectors");

@@ -142,7 +142,8 @@ class RandomVariableDifferentiableAAD:
         return self._new("AVERAGE", self.values.average(), (self,))
 
     def apply(self, *a, **k):
-        """apply(TabulatedFunction): a curve has a derivative, the curve of its segments' derivatives.  Value and derivative come from ONE
+        """apply(NamedFunction): the normal distribution function, its density, its quantile (analytic.py).
+        apply(TabulatedFunction): a curve has a derivative, the curve of its segments' derivatives.  Value and derivative come from ONE
         table_apply of the pair (one read of x) where the inner value is a device vector; a constant is mapped in double; the values of any
         other inner implementation go through the definition on the host (fmhip_table_apply_host) and back through the inner factory.
         Anything else has no derivative."""
@@ -160,6 +161,35 @@ class RandomVariableDifferentiableAAD:
             else:
                 columns = table_apply_host(np.asarray(x.getRealizations(), dtype=np.float32), [f, df])
                 value, slope = (self.factory.inner.createRandomVariable(x.getFiltrationTime(), c) for c in columns)
+            return RandomVariableDifferentiableAAD(value, _Node("APPLY_TABLE", (self.node,), (slope,), 0.0), self.factory)
+        from .analytic import NORMAL_CDF, NORMAL_DENSITY, NORMAL_QUANTILE, NamedFunction, function_apply, function_apply_host
+        if len(a) == 1 and not k and isinstance(a[0], NamedFunction):
+            # apply(NamedFunction): Φ takes value and derivative from ONE call of the pair [Φ, φ] (one read of x); φ' = −x·φ and
+            # (Φ⁻¹)' = 1/φ(Φ⁻¹) are composed in the inner implementation's operations.
+            f, x = a[0], self.values
+            realizations = getattr(x, "realizations", None)
+
+            def named(v, functions):
+                if hasattr(v, "_sto"):
+                    r = getattr(v, "realizations", None)
+                    return [v._sto(o) for o in function_apply(r, functions)] if r is not None else [v.apply(g) for g in functions]
+                if self.factory is None:
+                    raise NotImplementedError("apply(NamedFunction) on this inner implementation needs the factory that made the variable")
+                if v.isDeterministic():
+                    return [self.factory.inner.createRandomVariable(v.getFiltrationTime(), g(v.doubleValue())) for g in functions]
+                columns = function_apply_host(np.asarray(v.getRealizations(), dtype=np.float32), functions)
+                return [self.factory.inner.createRandomVariable(v.getFiltrationTime(), c) for c in columns]
+
+            if f is NORMAL_CDF:
+                value, slope = named(x, [NORMAL_CDF, NORMAL_DENSITY])
+            elif f is NORMAL_DENSITY:
+                value, = named(x, [NORMAL_DENSITY])
+                slope = x.mult(value).mult(-1.0)
+            elif f is NORMAL_QUANTILE:
+                value, = named(x, [NORMAL_QUANTILE])
+                slope = named(value, [NORMAL_DENSITY])[0].invert()
+            else:
+                raise NotImplementedError(f"apply({f!r}) has no derivative")
             return RandomVariableDifferentiableAAD(value, _Node("APPLY_TABLE", (self.node,), (slope,), 0.0), self.factory)
         raise NotImplementedError("UnsupportedOperationException: apply(lambda) has no derivative")
 
@@ -274,6 +304,7 @@ def _partial_times(nd, k, d, const):
         return d.mult(X.choose(one, zero)) if k == 1 else d.mult(X.choose(zero, one))
     if op == "AVERAGE": return d.average()
     if op == "APPLY_TABLE": return d.mult(X)                                # X holds f'(x): x.apply(f.derivative())
+    if op == "OPTION_FORMULA": return d.mult(nd.arg_values[k])               # (delta, vega) of the unit value: analytic.option_formula
     raise NotImplementedError(op)
 
 

@@ -82,7 +82,9 @@ public:
     virtual RV isNaN() const = 0;
     virtual RV sin() const = 0;                                     // GPU class throws (:1373-1384); semantics from the twin (:927-954)
     virtual RV cos() const = 0;
-    // apply maps on the host, as the reference does; the order statistics below are selected and counted on the DEVICE when the object
+    // apply maps on the host, as the reference does (a std::function has no name the device could know: a caller who wants Φ, φ, Φ⁻¹ or a
+    // Black–Scholes / Bachelier value per path on the device calls fmhip_function_apply / fmhip_option_formula on the handles, DESIGN.md
+    // §4.21); the order statistics below are selected and counted on the DEVICE when the object
     // has a device vector (orderStatisticsHandle) — fmhip_select_ranks_batch, fmhip_rank_sums_batch, fmhip_count_not_above — and sort
     // on the host as the reference does (:970-1091; twin :473-602, :667-748) otherwise, or with FMHIP_DEVICE_ORDER_STATS=0
     virtual RV apply(const std::function<double(double)>& f) const = 0;

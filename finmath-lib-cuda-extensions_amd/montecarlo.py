@@ -8,6 +8,8 @@ a RandomVariableFactory by injection (LIBORMarketModelCalibrationATMTest.java:35
     local_volatility_call_mc  the same scheme under a tabulated surface σ(t, S): the volatility of a step is a row of the surface applied
                             to the state by RandomVariable.apply(TabulatedFunction) (tabulated.py)
     heston_call_mc          BASELINE.json configs[2]: Euler full-truncation Heston driven by BrownianMotionHip
+    heston_call_conditional_mc  the same scheme by conditional Monte-Carlo: the variance path alone is simulated, the payoff's conditional
+                            expectation is a Black–Scholes value per path (analytic.py)
     stochastic_local_volatility_call_mc  Heston's variance under a leverage function calibrated to a Dupire surface by the particle
                             method: E[v | ln S] re-estimated at every step by kernel regression on the device (kernel_regression.py,
                             DESIGN.md §4.19)
@@ -236,6 +238,39 @@ def heston_call_mc(brownian_motion, initial_value, risk_free_rate, v0, kappa, th
         t = td.getTime(i)
     payoff = x.exp().sub(strike).floor(0.0)
     value = payoff.div(math.exp(risk_free_rate * maturity))
+    return value.getAverage(), value
+
+
+def heston_call_conditional_mc(brownian_motion, initial_value, risk_free_rate, v0, kappa, theta, xi, rho, maturity, strike):
+    """CONDITIONAL Monte-Carlo ("mixing") for heston_call_mc's scheme: only the variance is simulated,
+        v_{i+1} = v_i + κ(θ − v⁺) Δt + ξ sqrt(v⁺) ΔZ,   v⁺ = max(v, 0),   ΔZ = factor 0 of the Brownian motion,
+    with I = Σ v⁺ Δt and J = Σ sqrt(v⁺) ΔZ accumulated along the path.  Given the path of Z, the Euler log-price
+    X_T = ln S₀ + rT − I/2 + ρ J + sqrt(1 − ρ²) Σ sqrt(v⁺) ΔW^⊥ is normal: the payoff's conditional expectation is the Black–Scholes value
+        black_scholes_option_value(S₀ e^{rT} exp(ρ J − ρ² I / 2), sqrt((1 − ρ²) I / T), T, K, e^{−rT})
+    per path (analytic.py, DESIGN.md §4.21: one launch on the three vectors, nothing leaves the device).  This is the exact conditional law
+    of the Euler scheme, so the average has the expectation of heston_call_mc's, with less variance.  Returns (average, vector)."""
+    from .analytic import black_scholes_option_value
+    td = brownian_motion.getTimeDiscretization()
+    v = brownian_motion.getRandomVariableForConstant(v0)
+    integral = brownian_motion.getRandomVariableForConstant(0.0)
+    stochastic = brownian_motion.getRandomVariableForConstant(0.0)
+    t, i = td.getTime(0), 0
+    while t < maturity - 1e-12:
+        dt = td.getTimeStep(i)
+        dz = brownian_motion.getBrownianIncrement(i, 0)
+        vp = v.floor(0.0)
+        sq = vp.sqrt()
+        integral = integral.addProduct(vp, dt)
+        stochastic = stochastic.addProduct(sq, dz)
+        if xi != 0.0:
+            v = v.addProduct(vp.bus(theta), kappa * dt).addProduct(sq.mult(xi), dz)
+        else:
+            v = v.addProduct(vp.bus(theta), kappa * dt)
+        i += 1
+        t = td.getTime(i)
+    forward = stochastic.mult(rho).addProduct(integral, -0.5 * rho * rho).exp().mult(initial_value * math.exp(risk_free_rate * maturity))
+    volatility = integral.mult((1.0 - rho * rho) / maturity).sqrt()
+    value = black_scholes_option_value(forward, volatility, maturity, strike, math.exp(-risk_free_rate * maturity))
     return value.getAverage(), value
 
 

@@ -564,11 +564,17 @@ class RandomVariableHip:
 
     def apply(self, *args):
         """apply(TabulatedFunction): the curve at every path, on the device (tabulated.py); a constant is mapped in double
-        as the twin maps scalars.  Any other function cannot run on the device (the reference maps it on the host, :1146-1169)."""
+        as the twin maps scalars.  apply(NamedFunction): the normal distribution function, its density or its quantile at every path, on the
+        device (analytic.py); the time is kept, a constant is mapped in double.  Any other function cannot run on the
+        device (the reference maps it on the host, :1146-1169)."""
         from .tabulated import TabulatedFunction, table_apply
         if len(args) == 1 and isinstance(args[0], TabulatedFunction):
             if self.isDeterministic(): return self._det(args[0](self.value))
             return self._sto(table_apply(self.realizations, [args[0]])[0])
+        from .analytic import NamedFunction, function_apply
+        if len(args) == 1 and isinstance(args[0], NamedFunction):
+            if self.isDeterministic(): return self._det(args[0](self.value))
+            return self._sto(function_apply(self.realizations, [args[0]])[0])
         raise NotImplementedError("UnsupportedOperationException: apply(lambda) cannot run on the device (:1146-1169)")
 
     def __repr__(self):

@@ -495,6 +495,53 @@ int fmhip_table_apply(fmhip_vec x, const double* knots, int count, const double*
 int fmhip_table_apply_host(const float* x, int64_t n, const double* knots, int count, const double* coefficients, int n_tables,
                            float* const* out);
 
+/* Named functions and option formulas per path on the device: the most common arguments of RandomVariable.apply — the
+ * normal distribution function, its density, its quantile — and the closed-form prices built on them, without the vectors leaving the
+ * device.  The definition is host/normal_functions.hpp, one header for the host and the device: fp64, + - * /, sqrt and the exp and log of
+ * host/gamma_icdf.hpp, every operation rounded on its own; the device's bits EQUAL the host entry points'.
+ * A function of an element x (fp32): X = (double)x, the result (float)f(X); a result that is a NaN is the quiet NaN 0x7fc00000.
+ *   FMHIP_FN_NORMAL_DENSITY   exp(-X*X/2)/sqrt(2 pi); 0 at +-inf.
+ *   FMHIP_FN_NORMAL_CDF       Phi(X); for X <= 0 the density times a piecewise fit of the Mills ratio (tools/normal_cdf_coefficients.py),
+ *                             1 - Phi(-X) above; 0 at -inf, 1 at +inf.  The fp64 value is within 2^-40 relative of Phi over every fp32 x in
+ *                             [-14.3, 8.3] (and the density's over [-14.3, 14.3]): the fp32 result is at most one ulp from the correctly
+ *                             rounded one.
+ *   FMHIP_FN_NORMAL_QUANTILE  Wichura's AS 241 in fp64; 0 -> -inf, 1 -> +inf, x < 0, x > 1 or a NaN -> NaN.
+ * fmhip_function_apply: n_functions (1 ... 4) of them, kinds[f], applied to every element of x in ONE launch that reads x once:
+ *   out[0 ... n_functions) are new, materialised vectors of x's size ([Phi, density] is the pair a derivative needs).
+ * An option formula: a call in forward form.  Operands: forward F, volatility sigma, payoff unit N (a discount factor, a notional) — each
+ *   a vector, (double) of its fp32 elements, or with a handle of 0 the fp64 scalar beside it — and the fp64 scalars maturity T >= 0 and
+ *   strike K.  With s = sigma*sqrt(T):
+ *   FMHIP_FORMULA_BLACK_SCHOLES  d+ = (log(F/K) + s*s/2)/s, d- = d+ - s: value N*(F*Phi(d+) - K*Phi(d-)), delta N*Phi(d+),
+ *                                vega N*F*density(d+)*sqrt(T).
+ *   FMHIP_FORMULA_BACHELIER      d = (F - K)/s: value N*((F - K)*Phi(d) + s*density(d)), delta N*Phi(d), vega N*sqrt(T)*density(d).
+ *   An element with s <= 0, and for Black-Scholes also with F <= 0 or K <= 0, is the limit: value N*max(F - K, 0), delta N*[F > K],
+ *   vega 0.  A NaN among F, sigma, N gives the quiet NaN 0x7fc00000 in every output.  A put is call - N*(F - K): the mirrors' business.
+ * fmhip_option_formula: outputs is a mask of FMHIP_FORMULA_VALUE, _DELTA, _VEGA; out receives one new, materialised vector per set bit, in
+ *   bit order, from ONE launch.  At least one operand is a vector, and all vectors have one size.
+ * fmhip_function_apply_host, fmhip_option_formula_host (host only): the DEFINITIONS over host float arrays of n (1 ... 2^31) elements;
+ *   out[f][p]; an operand array that is NULL is the scalar beside it; they need no device.
+ * Both passes are elementwise: with a device list every shard runs the call on its block.  Everything is checked on the host before anything
+ * is flushed or launched: counts out of range, an unknown function or model, a mask outside 1 ... 7, a NULL pointer, x = 0, no vector operand,
+ * a maturity that is negative or not finite, a strike that is not finite -> FMHIP_ERR_INVALID_ARGUMENT; vectors of different sizes ->
+ * FMHIP_ERR_SIZE_MISMATCH; FMHIP_ERR_INVALID_HANDLE.  A vector whose values were given up is the error a read of it is.  A build without
+ * the kernels answers FMHIP_ERR_UNSUPPORTED; it never falls back. */
+#define FMHIP_FN_NORMAL_CDF 0
+#define FMHIP_FN_NORMAL_DENSITY 1
+#define FMHIP_FN_NORMAL_QUANTILE 2
+#define FMHIP_FORMULA_BLACK_SCHOLES 0
+#define FMHIP_FORMULA_BACHELIER 1
+#define FMHIP_FORMULA_VALUE 1
+#define FMHIP_FORMULA_DELTA 2
+#define FMHIP_FORMULA_VEGA  4
+int fmhip_function_apply(fmhip_vec x, const int* kinds, int n_functions /* 1 ... 4 */, fmhip_vec* out);
+int fmhip_function_apply_host(const float* x, int64_t n, const int* kinds, int n_functions, float* const* out);
+int fmhip_option_formula(int model, fmhip_vec forward, double forward_scalar, fmhip_vec volatility, double volatility_scalar,
+                         fmhip_vec payoff_unit, double payoff_unit_scalar, double maturity, double strike,
+                         int outputs /* mask */, fmhip_vec* out /* one new vector per set bit, in bit order */);
+int fmhip_option_formula_host(int model, const float* forward, double forward_scalar, const float* volatility, double volatility_scalar,
+                              const float* payoff_unit, double payoff_unit_scalar, int64_t n, double maturity, double strike,
+                              int outputs, float* const* out);
+
 /* Kernel regression on the device: kernel-weighted LOCAL MOMENTS of up to four vectors at a grid of points of a key vector
  * in one pass — E[y | x = p_q] as a curve: the inner step of the particle method for local-stochastic-volatility calibration
  * (E[v_t | S_t = S] at every time step), kernel density estimates, smooth exercise boundaries, exposure profiles — without the vectors

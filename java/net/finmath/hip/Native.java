@@ -117,6 +117,15 @@ final class Native {
 	static native int tableApply(long x, double[] knots, double[] coefficients, int nTables, long[] out);
 	/** The definition of tableApply over a host array: outColumns holds nTables columns of x.length floats. */
 	static native int tableApplyHost(float[] x, double[] knots, double[] coefficients, int nTables, float[] outColumns);
+	// ---- named functions and option formulas per path: the normal distribution function, density and quantile; Black-Scholes and Bachelier
+	/** out[f] = a new vector: function kinds[f] (0 normal distribution function, 1 its density, 2 its quantile) at every element of x; 1 ... 4 functions from one launch that reads x once. */
+	static native int functionApply(long x, int[] kinds, long[] out);
+	/** The definition of functionApply over a host array: outColumns holds kinds.length columns of x.length floats. */
+	static native int functionApplyHost(float[] x, int[] kinds, float[] outColumns);
+	/** out = one new vector per set bit of outputs (1 value, 2 delta, 4 vega), in bit order: the call of model 0 (Black-Scholes) or 1 (Bachelier) in forward form; an operand handle of 0 is the scalar beside it, at least one is a vector. */
+	static native int optionFormula(int model, long forward, double forwardScalar, long volatility, double volatilityScalar, long payoffUnit, double payoffUnitScalar, double maturity, double strike, int outputs, long[] out);
+	/** The definition of optionFormula over host arrays of n floats; an operand array that is null is the scalar beside it; outColumns holds one column of n floats per set bit. */
+	static native int optionFormulaHost(int model, float[] forwardOrNull, double forwardScalar, float[] volatilityOrNull, double volatilityScalar, float[] payoffUnitOrNull, double payoffUnitScalar, int n, double maturity, double strike, int outputs, float[] outColumns);
 	// ---- kernel regression: kernel-weighted local moments of up to 4 vectors at up to 256 points of a key from one launch
 	/** sumsOut[points.length][order 0: 1 + y.length; order 1: 3 + 2 y.length]: per point the fp64 sums [w, w*y...] or [w, w*d, w*d*d, w*y..., w*d*y...] over its members (lower &lt; key &lt; upper); kernel 0 uniform, 1 triangular, 2 Epanechnikov, 3 quartic, 4 triweight. */
 	static native int kernelMoments(long key, double[] points, double[] bandwidths, int kernel, int order, long[] y, double[] sumsOut);

@@ -443,6 +443,11 @@ public class RandomVariableHip implements RandomVariable {
 			Native.check(Native.tableApply(deviceHandle(), table.getKnots(), table.getCoefficients(), 1, out));
 			return new RandomVariableHip(time, new DeviceVector(out[0], size()));
 		}
+		if(function instanceof NormalDistributionHip) {					// the normal distribution function, density or quantile: one launch (fmhip_function_apply)
+			final long[] out = new long[1];
+			Native.check(Native.functionApply(deviceHandle(), new int[] { ((NormalDistributionHip)function).getKind() }, out));
+			return new RandomVariableHip(time, new DeviceVector(out[0], size()));
+		}
 		final double[] values = getRealizations();						// the twin maps on the host (twin:667-676); RandomVariableCuda throws (:1146-1159)
 		for(int i = 0; i < values.length; i++) {
 			values[i] = function.applyAsDouble(values[i]);

@@ -354,6 +354,50 @@ FMJ(jint, kernelMomentsHost)(JNIEnv* env, jclass, jfloatArray key, jdoubleArray 
     if ((int64_t)po.length() < q * kernel_entries(order, nY)) return FMHIP_ERR_INVALID_ARGUMENT;
     return fmhip_kernel_moments_host(pk.p, n, pp.p, pb.p, (int)q, (int)kernel, (int)order, nY ? ys.data() : nullptr, nY, po.p);
 }
+// ---------------------------------------------------------------- named functions and option formulas per path
+FMJ(jint, functionApply)(JNIEnv* env, jclass, jlong x, jintArray kinds, jlongArray out) {
+    Pin<jint> pk(env, kinds, JNI_ABORT);
+    const jsize count = pk.length();
+    if (!pk.p || !out || count < 1 || count > 4 || env->GetArrayLength(out) < count) return FMHIP_ERR_INVALID_ARGUMENT;
+    int k[4] = { 0, 0, 0, 0 };
+    for (jsize f = 0; f < count; ++f) k[f] = (int)pk.p[f];
+    fmhip_vec h[4] = { 0, 0, 0, 0 };
+    const int st = fmhip_function_apply(x, k, (int)count, h);
+    if (st == FMHIP_OK) { jlong o[4]; for (jsize f = 0; f < count; ++f) o[f] = (jlong)h[f]; env->SetLongArrayRegion(out, 0, count, o); }
+    return st;
+}
+FMJ(jint, functionApplyHost)(JNIEnv* env, jclass, jfloatArray x, jintArray kinds, jfloatArray outColumns) {
+    Pin<jfloat> px(env, x, JNI_ABORT); Pin<jint> pk(env, kinds, JNI_ABORT); Pin<jfloat> po(env, outColumns);
+    const jsize count = pk.length();
+    if (!px.p || !pk.p || !po.p || count < 1 || count > 4) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int64_t n = px.length();
+    if ((int64_t)po.length() < (int64_t)count * n) return FMHIP_ERR_INVALID_ARGUMENT;
+    int k[4] = { 0, 0, 0, 0 };
+    float* columns[4] = { nullptr, nullptr, nullptr, nullptr };
+    for (jsize f = 0; f < count; ++f) { k[f] = (int)pk.p[f]; columns[f] = po.p + (int64_t)f * n; }
+    return fmhip_function_apply_host(px.p, n, k, (int)count, columns);
+}
+FMJ(jint, optionFormula)(JNIEnv* env, jclass, jint model, jlong forward, jdouble forwardScalar, jlong volatility, jdouble volatilityScalar, jlong payoffUnit, jdouble payoffUnitScalar,
+                         jdouble maturity, jdouble strike, jint outputs, jlongArray out) {
+    if (!out || outputs < 1 || outputs > 7) return FMHIP_ERR_INVALID_ARGUMENT;
+    const jsize count = (jsize)((outputs & 1) + ((outputs >> 1) & 1) + ((outputs >> 2) & 1));
+    if (env->GetArrayLength(out) < count) return FMHIP_ERR_INVALID_ARGUMENT;
+    fmhip_vec h[3] = { 0, 0, 0 };
+    const int st = fmhip_option_formula((int)model, forward, forwardScalar, volatility, volatilityScalar, payoffUnit, payoffUnitScalar, maturity, strike, (int)outputs, h);
+    if (st == FMHIP_OK) { jlong o[3]; for (jsize f = 0; f < count; ++f) o[f] = (jlong)h[f]; env->SetLongArrayRegion(out, 0, count, o); }
+    return st;
+}
+FMJ(jint, optionFormulaHost)(JNIEnv* env, jclass, jint model, jfloatArray forwardOrNull, jdouble forwardScalar, jfloatArray volatilityOrNull, jdouble volatilityScalar,
+                             jfloatArray payoffUnitOrNull, jdouble payoffUnitScalar, jint n, jdouble maturity, jdouble strike, jint outputs, jfloatArray outColumns) {
+    Pin<jfloat> pf(env, forwardOrNull, JNI_ABORT); Pin<jfloat> pv(env, volatilityOrNull, JNI_ABORT); Pin<jfloat> pn(env, payoffUnitOrNull, JNI_ABORT); Pin<jfloat> po(env, outColumns);
+    if (!po.p || n < 1 || outputs < 1 || outputs > 7) return FMHIP_ERR_INVALID_ARGUMENT;
+    if ((forwardOrNull && (!pf.p || pf.length() < n)) || (volatilityOrNull && (!pv.p || pv.length() < n)) || (payoffUnitOrNull && (!pn.p || pn.length() < n))) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int count = (outputs & 1) + ((outputs >> 1) & 1) + ((outputs >> 2) & 1);
+    if ((int64_t)po.length() < (int64_t)count * n) return FMHIP_ERR_INVALID_ARGUMENT;
+    float* columns[3] = { nullptr, nullptr, nullptr };
+    for (int f = 0; f < count; ++f) columns[f] = po.p + (int64_t)f * n;
+    return fmhip_option_formula_host((int)model, pf.p, forwardScalar, pv.p, volatilityScalar, pn.p, payoffUnitScalar, (int64_t)n, maturity, strike, (int)outputs, columns);
+}
 // ---------------------------------------------------------------- polynomial regression in one pass: the monomials of the states are formed in registers
 // exponents: states.length (nStates) entries per term, each 0 … 6, as ints; anything outside a byte is refused here, the rest by the library
 static bool poly_exponents(const jint* e, int64_t count, std::vector<uint8_t>& out) {
