@@ -956,6 +956,29 @@ int fmhip_option_formula(int model, fmhip_vec forward, double forward_scalar, fm
     return guarded([&] { Engine::get().option_formula(model, forward, forward_scalar, volatility, volatility_scalar, payoff_unit, payoff_unit_scalar, maturity, strike, outputs, out); });
 }
 
+// ---------------------------------------------------------------- nested simulation: block moments and the repeat (nested_engine.hpp)
+int fmhip_block_moments_host(const float* v, int64_t n, int64_t block, uint32_t mask, float* outs) {
+    return host_only([&] { fm::block_moments_host_checked(v, n, block, mask, outs); });
+}
+int fmhip_block_moments(const fmhip_vec* vs, int n_vs, int64_t block, uint32_t mask, fmhip_vec* outs) {
+    FRONT(block_moments(vs, n_vs, block, mask, outs));
+    if (te::active()) {
+        const int rc = host_only([&] { fm::nested_check_moments(vs, n_vs, block, mask, outs); });
+        if (rc != FMHIP_OK) return rc;
+        TE_LOCAL(vs, n_vs, L, fmhip_block_moments(L, n_vs, block, mask, outs));
+    }
+    return guarded([&] { Engine::get().block_moments(vs, n_vs, block, mask, outs); });
+}
+int fmhip_vec_repeat(fmhip_vec v, int64_t each, int64_t times, fmhip_vec* out) {
+    FRONT(vec_repeat(v, each, times, out));
+    if (te::active()) {
+        const int rc = host_only([&] { fm::nested_check_repeat(v, each, times, out); });
+        if (rc != FMHIP_OK) return rc;
+        TE_LOCAL(&v, 1, L, fmhip_vec_repeat(L[0], each, times, out));
+    }
+    return guarded([&] { const fmhip_vec r = Engine::get().repeat(v, each, times, out); *out = r; });
+}
+
 // The one call of a caller that values product after product: the engine lock is held for the bookkeeping (graph → launch → commit),
 // NOT while the device computes — other threads record and launch meanwhile.  The moments arrive in a slot of pinned memory of their
 // own; this thread polls its flag, then takes the lock again to copy them out and give the launch's buffers back.

@@ -425,6 +425,14 @@ public:
     void option_formula(int model, fmhip_vec forward, double forward_scalar, fmhip_vec volatility, double volatility_scalar, fmhip_vec payoff_unit,
                         double payoff_unit_scalar, double maturity, double strike, int outputs, fmhip_vec* out);
 
+    // nested simulation (nested_engine.hpp): the moments of the n / block consecutive blocks of up to four vectors — sum, mean,
+    // population variance by a mask, fp64 sums in an association that is a function of `block` alone (host/block_moments.hpp) — as new,
+    // materialised vectors of n / block elements, outs[i·popcount(mask) + j]; and the repeat out[(t·n + p)·each + e] = v[p], bit for bit.
+    // Arguments are checked before anything is flushed or launched; outs is written only when the call succeeds.  Local to this engine's
+    // vector (a communicator changes nothing).
+    void block_moments(const fmhip_vec* vs, int n_vs, int64_t block, uint32_t mask, fmhip_vec* outs);
+    fmhip_vec repeat(fmhip_vec v, int64_t each, int64_t times, const fmhip_vec* out_checked);
+
     // kernel regression (kreg_engine.hpp): the kernel-weighted local moments of n_y vectors at n_points points of `key`
     // (host/kernel_regression.hpp), sums_out[n_points][order 0: 1 + n_y, order 1: 3 + 2 n_y], from ONE launch.  Arguments are checked before
     // anything is flushed or launched.
@@ -835,6 +843,11 @@ void analytic_check_formula(int model, fmhip_vec forward, fmhip_vec volatility, 
 void function_apply_host_checked(const float* x, int64_t n, const int* kinds, int n_functions, float* const* out);
 void option_formula_host_checked(int model, const float* forward, double forward_scalar, const float* volatility, double volatility_scalar, const float* payoff_unit,
                                  double payoff_unit_scalar, int64_t n, double maturity, double strike, int outputs, float* const* out);
+// the same for fmhip_block_moments / fmhip_vec_repeat, and the definition behind fmhip_block_moments_host (nested_engine.hpp; the rules are
+// host/block_moments.hpp's): all throw FMHIP_ERR_INVALID_ARGUMENT
+void nested_check_moments(const fmhip_vec* vs, int n_vs, int64_t block, uint32_t mask, const fmhip_vec* outs);
+void nested_check_repeat(fmhip_vec v, int64_t each, int64_t times, const fmhip_vec* out);
+void block_moments_host_checked(const float* v, int64_t n, int64_t block, uint32_t mask, float* outs);
 // what can be said about the arguments of fmhip_binned_cross_moments / fmhip_binned_evaluate without looking at a vector (binned_engine.hpp; the
 // rules are fmhost::binnedCheck*'s, host/binned_regression.hpp), and the host definitions: all throw FMHIP_ERR_INVALID_ARGUMENT
 void binned_check_moments(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, const int64_t* counts_out, const double* sums_out);

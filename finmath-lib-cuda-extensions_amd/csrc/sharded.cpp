@@ -1062,6 +1062,44 @@ int option_formula(int model, fmhip_vec forward, double forward_scalar, fmhip_ve
     });
 }
 
+// Nested simulation (nested_engine.hpp).  The blocks of a sample that is spread over several shards would straddle them, and a repeat's
+// output is laid out over the whole sample: a list of more than one shard answers FMHIP_ERR_UNSUPPORTED, never the moments of a part.  A
+// list of ONE shard is that shard's call.
+static void nested_one_shard(Shards& s, const char* what) {
+    if (s.D() > 1) throw Error(FMHIP_ERR_UNSUPPORTED, std::string(what) + " with a device list of " + std::to_string(s.D()) + " shards: blocks would straddle the shards");
+}
+int block_moments(const fmhip_vec* vs, int n_vs, int64_t block, uint32_t mask, fmhip_vec* outs) {
+    return fronted([&](Shards& s) {
+        nested_check_moments(vs, n_vs, block, mask, outs);
+        const int64_t n = front_size(s, vs, n_vs, "block moments", false);
+        if (n % block != 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "block moments: " + std::to_string(n) + " elements are no whole number of blocks of " + std::to_string(block));
+        nested_one_shard(s, "block moments");
+        const int total = n_vs * ((int)(mask & 1u) + (int)((mask >> 1) & 1u) + (int)((mask >> 2) & 1u));
+        std::vector<fmhip_vec> ids;
+        for (int k = 0; k < total; ++k) ids.push_back(s.fresh(n / block));
+        s.post([&](Worker& w) {
+            const std::vector<fmhip_vec> l = localize(w, vs, n_vs);
+            std::vector<fmhip_vec> h((size_t)total, 0);
+            if (!w.ok(fmhip_block_moments(l.data(), n_vs, block, mask, h.data()))) return;
+            for (int k = 0; k < total; ++k) w.bind(ids[(size_t)k], h[(size_t)k]);
+        });
+        try { s.wait(); } catch (...) { for (fmhip_vec id : ids) s.meta.erase(id); throw; }
+        for (int k = 0; k < total; ++k) outs[k] = ids[(size_t)k];
+    });
+}
+int vec_repeat(fmhip_vec v, int64_t each, int64_t times, fmhip_vec* out) {
+    return fronted([&](Shards& s) {
+        nested_check_repeat(v, each, times, out);
+        const int64_t n = front_size(s, &v, 1, "repeat", false);
+        if (each > 0x7fffffffLL / n || times > 0x7fffffffLL / (n * each)) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "repeat: an output beyond 2^31 - 1 elements");
+        nested_one_shard(s, "repeat");
+        const fmhip_vec id = s.fresh(n * each * times);
+        s.post([&](Worker& w) { fmhip_vec h = 0; if (w.ok(fmhip_vec_repeat(w.at(v), each, times, &h))) w.bind(id, h); });
+        try { s.wait(); } catch (...) { s.meta.erase(id); throw; }
+        *out = id;
+    });
+}
+
 int vec_give_up_values(const fmhip_vec* vectors, int count) {
     return fronted([&](Shards& s) {
         need(vectors, "vectors");

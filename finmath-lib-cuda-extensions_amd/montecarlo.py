@@ -23,6 +23,8 @@ a RandomVariableFactory by injection (LIBORMarketModelCalibrationATMTest.java:35
                             time, integrated against its density — as its check
     bermudan_option_mc      Longstaff–Schwartz backward induction over MonteCarloConditionalExpectationRegression (regression.py):
                             what finmath-lib's BermudanOption does with its conditional-expectation estimator
+    bermudan_option_bounds_mc  the primal–dual bounds of Andersen & Broadie for the same option: the fitted policy on fresh paths, and a
+                            martingale from inner simulations at every exercise date of every outer path (nested.py)
     bermudan_max_call_mc    the same induction for a call on the maximum of several assets, regressed on all monomials of the assets up
                             to a total degree: 10 … 56 basis functions, the wide one-pass normal equations
 """
@@ -362,6 +364,107 @@ def bermudan_option_mc(brownian_motion, initial_value, risk_free_rate, volatilit
         exercise = exercise_value(s, dates[k])
         value = exercise.sub(continuation).choose(exercise, value)
     return value.getAverage(), value
+
+
+def bermudan_option_bounds_mc(brownian_motion_fit, brownian_motion_outer, inner_paths, inner_seed, initial_value, risk_free_rate, volatility,
+                              exercise_dates, strike, call=False, basis_order=3):
+    """Primal–dual bounds of a Bermudan option under Black–Scholes (Andersen & Broadie 2004); model, scheme and payoff of bermudan_option_mc,
+    whose in-sample value is neither bound.  Returns dict(lower, lower_se, upper, upper_se), all discounted to time 0.
+    POLICY: the coefficients β_j of the continuation value on 1, S, …, S^basis_order come from the FIT sample by getLinearRegressionParameters
+    at each date, backwards, exactly as bermudan_option_mc regresses; a path stops at the first date j with h_j − Σβ_{j,i}S^i >= 0, and at the
+    last date always.
+    LOWER: the mean, over the OUTER sample (independent of the fit sample), of the discounted payoff at the policy's stopping date.
+    UPPER: for j = −1 (the root) and every date j = 0 … J−2, inner_paths inner paths are started from each outer path's state at j
+    (nested.repeat_each; a Brownian motion of m·inner_paths paths seeded inner_seed + j + 1) and follow the policy from date j+1 on; the
+    block mean of their discounted payoffs is C_j, an unbiased estimate of E_j[V_{j+1}] (nested.block_means).  V_j = h_j where the policy
+    stops at j (and at the last date), else C_j; M_{−1} = 0, M_j = M_{j−1} + V_j − C_{j−1}; upper = mean(max_j(h_j − M_j)).  The inner noise
+    biases the upper bound upwards, by less with more inner paths.  The standard errors are taken over the outer paths.
+    With FMHIP_DEVICE_NESTED=0 the four numbers are the same to the last bit: the host definition of the block means is the device's."""
+    import numpy as np
+    from .brownian_motion import BrownianMotionHip, TimeDiscretization
+    from .nested import block_means, repeat_each
+    from .regression import MonteCarloConditionalExpectationRegression
+    dates = sorted(float(d) for d in exercise_dates)
+    if not dates: raise ValueError("no exercise date")
+    inner_paths = int(inner_paths)
+    if inner_paths < 1: raise ValueError("at least one inner path per outer path")
+    drift = risk_free_rate - 0.5 * volatility * volatility
+
+    def states_at(bm, x, wanted):
+        """[(log state, state) at each date of `wanted`] by the log-Euler scheme from x at the first time of bm's discretisation."""
+        td = bm.getTimeDiscretization()
+        out, t, i = [], td.getTime(0), 0
+        if wanted and abs(t - wanted[0]) <= 1e-12: out.append((x, x.exp()))
+        while len(out) < len(wanted):
+            x = x.add(drift * td.getTimeStep(i)).addProduct(bm.getBrownianIncrement(i, 0), volatility)
+            i += 1
+            t = td.getTime(i)
+            if t > wanted[len(out)] + 1e-12: raise ValueError("an exercise date is not a point of the time discretisation")
+            if abs(t - wanted[len(out)]) <= 1e-12: out.append((x, x.exp()))
+        return out
+
+    def exercise_value(s, date):
+        payoff = s.sub(strike).floor(0.0) if call else s.bus(strike).floor(0.0)
+        return payoff.div(math.exp(risk_free_rate * date))
+
+    def continuation(s, beta, one):
+        ce = one.mult(float(beta[0]))
+        power = s
+        for i in range(1, len(beta)):
+            ce = ce.addProduct(power, float(beta[i]))
+            if i + 1 < len(beta): power = power.mult(s)
+        return ce
+
+    def policy_value(states, first, one):
+        """The discounted payoff at the policy's stopping date, for paths that are alive at date `first`; states[k - first] = S at date k."""
+        value = exercise_value(states[-1], dates[-1])
+        for k in range(len(dates) - 2, first - 1, -1):
+            exercise = exercise_value(states[k - first], dates[k])
+            value = exercise.sub(continuation(states[k - first], betas[k], one)).choose(exercise, value)
+        return value
+
+    # the policy, from the fit sample
+    one = brownian_motion_fit.getRandomVariableForConstant(1.0)
+    fit = [s for _, s in states_at(brownian_motion_fit, brownian_motion_fit.getRandomVariableForConstant(math.log(initial_value)), dates)]
+    betas = [None] * len(dates)
+    value = exercise_value(fit[-1], dates[-1])
+    for k in range(len(dates) - 2, -1, -1):
+        s = fit[k]
+        basis = [one, s]
+        for _ in range(2, basis_order + 1): basis.append(basis[-1].mult(s))
+        basis = basis[:basis_order + 1]
+        betas[k] = MonteCarloConditionalExpectationRegression(basis).getLinearRegressionParameters(value)
+        exercise = exercise_value(s, dates[k])
+        value = exercise.sub(continuation(s, betas[k], one)).choose(exercise, value)
+
+    # the lower bound: the policy on the outer sample
+    one = brownian_motion_outer.getRandomVariableForConstant(1.0)
+    x0 = brownian_motion_outer.getRandomVariableForConstant(math.log(initial_value))
+    outer = states_at(brownian_motion_outer, x0, dates)
+    lower = policy_value([s for _, s in outer], 0, one)
+
+    # the upper bound: the martingale from inner simulations at the root and at every date but the last
+    m = brownian_motion_outer.getNumberOfPaths()
+    times = brownian_motion_outer.getTimeDiscretization().getAsDoubleArray()
+    previous_c, martingale, worst = None, None, None
+    for j in range(-1, len(dates)):
+        if j < len(dates) - 1:
+            start_time = times[0] if j < 0 else dates[j]
+            first_index = int(np.argmin(np.abs(times - start_time)))
+            inner_bm = BrownianMotionHip(TimeDiscretization(times[first_index:]), 1, m * inner_paths, inner_seed + j + 1)
+            start = x0 if j < 0 else repeat_each(outer[j][0], inner_paths)
+            inner = states_at(inner_bm, start, dates[j + 1:])
+            c = block_means(policy_value([s for _, s in inner], j + 1, one), inner_paths)
+        else: c = None
+        if j >= 0:
+            h = exercise_value(outer[j][1], dates[j])
+            v = h if c is None else h.sub(continuation(outer[j][1], betas[j], one)).choose(h, c)
+            increment = v.sub(previous_c)
+            martingale = increment if martingale is None else martingale.add(increment)
+            gap = h.sub(martingale)
+            worst = gap if worst is None else worst.floor(gap)
+        previous_c = c
+    return dict(lower=lower.getAverage(), lower_se=lower.getStandardError(), upper=worst.getAverage(), upper_se=worst.getStandardError())
 
 
 def monomial_exponents(n_assets, order):

@@ -542,6 +542,40 @@ int fmhip_option_formula_host(int model, const float* forward, double forward_sc
                               const float* payoff_unit, double payoff_unit_scalar, int64_t n, double maturity, double strike,
                               int outputs, float* const* out);
 
+/* Nested simulation on the device: the two operations that change the SHAPE of a sample — k inner paths started from each
+ * of m outer states (fmhip_vec_repeat), and the m*k inner payoffs reduced to m conditional means with their inner variances
+ * (fmhip_block_moments) — without the vectors leaving the device.  The definition is host/block_moments.hpp, one header for the host and
+ * the device: fp64, + - * / and comparisons.
+ * A vector of n = m*block elements is m consecutive blocks of `block` elements.  For block q, S1[q] is the fp64 sum of (double)v[q*block + i]
+ *   and S2[q] the fp64 sum of the exact squares (double)x*(double)x, both in ONE association that is a function of `block` alone (not of q,
+ *   m, the vectors of the call, a vector's slot, the mask or the launch): segments of 2048 consecutive elements, each summed as 64 leaves —
+ *   leaf l is the running sum of the segment's elements l, l + 64, ... — joined by a butterfly over the leaf index, bit 5 first; the segment
+ *   sums of a block above 2048 elements are summed as one more such unit.  |S - exact| <= (fm_block_chain(block) + 1) * 2^-53 * sum|terms|.
+ *   The device's outputs EQUAL fmhip_block_moments_host's bit for bit.
+ * Outputs per block, each rounded to fp32 once from fp64 (a NaN result is the quiet NaN 0x7fc00000):
+ *   FMHIP_BLOCK_SUM (float)S1;  FMHIP_BLOCK_MEAN (float)(S1/block);  FMHIP_BLOCK_VARIANCE (float)max(0, S2/block - (S1/block)^2), the
+ *   population variance from RAW moments: absolute error about fm_block_chain(block) * 2^-53 * S2/block — adequate for the standard error
+ *   of an inner estimate, no replacement for the shifted pass of fmhip_reduce_moments.  NaN and +-inf propagate as fp64 arithmetic
+ *   propagates them, inside their block only.
+ * fmhip_block_moments: n_vs = 1 ... 4 vectors of one size n (1 ... 2^31 - 1, a multiple of block >= 1), each read once; mask: at least one
+ *   of the three bits; outs[i*popcount(mask) + j] = a new, materialised vector of n/block elements, j over the set bits in ascending order.
+ * fmhip_block_moments_host: the DEFINITION over a host float array: outs[j*(n/block) + q]; needs no device.
+ * fmhip_vec_repeat: *out = a new, materialised vector of n*each*times (<= 2^31 - 1) elements, out[(t*n + p)*each + e] = v[p] copied bit
+ *   for bit (a NaN keeps its payload, a zero its sign): each = k, times = 1 starts k inner paths per outer state; each = 1 tiles.
+ * Everything is checked on the host before anything is flushed or launched: n_vs outside 1 ... 4, a mask of 0 or with unknown bits,
+ * block < 1, n no multiple of block, each < 1, times < 1, an output beyond 2^31 - 1 elements, a NULL pointer, a handle of 0 ->
+ * FMHIP_ERR_INVALID_ARGUMENT; vectors of different sizes -> FMHIP_ERR_SIZE_MISMATCH; FMHIP_ERR_INVALID_HANDLE.  A vector whose values were
+ * given up is the error a read of it is.  A build without the kernels answers FMHIP_ERR_UNSUPPORTED; it never falls back.  With a device
+ * list of more than one shard both device calls answer FMHIP_ERR_UNSUPPORTED (blocks would straddle the shards); under an expectation
+ * communicator they act on this rank's own vector, as fmhip_vec_read_elements does. */
+#define FMHIP_BLOCK_SUM 1u
+#define FMHIP_BLOCK_MEAN 2u
+#define FMHIP_BLOCK_VARIANCE 4u
+int fmhip_block_moments(const fmhip_vec* vs, int n_vs, int64_t block, uint32_t mask, fmhip_vec* outs);
+    /* outs[i*popcount(mask) + j]: new vectors of size n/block, j in ascending bit order */
+int fmhip_block_moments_host(const float* v, int64_t n, int64_t block, uint32_t mask, float* outs);   /* the DEFINITION; no device */
+int fmhip_vec_repeat(fmhip_vec v, int64_t each, int64_t times, fmhip_vec* out);
+
 /* Kernel regression on the device: kernel-weighted LOCAL MOMENTS of up to four vectors at a grid of points of a key vector
  * in one pass — E[y | x = p_q] as a curve: the inner step of the particle method for local-stochastic-volatility calibration
  * (E[v_t | S_t = S] at every time step), kernel density estimates, smooth exercise boundaries, exposure profiles — without the vectors

@@ -126,6 +126,13 @@ final class Native {
 	static native int optionFormula(int model, long forward, double forwardScalar, long volatility, double volatilityScalar, long payoffUnit, double payoffUnitScalar, double maturity, double strike, int outputs, long[] out);
 	/** The definition of optionFormula over host arrays of n floats; an operand array that is null is the scalar beside it; outColumns holds one column of n floats per set bit. */
 	static native int optionFormulaHost(int model, float[] forwardOrNull, double forwardScalar, float[] volatilityOrNull, double volatilityScalar, float[] payoffUnitOrNull, double payoffUnitScalar, int n, double maturity, double strike, int outputs, float[] outColumns);
+	// ---- nested simulation: the moments of consecutive blocks as new vectors, and the repeat that starts k inner paths per outer state
+	/** outs[i * popcount(mask) + j] = a new vector of n / block elements: output j (mask bits in ascending order: 1 sum, 2 mean, 4 population variance) of the consecutive blocks of vs[i]; 1 ... 4 vectors of one size, each read once; the bits are those of blockMomentsHost. */
+	static native int blockMoments(long[] vs, long block, int mask, long[] outs);
+	/** The definition of blockMoments over a host array: outColumns holds one column of v.length / block floats per set bit of mask. */
+	static native int blockMomentsHost(float[] v, long block, int mask, float[] outColumns);
+	/** out[0] = a new vector of n * each * times elements: out[(t * n + p) * each + e] = v[p], copied bit for bit. */
+	static native int vecRepeat(long v, long each, long times, long[] out);
 	// ---- kernel regression: kernel-weighted local moments of up to 4 vectors at up to 256 points of a key from one launch
 	/** sumsOut[points.length][order 0: 1 + y.length; order 1: 3 + 2 y.length]: per point the fp64 sums [w, w*y...] or [w, w*d, w*d*d, w*y..., w*d*y...] over its members (lower &lt; key &lt; upper); kernel 0 uniform, 1 triangular, 2 Epanechnikov, 3 quartic, 4 triweight. */
 	static native int kernelMoments(long key, double[] points, double[] bandwidths, int kernel, int order, long[] y, double[] sumsOut);

@@ -354,6 +354,32 @@ FMJ(jint, kernelMomentsHost)(JNIEnv* env, jclass, jfloatArray key, jdoubleArray 
     if ((int64_t)po.length() < q * kernel_entries(order, nY)) return FMHIP_ERR_INVALID_ARGUMENT;
     return fmhip_kernel_moments_host(pk.p, n, pp.p, pb.p, (int)q, (int)kernel, (int)order, nY ? ys.data() : nullptr, nY, po.p);
 }
+// ---------------------------------------------------------------- nested simulation: block moments and the repeat
+FMJ(jint, blockMoments)(JNIEnv* env, jclass, jlongArray vs, jlong block, jint mask, jlongArray outs) {
+    Pin<jlong> pv(env, vs, JNI_ABORT);
+    const int64_t nv = pv.p ? pv.length() : 0;
+    if (nv < 1 || nv > 4 || mask < 1 || mask > 7 || !outs) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int total = (int)nv * ((mask & 1) + ((mask >> 1) & 1) + ((mask >> 2) & 1));
+    if (env->GetArrayLength(outs) < total) return FMHIP_ERR_INVALID_ARGUMENT;
+    fmhip_vec h[12] = { 0 };
+    const int st = fmhip_block_moments((const fmhip_vec*)pv.p, (int)nv, (int64_t)block, (uint32_t)mask, h);
+    if (st == FMHIP_OK) { jlong o[12]; for (int k = 0; k < total; ++k) o[k] = (jlong)h[k]; env->SetLongArrayRegion(outs, 0, (jsize)total, o); }
+    return st;
+}
+FMJ(jint, blockMomentsHost)(JNIEnv* env, jclass, jfloatArray v, jlong block, jint mask, jfloatArray outColumns) {
+    Pin<jfloat> pv(env, v, JNI_ABORT); Pin<jfloat> po(env, outColumns);
+    if (!pv.p || !po.p || block < 1 || mask < 1 || mask > 7) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int64_t n = pv.length(), columns = (mask & 1) + ((mask >> 1) & 1) + ((mask >> 2) & 1);
+    if ((int64_t)po.length() < columns * (n / (int64_t)block)) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_block_moments_host(pv.p, n, (int64_t)block, (uint32_t)mask, po.p);
+}
+FMJ(jint, vecRepeat)(JNIEnv* env, jclass, jlong v, jlong each, jlong times, jlongArray out) {
+    if (!out || env->GetArrayLength(out) < 1) return FMHIP_ERR_INVALID_ARGUMENT;
+    fmhip_vec h = 0;
+    const int st = fmhip_vec_repeat(v, (int64_t)each, (int64_t)times, &h);
+    if (st == FMHIP_OK) set1(env, out, (jlong)h);
+    return st;
+}
 // ---------------------------------------------------------------- named functions and option formulas per path
 FMJ(jint, functionApply)(JNIEnv* env, jclass, jlong x, jintArray kinds, jlongArray out) {
     Pin<jint> pk(env, kinds, JNI_ABORT);
