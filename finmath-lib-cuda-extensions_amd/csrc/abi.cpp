@@ -243,7 +243,7 @@ template <typename F> static int on_all(F&& call) {
 }
 #define TE_OWNER(h, call) do { if (te::active()) { const int te_rc = te::owner_routed((h), [&]() -> int { return call; }); if (te_rc != te::NOT_MINE_TO_HANDLE) return te_rc; } } while (0)
 #define TE_LOCAL(arr, n, L, call) do { if (te::active()) { const int te_rc = te::with_local((arr), (n), [&](const fmhip_vec* L) -> int { return call; }); if (te_rc != te::NOT_MINE_TO_HANDLE) return te_rc; } } while (0)
-// the operands of a side pass as ONE list for TE_LOCAL (key?, x…, y…), so that foreign operands of any of them are imported by one call
+// the operands of a side pass as one list (key?, x…, y…)
 static std::vector<fmhip_vec> te_operands(fmhip_vec key, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y) {
     std::vector<fmhip_vec> all;
     if (key) all.push_back(key);
@@ -251,6 +251,11 @@ static std::vector<fmhip_vec> te_operands(fmhip_vec key, const fmhip_vec* x, int
     all.insert(all.end(), y, y + n_y);
     return all;
 }
+// A side pass with thread engines: `check` — what can be said about the arguments on the host — runs before any foreign operand is imported;
+// then TE_LOCAL with the operands as ONE list (te_operands, te_poly_operands), so that foreign ones among any of them are imported by one call.
+#define TE_CHECKED_LOCAL(check, operands, L, call) do { if (te::active()) { \
+    const int te_checked = host_only([&] { check; }); if (te_checked != FMHIP_OK) return te_checked; \
+    const std::vector<fmhip_vec> te_all = (operands); TE_LOCAL(te_all.data(), (int)te_all.size(), L, call); } } while (0)
 #define TE_ALL(mine, call) do { if (te::active()) return te::on_all([&](bool mine) -> int { (void)mine; return call; }); } while (0)
 
 extern "C" {
@@ -751,12 +756,8 @@ static std::vector<fmhip_vec> te_poly_operands(const fmhip_vec* states, int n_st
 }
 int fmhip_polynomial_cross_moments(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const fmhip_vec* y, int n_y, double* sums_out) {
     FRONT(polynomial_cross_moments(states, n_states, exponents, n_terms, extra_x, n_extra, y, n_y, sums_out));
-    if (te::active()) {
-        const int rc = host_only([&] { fm::poly_check_moments(states, n_states, exponents, n_terms, extra_x, n_extra, y, n_y, sums_out); });
-        if (rc != FMHIP_OK) return rc;
-        const std::vector<fmhip_vec> all = te_poly_operands(states, n_states, extra_x, n_extra, y, n_y);
-        TE_LOCAL(all.data(), n_states + n_extra + n_y, L, fmhip_polynomial_cross_moments(L, n_states, exponents, n_terms, L + n_states, n_extra, L + n_states + n_extra, n_y, sums_out));
-    }
+    TE_CHECKED_LOCAL(fm::poly_check_moments(states, n_states, exponents, n_terms, extra_x, n_extra, y, n_y, sums_out), te_poly_operands(states, n_states, extra_x, n_extra, y, n_y), L,
+                     fmhip_polynomial_cross_moments(L, n_states, exponents, n_terms, L + n_states, n_extra, L + n_states + n_extra, n_y, sums_out));
     return guarded([&] {
         Engine& e = Engine::get();
         e.xmom_poly_pass(states, n_states, exponents, n_terms, extra_x, n_extra, y, n_y, sums_out);
@@ -766,13 +767,9 @@ int fmhip_polynomial_cross_moments(const fmhip_vec* states, int n_states, const 
 }
 int fmhip_polynomial_evaluate(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const double* coefficients, fmhip_vec* out) {
     FRONT(polynomial_evaluate(states, n_states, exponents, n_terms, extra_x, n_extra, coefficients, out));
-    if (te::active()) {
-        const int rc = host_only([&] { fm::poly_check_evaluate(states, n_states, exponents, n_terms, extra_x, n_extra, coefficients, out); });
-        if (rc != FMHIP_OK) return rc;
-        const std::vector<fmhip_vec> all = te_poly_operands(states, n_states, extra_x, n_extra, nullptr, 0);
-        TE_LOCAL(all.data(), n_states + n_extra, L, fmhip_polynomial_evaluate(L, n_states, exponents, n_terms, L + n_states, n_extra, coefficients, out));
-    }
-    return guarded([&] { const fmhip_vec r = Engine::get().poly_eval(states, n_states, exponents, n_terms, extra_x, n_extra, coefficients, out); *out = r; });
+    TE_CHECKED_LOCAL(fm::poly_check_evaluate(states, n_states, exponents, n_terms, extra_x, n_extra, coefficients, out), te_poly_operands(states, n_states, extra_x, n_extra, nullptr, 0), L,
+                     fmhip_polynomial_evaluate(L, n_states, exponents, n_terms, L + n_states, n_extra, coefficients, out));
+    return guarded([&] { Engine::get().poly_eval(states, n_states, exponents, n_terms, extra_x, n_extra, coefficients, out); });
 }
 
 // ---------------------------------------------------------------- localized regression (binned_engine.hpp)
@@ -791,12 +788,8 @@ int fmhip_binned_evaluate_host(const float* key, int64_t n, const double* bounds
 }
 int fmhip_binned_cross_moments(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, int64_t* counts_out, double* sums_out) {
     FRONT(binned_cross_moments(key, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out));
-    if (te::active()) {
-        const int rc = host_only([&] { fm::binned_check_moments(key, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out); });
-        if (rc != FMHIP_OK) return rc;
-        const std::vector<fmhip_vec> all = te_operands(key, x, n_x, y, n_y);
-        TE_LOCAL(all.data(), 1 + n_x + n_y, L, fmhip_binned_cross_moments(L[0], bounds, n_bins, L + 1, n_x, L + 1 + n_x, n_y, counts_out, sums_out));
-    }
+    TE_CHECKED_LOCAL(fm::binned_check_moments(key, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out), te_operands(key, x, n_x, y, n_y), L,
+                     fmhip_binned_cross_moments(L[0], bounds, n_bins, L + 1, n_x, L + 1 + n_x, n_y, counts_out, sums_out));
     return guarded([&] {
         Engine& e = Engine::get();
         e.binned_xmom_pass(key, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out);
@@ -813,13 +806,9 @@ int fmhip_binned_cross_moments(fmhip_vec key, const double* bounds, int n_bins, 
 }
 int fmhip_binned_evaluate(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const double* coefficients, fmhip_vec* out) {
     FRONT(binned_evaluate(key, bounds, n_bins, x, n_x, coefficients, out));
-    if (te::active()) {
-        const int rc = host_only([&] { fm::binned_check_evaluate(key, bounds, n_bins, x, n_x, coefficients, out); });
-        if (rc != FMHIP_OK) return rc;
-        const std::vector<fmhip_vec> all = te_operands(key, x, n_x, nullptr, 0);
-        TE_LOCAL(all.data(), 1 + n_x, L, fmhip_binned_evaluate(L[0], bounds, n_bins, L + 1, n_x, coefficients, out));
-    }
-    return guarded([&] { const fmhip_vec r = Engine::get().binned_eval(key, bounds, n_bins, x, n_x, coefficients, out); *out = r; });
+    TE_CHECKED_LOCAL(fm::binned_check_evaluate(key, bounds, n_bins, x, n_x, coefficients, out), te_operands(key, x, n_x, nullptr, 0), L,
+                     fmhip_binned_evaluate(L[0], bounds, n_bins, L + 1, n_x, coefficients, out));
+    return guarded([&] { Engine::get().binned_eval(key, bounds, n_bins, x, n_x, coefficients, out); });
 }
 
 // ---------------------------------------------------------------- the device sort (sort_engine.hpp)
@@ -828,12 +817,8 @@ int fmhip_argsort_host(const float* key, int64_t n, int64_t* permutation_out) {
 }
 int fmhip_sort_by_key(fmhip_vec key, const fmhip_vec* values, int n_values, fmhip_vec* sorted_key_out, fmhip_vec* sorted_values_out) {
     FRONT(sort_by_key(key, values, n_values, sorted_key_out, sorted_values_out));
-    if (te::active()) {
-        const int rc = host_only([&] { fm::sort_check_by_key(key, values, n_values, sorted_key_out, sorted_values_out); });
-        if (rc != FMHIP_OK) return rc;
-        const std::vector<fmhip_vec> all = te_operands(key, values, n_values, nullptr, 0);
-        TE_LOCAL(all.data(), 1 + n_values, L, fmhip_sort_by_key(L[0], L + 1, n_values, sorted_key_out, sorted_values_out));
-    }
+    TE_CHECKED_LOCAL(fm::sort_check_by_key(key, values, n_values, sorted_key_out, sorted_values_out), te_operands(key, values, n_values, nullptr, 0), L,
+                     fmhip_sort_by_key(L[0], L + 1, n_values, sorted_key_out, sorted_values_out));
     return guarded([&] { Engine::get().sort_by_key(key, values, n_values, sorted_key_out, sorted_values_out); });
 }
 int fmhip_argsort(fmhip_vec key, int64_t* permutation_out) {
@@ -843,11 +828,8 @@ int fmhip_argsort(fmhip_vec key, int64_t* permutation_out) {
 }
 int fmhip_rank_scores(fmhip_vec key, fmhip_vec* out) {
     FRONT(rank_scores(key, out));
-    if (te::active()) {
-        if (!out) { g_last_error = "null pointer: out"; return FMHIP_ERR_INVALID_ARGUMENT; }
-        TE_LOCAL(&key, 1, L, fmhip_rank_scores(L[0], out));
-    }
-    return guarded([&] { const fmhip_vec r = Engine::get().rank_scores(key, out); *out = r; });
+    TE_CHECKED_LOCAL(need(out, "out"), te_operands(key, nullptr, 0, nullptr, 0), L, fmhip_rank_scores(L[0], out));
+    return guarded([&] { Engine::get().rank_scores(key, out); });
 }
 int fmhip_vec_read_elements(fmhip_vec v, const int64_t* positions, int count, double* out) {
     FRONT(vec_read_elements(v, positions, count, out));
@@ -861,12 +843,8 @@ int fmhip_prefix_sums_host(const float* v, int64_t n, double* prefix_out) {
 }
 int fmhip_prefix_sums(fmhip_vec v, int mode, fmhip_vec* out, double* total_out) {
     FRONT(prefix_sums(v, mode, out, total_out));
-    if (te::active()) {
-        const int rc = host_only([&] { fm::prefix_check_sums(v, mode, out); });
-        if (rc != FMHIP_OK) return rc;
-        TE_LOCAL(&v, 1, L, fmhip_prefix_sums(L[0], mode, out, total_out));
-    }
-    return guarded([&] { const fmhip_vec r = Engine::get().prefix_sums(v, mode, out, total_out); *out = r; });
+    TE_CHECKED_LOCAL(fm::prefix_check_sums(v, mode, out), te_operands(v, nullptr, 0, nullptr, 0), L, fmhip_prefix_sums(L[0], mode, out, total_out));
+    return guarded([&] { Engine::get().prefix_sums(v, mode, out, total_out); });
 }
 int fmhip_prefix_sums_at(fmhip_vec v, const int64_t* positions, int count, double* sums_out) {
     FRONT(prefix_sums_at(v, positions, count, sums_out));
@@ -888,11 +866,7 @@ int fmhip_table_apply_host(const float* x, int64_t n, const double* knots, int c
 }
 int fmhip_table_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, fmhip_vec* out) {
     FRONT(table_apply(x, knots, count, coefficients, n_tables, out));
-    if (te::active()) {
-        const int rc = host_only([&] { fm::table_check_apply(x, knots, count, coefficients, n_tables, out); });
-        if (rc != FMHIP_OK) return rc;
-        TE_LOCAL(&x, 1, L, fmhip_table_apply(L[0], knots, count, coefficients, n_tables, out));
-    }
+    TE_CHECKED_LOCAL(fm::table_check_apply(x, knots, count, coefficients, n_tables, out), te_operands(x, nullptr, 0, nullptr, 0), L, fmhip_table_apply(L[0], knots, count, coefficients, n_tables, out));
     return guarded([&] { Engine::get().table_apply(x, knots, count, coefficients, n_tables, out); });
 }
 
@@ -909,12 +883,8 @@ int fmhip_kernel_moments_host(const float* key, int64_t n, const double* points,
 }
 int fmhip_kernel_moments(fmhip_vec key, const double* points, const double* bandwidths, int n_points, int kernel, int order, const fmhip_vec* y, int n_y, double* sums_out) {
     FRONT(kernel_moments(key, points, bandwidths, n_points, kernel, order, y, n_y, sums_out));
-    if (te::active()) {
-        const int rc = host_only([&] { fm::kernel_moments_check(key, points, bandwidths, n_points, kernel, order, y, n_y, sums_out); });
-        if (rc != FMHIP_OK) return rc;
-        const std::vector<fmhip_vec> all = te_operands(key, y, n_y, nullptr, 0);      // key and y as ONE list
-        TE_LOCAL(all.data(), 1 + n_y, L, fmhip_kernel_moments(L[0], points, bandwidths, n_points, kernel, order, L + 1, n_y, sums_out));
-    }
+    TE_CHECKED_LOCAL(fm::kernel_moments_check(key, points, bandwidths, n_points, kernel, order, y, n_y, sums_out), te_operands(key, y, n_y, nullptr, 0), L,
+                     fmhip_kernel_moments(L[0], points, bandwidths, n_points, kernel, order, L + 1, n_y, sums_out));
     return guarded([&] {
         Engine& e = Engine::get();
         e.kernel_moments_pass(key, points, bandwidths, n_points, kernel, order, y, n_y, sums_out);
@@ -932,27 +902,16 @@ int fmhip_option_formula_host(int model, const float* forward, double forward_sc
 }
 int fmhip_function_apply(fmhip_vec x, const int* kinds, int n_functions, fmhip_vec* out) {
     FRONT(function_apply(x, kinds, n_functions, out));
-    if (te::active()) {
-        const int rc = host_only([&] { fm::analytic_check_function(x, kinds, n_functions, out); });
-        if (rc != FMHIP_OK) return rc;
-        TE_LOCAL(&x, 1, L, fmhip_function_apply(L[0], kinds, n_functions, out));
-    }
+    TE_CHECKED_LOCAL(fm::analytic_check_function(x, kinds, n_functions, out), te_operands(x, nullptr, 0, nullptr, 0), L, fmhip_function_apply(L[0], kinds, n_functions, out));
     return guarded([&] { Engine::get().function_apply(x, kinds, n_functions, out); });
 }
 int fmhip_option_formula(int model, fmhip_vec forward, double forward_scalar, fmhip_vec volatility, double volatility_scalar, fmhip_vec payoff_unit,
                          double payoff_unit_scalar, double maturity, double strike, int outputs, fmhip_vec* out) {
     FRONT(option_formula(model, forward, forward_scalar, volatility, volatility_scalar, payoff_unit, payoff_unit_scalar, maturity, strike, outputs, out));
-    if (te::active()) {
-        const int rc = host_only([&] { fm::analytic_check_formula(model, forward, volatility, payoff_unit, maturity, strike, outputs, out); });
-        if (rc != FMHIP_OK) return rc;
-        // the vector operands as ONE list, so that foreign ones are imported by one call; a handle of 0 stays the scalar
-        fmhip_vec all[3]; int count = 0;
-        const int at_f = forward ? count : -1; if (forward) all[count++] = forward;
-        const int at_v = volatility ? count : -1; if (volatility) all[count++] = volatility;
-        const int at_n = payoff_unit ? count : -1; if (payoff_unit) all[count++] = payoff_unit;
-        TE_LOCAL(all, count, L, fmhip_option_formula(model, at_f < 0 ? 0 : L[at_f], forward_scalar, at_v < 0 ? 0 : L[at_v], volatility_scalar, at_n < 0 ? 0 : L[at_n],
-                                                     payoff_unit_scalar, maturity, strike, outputs, out));
-    }
+    // (all three in the list: a handle of 0 stays 0, the scalar beside it)
+    const fmhip_vec operands[3] = { forward, volatility, payoff_unit };
+    TE_CHECKED_LOCAL(fm::analytic_check_formula(model, forward, volatility, payoff_unit, maturity, strike, outputs, out), te_operands(0, operands, 3, nullptr, 0), L,
+                     fmhip_option_formula(model, L[0], forward_scalar, L[1], volatility_scalar, L[2], payoff_unit_scalar, maturity, strike, outputs, out));
     return guarded([&] { Engine::get().option_formula(model, forward, forward_scalar, volatility, volatility_scalar, payoff_unit, payoff_unit_scalar, maturity, strike, outputs, out); });
 }
 
@@ -962,21 +921,13 @@ int fmhip_block_moments_host(const float* v, int64_t n, int64_t block, uint32_t 
 }
 int fmhip_block_moments(const fmhip_vec* vs, int n_vs, int64_t block, uint32_t mask, fmhip_vec* outs) {
     FRONT(block_moments(vs, n_vs, block, mask, outs));
-    if (te::active()) {
-        const int rc = host_only([&] { fm::nested_check_moments(vs, n_vs, block, mask, outs); });
-        if (rc != FMHIP_OK) return rc;
-        TE_LOCAL(vs, n_vs, L, fmhip_block_moments(L, n_vs, block, mask, outs));
-    }
+    TE_CHECKED_LOCAL(fm::nested_check_moments(vs, n_vs, block, mask, outs), te_operands(0, vs, n_vs, nullptr, 0), L, fmhip_block_moments(L, n_vs, block, mask, outs));
     return guarded([&] { Engine::get().block_moments(vs, n_vs, block, mask, outs); });
 }
 int fmhip_vec_repeat(fmhip_vec v, int64_t each, int64_t times, fmhip_vec* out) {
     FRONT(vec_repeat(v, each, times, out));
-    if (te::active()) {
-        const int rc = host_only([&] { fm::nested_check_repeat(v, each, times, out); });
-        if (rc != FMHIP_OK) return rc;
-        TE_LOCAL(&v, 1, L, fmhip_vec_repeat(L[0], each, times, out));
-    }
-    return guarded([&] { const fmhip_vec r = Engine::get().repeat(v, each, times, out); *out = r; });
+    TE_CHECKED_LOCAL(fm::nested_check_repeat(v, each, times, out), te_operands(v, nullptr, 0, nullptr, 0), L, fmhip_vec_repeat(L[0], each, times, out));
+    return guarded([&] { Engine::get().repeat(v, each, times, out); });
 }
 
 // The one call of a caller that values product after product: the engine lock is held for the bookkeeping (graph → launch → commit),

@@ -1,14 +1,11 @@
 // analytic_engine.hpp — the engine's side of the named functions and the option formulas per path (kernels:
-// analytic_kernel.hip; definition and argument checks: host/normal_functions.hpp).  Part of runtime.cpp's translation unit (included at its
-// end behind side_pass_engine.hpp, nowhere else).
+// analytic_kernel.hip; definition and argument checks: host/normal_functions.hpp).  Producing passes in the frame of side_pass_engine.hpp
+// (which says what every such pass does).
 //
-// function_apply: up to four of Φ, φ, Φ⁻¹ applied to every element of x, each result a NEW, materialised vector.  option_formula: value,
-// delta and vega (any of them, by a mask) of a Black–Scholes or Bachelier call whose forward, volatility and payoff unit are each a vector
-// or a scalar; one new vector per set bit.  Both: the arguments are checked before anything is flushed; one flush for pending operands,
-// their storage held; the outputs are allocated first, so that a failed allocation leaves nothing launched and gives the earlier buffers
-// back; one launch, not waited for; nothing goes through the pinned stage — the arguments are the launch's.  The passes are elementwise:
-// a device list runs them per shard (sharded.cpp), a communicator's ranks each on their own paths.  Without the kernels the calls are
-// FMHIP_ERR_UNSUPPORTED: the mirrors' host path is a caller's choice (FMHIP_DEVICE_ANALYTIC=0), never the engine's.
+// function_apply: up to four of Φ, φ, Φ⁻¹ applied to every element of x, each result a new vector.  option_formula: value, delta and vega
+// (any of them, by a mask) of a Black–Scholes or Bachelier call whose forward, volatility and payoff unit are each a vector or a scalar;
+// one new vector per set bit.  Both: one launch, not waited for; nothing goes through the pinned stage — the arguments are the launch's.
+// The passes are elementwise: a device list runs them per shard (sharded.cpp), a communicator's ranks each on their own paths.
 #include "runtime.hpp"
 #include "analytic_kernel.h"
 
@@ -24,25 +21,21 @@ static_assert(FMHIP_FN_NORMAL_CDF == fmhost::FM_FN_NORMAL_CDF && FMHIP_FN_NORMAL
 hipError_t launch_function_apply(const DevFunctionArgs& a, hipStream_t st) __attribute__((weak));
 hipError_t launch_option_formula(const DevFormulaArgs& a, hipStream_t st) __attribute__((weak));
 
-template <class F> static void analytic_as_engine_error(F&& f) {
-    try { f(); }
-    catch (const std::invalid_argument& e) { throw Error(FMHIP_ERR_INVALID_ARGUMENT, e.what()); }
-}
 void analytic_check_function(fmhip_vec x, const int* kinds, int n_functions, const fmhip_vec* out) {
     if (!x) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "named functions: of a vector");
-    analytic_as_engine_error([&] { fmhost::functionCheckApply(kinds, n_functions, out); });
+    pass_as_engine_error([&] { fmhost::functionCheckApply(kinds, n_functions, out); });
 }
 void analytic_check_formula(int model, fmhip_vec forward, fmhip_vec volatility, fmhip_vec payoff_unit, double maturity, double strike, int outputs, const fmhip_vec* out) {
-    analytic_as_engine_error([&] { fmhost::formulaCheck(model, maturity, strike, outputs, out); });
+    pass_as_engine_error([&] { fmhost::formulaCheck(model, maturity, strike, outputs, out); });
     if (!forward && !volatility && !payoff_unit) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "option formula: at least one of forward, volatility and payoff unit is a vector");
 }
 // fmhip_function_apply_host and fmhip_option_formula_host: the definitions, with their complaints as engine errors
 void function_apply_host_checked(const float* x, int64_t n, const int* kinds, int n_functions, float* const* out) {
-    analytic_as_engine_error([&] { fmhost::function_apply_host(x, n, kinds, n_functions, out); });
+    pass_as_engine_error([&] { fmhost::function_apply_host(x, n, kinds, n_functions, out); });
 }
 void option_formula_host_checked(int model, const float* forward, double forward_scalar, const float* volatility, double volatility_scalar, const float* payoff_unit,
                                  double payoff_unit_scalar, int64_t n, double maturity, double strike, int outputs, float* const* out) {
-    analytic_as_engine_error([&] { fmhost::option_formula_host(model, forward, forward_scalar, volatility, volatility_scalar, payoff_unit, payoff_unit_scalar, n, maturity, strike, outputs, out); });
+    pass_as_engine_error([&] { fmhost::option_formula_host(model, forward, forward_scalar, volatility, volatility_scalar, payoff_unit, payoff_unit_scalar, n, maturity, strike, outputs, out); });
 }
 
 void Engine::function_apply(fmhip_vec x, const int* kinds, int n_functions, fmhip_vec* out) {
@@ -56,19 +49,13 @@ void Engine::function_apply(fmhip_vec x, const int* kinds, int n_functions, fmhi
     a.n = hold.n; a.n_functions = (uint32_t)n_functions;
     for (int f = 0; f < n_functions; ++f) a.kinds[f] = (uint32_t)kinds[f];
     a.x = hold.ptrs[0];
-    // the outputs first: an allocation that fails leaves nothing launched
-    struct Outs { Engine* e; Buffer* b[fmhost::FM_FN_MAX_FUNCTIONS] = {}; ~Outs() { for (Buffer* p : b) if (p) e->buffer_unref(p); } } outs{ this };
-    for (int f = 0; f < n_functions; ++f) { outs.b[f] = new_buffer(hold.n); a.out[f] = (uint64_t)(uintptr_t)outs.b[f]->ptr; }
-    hip_check(launch_function_apply(a, stream_), "launch fm_function_apply_kernel");      // (a failed launch: ~Outs gives the buffers back)
+    PassOutputs outs(this);
+    for (int f = 0; f < n_functions; ++f) a.out[f] = outs.add(hold.n);
+    hip_check(launch_function_apply(a, stream_), "launch fm_function_apply_kernel");
     ++n_launches_;
     algorithmic_bytes_ += 4 * hold.n * (1 + n_functions);
     bytes_written_ += 4 * hold.n * n_functions;
-    for (int f = 0; f < n_functions; ++f) {
-        Node* nd = new_node(hold.n);
-        nd->buf = outs.b[f];
-        outs.b[f] = nullptr;
-        out[f] = nd->id;
-    }
+    outs.commit(out);
 }
 
 void Engine::option_formula(int model, fmhip_vec forward, double forward_scalar, fmhip_vec volatility, double volatility_scalar, fmhip_vec payoff_unit,
@@ -88,19 +75,13 @@ void Engine::option_formula(int model, fmhip_vec forward, double forward_scalar,
     a.scalar[0] = forward_scalar; a.scalar[1] = volatility_scalar; a.scalar[2] = payoff_unit_scalar;
     a.root_T = __builtin_sqrt(maturity); a.strike = strike;
     for (int v = 0; v < n_vectors; ++v) a.in[slot[v]] = hold.ptrs[(size_t)v];
-    // the outputs first: an allocation that fails leaves nothing launched
-    struct Outs { Engine* e; Buffer* b[fmhost::FM_FORMULA_MAX_OUTPUTS] = {}; ~Outs() { for (Buffer* p : b) if (p) e->buffer_unref(p); } } outs{ this };
-    for (int f = 0; f < n_out; ++f) { outs.b[f] = new_buffer(hold.n); a.out[f] = (uint64_t)(uintptr_t)outs.b[f]->ptr; }
-    hip_check(launch_option_formula(a, stream_), "launch fm_option_formula_kernel");      // (a failed launch: ~Outs gives the buffers back)
+    PassOutputs outs(this);
+    for (int f = 0; f < n_out; ++f) a.out[f] = outs.add(hold.n);
+    hip_check(launch_option_formula(a, stream_), "launch fm_option_formula_kernel");
     ++n_launches_;
     algorithmic_bytes_ += 4 * hold.n * (n_vectors + n_out);
     bytes_written_ += 4 * hold.n * n_out;
-    for (int f = 0; f < n_out; ++f) {
-        Node* nd = new_node(hold.n);
-        nd->buf = outs.b[f];
-        outs.b[f] = nullptr;
-        out[f] = nd->id;
-    }
+    outs.commit(out);
 }
 
 } // namespace fm

@@ -1,14 +1,11 @@
 // binned_engine.hpp — the engine's side of the localized regression (kernels: binned_kernel.hip; definition and argument
-// checks: host/binned_regression.hpp).  Part of runtime.cpp's translation unit (included at its end behind side_pass_engine.hpp, nowhere
-// else); the first of the two is a pass in that frame, as the cross moments are.
+// checks: host/binned_regression.hpp).  Passes in the frame of side_pass_engine.hpp (which says what every such pass does): the first a
+// reducing one, as the cross moments are, the second a producing one.
 //
 // binned_xmom_pass: the count and the cross moments of up to 3 + 4 vectors PER BIN of a key vector — the block-diagonal normal equations of
-// a regression that is local in the key — from ONE launch: one flush, the vectors' storage held, the wait under the engine lock.
-// binned_eval: the piecewise estimate as a NEW, materialised vector: one flush for pending operands, the bounds and the narrowed coefficients
-// go up in one copy that the host waits for (the pinned staging block is the engine's: it must be free again when the call returns), one
-// launch, and no wait for the launch itself.
-// The arguments of both are checked by the functions the host entry points use, before anything is flushed or launched.  Without the
-// kernels a pass is FMHIP_ERR_UNSUPPORTED: the mirrors' generic path is a caller's choice (FMHIP_DEVICE_BINNED_MOMENTS=0), never the engine's.
+// a regression that is local in the key — from ONE launch.
+// binned_eval: the piecewise estimate as a new vector: the bounds and the narrowed coefficients go up in one copy that the host waits for
+// (the pinned staging block is the engine's: it must be free again when the call returns); the launch itself is not waited for.
 #include "runtime.hpp"
 #include "binned_kernel.h"
 #include "../host/binned_regression.hpp"
@@ -24,22 +21,18 @@ static_assert(FM_BINNED_MAX_BINS == fmhost::FM_BINNED_MAX_BINS && FM_BINNED_MAX_
 hipError_t launch_binned_xmom(const DevBinnedXmomArgs& a, hipStream_t st) __attribute__((weak));
 hipError_t launch_binned_eval(const DevBinnedEvalArgs& a, hipStream_t st) __attribute__((weak));
 
-template <class F> static void binned_as_engine_error(F&& f) {
-    try { f(); }
-    catch (const std::invalid_argument& e) { throw Error(FMHIP_ERR_INVALID_ARGUMENT, e.what()); }
-}
 void binned_check_moments(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, const int64_t* counts_out, const double* sums_out) {
-    binned_as_engine_error([&] { fmhost::binnedCheckMoments<fmhip_vec>(key, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out); });
+    pass_as_engine_error([&] { fmhost::binnedCheckMoments<fmhip_vec>(key, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out); });
 }
 void binned_check_evaluate(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const double* coefficients, const fmhip_vec* out) {
-    binned_as_engine_error([&] { fmhost::binnedCheckEvaluate<fmhip_vec>(key, bounds, n_bins, x, n_x, coefficients, out); });
+    pass_as_engine_error([&] { fmhost::binnedCheckEvaluate<fmhip_vec>(key, bounds, n_bins, x, n_x, coefficients, out); });
 }
 // fmhip_binned_cross_moments_host and fmhip_binned_evaluate_host: the definition, with its complaints as engine errors
 void binned_cross_moments_host(const float* key, int64_t n, const double* bounds, int n_bins, const float* const* x, int n_x, const float* const* y, int n_y, int64_t* counts_out, double* sums_out) {
-    binned_as_engine_error([&] { fmhost::binnedCrossMoments(key, n, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out); });
+    pass_as_engine_error([&] { fmhost::binnedCrossMoments(key, n, bounds, n_bins, x, n_x, y, n_y, counts_out, sums_out); });
 }
 void binned_evaluate_host(const float* key, int64_t n, const double* bounds, int n_bins, const float* const* x, int n_x, const double* coefficients, float* out) {
-    binned_as_engine_error([&] { fmhost::binnedEvaluate(key, n, bounds, n_bins, x, n_x, coefficients, out); });
+    pass_as_engine_error([&] { fmhost::binnedEvaluate(key, n, bounds, n_bins, x, n_x, coefficients, out); });
 }
 
 // key first, then the vectors among x and y: handles, one size, n > 0 — before anything is flushed or launched
@@ -107,9 +100,9 @@ void Engine::binned_xmom_pass(fmhip_vec key, const double* bounds, int n_bins, c
     }
 }
 
-fmhip_vec Engine::binned_eval(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const double* coefficients, const fmhip_vec* out_checked) {
+void Engine::binned_eval(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const double* coefficients, fmhip_vec* out) {
     require_init();
-    binned_check_evaluate(key, bounds, n_bins, x, n_x, coefficients, out_checked);
+    binned_check_evaluate(key, bounds, n_bins, x, n_x, coefficients, out);
     fmhip_vec real[1 + FM_BINNED_MAX_X];
     const int n_real = binned_real(*this, key, x, n_x, nullptr, 0, real, "binned evaluation");
     pass_need_kernel(launch_binned_eval != nullptr, "binned evaluation");
@@ -120,6 +113,8 @@ fmhip_vec Engine::binned_eval(fmhip_vec key, const double* bounds, int n_bins, c
     a.key = hold.ptrs[(size_t)r++];
     for (int i = 0; i < n_x; ++i) a.x[i] = x[i] ? hold.ptrs[(size_t)r++] : 0;
     a.n = hold.n; a.n_bins = (uint32_t)n_bins; a.n_x = (uint32_t)n_x;
+    PassOutputs outs(this);
+    a.out = outs.add(hold.n);
     // bounds and the coefficients narrowed to fp32 go up in one copy; the copy has left the pinned block before this call returns
     const size_t tab_bytes = pass_up256((size_t)FM_BINNED_MAX_BINS * 8), coef_bytes = pass_up256((size_t)FM_BINNED_MAX_BINS * FM_BINNED_MAX_X * 4);
     char* stage = (char*)ensure_stage(tab_bytes + coef_bytes);
@@ -132,16 +127,11 @@ fmhip_vec Engine::binned_eval(fmhip_vec key, const double* bounds, int n_bins, c
     hip_check(hipStreamSynchronize(stream_), "sync");
     a.bounds = (const double*)pass_other_;
     a.coefficients = reinterpret_cast<const float*>((const char*)pass_other_ + tab_bytes);
-    Buffer* b = new_buffer(hold.n);
-    a.out = (uint64_t)(uintptr_t)b->ptr;
-    const hipError_t e = launch_binned_eval(a, stream_);
-    if (e != hipSuccess) { buffer_unref(b); hip_check(e, "launch fm_binned_eval_kernel"); }
+    hip_check(launch_binned_eval(a, stream_), "launch fm_binned_eval_kernel");
     ++n_launches_;
     algorithmic_bytes_ += 4 * hold.n * (n_real + 1);
     bytes_written_ += 4 * hold.n;
-    Node* nd = new_node(hold.n);
-    nd->buf = b;
-    return nd->id;
+    outs.commit(out);
 }
 
 } // namespace fm

@@ -27,16 +27,12 @@ static_assert((FM_KREG_MAX_POINTS + FM_KREG_ENTRIES / FM_KREG_MAX_ENTRIES_PER_PO
 // WEAK: see pass_need_kernel (tests/nulldev/null_kreg.cpp has the stand-in).
 hipError_t launch_kernel_moments(const DevKernelMomentsArgs& a, hipStream_t st) __attribute__((weak));
 
-template <class F> static void kreg_as_engine_error(F&& f) {
-    try { f(); }
-    catch (const std::invalid_argument& e) { throw Error(FMHIP_ERR_INVALID_ARGUMENT, e.what()); }
-}
 void kernel_moments_check(fmhip_vec key, const double* points, const double* bandwidths, int n_points, int kernel, int order, const fmhip_vec* y, int n_y, const double* sums_out) {
-    kreg_as_engine_error([&] { fmhost::kernelMomentsCheck<fmhip_vec>(key, points, bandwidths, n_points, kernel, order, y, n_y, sums_out); });
+    pass_as_engine_error([&] { fmhost::kernelMomentsCheck<fmhip_vec>(key, points, bandwidths, n_points, kernel, order, y, n_y, sums_out); });
 }
 // fmhip_kernel_moments_host: the definition, with its complaints as engine errors
 void kernel_moments_host_checked(const float* key, int64_t n, const double* points, const double* bandwidths, int n_points, int kernel, int order, const float* const* y, int n_y, double* sums_out) {
-    kreg_as_engine_error([&] { fmhost::kernel_moments_host(key, n, points, bandwidths, n_points, kernel, order, y, n_y, sums_out); });
+    pass_as_engine_error([&] { fmhost::kernel_moments_host(key, n, points, bandwidths, n_points, kernel, order, y, n_y, sums_out); });
 }
 
 void Engine::kernel_moments_pass(fmhip_vec key, const double* points, const double* bandwidths, int n_points, int kernel, int order, const fmhip_vec* y, int n_y, double* sums_out) {

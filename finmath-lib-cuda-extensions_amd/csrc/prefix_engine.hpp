@@ -1,18 +1,15 @@
 // prefix_engine.hpp — the engine's side of the device prefix sums (kernels: prefix_kernel.hip; definition, tree and chunk
-// arithmetic: prefix_host.hpp).  Part of runtime.cpp's translation unit (included at its end behind side_pass_engine.hpp, nowhere else).
+// arithmetic: prefix_host.hpp).  Passes in the frame of side_pass_engine.hpp (which says what every such pass does).
 //
 // Every statistic of the other passes weighs the paths equally.  A weighted sample — importance sampling, likelihood-ratio weights — needs
 // the running sum of its weights along the sorted sample: a weighted quantile, a weighted expected shortfall, the whole expected-shortfall
 // curve, the running average of an estimator.  The sort (§4.16) returns the weights reordered by the key; this is the prefix sum behind it,
 // in fp64 like every other sum here, in a tree that is a function of n alone.
 //
-// Every call stands in the frame of side_pass_engine.hpp: arguments checked before anything is flushed or launched, one flush, the vector's
-// storage held, the rows, bases and queries in the side-pass scratch, ONE pass_launch whose chain ends in the kernel that raises the flag,
-// the wait under the engine lock.  The output vector is created materialised.
+// Every call: the rows, bases and queries in the side-pass scratch, one launch that raises the flag and is waited for.
 //
 // One engine, one sample: a carry between the shards of a device list or the ranks of an expectation communicator is not built — such a
-// call is FMHIP_ERR_UNSUPPORTED (abi.cpp, sharded.cpp and below), never the prefix sums of a part.  Without the kernels a call is
-// FMHIP_ERR_UNSUPPORTED as well: the mirrors' host path is a caller's choice (FMHIP_DEVICE_PREFIX=0), never the engine's.
+// call is FMHIP_ERR_UNSUPPORTED (abi.cpp, sharded.cpp and below), never the prefix sums of a part.
 #include "runtime.hpp"
 #include "prefix_kernel.h"
 
@@ -20,7 +17,7 @@
 
 namespace fm {
 
-// WEAK: see pass_need_kernel.  (launch_sort_done, the one-lane kernel that raises the flag, is declared weak in sort_engine.hpp.)
+// WEAK: see pass_need_kernel.
 hipError_t launch_prefix_sums(const DevPrefixArgs& a, hipStream_t st) __attribute__((weak));
 hipError_t launch_prefix_queries(const DevPrefixArgs& a, hipStream_t st) __attribute__((weak));
 
@@ -37,8 +34,7 @@ void prefix_check_queries(fmhip_vec v, const void* queries, int count, const voi
 }
 // fmhip_prefix_sums_host: the definition, with its complaints as engine errors
 void prefix_sums_host_checked(const float* v, int64_t n, double* prefix_out) {
-    try { prefix_sums_host(v, n, prefix_out); }
-    catch (const std::invalid_argument& e) { throw Error(FMHIP_ERR_INVALID_ARGUMENT, e.what()); }
+    pass_as_engine_error([&] { prefix_sums_host(v, n, prefix_out); });
 }
 
 // the size of the sample, or the refusals that need no look at the values: before anything is flushed or launched
@@ -50,14 +46,14 @@ int64_t Engine::prefix_size(fmhip_vec v, const char* what) {
     return n;
 }
 
-fmhip_vec Engine::prefix_sums(fmhip_vec v, int mode, const fmhip_vec* out_checked, double* total_out) {
+void Engine::prefix_sums(fmhip_vec v, int mode, fmhip_vec* out, double* total_out) {
     require_init();
-    prefix_check_sums(v, mode, out_checked);
+    prefix_check_sums(v, mode, out);
     const int64_t n = prefix_size(v, "prefix sums");
     PassHold hold;
     pass_prepare(&v, 1, hold, "prefix sums");
-    Buffer* out = new_buffer(n);
-    struct Out { Engine* e; Buffer*& b; ~Out() { if (b) e->buffer_unref(b); } } keep{ this, out };
+    PassOutputs outs(this);
+    const uint64_t sums = outs.add(n);
     // pinned: [the total] [flag]
     char* stage = (char*)ensure_stage(256 + 64);
     pass_scratch(pass_up256(8), prefix_scratch_bytes(n, 0));
@@ -65,20 +61,12 @@ fmhip_vec Engine::prefix_sums(fmhip_vec v, int mode, const fmhip_vec* out_checke
     volatile uint64_t* flag = reinterpret_cast<volatile uint64_t*>(stage + 256);
     DevPrefixArgs a{};
     a.n = (uint32_t)n; a.chunk_tiles = prefix_chunk_tiles(n); a.mode = (uint32_t)mode; a.kind = FM_PREFIX_QUERY_NONE;
-    a.v = hold.ptrs[0]; a.out = (uint64_t)(uintptr_t)out->ptr; a.scratch = (char*)pass_other_; a.total_host = total_host;
-    uint64_t* done_flag = nullptr; uint64_t done_value = 0;
-    pass_launch(flag, done_flag, done_value, "prefix sums", [&] {
-        hipError_t e = launch_prefix_sums(a, stream_);
-        if (e == hipSuccess) e = launch_sort_done(done_flag, done_value, stream_);
-        return e;
-    });
+    a.v = hold.ptrs[0]; a.out = sums; a.scratch = (char*)pass_other_; a.total_host = total_host;
+    pass_launch_raising(flag, "prefix sums", [&] { return launch_prefix_sums(a, stream_); });
     algorithmic_bytes_ += 12 * n;                 // the totals read 4n, the apply reads 4n and writes 4n
     bytes_written_ += 4 * n;
+    outs.commit(out);
     if (total_out) *total_out = *total_host;
-    Node* nd = new_node(n);
-    nd->buf = out;
-    out = nullptr;
-    return nd->id;
 }
 
 // positions (at) or thresholds (search): one chain, the answers in the pinned block
@@ -110,12 +98,7 @@ void Engine::prefix_query_pass(fmhip_vec v, const int64_t* positions, const doub
     a.count = (uint32_t)count; a.relative = relative != 0 ? 1u : 0u;
     a.v = hold.ptrs[0]; a.scratch = (char*)pass_other_; a.total_host = total_host; a.sums_host = sums_host; a.positions_host = pos_host;
     hip_check(hipMemcpyAsync(prefix_queries(a), stage, (size_t)count * 8, hipMemcpyHostToDevice, stream_), "H2D(prefix queries)");
-    uint64_t* done_flag = nullptr; uint64_t done_value = 0;
-    pass_launch(flag, done_flag, done_value, what, [&] {
-        hipError_t e = launch_prefix_queries(a, stream_);
-        if (e == hipSuccess) e = launch_sort_done(done_flag, done_value, stream_);
-        return e;
-    });
+    pass_launch_raising(flag, what, [&] { return launch_prefix_queries(a, stream_); });
     algorithmic_bytes_ += 4 * n;                  // the totals read the vector once; a query reads its chunk again
     for (int j = 0; j < count; ++j) sums_out[j] = sums_host[j];
     if (positions_out) for (int j = 0; j < count; ++j) positions_out[j] = (int64_t)pos_host[j];

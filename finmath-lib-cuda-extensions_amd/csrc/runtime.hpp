@@ -387,13 +387,13 @@ public:
     // states (exponents[n_terms][n_states]), extra_x, y] with the monomials formed in registers; and the fitted polynomial as a new,
     // materialised vector.  Arguments are checked before anything is flushed or launched.
     void xmom_poly_pass(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const fmhip_vec* y, int n_y, double* sums_out);
-    fmhip_vec poly_eval(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const double* coefficients, const fmhip_vec* out_checked);
+    void poly_eval(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const double* coefficients, fmhip_vec* out);
 
     // localized regression (binned_engine.hpp): per bin of `key` (bin(k) = #{ j : bounds[j] < k }) the count and the cross moments
     // of fmhip_cross_moments' layout, from ONE launch; and Σ_i x_i·(float)coefficients[bin·n_x + i] as a new, materialised vector.  Arguments are
     // checked before anything is flushed or launched.
     void binned_xmom_pass(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, int64_t* counts_out, double* sums_out);
-    fmhip_vec binned_eval(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const double* coefficients, const fmhip_vec* out_checked);
+    void binned_eval(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const double* coefficients, fmhip_vec* out);
 
     // the device sort (sort_engine.hpp): a stable radix sort of (key, path index) pairs by the key of §4.7 — equal keys in
     // ascending path order —, and what is made of its permutation: the key and up to 8 companions gathered as new, materialised vectors; the
@@ -401,14 +401,14 @@ public:
     // few positions.  Arguments are checked before anything is flushed or launched; one engine's sample only (UNSUPPORTED with a communicator).
     void sort_by_key(fmhip_vec key, const fmhip_vec* values, int n_values, fmhip_vec* sorted_key_out, fmhip_vec* sorted_values_out);
     void argsort(fmhip_vec key, int64_t* permutation_out);
-    fmhip_vec rank_scores(fmhip_vec key, const fmhip_vec* out_checked);
+    void rank_scores(fmhip_vec key, fmhip_vec* out);
     void read_elements(fmhip_vec v, const int64_t* positions, int count, double* out);
 
     // prefix sums (prefix_engine.hpp): P[r] = the fp64 sum of (double)v[0..r] in the nested tree of prefix_host.hpp, a function
     // of n and r alone — every prefix (or every running mean) rounded to fp32 as a new, materialised vector; the prefixes at a few positions;
     // the first position whose prefix reaches a threshold.  Arguments are checked before anything is flushed or launched; one engine's sample
     // only (UNSUPPORTED with a communicator).
-    fmhip_vec prefix_sums(fmhip_vec v, int mode, const fmhip_vec* out_checked, double* total_out);
+    void prefix_sums(fmhip_vec v, int mode, fmhip_vec* out, double* total_out);
     void prefix_sums_at(fmhip_vec v, const int64_t* positions, int count, double* sums_out);
     void prefix_search(fmhip_vec v, const double* thresholds, int count, int relative, int64_t* positions_out, double* sums_out, double* total_out);
 
@@ -431,7 +431,7 @@ public:
     // Arguments are checked before anything is flushed or launched; outs is written only when the call succeeds.  Local to this engine's
     // vector (a communicator changes nothing).
     void block_moments(const fmhip_vec* vs, int n_vs, int64_t block, uint32_t mask, fmhip_vec* outs);
-    fmhip_vec repeat(fmhip_vec v, int64_t each, int64_t times, const fmhip_vec* out_checked);
+    void repeat(fmhip_vec v, int64_t each, int64_t times, fmhip_vec* out);
 
     // kernel regression (kreg_engine.hpp): the kernel-weighted local moments of n_y vectors at n_points points of `key`
     // (host/kernel_regression.hpp), sums_out[n_points][order 0: 1 + n_y, order 1: 3 + 2 n_y], from ONE launch.  Arguments are checked before
@@ -525,10 +525,11 @@ private:
     void*  ensure_stage(size_t bytes);
     size_t ring_reserve(size_t bytes);
 
-    // the frame of the reducing side passes (side_pass_engine.hpp): device scratch that is ZERO between launches (arrival counters,
-    // histograms; the kernels leave it so), scratch that need not be (tables, partial sums), the sequence number the completion flag
-    // receives.  `what` names the pass in the frame's messages.
+    // the frame of the side passes (side_pass_engine.hpp): device scratch that is ZERO between launches (arrival counters, histograms; the
+    // kernels leave it so), scratch that need not be (tables, partial sums), the sequence number the completion flag receives; the held
+    // storage of a pass's operands and the fresh outputs of a producing pass.  `what` names the pass in the frame's messages.
     struct PassHold;
+    struct PassOutputs;
     struct SortBuffers;
     int64_t sort_size(const fmhip_vec* hs, int count, const char* what);
     hipError_t sort_enqueue(uint64_t key_ptr, int64_t n, const SortBuffers& s);
@@ -537,6 +538,7 @@ private:
     void pass_prepare(const fmhip_vec* hs, int count, PassHold& hold, const char* what);
     void pass_scratch(size_t zero_bytes, size_t other_bytes);
     template <class Launch> void pass_launch(volatile uint64_t* flag, uint64_t*& done_flag, uint64_t& done_value, const char* what, Launch launch);
+    template <class Enqueue> void pass_launch_raising(volatile uint64_t* flag, const char* what, Enqueue enqueue);
     void pass_wait(volatile uint64_t* flag, uint64_t value, const char* what);
     void pass_release();
     void* pass_zero_ = nullptr; size_t pass_zero_cap_ = 0; void* pass_other_ = nullptr; size_t pass_other_cap_ = 0;

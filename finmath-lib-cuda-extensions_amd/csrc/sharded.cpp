@@ -719,6 +719,44 @@ static void add_sums(const std::vector<std::vector<double>>& per, size_t m, doub
     }
 }
 
+
+// The producing side passes — new vectors from a kernel of their own (side_pass_engine.hpp).  What they share:
+// n_out new vectors of n paths, out[0 … n_out): call(w, got) = the shard's status, its n_out new vectors in got.  A shard that holds no path
+// of such a vector binds empty ones.  Eager, like the call on one engine: a shard's refusal (no kernel, a value that was given up) is THIS
+// call's status — what the other shards bound is released, the front's ids are erased, out stays as it was.
+template <class Call>
+static void produce_per_shard(Shards& s, int64_t n, int n_out, fmhip_vec* out, Call call) {
+    std::vector<fmhip_vec> ids;
+    for (int f = 0; f < n_out; ++f) ids.push_back(s.fresh(n));
+    s.post([&](Worker& w) {
+        int64_t off, cnt; shard_range(n, w.shards, w.shard, &off, &cnt);
+        std::vector<fmhip_vec> got((size_t)n_out, 0);
+        if (cnt <= 0) { for (int f = 0; f < n_out; ++f) if (w.ok(fmhip_vec_create_uninitialized(0, &got[(size_t)f]))) w.bind(ids[(size_t)f], got[(size_t)f]); return; }
+        if (w.ok(call(w, got.data()))) for (int f = 0; f < n_out; ++f) w.bind(ids[(size_t)f], got[(size_t)f]);
+    });
+    try { s.wait(); }
+    catch (...) {
+        s.post([ids](Worker& w) { for (fmhip_vec id : ids) if (const fmhip_vec h = w.at(id)) { (void)fmhip_vec_release(h); w.local.erase(id); } });      // (not waited for: its own copy of the ids)
+        for (fmhip_vec id : ids) s.meta.erase(id);
+        throw;
+    }
+    for (int f = 0; f < n_out; ++f) out[f] = ids[(size_t)f];
+}
+// A pass over the whole of a sample runs on ONE engine: a list of more than one shard answers FMHIP_ERR_UNSUPPORTED — `why`: what the
+// shards would have to do for it —, never the result of a part.  A list of one shard is that shard's call: produce_per_shard where it
+// makes vectors (the one shard holds every path), on_the_shard where the results are the host's.
+static void one_shard(Shards& s, const char* what, const char* why) {
+    if (s.D() > 1) throw Error(FMHIP_ERR_UNSUPPORTED, std::string(what) + " with a device list of " + std::to_string(s.D()) + " shards: " + why);
+}
+static const char* const SORT_WHY = "a global order needs an exchange of elements between the shards";
+static const char* const PREFIX_WHY = "a carry between the shards is not built";
+static const char* const NESTED_WHY = "blocks would straddle the shards";
+template <class Call>
+static void on_the_shard(Shards& s, Call call) {
+    s.post([&](Worker& w) { w.ok(call(w)); });
+    s.wait();
+}
+
 // Order statistics: the host loop over the passes is the one a single engine runs.
 static void os_front_select(Shards& s, const fmhip_vec* vectors, int count, int64_t n, const int64_t* ranks, int n_ranks, os::Selected* sel) {
     os::select([&](int S, const uint32_t* slots, uint32_t shift, uint64_t* hist) {
@@ -815,21 +853,12 @@ int polynomial_cross_moments(const fmhip_vec* states, int n_states, const uint8_
 int polynomial_evaluate(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const double* coefficients, fmhip_vec* out) {
     return fronted([&](Shards& s) {
         poly_check_evaluate(states, n_states, exponents, n_terms, extra_x, n_extra, coefficients, out);
-        auto all = std::make_shared<std::vector<fmhip_vec>>(poly_all(states, n_states, extra_x, n_extra));
-        const int64_t n = front_size(s, all->data(), n_states + n_extra, "polynomial evaluation", true);
-        auto ex = std::make_shared<std::vector<uint8_t>>(exponents, exponents + (size_t)n_terms * n_states);
-        auto co = std::make_shared<std::vector<double>>(coefficients, coefficients + (size_t)(n_terms + n_extra));
-        const fmhip_vec id = s.fresh(n);
-        s.post([=](Worker& w) {
-            int64_t off, cnt; shard_range(n, w.shards, w.shard, &off, &cnt);
-            fmhip_vec h = 0;
-            if (cnt <= 0) { if (w.ok(fmhip_vec_create_uninitialized(0, &h))) w.bind(id, h); return; }
-            const std::vector<fmhip_vec> l = localize(w, all->data(), n_states + n_extra);
-            if (w.ok(fmhip_polynomial_evaluate(l.data(), n_states, ex->data(), n_terms, l.data() + n_states, n_extra, co->data(), &h))) w.bind(id, h);
+        const std::vector<fmhip_vec> all = poly_all(states, n_states, extra_x, n_extra);
+        const int64_t n = front_size(s, all.data(), n_states + n_extra, "polynomial evaluation", true);
+        produce_per_shard(s, n, 1, out, [&](Worker& w, fmhip_vec* got) {
+            const std::vector<fmhip_vec> l = localize(w, all.data(), n_states + n_extra);
+            return fmhip_polynomial_evaluate(l.data(), n_states, exponents, n_terms, l.data() + n_states, n_extra, coefficients, got);
         });
-        // eager, like the call on one engine: a shard's refusal (no kernel, a value that was given up) is THIS call's status
-        try { s.wait(); } catch (...) { s.post([=](Worker& w) { if (const fmhip_vec h = w.at(id)) { (void)fmhip_vec_release(h); w.local.erase(id); } }); s.meta.erase(id); throw; }
-        *out = id;
     });
 }
 
@@ -859,21 +888,12 @@ int binned_cross_moments(fmhip_vec key, const double* bounds, int n_bins, const 
 int binned_evaluate(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const double* coefficients, fmhip_vec* out) {
     return fronted([&](Shards& s) {
         binned_check_evaluate(key, bounds, n_bins, x, n_x, coefficients, out);
-        auto all = std::make_shared<std::vector<fmhip_vec>>(binned_all(key, x, n_x, nullptr, 0));
-        const int64_t n = front_size(s, all->data(), 1 + n_x, "binned evaluation", true);
-        auto bd = std::make_shared<std::vector<double>>(bounds ? bounds : coefficients, (bounds ? bounds : coefficients) + (bounds ? n_bins - 1 : 0));
-        auto co = std::make_shared<std::vector<double>>(coefficients, coefficients + (size_t)n_bins * n_x);
-        const fmhip_vec id = s.fresh(n);
-        s.post([=](Worker& w) {
-            int64_t off, cnt; shard_range(n, w.shards, w.shard, &off, &cnt);
-            fmhip_vec h = 0;
-            if (cnt <= 0) { if (w.ok(fmhip_vec_create_uninitialized(0, &h))) w.bind(id, h); return; }
-            const std::vector<fmhip_vec> l = localize(w, all->data(), 1 + n_x);
-            if (w.ok(fmhip_binned_evaluate(l[0], bd->data(), n_bins, l.data() + 1, n_x, co->data(), &h))) w.bind(id, h);
+        const std::vector<fmhip_vec> all = binned_all(key, x, n_x, nullptr, 0);
+        const int64_t n = front_size(s, all.data(), 1 + n_x, "binned evaluation", true);
+        produce_per_shard(s, n, 1, out, [&](Worker& w, fmhip_vec* got) {
+            const std::vector<fmhip_vec> l = localize(w, all.data(), 1 + n_x);
+            return fmhip_binned_evaluate(l[0], bounds, n_bins, l.data() + 1, n_x, coefficients, got);
         });
-        // eager, like the call on one engine: a shard's refusal (no kernel, a value that was given up) is THIS call's status
-        try { s.wait(); } catch (...) { s.post([=](Worker& w) { if (const fmhip_vec h = w.at(id)) { (void)fmhip_vec_release(h); w.local.erase(id); } }); s.meta.erase(id); throw; }
-        *out = id;
     });
 }
 
@@ -894,89 +914,65 @@ int kernel_moments(fmhip_vec key, const double* points, const double* bandwidths
 }
 
 // The device sort (sort_engine.hpp).  The order of a sample that is spread over several shards needs an exchange of elements between them,
-// which nothing does: a list of more than one shard answers FMHIP_ERR_UNSUPPORTED, never the order of a part.  A list of ONE shard is that
-// shard's call.
-static void sort_one_shard(Shards& s, const char* what) {
-    if (s.D() > 1) throw Error(FMHIP_ERR_UNSUPPORTED, std::string(what) + " with a device list of " + std::to_string(s.D()) + " shards: a global order needs an exchange of elements between the shards");
-}
+// which nothing does (one_shard).
 int sort_by_key(fmhip_vec key, const fmhip_vec* values, int n_values, fmhip_vec* sorted_key_out, fmhip_vec* sorted_values_out) {
     return fronted([&](Shards& s) {
         sort_check_by_key(key, values, n_values, sorted_key_out, sorted_values_out);
         std::vector<fmhip_vec> all(1, key);
         all.insert(all.end(), values, values + n_values);
         const int64_t n = front_size(s, all.data(), 1 + n_values, "sort by key", false);
-        sort_one_shard(s, "sort by key");
-        const bool want_key = sorted_key_out != nullptr;
-        std::vector<fmhip_vec> ids;
-        for (int i = want_key ? 0 : 1; i < 1 + n_values; ++i) ids.push_back(s.fresh(n));
-        s.post([&](Worker& w) {
+        one_shard(s, "sort by key", SORT_WHY);
+        const int want_key = sorted_key_out ? 1 : 0;
+        std::vector<fmhip_vec> ids((size_t)(want_key + n_values), 0);                 // the key if it is asked for, then the companions
+        produce_per_shard(s, n, want_key + n_values, ids.data(), [&](Worker& w, fmhip_vec* got) {
             const std::vector<fmhip_vec> l = localize(w, all.data(), 1 + n_values);
-            fmhip_vec k = 0; std::vector<fmhip_vec> v((size_t)n_values + 1, 0);
-            if (!w.ok(fmhip_sort_by_key(l[0], l.data() + 1, n_values, want_key ? &k : nullptr, v.data()))) return;
-            size_t at = 0;
-            if (want_key) w.bind(ids[at++], k);
-            for (int i = 0; i < n_values; ++i) w.bind(ids[at++], v[(size_t)i]);
+            return fmhip_sort_by_key(l[0], l.data() + 1, n_values, want_key ? got : nullptr, got + want_key);
         });
-        try { s.wait(); } catch (...) { for (fmhip_vec id : ids) s.meta.erase(id); throw; }
-        size_t at = 0;
-        if (want_key) *sorted_key_out = ids[at++];
-        for (int i = 0; i < n_values; ++i) sorted_values_out[i] = ids[at++];
+        if (want_key) *sorted_key_out = ids[0];
+        for (int i = 0; i < n_values; ++i) sorted_values_out[i] = ids[(size_t)(want_key + i)];
     });
 }
 int argsort(fmhip_vec key, int64_t* permutation_out) {
     return fronted([&](Shards& s) {
         need(permutation_out, "permutation_out");
         front_size(s, &key, 1, "argsort", false);
-        sort_one_shard(s, "argsort");
-        s.post([&](Worker& w) { w.ok(fmhip_argsort(w.at(key), permutation_out)); });
-        s.wait();
+        one_shard(s, "argsort", SORT_WHY);
+        on_the_shard(s, [&](Worker& w) { return fmhip_argsort(w.at(key), permutation_out); });
     });
 }
 int rank_scores(fmhip_vec key, fmhip_vec* out) {
     return fronted([&](Shards& s) {
         need(out, "out");
         const int64_t n = front_size(s, &key, 1, "rank scores", false);
-        sort_one_shard(s, "rank scores");
-        const fmhip_vec id = s.fresh(n);
-        s.post([&](Worker& w) { fmhip_vec h = 0; if (w.ok(fmhip_rank_scores(w.at(key), &h))) w.bind(id, h); });
-        try { s.wait(); } catch (...) { s.meta.erase(id); throw; }
-        *out = id;
+        one_shard(s, "rank scores", SORT_WHY);
+        produce_per_shard(s, n, 1, out, [&](Worker& w, fmhip_vec* got) { return fmhip_rank_scores(w.at(key), got); });
     });
 }
 int vec_read_elements(fmhip_vec v, const int64_t* positions, int count, double* out) {
     return fronted([&](Shards& s) {
         sort_check_read_elements(v, positions, count, out);
         front_size(s, &v, 1, "read elements", false);
-        sort_one_shard(s, "read elements");
-        s.post([&](Worker& w) { w.ok(fmhip_vec_read_elements(w.at(v), positions, count, out)); });
-        s.wait();
+        one_shard(s, "read elements", SORT_WHY);
+        on_the_shard(s, [&](Worker& w) { return fmhip_vec_read_elements(w.at(v), positions, count, out); });
     });
 }
 
 // Prefix sums (prefix_engine.hpp).  The prefixes of a sample that is spread over several shards need a carry between them, which is not
-// built: a list of more than one shard answers FMHIP_ERR_UNSUPPORTED, never the prefix sums of a part.  A list of ONE shard is that
-// shard's call.
-static void prefix_one_shard(Shards& s, const char* what) {
-    if (s.D() > 1) throw Error(FMHIP_ERR_UNSUPPORTED, std::string(what) + " with a device list of " + std::to_string(s.D()) + " shards: a carry between the shards is not built");
-}
+// built (one_shard).
 int prefix_sums(fmhip_vec v, int mode, fmhip_vec* out, double* total_out) {
     return fronted([&](Shards& s) {
         prefix_check_sums(v, mode, out);
         const int64_t n = front_size(s, &v, 1, "prefix sums", false);
-        prefix_one_shard(s, "prefix sums");
-        const fmhip_vec id = s.fresh(n);
-        s.post([&](Worker& w) { fmhip_vec h = 0; if (w.ok(fmhip_prefix_sums(w.at(v), mode, &h, total_out))) w.bind(id, h); });
-        try { s.wait(); } catch (...) { s.meta.erase(id); throw; }
-        *out = id;
+        one_shard(s, "prefix sums", PREFIX_WHY);
+        produce_per_shard(s, n, 1, out, [&](Worker& w, fmhip_vec* got) { return fmhip_prefix_sums(w.at(v), mode, got, total_out); });
     });
 }
 int prefix_sums_at(fmhip_vec v, const int64_t* positions, int count, double* sums_out) {
     return fronted([&](Shards& s) {
         prefix_check_queries(v, positions, count, sums_out, "prefix sums at");
         front_size(s, &v, 1, "prefix sums at", false);
-        prefix_one_shard(s, "prefix sums at");
-        s.post([&](Worker& w) { w.ok(fmhip_prefix_sums_at(w.at(v), positions, count, sums_out)); });
-        s.wait();
+        one_shard(s, "prefix sums at", PREFIX_WHY);
+        on_the_shard(s, [&](Worker& w) { return fmhip_prefix_sums_at(w.at(v), positions, count, sums_out); });
     });
 }
 int prefix_search(fmhip_vec v, const double* thresholds, int count, int relative, int64_t* positions_out, double* sums_out, double* total_out) {
@@ -984,9 +980,8 @@ int prefix_search(fmhip_vec v, const double* thresholds, int count, int relative
         prefix_check_queries(v, thresholds, count, sums_out, "prefix search");
         need(positions_out, "positions_out");
         front_size(s, &v, 1, "prefix search", false);
-        prefix_one_shard(s, "prefix search");
-        s.post([&](Worker& w) { w.ok(fmhip_prefix_search(w.at(v), thresholds, count, relative, positions_out, sums_out, total_out)); });
-        s.wait();
+        one_shard(s, "prefix search", PREFIX_WHY);
+        on_the_shard(s, [&](Worker& w) { return fmhip_prefix_search(w.at(v), thresholds, count, relative, positions_out, sums_out, total_out); });
     });
 }
 
@@ -995,56 +990,17 @@ int table_apply(fmhip_vec x, const double* knots, int count, const double* coeff
     return fronted([&](Shards& s) {
         table_check_apply(x, knots, count, coefficients, n_tables, out);
         const int64_t n = front_size(s, &x, 1, "tabulated function", false);
-        auto kn = std::make_shared<std::vector<double>>(knots, knots + count);
-        auto co = std::make_shared<std::vector<double>>(coefficients, coefficients + (size_t)n_tables * (size_t)(count + 1) * 4);
-        auto ids = std::make_shared<std::vector<fmhip_vec>>();
-        for (int f = 0; f < n_tables; ++f) ids->push_back(s.fresh(n));
-        s.post([=](Worker& w) {
-            int64_t off, cnt; shard_range(n, w.shards, w.shard, &off, &cnt);
-            fmhip_vec h[4] = { 0, 0, 0, 0 };
-            if (cnt <= 0) { for (int f = 0; f < n_tables; ++f) if (w.ok(fmhip_vec_create_uninitialized(0, &h[f]))) w.bind((*ids)[(size_t)f], h[f]); return; }
-            if (w.ok(fmhip_table_apply(w.at(x), kn->data(), count, co->data(), n_tables, h))) for (int f = 0; f < n_tables; ++f) w.bind((*ids)[(size_t)f], h[f]);
-        });
-        // eager, like the call on one engine: a shard's refusal (no kernel, a value that was given up) is THIS call's status
-        try { s.wait(); }
-        catch (...) {
-            s.post([=](Worker& w) { for (fmhip_vec id : *ids) if (const fmhip_vec h = w.at(id)) { (void)fmhip_vec_release(h); w.local.erase(id); } });
-            for (fmhip_vec id : *ids) s.meta.erase(id);
-            throw;
-        }
-        for (int f = 0; f < n_tables; ++f) out[f] = (*ids)[(size_t)f];
+        produce_per_shard(s, n, n_tables, out, [&](Worker& w, fmhip_vec* got) { return fmhip_table_apply(w.at(x), knots, count, coefficients, n_tables, got); });
     });
 }
 
 // Named functions and option formulas per path (analytic_engine.hpp).  Elementwise: every shard runs the call on its block; the new vectors'
-// blocks are the shards' results.  `call`: the shard's call, given the shard's handles of `operands` (0 stays 0: the scalar) and n_out slots.
-template <class Call> static void analytic_per_shard(Shards& s, int64_t n, const std::vector<fmhip_vec>& operands, int n_out, fmhip_vec* out, Call call) {
-    auto ids = std::make_shared<std::vector<fmhip_vec>>();
-    for (int f = 0; f < n_out; ++f) ids->push_back(s.fresh(n));
-    s.post([=](Worker& w) {
-        int64_t off, cnt; shard_range(n, w.shards, w.shard, &off, &cnt);
-        fmhip_vec h[4] = { 0, 0, 0, 0 };
-        if (cnt <= 0) { for (int f = 0; f < n_out; ++f) if (w.ok(fmhip_vec_create_uninitialized(0, &h[f]))) w.bind((*ids)[(size_t)f], h[f]); return; }
-        fmhip_vec mine[3] = { 0, 0, 0 };
-        for (size_t k = 0; k < operands.size(); ++k) mine[k] = operands[k] ? w.at(operands[k]) : 0;
-        if (w.ok(call(mine, h))) for (int f = 0; f < n_out; ++f) w.bind((*ids)[(size_t)f], h[f]);
-    });
-    // eager, like the call on one engine: a shard's refusal (no kernel, a value that was given up) is THIS call's status
-    try { s.wait(); }
-    catch (...) {
-        s.post([=](Worker& w) { for (fmhip_vec id : *ids) if (const fmhip_vec h = w.at(id)) { (void)fmhip_vec_release(h); w.local.erase(id); } });
-        for (fmhip_vec id : *ids) s.meta.erase(id);
-        throw;
-    }
-    for (int f = 0; f < n_out; ++f) out[f] = (*ids)[(size_t)f];
-}
-
+// blocks are the shards' results.
 int function_apply(fmhip_vec x, const int* kinds, int n_functions, fmhip_vec* out) {
     return fronted([&](Shards& s) {
         analytic_check_function(x, kinds, n_functions, out);
         const int64_t n = front_size(s, &x, 1, "named functions", false);
-        auto kd = std::make_shared<std::vector<int>>(kinds, kinds + n_functions);
-        analytic_per_shard(s, n, { x }, n_functions, out, [=](const fmhip_vec* mine, fmhip_vec* h) { return fmhip_function_apply(mine[0], kd->data(), n_functions, h); });
+        produce_per_shard(s, n, n_functions, out, [&](Worker& w, fmhip_vec* got) { return fmhip_function_apply(w.at(x), kinds, n_functions, got); });
     });
 }
 
@@ -1056,35 +1012,22 @@ int option_formula(int model, fmhip_vec forward, double forward_scalar, fmhip_ve
         for (fmhip_vec h : { forward, volatility, payoff_unit }) if (h) vectors.push_back(h);
         const int64_t n = front_size(s, vectors.data(), (int)vectors.size(), "option formula", false);
         const int n_out = (outputs & 1) + ((outputs >> 1) & 1) + ((outputs >> 2) & 1);      // one new vector per set bit of the mask
-        analytic_per_shard(s, n, { forward, volatility, payoff_unit }, n_out, out, [=](const fmhip_vec* mine, fmhip_vec* h) {
-            return fmhip_option_formula(model, mine[0], forward_scalar, mine[1], volatility_scalar, mine[2], payoff_unit_scalar, maturity, strike, outputs, h);
+        produce_per_shard(s, n, n_out, out, [&](Worker& w, fmhip_vec* got) {            // (a handle of 0 stays 0 on every shard: the scalar)
+            return fmhip_option_formula(model, w.at(forward), forward_scalar, w.at(volatility), volatility_scalar, w.at(payoff_unit), payoff_unit_scalar, maturity, strike, outputs, got);
         });
     });
 }
 
 // Nested simulation (nested_engine.hpp).  The blocks of a sample that is spread over several shards would straddle them, and a repeat's
-// output is laid out over the whole sample: a list of more than one shard answers FMHIP_ERR_UNSUPPORTED, never the moments of a part.  A
-// list of ONE shard is that shard's call.
-static void nested_one_shard(Shards& s, const char* what) {
-    if (s.D() > 1) throw Error(FMHIP_ERR_UNSUPPORTED, std::string(what) + " with a device list of " + std::to_string(s.D()) + " shards: blocks would straddle the shards");
-}
+// output is laid out over the whole sample (one_shard).
 int block_moments(const fmhip_vec* vs, int n_vs, int64_t block, uint32_t mask, fmhip_vec* outs) {
     return fronted([&](Shards& s) {
         nested_check_moments(vs, n_vs, block, mask, outs);
         const int64_t n = front_size(s, vs, n_vs, "block moments", false);
         if (n % block != 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "block moments: " + std::to_string(n) + " elements are no whole number of blocks of " + std::to_string(block));
-        nested_one_shard(s, "block moments");
+        one_shard(s, "block moments", NESTED_WHY);
         const int total = n_vs * ((int)(mask & 1u) + (int)((mask >> 1) & 1u) + (int)((mask >> 2) & 1u));
-        std::vector<fmhip_vec> ids;
-        for (int k = 0; k < total; ++k) ids.push_back(s.fresh(n / block));
-        s.post([&](Worker& w) {
-            const std::vector<fmhip_vec> l = localize(w, vs, n_vs);
-            std::vector<fmhip_vec> h((size_t)total, 0);
-            if (!w.ok(fmhip_block_moments(l.data(), n_vs, block, mask, h.data()))) return;
-            for (int k = 0; k < total; ++k) w.bind(ids[(size_t)k], h[(size_t)k]);
-        });
-        try { s.wait(); } catch (...) { for (fmhip_vec id : ids) s.meta.erase(id); throw; }
-        for (int k = 0; k < total; ++k) outs[k] = ids[(size_t)k];
+        produce_per_shard(s, n / block, total, outs, [&](Worker& w, fmhip_vec* got) { return fmhip_block_moments(localize(w, vs, n_vs).data(), n_vs, block, mask, got); });
     });
 }
 int vec_repeat(fmhip_vec v, int64_t each, int64_t times, fmhip_vec* out) {
@@ -1092,11 +1035,8 @@ int vec_repeat(fmhip_vec v, int64_t each, int64_t times, fmhip_vec* out) {
         nested_check_repeat(v, each, times, out);
         const int64_t n = front_size(s, &v, 1, "repeat", false);
         if (each > 0x7fffffffLL / n || times > 0x7fffffffLL / (n * each)) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "repeat: an output beyond 2^31 - 1 elements");
-        nested_one_shard(s, "repeat");
-        const fmhip_vec id = s.fresh(n * each * times);
-        s.post([&](Worker& w) { fmhip_vec h = 0; if (w.ok(fmhip_vec_repeat(w.at(v), each, times, &h))) w.bind(id, h); });
-        try { s.wait(); } catch (...) { s.meta.erase(id); throw; }
-        *out = id;
+        one_shard(s, "repeat", NESTED_WHY);
+        produce_per_shard(s, n * each * times, 1, out, [&](Worker& w, fmhip_vec* got) { return fmhip_vec_repeat(w.at(v), each, times, got); });
     });
 }
 

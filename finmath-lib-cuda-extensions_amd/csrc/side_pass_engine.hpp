@@ -1,19 +1,27 @@
-// side_pass_engine.hpp — the frame of the engine's reducing side passes: a kernel of its own beside the lazy graph that leaves a few numbers
-// in pinned memory (order_stats_engine.hpp, cross_moments_engine.hpp, binned_engine.hpp).  Part of runtime.cpp's translation unit (included
-// at its end, before the passes, nowhere else): Engine member functions in a file of their own because runtime.cpp is long enough, and in
-// that translation unit so that every build that lists the engine's sources — the library's, the sanitizer builds against the null device —
-// has them without being told.
+// side_pass_engine.hpp — the frame of the engine's side passes: a kernel of its own beside the lazy graph that leaves a few numbers in
+// pinned memory (the REDUCING passes: order_stats_engine.hpp, cross_moments_engine.hpp, binned_engine.hpp …) or new, materialised vectors
+// (the PRODUCING passes: table_engine.hpp, analytic_engine.hpp, nested_engine.hpp, sort_engine.hpp, prefix_engine.hpp and the evaluations
+// of binned_engine.hpp and xmom_poly_engine.hpp).  Part of runtime.cpp's translation unit (included at its end, before the passes, nowhere
+// else): Engine member functions in a file of their own because runtime.cpp is long enough, and in that translation unit so that every
+// build that lists the engine's sources — the library's, the sanitizer builds against the null device — has them without being told.
 //
-// A pass: checks its arguments (pass_size among them) before anything is flushed or launched, ends a step group, counts as a use of every
-// vector (escape policy), computes what is pending or deferred below the batch in ONE flush, takes a reference on every vector's STORAGE and
-// forgets the nodes (pass_prepare) — the wait that follows may not rely on a Node* (queued releases are not performed during it either: it
-// polls the flag and falls back to the plain stream wait) —, lays out its pinned block as [tables the launch reads] [what it writes] [flag]
-// and its device scratch (pass_scratch), launches once and waits under the engine lock as read() does (pass_launch).  Shared storage (common
-// rows) is only read.  `what` names the pass in whatever the frame has to say.
+// A pass: checks its arguments (pass_size among them) before anything is flushed or launched, refuses a build without its kernel
+// (pass_need_kernel: FMHIP_ERR_UNSUPPORTED — the mirrors' host path is a caller's choice, never the engine's), ends a step group, counts as
+// a use of every vector (escape policy), computes what is pending or deferred below the batch in ONE flush, takes a reference on every
+// vector's STORAGE and forgets the nodes (pass_prepare) — the wait that follows may not rely on a Node* (queued releases are not performed
+// during it either: it polls the flag and falls back to the plain stream wait) —, lays out its pinned block as [tables the launch reads]
+// [what it writes] [flag] and its device scratch (pass_scratch), launches once and waits under the engine lock as read() does (pass_launch;
+// pass_launch_raising where the chain ends in the one-lane kernel that raises the flag).  Shared storage (common rows) is only read.
+// `what` names the pass in whatever the frame has to say.
+//
+// A producing pass allocates its outputs through PassOutputs behind pass_prepare and BEFORE anything is staged or launched — an allocation
+// that fails leaves nothing copied or launched — and ends in PassOutputs::commit, the one place that writes a caller's handle: a refusal at
+// any stage leaves `out` untouched, no vector and no byte behind.
 #include "runtime.hpp"
 #include "pinned_wait.hpp"
 
 #include <algorithm>
+#include <stdexcept>
 #include <string>
 
 namespace fm {
@@ -27,12 +35,46 @@ static void pass_need_kernel(bool present, const char* what) {
 
 static size_t pass_up256(size_t b) { return (b + 255) & ~size_t(255); }
 
+// the host definitions and argument rules (host/*.hpp) complain with std::invalid_argument: the same complaint as an engine error
+template <class F> static void pass_as_engine_error(F&& f) {
+    try { f(); }
+    catch (const std::invalid_argument& e) { throw Error(FMHIP_ERR_INVALID_ARGUMENT, e.what()); }
+}
+
+// the one-lane kernel that raises the flag behind a chain of launches (sort_kernel.hip); WEAK like every launcher of a pass
+hipError_t launch_sort_done(uint64_t* done_flag, uint64_t done_value, hipStream_t st) __attribute__((weak));
+
 struct Engine::PassHold {          // the storage of a batch, referenced for the duration of a pass
     Engine* e = nullptr;
     std::vector<Buffer*> held;
     std::vector<uint64_t> ptrs;
     int64_t n = 0;
     ~PassHold() { for (Buffer* b : held) e->buffer_unref(b); }
+};
+
+struct Engine::PassOutputs {       // the freshly allocated outputs of a producing pass: back in the pool unless the pass commits them
+    struct Slot { Buffer* b; int64_t n; fmhip_vec id; };
+    Engine* e;
+    std::vector<Slot> slots;
+    bool committed = false;
+    explicit PassOutputs(Engine* eng) : e(eng) {}
+    PassOutputs(const PassOutputs&) = delete;
+    ~PassOutputs() { for (Slot& s : slots) { if (s.b) e->buffer_unref(s.b); else if (s.id && !committed) e->release(s.id); } }
+    uint64_t add(int64_t n_floats) {
+        slots.push_back({ nullptr, n_floats, 0 });             // the slot first: nothing can throw between an allocation and its guard
+        slots.back().b = e->new_buffer(n_floats);
+        return (uint64_t)(uintptr_t)slots.back().b->ptr;
+    }
+    // One node per buffer, in the order of allocation; the handles are written when every node exists: first, if given, receives the first
+    // one, out the others.  A new_node that throws half-way writes nothing: the nodes made so far own their buffers and are released with
+    // them, the other buffers are given back (~PassOutputs).
+    void commit(fmhip_vec* out, fmhip_vec* first = nullptr) {
+        for (Slot& s : slots) { Node* nd = e->new_node(s.n); nd->buf = s.b; s.b = nullptr; s.id = nd->id; }
+        committed = true;
+        size_t k = 0;
+        if (first) *first = slots[k++].id;
+        for (; k < slots.size(); ++k) *out++ = slots[k].id;
+    }
 };
 
 // hs: the handles of a pass that have a node (the constant 1, handle 0 among the x of a regression, has none and no size: its callers leave it out)
@@ -116,6 +158,17 @@ inline void Engine::pass_launch(volatile uint64_t* flag, uint64_t*& done_flag, u
     hip_check(launch(), what);
     ++n_launches_;
     pass_wait(flag, done_value, what);
+}
+
+// The same for a chain that knows no flag: enqueue(), then the one-lane kernel that raises it.
+template <class Enqueue>
+inline void Engine::pass_launch_raising(volatile uint64_t* flag, const char* what, Enqueue enqueue) {
+    uint64_t* done_flag = nullptr; uint64_t done_value = 0;
+    pass_launch(flag, done_flag, done_value, what, [&] {
+        hipError_t e = enqueue();
+        if (e == hipSuccess) e = launch_sort_done(done_flag, done_value, stream_);
+        return e;
+    });
 }
 
 } // namespace fm

@@ -1,5 +1,5 @@
 // sort_engine.hpp — the engine's side of the device sort (kernels: sort_kernel.hip; definition and chunk arithmetic:
-// sort_host.hpp).  Part of runtime.cpp's translation unit (included at its end behind side_pass_engine.hpp, nowhere else).
+// sort_host.hpp).  Passes in the frame of side_pass_engine.hpp (which says what every such pass does).
 //
 // The reference downloads a vector and sorts it on the host whenever it needs more than a few ranks: the whole ordered sample, the
 // permutation, ranks per path.  Here the vector stays where it is: a stable radix sort of (key, path index) pairs leaves the permutation in
@@ -7,15 +7,12 @@
 // itself (argsort), the rank scores scattered back to the paths (rank_scores).  read_elements is the other half of a quantile table: a few
 // elements of a vector into pinned memory, not the vector.
 //
-// Every call stands in the frame of side_pass_engine.hpp: arguments checked before anything is flushed or launched, one flush, the vectors'
-// storage held, the count table in the side-pass scratch, ONE pass_launch whose chain ends in the kernel that raises the flag, the wait
-// under the engine lock.  The four ping-pong buffers (16·n bytes) come from the pool like vector storage and are back in it when the call
-// returns.  Output vectors are created materialised.
+// Every call: the count table in the side-pass scratch, one chain of launches that raises the flag and is waited for.  The four ping-pong
+// buffers (16·n bytes) come from the pool like vector storage, BEFORE the outputs, and are back in it when the call returns.
 //
 // One engine, one sample: the order of a sample that is spread over the shards of a device list or the ranks of an expectation communicator
 // needs an exchange of ELEMENTS, which nothing here does — such a call is FMHIP_ERR_UNSUPPORTED (abi.cpp, sharded.cpp and below), never
-// the order of a part.  Without the kernels a call is FMHIP_ERR_UNSUPPORTED as well: the mirrors' host path is a caller's choice
-// (FMHIP_DEVICE_SORT=0), never the engine's.
+// the order of a part.
 #include "runtime.hpp"
 #include "sort_kernel.h"
 
@@ -23,12 +20,11 @@
 
 namespace fm {
 
-// WEAK: see pass_need_kernel.
+// WEAK: see pass_need_kernel (launch_sort_done, which these share with every chain that raises the flag, is declared by the frame).
 hipError_t launch_sort_pass(const DevSortPassArgs& a, hipStream_t st) __attribute__((weak));
 hipError_t launch_sort_gather(const DevSortGatherArgs& a, hipStream_t st) __attribute__((weak));
 hipError_t launch_sort_scores(uint64_t perm, uint64_t out, uint32_t n, hipStream_t st) __attribute__((weak));
 hipError_t launch_sort_read_elements(uint64_t v, const uint32_t* pos, uint32_t count, double* out_host, hipStream_t st) __attribute__((weak));
-hipError_t launch_sort_done(uint64_t* done_flag, uint64_t done_value, hipStream_t st) __attribute__((weak));
 
 // what can be said about the arguments without looking at a vector: FMHIP_ERR_INVALID_ARGUMENT
 void sort_check_by_key(fmhip_vec key, const fmhip_vec* values, int n_values, const fmhip_vec* sorted_key_out, const fmhip_vec* sorted_values_out) {
@@ -45,8 +41,7 @@ void sort_check_read_elements(fmhip_vec v, const int64_t* positions, int count, 
 }
 // fmhip_argsort_host: the definition, with its complaints as engine errors
 void sort_argsort_host_checked(const float* key, int64_t n, int64_t* permutation_out) {
-    try { sort_argsort_host(key, n, permutation_out); }
-    catch (const std::invalid_argument& e) { throw Error(FMHIP_ERR_INVALID_ARGUMENT, e.what()); }
+    pass_as_engine_error([&] { sort_argsort_host(key, n, permutation_out); });
 }
 
 // The ping-pong buffers of a sort, from the pool, back in it when the call ends — however it ends.
@@ -99,30 +94,23 @@ void Engine::sort_by_key(fmhip_vec key, const fmhip_vec* values, int n_values, f
     pass_prepare(all, 1 + n_values, hold, "sort by key");
     SortBuffers s(this, n);
     // the outputs, in the order of the gather's list: the key if it is asked for, then the companions
-    struct Outs { Engine* e; std::vector<Buffer*> b; ~Outs() { for (Buffer* x : b) e->buffer_unref(x); } } outs{ this, {} };
+    PassOutputs outs(this);
     DevSortGatherArgs g{};
     g.n = (uint32_t)n; g.perm = s.at(3);
     for (int i = sorted_key_out ? 0 : 1; i < 1 + n_values; ++i) {
-        outs.b.push_back(new_buffer(n));
         g.src[g.count] = hold.ptrs[(size_t)i];
-        g.dst[g.count++] = (uint64_t)(uintptr_t)outs.b.back()->ptr;
+        g.dst[g.count++] = outs.add(n);
     }
     char* stage = (char*)ensure_stage(64);
     pass_scratch(pass_up256(8), sort_table_bytes(n));
     volatile uint64_t* flag = reinterpret_cast<volatile uint64_t*>(stage);
-    uint64_t* done_flag = nullptr; uint64_t done_value = 0;
-    pass_launch(flag, done_flag, done_value, "sort by key", [&] {
-        hipError_t e = sort_enqueue(hold.ptrs[0], n, s);
-        if (e == hipSuccess) e = launch_sort_gather(g, stream_);
-        if (e == hipSuccess) e = launch_sort_done(done_flag, done_value, stream_);
-        return e;
+    pass_launch_raising(flag, "sort by key", [&] {
+        const hipError_t e = sort_enqueue(hold.ptrs[0], n, s);
+        return e == hipSuccess ? launch_sort_gather(g, stream_) : e;
     });
     algorithmic_bytes_ += 4 * n + 8 * n * (int64_t)g.count;
     bytes_written_ += 4 * n * (int64_t)g.count;
-    size_t at = 0;
-    if (sorted_key_out) { Node* nd = new_node(n); nd->buf = outs.b[at++]; *sorted_key_out = nd->id; }
-    for (int i = 0; i < n_values; ++i) { Node* nd = new_node(n); nd->buf = outs.b[at++]; sorted_values_out[i] = nd->id; }
-    outs.b.clear();
+    outs.commit(sorted_values_out, sorted_key_out);
 }
 
 void Engine::argsort(fmhip_vec key, int64_t* permutation_out) {
@@ -135,12 +123,7 @@ void Engine::argsort(fmhip_vec key, int64_t* permutation_out) {
     char* stage = (char*)ensure_stage(64);
     pass_scratch(pass_up256(8), sort_table_bytes(n));
     volatile uint64_t* flag = reinterpret_cast<volatile uint64_t*>(stage);
-    uint64_t* done_flag = nullptr; uint64_t done_value = 0;
-    pass_launch(flag, done_flag, done_value, "argsort", [&] {
-        hipError_t e = sort_enqueue(hold.ptrs[0], n, s);
-        if (e == hipSuccess) e = launch_sort_done(done_flag, done_value, stream_);
-        return e;
-    });
+    pass_launch_raising(flag, "argsort", [&] { return sort_enqueue(hold.ptrs[0], n, s); });
     // the permutation comes down as read() brings a vector down: through the pinned block, widened on the way
     const uint32_t* perm = reinterpret_cast<const uint32_t*>(s.b[3]->ptr);
     const int64_t chunk = FM_SORT_READBACK_CHUNK;
@@ -153,31 +136,25 @@ void Engine::argsort(fmhip_vec key, int64_t* permutation_out) {
     }
 }
 
-fmhip_vec Engine::rank_scores(fmhip_vec key, const fmhip_vec* out_checked) {
+void Engine::rank_scores(fmhip_vec key, fmhip_vec* out) {
     require_init();
-    if (!key || !out_checked) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "rank scores: of a vector, into a handle");
+    if (!key || !out) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "rank scores: of a vector, into a handle");
     const int64_t n = sort_size(&key, 1, "rank scores");
     PassHold hold;
     pass_prepare(&key, 1, hold, "rank scores");
     SortBuffers s(this, n);
-    Buffer* out = new_buffer(n);
-    struct Out { Engine* e; Buffer*& b; ~Out() { if (b) e->buffer_unref(b); } } keep{ this, out };
+    PassOutputs outs(this);
+    const uint64_t scores = outs.add(n);
     char* stage = (char*)ensure_stage(64);
     pass_scratch(pass_up256(8), sort_table_bytes(n));
     volatile uint64_t* flag = reinterpret_cast<volatile uint64_t*>(stage);
-    uint64_t* done_flag = nullptr; uint64_t done_value = 0;
-    pass_launch(flag, done_flag, done_value, "rank scores", [&] {
-        hipError_t e = sort_enqueue(hold.ptrs[0], n, s);
-        if (e == hipSuccess) e = launch_sort_scores(s.at(3), (uint64_t)(uintptr_t)out->ptr, (uint32_t)n, stream_);
-        if (e == hipSuccess) e = launch_sort_done(done_flag, done_value, stream_);
-        return e;
+    pass_launch_raising(flag, "rank scores", [&] {
+        const hipError_t e = sort_enqueue(hold.ptrs[0], n, s);
+        return e == hipSuccess ? launch_sort_scores(s.at(3), scores, (uint32_t)n, stream_) : e;
     });
     algorithmic_bytes_ += 8 * n;
     bytes_written_ += 4 * n;
-    Node* nd = new_node(n);
-    nd->buf = out;
-    out = nullptr;
-    return nd->id;
+    outs.commit(out);
 }
 
 void Engine::read_elements(fmhip_vec v, const int64_t* positions, int count, double* out) {
@@ -199,12 +176,7 @@ void Engine::read_elements(fmhip_vec v, const int64_t* positions, int count, dou
     volatile uint64_t* flag = reinterpret_cast<volatile uint64_t*>(stage + tab_bytes + out_bytes);
     for (int j = 0; j < count; ++j) pos_host[j] = (uint32_t)positions[j];
     hip_check(hipMemcpyAsync(pass_other_, stage, tab_bytes, hipMemcpyHostToDevice, stream_), "H2D(positions)");
-    uint64_t* done_flag = nullptr; uint64_t done_value = 0;
-    pass_launch(flag, done_flag, done_value, "read elements", [&] {
-        hipError_t e = launch_sort_read_elements(hold.ptrs[0], (const uint32_t*)pass_other_, (uint32_t)count, out_host, stream_);
-        if (e == hipSuccess) e = launch_sort_done(done_flag, done_value, stream_);
-        return e;
-    });
+    pass_launch_raising(flag, "read elements", [&] { return launch_sort_read_elements(hold.ptrs[0], (const uint32_t*)pass_other_, (uint32_t)count, out_host, stream_); });
     for (int j = 0; j < count; ++j) out[j] = out_host[j];
 }
 

@@ -1,14 +1,10 @@
 // table_engine.hpp — the engine's side of the tabulated functions (kernel: table_kernel.hip; definition, index and argument
-// checks: host/tabulated_function.hpp).  Part of runtime.cpp's translation unit (included at its end behind side_pass_engine.hpp, nowhere
-// else).
+// checks: host/tabulated_function.hpp).  A producing pass in the frame of side_pass_engine.hpp (which says what every such pass does).
 //
-// table_apply: up to four functions on the same knots applied to every element of x, each result a NEW, materialised vector: one flush
-// for a pending x, its storage held; the knots, the coefficients and the coarse index go up in ONE in-stream copy from the pinned stage
-// that the host waits for (the staging block is the engine's: it must be free again when the call returns), one launch, and no wait for
-// the launch itself — as Engine::binned_eval.  The arguments are checked by the function the host entry point uses, before anything is
-// flushed or launched.  The pass is elementwise: a device list runs it per shard (sharded.cpp), a communicator's ranks each on their own
-// paths.  Without the kernel the call is FMHIP_ERR_UNSUPPORTED: the mirrors' host path is a caller's choice (FMHIP_DEVICE_TABLE=0), never
-// the engine's.
+// table_apply: up to four functions on the same knots applied to every element of x, each result a new vector.  The knots, the coefficients
+// and the coarse index go up in ONE in-stream copy from the pinned stage that the host waits for (the staging block is the engine's: it
+// must be free again when the call returns); the launch itself is not waited for — as Engine::binned_eval.  The pass is elementwise: a
+// device list runs it per shard (sharded.cpp), a communicator's ranks each on their own paths.
 #include "runtime.hpp"
 #include "table_kernel.h"
 
@@ -24,20 +20,16 @@ static_assert(FMHIP_TABLE_PIECEWISE_CONSTANT == fmhost::FM_TABLE_PIECEWISE_CONST
 // WEAK: see pass_need_kernel (tests/nulldev/null_table.cpp has the stand-in).
 hipError_t launch_table_apply(const DevTableArgs& a, hipStream_t st) __attribute__((weak));
 
-template <class F> static void table_as_engine_error(F&& f) {
-    try { f(); }
-    catch (const std::invalid_argument& e) { throw Error(FMHIP_ERR_INVALID_ARGUMENT, e.what()); }
-}
 void table_check_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, const fmhip_vec* out) {
     if (!x) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "tabulated function: of a vector");
-    table_as_engine_error([&] { fmhost::tableCheckApply(knots, count, coefficients, n_tables, out); });
+    pass_as_engine_error([&] { fmhost::tableCheckApply(knots, count, coefficients, n_tables, out); });
 }
 // fmhip_table_build and fmhip_table_apply_host: the definition, with its complaints as engine errors
 void table_build_checked(const double* knots, const double* values, int count, int interpolation, int extrapolation, int derivative, double* coefficients_out) {
-    table_as_engine_error([&] { fmhost::table_build(knots, values, count, interpolation, extrapolation, derivative, coefficients_out); });
+    pass_as_engine_error([&] { fmhost::table_build(knots, values, count, interpolation, extrapolation, derivative, coefficients_out); });
 }
 void table_apply_host_checked(const float* x, int64_t n, const double* knots, int count, const double* coefficients, int n_tables, float* const* out) {
-    table_as_engine_error([&] { fmhost::table_apply_host(x, n, knots, count, coefficients, n_tables, out); });
+    pass_as_engine_error([&] { fmhost::table_apply_host(x, n, knots, count, coefficients, n_tables, out); });
 }
 
 void Engine::table_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, fmhip_vec* out) {
@@ -51,9 +43,8 @@ void Engine::table_apply(fmhip_vec x, const double* knots, int count, const doub
     DevTableArgs a{};
     a.n = hold.n; a.m = (uint32_t)count; a.n_tables = (uint32_t)n_tables; a.cells = (uint32_t)cells;
     a.x = hold.ptrs[0];
-    // the outputs first: an allocation that fails leaves nothing copied or launched
-    struct Outs { Engine* e; Buffer* b[fmhost::FM_TABLE_MAX_FUNCTIONS] = {}; ~Outs() { for (Buffer* p : b) if (p) e->buffer_unref(p); } } outs{ this };
-    for (int f = 0; f < n_tables; ++f) { outs.b[f] = new_buffer(hold.n); a.out[f] = (uint64_t)(uintptr_t)outs.b[f]->ptr; }
+    PassOutputs outs(this);
+    for (int f = 0; f < n_tables; ++f) a.out[f] = outs.add(hold.n);
     // knots, coefficients and index go up in one copy; the copy has left the pinned block before this call returns
     const size_t k_bytes = table_knots_bytes(count), c_bytes = table_coefficients_bytes(count, n_tables), all_bytes = table_block_bytes(count, n_tables, cells);
     char* stage = (char*)ensure_stage(all_bytes);
@@ -67,16 +58,11 @@ void Engine::table_apply(fmhip_vec x, const double* knots, int count, const doub
     a.knots = (const double*)pass_other_;
     a.coefficients = reinterpret_cast<const double*>((const char*)pass_other_ + k_bytes);
     a.first = reinterpret_cast<const uint16_t*>((const char*)pass_other_ + k_bytes + c_bytes);
-    hip_check(launch_table_apply(a, stream_), "launch fm_table_apply_kernel");            // (a failed launch: ~Outs gives the buffers back)
+    hip_check(launch_table_apply(a, stream_), "launch fm_table_apply_kernel");
     ++n_launches_;
     algorithmic_bytes_ += 4 * hold.n * (1 + n_tables);
     bytes_written_ += 4 * hold.n * n_tables;
-    for (int f = 0; f < n_tables; ++f) {
-        Node* nd = new_node(hold.n);
-        nd->buf = outs.b[f];
-        outs.b[f] = nullptr;
-        out[f] = nd->id;
-    }
+    outs.commit(out);
 }
 
 } // namespace fm

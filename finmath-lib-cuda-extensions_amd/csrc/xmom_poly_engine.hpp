@@ -1,15 +1,10 @@
 // xmom_poly_engine.hpp — the engine's side of the polynomial regression in one pass (kernels: xmom_poly_kernel.hip;
-// definition and argument checks: host/polynomial_regression.hpp).  Part of runtime.cpp's translation unit (included at its end behind
-// side_pass_engine.hpp and xmom_wide_engine.hpp, nowhere else).
+// definition and argument checks: host/polynomial_regression.hpp).  Passes in the frame of side_pass_engine.hpp (which says what every such
+// pass does), behind xmom_wide_engine.hpp: the first a reducing one, the second a producing one.
 //
 // xmom_poly_pass: the sums of fmhip_cross_moments_wide for the list [monomials of the states…, extra vectors…, dependents…] — from the STATES:
-// the monomials are slots of the wide pass's list that carry exponents, and the kernel forms them in registers.  A pass in the frame of
-// side_pass_engine.hpp, laid out as xmom_wide_pass is: one flush, the vectors' storage held, one launch, the wait under the engine lock.
-// poly_eval: the fitted polynomial as a NEW, materialised vector: one flush for pending operands, one launch, no wait (exponents and
-// coefficients travel in the kernel arguments).
-// The arguments of both are checked by the functions the host entry points use, before anything is flushed or launched.  Without the
-// kernels a pass is FMHIP_ERR_UNSUPPORTED: the mirrors' materialised basis is a caller's choice (FMHIP_DEVICE_POLYNOMIAL_MOMENTS=0), never
-// the engine's.
+// the monomials are slots of the wide pass's list that carry exponents, and the kernel forms them in registers.  Laid out as xmom_wide_pass is.
+// poly_eval: the fitted polynomial as a new vector: one launch, no wait (exponents and coefficients travel in the kernel arguments).
 #include "runtime.hpp"
 #include "xmom_poly_kernel.h"
 #include "../host/polynomial_regression.hpp"
@@ -23,22 +18,18 @@ static_assert(FM_POLY_MAX_STATES == fmhost::FM_POLY_MAX_STATES && FM_POLY_MAX_EX
 hipError_t launch_xmom_poly(const DevXmomPolyArgs& a, hipStream_t st) __attribute__((weak));
 hipError_t launch_poly_eval(const DevPolyEvalArgs& a, hipStream_t st) __attribute__((weak));
 
-template <class F> static void poly_as_engine_error(F&& f) {
-    try { f(); }
-    catch (const std::invalid_argument& e) { throw Error(FMHIP_ERR_INVALID_ARGUMENT, e.what()); }
-}
 void poly_check_moments(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const fmhip_vec* y, int n_y, const double* sums_out) {
-    poly_as_engine_error([&] { fmhost::polynomialCheckMoments<fmhip_vec>(states, n_states, exponents, n_terms, extra_x, n_extra, y, n_y, sums_out); });
+    pass_as_engine_error([&] { fmhost::polynomialCheckMoments<fmhip_vec>(states, n_states, exponents, n_terms, extra_x, n_extra, y, n_y, sums_out); });
 }
 void poly_check_evaluate(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const double* coefficients, const fmhip_vec* out) {
-    poly_as_engine_error([&] { fmhost::polynomialCheckEvaluate<fmhip_vec>(states, n_states, exponents, n_terms, extra_x, n_extra, coefficients, out); });
+    pass_as_engine_error([&] { fmhost::polynomialCheckEvaluate<fmhip_vec>(states, n_states, exponents, n_terms, extra_x, n_extra, coefficients, out); });
 }
 // fmhip_polynomial_cross_moments_host and fmhip_polynomial_evaluate_host: the definition, with its complaints as engine errors
 void poly_cross_moments_host(const float* const* states, int64_t n, int n_states, const uint8_t* exponents, int n_terms, const float* const* extra_x, int n_extra, const float* const* y, int n_y, double* sums_out) {
-    poly_as_engine_error([&] { fmhost::polynomialCrossMoments(states, n, n_states, exponents, n_terms, extra_x, n_extra, y, n_y, sums_out); });
+    pass_as_engine_error([&] { fmhost::polynomialCrossMoments(states, n, n_states, exponents, n_terms, extra_x, n_extra, y, n_y, sums_out); });
 }
 void poly_evaluate_host(const float* const* states, int64_t n, int n_states, const uint8_t* exponents, int n_terms, const float* const* extra_x, int n_extra, const double* coefficients, float* out) {
-    poly_as_engine_error([&] { fmhost::polynomialEvaluate(states, n, n_states, exponents, n_terms, extra_x, n_extra, coefficients, out); });
+    pass_as_engine_error([&] { fmhost::polynomialEvaluate(states, n, n_states, exponents, n_terms, extra_x, n_extra, coefficients, out); });
 }
 
 // states first, then the vectors among extra_x, then y: handles, one size, n > 0 — before anything is flushed or launched
@@ -92,9 +83,9 @@ void Engine::xmom_poly_pass(const fmhip_vec* states, int n_states, const uint8_t
     for (int i = 0; i < n_x; ++i) for (int k = 0; k < n_y; ++k) *o++ = out_host[xmom_wide_entry(i, n_x + k)];
 }
 
-fmhip_vec Engine::poly_eval(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const double* coefficients, const fmhip_vec* out_checked) {
+void Engine::poly_eval(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const double* coefficients, fmhip_vec* out) {
     require_init();
-    poly_check_evaluate(states, n_states, exponents, n_terms, extra_x, n_extra, coefficients, out_checked);
+    poly_check_evaluate(states, n_states, exponents, n_terms, extra_x, n_extra, coefficients, out);
     fmhip_vec real[FM_POLY_MAX_STATES + FM_POLY_MAX_EVAL];
     const int n_real = poly_real(*this, states, n_states, extra_x, n_extra, nullptr, 0, real, "polynomial evaluation");
     pass_need_kernel(launch_poly_eval != nullptr, "polynomial evaluation");
@@ -111,16 +102,13 @@ fmhip_vec Engine::poly_eval(const fmhip_vec* states, int n_states, const uint8_t
     for (int i = 0; i < n_extra; ++i) a.extra[i] = extra_x[i] ? hold.ptrs[(size_t)r++] : 0;
     for (int i = 0; i < n_terms + n_extra; ++i) a.coefficient[i] = (float)coefficients[i];
     a.n = hold.n; a.n_states = (uint32_t)n_states; a.n_terms = (uint32_t)n_terms; a.n_extra = (uint32_t)n_extra;
-    Buffer* b = new_buffer(hold.n);
-    a.out = (uint64_t)(uintptr_t)b->ptr;
-    const hipError_t e = launch_poly_eval(a, stream_);
-    if (e != hipSuccess) { buffer_unref(b); hip_check(e, "launch fm_poly_eval_kernel"); }
+    PassOutputs outs(this);
+    a.out = outs.add(hold.n);
+    hip_check(launch_poly_eval(a, stream_), "launch fm_poly_eval_kernel");
     ++n_launches_;
     algorithmic_bytes_ += 4 * hold.n * (n_real + 1);
     bytes_written_ += 4 * hold.n;
-    Node* nd = new_node(hold.n);
-    nd->buf = b;
-    return nd->id;
+    outs.commit(out);
 }
 
 } // namespace fm

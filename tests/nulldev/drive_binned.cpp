@@ -4,9 +4,11 @@
 // operands while the call runs; counts, sums and the estimate are compared with fmhip_binned_*_host bit for bit.  Then the errors that are
 // found on the host.  Twice, with a shutdown and a re-initialisation in between.  FMNULL_DEVICES=N: behind a device list of N shards;
 // FMNULL_THREAD_ENGINES=1: an engine per caller thread, the vectors asked about by a thread that does not own them.
+// `failure` (with FMHIP_TEST_FAIL_ALLOC_AT set by the caller): one fmhip_binned_evaluate in which the allocation of the output fails.
 // The null device computes nothing element-wise, so pending operands are only counted on (their values are whatever the buffers hold).
 #include <cmath>
 #include <limits>
+#include <string>
 #include <thread>
 
 #include "drive_common.hpp"
@@ -126,7 +128,46 @@ static void scenario(bool thread_engines) {
     rel(d.hkey); for (V v : d.hcol) rel(v);
 }
 
-int main() {
+// FMHIP_TEST_FAIL_ALLOC_AT is set by the caller: the output of one fmhip_binned_evaluate is its one pool allocation.  Without it this is
+// the counting run that says where it is.
+static int failure() {
+    OK(fmhip_init(0));
+    const size_t n = 2051;
+    std::vector<float> key(n), col(n), want(n), got(n);
+    for (size_t p = 0; p < n; ++p) { key[p] = (float)((int)((p * 37) % 101) - 50); col[p] = (float)((int)((p * 3) % 17) - 8); }
+    const V hkey = upload(key), x[2] = { 0, upload(col) };
+    const float* px[2] = { nullptr, col.data() };
+    const double bounds[3] = { -20.0, 0.0, 20.0 }, coef[8] = { 1.0, 2.0, -1.0, 0.0, 3.0, -2.0, 0.0, 1.0 };
+    OK(fmhip_binned_evaluate_host(key.data(), (int64_t)n, bounds, 4, px, 2, coef, want.data()));
+    fmhip_pool_stats_t before, mid, after;
+    OK(fmhip_pool_stats(&before));
+    int first = -1;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        V est = 0;
+        const int st = fmhip_binned_evaluate(hkey, bounds, 4, x, 2, coef, &est);
+        if (attempt == 0) { first = st; OK(fmhip_pool_stats(&mid)); }
+        if (st != FMHIP_OK && !(attempt == 0 && st == FMHIP_ERR_OUT_OF_MEMORY)) { std::fprintf(stderr, "attempt %d: status %d (%s)\n", attempt, st, fmhip_last_error()); std::abort(); }
+        if (st == FMHIP_OK) {
+            OK(fmhip_vec_read_float(est, got.data(), (int64_t)n));
+            if (std::memcmp(got.data(), want.data(), n * 4) != 0) { std::fprintf(stderr, "attempt %d: the estimate differs from the definition\n", attempt); std::abort(); }
+            rel(est);
+        } else if (est != 0) { std::fprintf(stderr, "a failed call wrote its output\n"); std::abort(); }
+        OK(fmhip_pool_stats(&after));
+        if (after.n_live_vectors != before.n_live_vectors || after.bytes_in_use != before.bytes_in_use) {
+            std::fprintf(stderr, "a binned_evaluate left %lld vectors and %lld bytes behind\n", (long long)(after.n_live_vectors - before.n_live_vectors), (long long)(after.bytes_in_use - before.bytes_in_use));
+            std::abort();
+        }
+    }
+    std::printf("failure: %lld allocations before the call, %lld in it, status %d\n", (long long)(before.n_alloc_hits + before.n_alloc_misses),
+                (long long)(mid.n_alloc_hits + mid.n_alloc_misses - before.n_alloc_hits - before.n_alloc_misses), first);
+    rel(hkey); rel(x[1]);
+    OK(fmhip_shutdown());
+    std::printf("failure done\n");
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "failure") return failure();
     return two_rounds([](int cycle, bool thread_engines, bool) {
         scenario(thread_engines);
         std::printf("cycle %d: binned done\n", cycle);

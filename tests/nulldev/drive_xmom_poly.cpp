@@ -8,7 +8,9 @@
 // it: every entry of S and T between regressors of known value is checked exactly — v_i·v_j·n with v a monomial of 1.5 and 0.5 —, which is
 // a check of the slots the engine writes, of the layout it reads back and of the shard sums; the evaluation is read back and compared on
 // every path; statuses are checked, the sanitizers do the rest.
+// `failure` (with FMHIP_TEST_FAIL_ALLOC_AT set by the caller): one fmhip_polynomial_evaluate in which the allocation of the output fails.
 #include <cmath>
+#include <string>
 #include <thread>
 
 #include "drive_common.hpp"
@@ -126,7 +128,47 @@ static void scenario(bool thread_engines) {
     rel(stored); rel(other); rel(pending); rel(twin);
 }
 
-int main() {
+// FMHIP_TEST_FAIL_ALLOC_AT is set by the caller: the output of one fmhip_polynomial_evaluate is its one pool allocation.  Without it this
+// is the counting run that says where it is.
+static int failure() {
+    OK(fmhip_init(0));
+    const int64_t n = 2049;
+    const V states[2] = { filled(n, 1.5), filled(n, 0.5) }, extra[2] = { states[1], 0 };
+    const uint8_t e[6] = { 0, 0, 1, 2, 3, 0 };
+    const double c[5] = { 2.0, 3.0, -1.0, 4.0, 5.0 };
+    const float want = 2.0f + 3.0f * (1.5f * 0.25f) - 3.375f + 4.0f * 0.5f + 5.0f;
+    std::vector<float> got((size_t)n);
+    OK(fmhip_vec_read_float(states[0], got.data(), n));                      // (the filled vectors are stored before anything is counted)
+    OK(fmhip_vec_read_float(states[1], got.data(), n));
+    fmhip_pool_stats_t before, mid, after;
+    OK(fmhip_pool_stats(&before));
+    int first = -1;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        V out = 0;
+        const int st = fmhip_polynomial_evaluate(states, 2, e, 3, extra, 2, c, &out);
+        if (attempt == 0) { first = st; OK(fmhip_pool_stats(&mid)); }
+        if (st != FMHIP_OK && !(attempt == 0 && st == FMHIP_ERR_OUT_OF_MEMORY)) { std::fprintf(stderr, "attempt %d: status %d (%s)\n", attempt, st, fmhip_last_error()); std::abort(); }
+        if (st == FMHIP_OK) {
+            OK(fmhip_vec_read_float(out, got.data(), n));
+            for (int64_t p = 0; p < n; ++p) if (got[(size_t)p] != want) { std::fprintf(stderr, "attempt %d: path %lld = %g, expected %g\n", attempt, (long long)p, got[(size_t)p], want); std::abort(); }
+            rel(out);
+        } else if (out != 0) { std::fprintf(stderr, "a failed call wrote its output\n"); std::abort(); }
+        OK(fmhip_pool_stats(&after));
+        if (after.n_live_vectors != before.n_live_vectors || after.bytes_in_use != before.bytes_in_use) {
+            std::fprintf(stderr, "a polynomial_evaluate left %lld vectors and %lld bytes behind\n", (long long)(after.n_live_vectors - before.n_live_vectors), (long long)(after.bytes_in_use - before.bytes_in_use));
+            std::abort();
+        }
+    }
+    std::printf("failure: %lld allocations before the call, %lld in it, status %d\n", (long long)(before.n_alloc_hits + before.n_alloc_misses),
+                (long long)(mid.n_alloc_hits + mid.n_alloc_misses - before.n_alloc_hits - before.n_alloc_misses), first);
+    rel(states[0]); rel(states[1]);
+    OK(fmhip_shutdown());
+    std::printf("failure done\n");
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "failure") return failure();
     return two_rounds([](int cycle, bool thread_engines, bool) {
         scenario(thread_engines);
         std::printf("cycle %d: xmom poly done\n", cycle);

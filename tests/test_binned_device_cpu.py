@@ -4,6 +4,7 @@ compute with the host definition in the layout the engine asked for, and the dri
 with fmhip_binned_*_host bit for bit: one engine, device lists of 2 and 3 shards, thread engines, a second thread releasing the inputs of
 pending operands during the calls, every argument error, and a build without the launchers (drive_binned_absent.cpp): FMHIP_ERR_UNSUPPORTED."""
 import os
+import re
 import shutil
 import subprocess
 
@@ -52,3 +53,23 @@ def test_the_cross_moments_driver_is_unaffected(built, tmp_path):
     full = dict(os.environ, FMHIP_JIT_CACHE_DIR=str(tmp_path / "code_objects"), FMHIP_JIT_PACK_DIR="off", ASAN_OPTIONS="detect_leaks=1:abort_on_error=0")
     a = subprocess.run([os.path.join(built, "drive_xmom_asan")], capture_output=True, text=True, timeout=600, env=full)
     assert a.returncode == 0 and a.stdout.count("xmom done") == 2, a.stdout[-500:] + a.stderr[-3000:]
+
+
+def test_a_failing_allocation_inside_a_binned_evaluation_leaves_nothing_behind(built, tmp_path):
+    """One fmhip_binned_evaluate takes ONE buffer from the pool, its output.  The hook FMHIP_TEST_FAIL_ALLOC_AT is set on it (its position
+    from a counting run), and once where nothing reaches it: the call answers FMHIP_OK or FMHIP_ERR_OUT_OF_MEMORY, a result it gives is the
+    definition's, a failed call leaves its handle as it was, live vectors and bytes in use are what they were, the same call succeeds
+    afterwards (the driver checks all of it), and the process ends without a leak."""
+    exe = os.path.join(built, "drive_binned_asan")
+    env = dict(os.environ, FMHIP_JIT_CACHE_DIR=str(tmp_path / "code_objects"), FMHIP_JIT_PACK_DIR="off", FMHIP_RING_BYTES="16384", FMHIP_ARENA_BYTES="4096",
+               ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    counting = subprocess.run([exe, "failure"], capture_output=True, text=True, timeout=600, env=env)
+    assert counting.returncode == 0 and "Sanitizer" not in counting.stderr, counting.stdout[-500:] + counting.stderr[-6000:]
+    before, inside, status = map(int, re.search(r"failure: (\d+) allocations before the call, (\d+) in it, status (-?\d+)", counting.stdout).groups())
+    assert inside == 1 and status == 0
+    for at in list(range(before + 1, before + inside + 1)) + [10**9]:
+        r = subprocess.run([exe, "failure"], capture_output=True, text=True, timeout=600, env=dict(env, FMHIP_TEST_FAIL_ALLOC_AT=str(at)))
+        assert r.returncode == 0 and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr and r.stderr == "", (at, r.stdout[-500:] + r.stderr[-6000:])
+        assert "failure done" in r.stdout
+        failed = int(re.search(r"status (-?\d+)", r.stdout).group(1)) != 0
+        assert failed == (at <= before + inside), (at, r.stdout)

@@ -6,6 +6,7 @@ host programs only."""
 import ctypes as C
 import math
 import os
+import re
 import shutil
 import subprocess
 from importlib import import_module
@@ -277,3 +278,23 @@ def test_a_build_without_the_kernels_answers_unsupported(built, tmp_path, env):
     a = subprocess.run([os.path.join(built, "drive_xmom_poly_absent_asan")], capture_output=True, text=True, timeout=600, env=_env(tmp_path, env))
     assert a.returncode == 0 and "Sanitizer" not in a.stderr and "runtime error" not in a.stderr, a.stdout[-500:] + a.stderr[-6000:]
     assert a.stdout.count("xmom poly absent done") == 2
+
+
+def test_a_failing_allocation_inside_a_polynomial_evaluation_leaves_nothing_behind(built, tmp_path):
+    """One fmhip_polynomial_evaluate takes ONE buffer from the pool, its output.  The hook FMHIP_TEST_FAIL_ALLOC_AT is set on it (its position
+    from a counting run), and once where nothing reaches it: the call answers FMHIP_OK or FMHIP_ERR_OUT_OF_MEMORY, a result it gives is the
+    definition's, a failed call leaves its handle as it was, live vectors and bytes in use are what they were, the same call succeeds
+    afterwards (the driver checks all of it), and the process ends without a leak."""
+    exe = os.path.join(built, "drive_xmom_poly_asan")
+    env = dict(os.environ, FMHIP_JIT_CACHE_DIR=str(tmp_path / "code_objects"), FMHIP_JIT_PACK_DIR="off", FMHIP_RING_BYTES="16384", FMHIP_ARENA_BYTES="4096",
+               ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    counting = subprocess.run([exe, "failure"], capture_output=True, text=True, timeout=600, env=env)
+    assert counting.returncode == 0 and "Sanitizer" not in counting.stderr, counting.stdout[-500:] + counting.stderr[-6000:]
+    before, inside, status = map(int, re.search(r"failure: (\d+) allocations before the call, (\d+) in it, status (-?\d+)", counting.stdout).groups())
+    assert inside == 1 and status == 0
+    for at in list(range(before + 1, before + inside + 1)) + [10**9]:
+        r = subprocess.run([exe, "failure"], capture_output=True, text=True, timeout=600, env=dict(env, FMHIP_TEST_FAIL_ALLOC_AT=str(at)))
+        assert r.returncode == 0 and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr and r.stderr == "", (at, r.stdout[-500:] + r.stderr[-6000:])
+        assert "failure done" in r.stdout
+        failed = int(re.search(r"status (-?\d+)", r.stdout).group(1)) != 0
+        assert failed == (at <= before + inside), (at, r.stdout)
