@@ -32,6 +32,7 @@ SYMBOLS = [
     "fmhip_table_build", "fmhip_table_apply", "fmhip_table_apply_host",
     "fmhip_function_apply", "fmhip_function_apply_host", "fmhip_option_formula", "fmhip_option_formula_host",
     "fmhip_block_moments", "fmhip_block_moments_host", "fmhip_vec_repeat",
+    "fmhip_block_order_statistics", "fmhip_block_order_statistics_host", "fmhip_block_sort", "fmhip_block_sort_host",
     "fmhip_kernel_moments", "fmhip_kernel_moments_host",
     "fmhip_program_create", "fmhip_program_release", "fmhip_program_launch_count", "fmhip_program_shape",
     "fmhip_program_run", "fmhip_program_run_into",
@@ -194,6 +195,9 @@ def lib():
         "fmhip_option_formula_host": [i32, vp, dbl, vp, dbl, vp, dbl, i64, dbl, dbl, i32, C.POINTER(vp)],
         "fmhip_block_moments": [pv, i32, i64, C.c_uint32, pv], "fmhip_block_moments_host": [vp, i64, i64, C.c_uint32, vp],
         "fmhip_vec_repeat": [vec, i64, i64, pv],
+        "fmhip_block_order_statistics": [pv, i32, i64, C.POINTER(i64), i32, C.POINTER(i64), C.POINTER(i64), i32, pv],
+        "fmhip_block_order_statistics_host": [vp, i64, i64, C.POINTER(i64), i32, C.POINTER(i64), C.POINTER(i64), i32, vp],
+        "fmhip_block_sort": [vec, i64, pv], "fmhip_block_sort_host": [vp, i64, i64, vp],
         "fmhip_kernel_moments": [vec, C.POINTER(dbl), C.POINTER(dbl), i32, i32, i32, pv, i32, C.POINTER(dbl)],
         "fmhip_kernel_moments_host": [vp, i64, C.POINTER(dbl), C.POINTER(dbl), i32, i32, i32, C.POINTER(vp), i32, C.POINTER(dbl)],
         "fmhip_program_create": [C.POINTER(ProgOp), i32, i32, C.POINTER(C.c_int32), i32, C.POINTER(C.c_int32), i32, pv],

@@ -930,6 +930,27 @@ int fmhip_vec_repeat(fmhip_vec v, int64_t each, int64_t times, fmhip_vec* out) {
     return guarded([&] { Engine::get().repeat(v, each, times, out); });
 }
 
+// ---------------------------------------------------------------- block order statistics and the block sort (block_order_engine.hpp)
+int fmhip_block_order_statistics_host(const float* v, int64_t n, int64_t block, const int64_t* ranks, int n_ranks, const int64_t* range_from, const int64_t* range_to,
+                                      int n_ranges, float* outs) {
+    return host_only([&] { fm::block_order_statistics_host_checked(v, n, block, ranks, n_ranks, range_from, range_to, n_ranges, outs); });
+}
+int fmhip_block_sort_host(const float* v, int64_t n, int64_t block, float* out) {
+    return host_only([&] { fm::block_sort_host_checked(v, n, block, out); });
+}
+int fmhip_block_order_statistics(const fmhip_vec* vs, int n_vs, int64_t block, const int64_t* ranks, int n_ranks, const int64_t* range_from, const int64_t* range_to,
+                                 int n_ranges, fmhip_vec* outs) {
+    FRONT(block_order_statistics(vs, n_vs, block, ranks, n_ranks, range_from, range_to, n_ranges, outs));
+    TE_CHECKED_LOCAL(fm::block_order_check_statistics(vs, n_vs, block, ranks, n_ranks, range_from, range_to, n_ranges, outs), te_operands(0, vs, n_vs, nullptr, 0), L,
+                     fmhip_block_order_statistics(L, n_vs, block, ranks, n_ranks, range_from, range_to, n_ranges, outs));
+    return guarded([&] { Engine::get().block_order_statistics(vs, n_vs, block, ranks, n_ranks, range_from, range_to, n_ranges, outs); });
+}
+int fmhip_block_sort(fmhip_vec v, int64_t block, fmhip_vec* out) {
+    FRONT(block_sort(v, block, out));
+    TE_CHECKED_LOCAL(fm::block_order_check_sort(v, block, out), te_operands(v, nullptr, 0, nullptr, 0), L, fmhip_block_sort(L[0], block, out));
+    return guarded([&] { Engine::get().block_sort(v, block, out); });
+}
+
 // The one call of a caller that values product after product: the engine lock is held for the bookkeeping (graph → launch → commit),
 // NOT while the device computes — other threads record and launch meanwhile.  The moments arrive in a slot of pinned memory of their
 // own; this thread polls its flag, then takes the lock again to copy them out and give the launch's buffers back.

@@ -433,6 +433,14 @@ public:
     void block_moments(const fmhip_vec* vs, int n_vs, int64_t block, uint32_t mask, fmhip_vec* outs);
     void repeat(fmhip_vec v, int64_t each, int64_t times, fmhip_vec* out);
 
+    // block order statistics (block_order_engine.hpp): of the n / block consecutive blocks (block <= 4096) of up to four vectors,
+    // each sorted by the key of host/block_order.hpp, the elements at n_ranks ranks and the means over n_ranges ranges of ranks as new,
+    // materialised vectors of n / block elements, outs[i·(n_ranks + n_ranges) + j], ranks first; and the blocks sorted, as one new vector.
+    // Arguments are checked before anything is flushed or launched; outs is written only when the call succeeds.  Local to this engine's vector.
+    void block_order_statistics(const fmhip_vec* vs, int n_vs, int64_t block, const int64_t* ranks, int n_ranks, const int64_t* range_from, const int64_t* range_to,
+                                int n_ranges, fmhip_vec* outs);
+    void block_sort(fmhip_vec v, int64_t block, fmhip_vec* out);
+
     // kernel regression (kreg_engine.hpp): the kernel-weighted local moments of n_y vectors at n_points points of `key`
     // (host/kernel_regression.hpp), sums_out[n_points][order 0: 1 + n_y, order 1: 3 + 2 n_y], from ONE launch.  Arguments are checked before
     // anything is flushed or launched.
@@ -850,6 +858,14 @@ void option_formula_host_checked(int model, const float* forward, double forward
 void nested_check_moments(const fmhip_vec* vs, int n_vs, int64_t block, uint32_t mask, const fmhip_vec* outs);
 void nested_check_repeat(fmhip_vec v, int64_t each, int64_t times, const fmhip_vec* out);
 void block_moments_host_checked(const float* v, int64_t n, int64_t block, uint32_t mask, float* outs);
+// the same for fmhip_block_order_statistics / fmhip_block_sort, and the definitions behind their _host twins (block_order_engine.hpp; the rules
+// are host/block_order.hpp's): FMHIP_ERR_INVALID_ARGUMENT, then FMHIP_ERR_UNSUPPORTED for a block above 4096 elements
+void block_order_check_statistics(const fmhip_vec* vs, int n_vs, int64_t block, const int64_t* ranks, int n_ranks, const int64_t* range_from, const int64_t* range_to,
+                                  int n_ranges, const fmhip_vec* outs);
+void block_order_check_sort(fmhip_vec v, int64_t block, const fmhip_vec* out);
+void block_order_statistics_host_checked(const float* v, int64_t n, int64_t block, const int64_t* ranks, int n_ranks, const int64_t* range_from, const int64_t* range_to,
+                                         int n_ranges, float* outs);
+void block_sort_host_checked(const float* v, int64_t n, int64_t block, float* out);
 // what can be said about the arguments of fmhip_binned_cross_moments / fmhip_binned_evaluate without looking at a vector (binned_engine.hpp; the
 // rules are fmhost::binnedCheck*'s, host/binned_regression.hpp), and the host definitions: all throw FMHIP_ERR_INVALID_ARGUMENT
 void binned_check_moments(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, const int64_t* counts_out, const double* sums_out);

@@ -1039,6 +1039,28 @@ int vec_repeat(fmhip_vec v, int64_t each, int64_t times, fmhip_vec* out) {
         produce_per_shard(s, n * each * times, 1, out, [&](Worker& w, fmhip_vec* got) { return fmhip_vec_repeat(w.at(v), each, times, got); });
     });
 }
+// Block order statistics and the block sort (block_order_engine.hpp): blocks again, one shard again.
+int block_order_statistics(const fmhip_vec* vs, int n_vs, int64_t block, const int64_t* ranks, int n_ranks, const int64_t* range_from, const int64_t* range_to,
+                           int n_ranges, fmhip_vec* outs) {
+    return fronted([&](Shards& s) {
+        block_order_check_statistics(vs, n_vs, block, ranks, n_ranks, range_from, range_to, n_ranges, outs);
+        const int64_t n = front_size(s, vs, n_vs, "block order statistics", false);
+        if (n % block != 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "block order statistics: " + std::to_string(n) + " elements are no whole number of blocks of " + std::to_string(block));
+        one_shard(s, "block order statistics", NESTED_WHY);
+        produce_per_shard(s, n / block, n_vs * (n_ranks + n_ranges), outs, [&](Worker& w, fmhip_vec* got) {
+            return fmhip_block_order_statistics(localize(w, vs, n_vs).data(), n_vs, block, ranks, n_ranks, range_from, range_to, n_ranges, got);
+        });
+    });
+}
+int block_sort(fmhip_vec v, int64_t block, fmhip_vec* out) {
+    return fronted([&](Shards& s) {
+        block_order_check_sort(v, block, out);
+        const int64_t n = front_size(s, &v, 1, "block sort", false);
+        if (n % block != 0) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "block sort: " + std::to_string(n) + " elements are no whole number of blocks of " + std::to_string(block));
+        one_shard(s, "block sort", NESTED_WHY);
+        produce_per_shard(s, n, 1, out, [&](Worker& w, fmhip_vec* got) { return fmhip_block_sort(w.at(v), block, got); });
+    });
+}
 
 int vec_give_up_values(const fmhip_vec* vectors, int count) {
     return fronted([&](Shards& s) {

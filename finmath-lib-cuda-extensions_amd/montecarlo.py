@@ -25,6 +25,8 @@ a RandomVariableFactory by injection (LIBORMarketModelCalibrationATMTest.java:35
                             what finmath-lib's BermudanOption does with its conditional-expectation estimator
     bermudan_option_bounds_mc  the primal–dual bounds of Andersen & Broadie for the same option: the fitted policy on fresh paths, and a
                             martingale from inner simulations at every exercise date of every outer path (nested.py)
+    nested_initial_margin_mc  the dynamic initial margin of a forward contract at a future date: the quantile, per outer state, of the inner
+                            P&L over the margin period of risk — a block order statistic (nested.py)
     bermudan_max_call_mc    the same induction for a call on the maximum of several assets, regressed on all monomials of the assets up
                             to a total degree: 10 … 56 basis functions, the wide one-pass normal equations
 """
@@ -465,6 +467,42 @@ def bermudan_option_bounds_mc(brownian_motion_fit, brownian_motion_outer, inner_
             worst = gap if worst is None else worst.floor(gap)
         previous_c = c
     return dict(lower=lower.getAverage(), lower_se=lower.getStandardError(), upper=worst.getAverage(), upper_se=worst.getStandardError())
+
+
+def nested_initial_margin_mc(brownian_motion_outer, brownian_motion_inner, initial_value, risk_free_rate, volatility, time, margin_period, maturity, strike,
+                             inner_paths, quantile=0.99):
+    """Expected dynamic initial margin, at `time`, of a forward contract on a Black–Scholes asset by nested simulation: returns (E[IM], its
+    standard error over the outer paths).
+    OUTER: the m paths of brownian_motion_outer carry the log-Euler state from the first point of its time discretisation to `time` (a point
+    of it).  INNER: inner_paths paths per outer state (nested.repeat_each) follow the same scheme over the steps of brownian_motion_inner —
+    m·inner_paths paths — until `margin_period` has passed (a point of its discretisation, counted from its first).
+    The contract's value at u is V(u) = S_u − K·exp(−r(T − u)); the inner P&L is V(time + margin_period) − V(time), per inner path, and
+    IM = −getQuantile(quantile) of the inner P&L of each outer path (nested.block_quantiles: rank quantile_index(inner_paths, quantile) of
+    the ascending block — the loss that the fraction `quantile` of the inner P&Ls does not exceed).  Nothing leaves the device but the two
+    numbers.  With FMHIP_DEVICE_NESTED=0 they are the same to the last bit: the host definition of the block quantile is the device's."""
+    from .nested import block_quantiles, repeat_each
+    inner_paths = int(inner_paths)
+    if inner_paths < 1: raise ValueError("at least one inner path per outer path")
+    if brownian_motion_inner.getNumberOfPaths() != brownian_motion_outer.getNumberOfPaths() * inner_paths:
+        raise ValueError("the inner Brownian motion has not inner_paths paths per outer path")
+    drift = risk_free_rate - 0.5 * volatility * volatility
+
+    def advance(bm, x, span):
+        td = bm.getTimeDiscretization()
+        start, i = td.getTime(0), 0
+        while td.getTime(i) - start < span - 1e-12:
+            x = x.add(drift * td.getTimeStep(i)).addProduct(bm.getBrownianIncrement(i, 0), volatility)
+            i += 1
+        if abs(td.getTime(i) - start - span) > 1e-12: raise ValueError("the horizon is not a point of the time discretisation")
+        return x
+
+    t0 = brownian_motion_outer.getTimeDiscretization().getTime(0)
+    x = advance(brownian_motion_outer, brownian_motion_outer.getRandomVariableForConstant(math.log(initial_value)), time - t0)
+    inner = advance(brownian_motion_inner, repeat_each(x, inner_paths), margin_period)
+    value_change = strike * (math.exp(-risk_free_rate * (maturity - time - margin_period)) - math.exp(-risk_free_rate * (maturity - time)))
+    pnl = inner.exp().sub(repeat_each(x.exp(), inner_paths)).sub(value_change)
+    margin = block_quantiles(pnl, inner_paths, [quantile])[0].mult(-1.0)
+    return margin.getAverage(), margin.getStandardError()
 
 
 def monomial_exponents(n_assets, order):

@@ -576,6 +576,40 @@ int fmhip_block_moments(const fmhip_vec* vs, int n_vs, int64_t block, uint32_t m
 int fmhip_block_moments_host(const float* v, int64_t n, int64_t block, uint32_t mask, float* outs);   /* the DEFINITION; no device */
 int fmhip_vec_repeat(fmhip_vec v, int64_t each, int64_t times, fmhip_vec* out);
 
+/* Block order statistics on the device: what a nested risk measure needs of the m*k inner values beside their moments — the
+ * quantile of every block (dynamic initial margin, nested VaR), the mean of a tail of it (expected shortfall), its minimum and maximum,
+ * bootstrap percentile intervals per block — and the blocks sorted, without the vectors leaving the device.  The definition is
+ * host/block_order.hpp, one header for the host and the device.
+ * A vector of n = m*block elements is m consecutive blocks of `block` elements, 1 <= block <= 4096 (FM_BLOCK_ORDER_MAX).  s_q is block q in
+ *   ascending order of the 32-bit key of fmhip_select_ranks_batch — the order of java.util.Arrays.sort(float[]): -0.0 before +0.0, every NaN
+ *   equal and last.  Equal keys have equal bits apart from NaNs, so everything below is a function of the block's multiset alone (not of q,
+ *   m, the vectors of the call, a vector's slot, the other selectors or the launch).
+ *   The device's outputs EQUAL the _host calls' bit for bit.
+ * Rank r (0 <= r < block): out[q] = s_q[r], an element of the block bit for bit (the sign of a zero, a denormal); a position in the NaN tail
+ *   gives the quiet NaN 0x7fc00000.  Duplicate ranks are allowed.
+ * Range mean [from, to] (0 <= from <= to < block): S = the fp64 sum of s_q[from..to] in the association fmhip_block_moments gives a block of
+ *   to - from + 1 elements (64 strided leaves from -0.0 per 2048 terms, the butterfly with bit 5 first, one more unit above 2048 terms);
+ *   out[q] = (float)(S / (to - from + 1)), rounded once.  A range that reaches the NaN tail, or that holds both infinities, gives 0x7fc00000.
+ * fmhip_block_order_statistics: n_vs = 1 ... 4 vectors of one size n (1 ... 2^31 - 1, a multiple of block), each read once; n_ranks = 0 ... 8,
+ *   n_ranges = 0 ... 4, at least one selector; outs[i*(n_ranks + n_ranges) + j] = a new, materialised vector of n/block elements, ranks first.
+ * fmhip_block_sort: *out = a new, materialised vector of n elements, out[q*block + i] = s_q[i]; every NaN comes back as 0x7fc00000.  Keys are
+ *   carried, not (key, index) pairs: fmhip_sort_by_key is the stable, payload-preserving sort.
+ * The _host calls are the DEFINITION over a host float array (outs[j*(n/block) + q]); they need no device.
+ * Everything is checked on the host before anything is flushed or launched: n_ranks + n_ranges == 0, a count outside its limits, a rank or a
+ * range outside the block, from > to, block < 1, n no multiple of block, a NULL pointer, a handle of 0 -> FMHIP_ERR_INVALID_ARGUMENT;
+ * block > 4096 -> FMHIP_ERR_UNSUPPORTED (fmhip_select_ranks_batch selects in whole vectors, fmhip_sort_by_key sorts them); vectors of
+ * different sizes -> FMHIP_ERR_SIZE_MISMATCH; FMHIP_ERR_INVALID_HANDLE.  A vector whose values were given up is the error a read of it is.
+ * A build without the kernel answers FMHIP_ERR_UNSUPPORTED; it never falls back.  With a device list of more than one shard both device
+ * calls answer FMHIP_ERR_UNSUPPORTED (blocks would straddle the shards); under an expectation communicator they act on this rank's own
+ * vector, as fmhip_block_moments does. */
+int fmhip_block_order_statistics(const fmhip_vec* vs, int n_vs, int64_t block, const int64_t* ranks, int n_ranks,
+                                 const int64_t* range_from, const int64_t* range_to, int n_ranges, fmhip_vec* outs);
+    /* outs[i*(n_ranks+n_ranges) + j]: new vectors of size n/block, ranks first */
+int fmhip_block_order_statistics_host(const float* v, int64_t n, int64_t block, const int64_t* ranks, int n_ranks,
+                                      const int64_t* range_from, const int64_t* range_to, int n_ranges, float* outs);   /* the DEFINITION; no device */
+int fmhip_block_sort(fmhip_vec v, int64_t block, fmhip_vec* out);
+int fmhip_block_sort_host(const float* v, int64_t n, int64_t block, float* out);                                        /* the DEFINITION; no device */
+
 /* Kernel regression on the device: kernel-weighted LOCAL MOMENTS of up to four vectors at a grid of points of a key vector
  * in one pass — E[y | x = p_q] as a curve: the inner step of the particle method for local-stochastic-volatility calibration
  * (E[v_t | S_t = S] at every time step), kernel density estimates, smooth exercise boundaries, exposure profiles — without the vectors

@@ -133,6 +133,15 @@ final class Native {
 	static native int blockMomentsHost(float[] v, long block, int mask, float[] outColumns);
 	/** out[0] = a new vector of n * each * times elements: out[(t * n + p) * each + e] = v[p], copied bit for bit. */
 	static native int vecRepeat(long v, long each, long times, long[] out);
+	// ---- block order statistics: ranks and range means of consecutive blocks (at most 4096 elements) as new vectors, and the blocks sorted
+	/** outs[i * (ranks.length + rangeFrom.length) + j] = a new vector of n / block elements, ranks first: the element at rank ranks[j] of every ascending-sorted block of vs[i] (the order of Arrays.sort(float[])), resp. the mean of its ranks rangeFrom[j] ... rangeTo[j]; 1 ... 4 vectors of one size, 0 ... 8 ranks, 0 ... 4 ranges, at least one; the bits are those of blockOrderStatisticsHost. */
+	static native int blockOrderStatistics(long[] vs, long block, long[] ranks, long[] rangeFrom, long[] rangeTo, long[] outs);
+	/** The definition of blockOrderStatistics over a host array: outColumns holds one column of v.length / block floats per rank, then per range. */
+	static native int blockOrderStatisticsHost(float[] v, long block, long[] ranks, long[] rangeFrom, long[] rangeTo, float[] outColumns);
+	/** out[0] = a new vector of n elements: every block of `block` elements of v sorted ascending; every NaN comes back as the quiet NaN. */
+	static native int blockSort(long v, long block, long[] out);
+	/** The definition of blockSort over a host array. */
+	static native int blockSortHost(float[] v, long block, float[] out);
 	// ---- kernel regression: kernel-weighted local moments of up to 4 vectors at up to 256 points of a key from one launch
 	/** sumsOut[points.length][order 0: 1 + y.length; order 1: 3 + 2 y.length]: per point the fp64 sums [w, w*y...] or [w, w*d, w*d*d, w*y..., w*d*y...] over its members (lower &lt; key &lt; upper); kernel 0 uniform, 1 triangular, 2 Epanechnikov, 3 quartic, 4 triweight. */
 	static native int kernelMoments(long key, double[] points, double[] bandwidths, int kernel, int order, long[] y, double[] sumsOut);

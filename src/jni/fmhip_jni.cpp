@@ -380,6 +380,38 @@ FMJ(jint, vecRepeat)(JNIEnv* env, jclass, jlong v, jlong each, jlong times, jlon
     if (st == FMHIP_OK) set1(env, out, (jlong)h);
     return st;
 }
+// ---------------------------------------------------------------- block order statistics and the block sort
+FMJ(jint, blockOrderStatistics)(JNIEnv* env, jclass, jlongArray vs, jlong block, jlongArray ranks, jlongArray rangeFrom, jlongArray rangeTo, jlongArray outs) {
+    Pin<jlong> pv(env, vs, JNI_ABORT); Pin<jlong> pr(env, ranks, JNI_ABORT); Pin<jlong> pf(env, rangeFrom, JNI_ABORT); Pin<jlong> pt(env, rangeTo, JNI_ABORT);
+    const int64_t nv = pv.p ? pv.length() : 0, nr = pr.p ? pr.length() : 0, ng = pf.p ? pf.length() : 0;
+    if (nv < 1 || nv > 4 || nr > 8 || ng > 4 || nr + ng < 1 || (int64_t)(pt.p ? pt.length() : 0) != ng || !outs) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int total = (int)(nv * (nr + ng));
+    if (env->GetArrayLength(outs) < total) return FMHIP_ERR_INVALID_ARGUMENT;
+    fmhip_vec h[48] = { 0 };
+    const int st = fmhip_block_order_statistics((const fmhip_vec*)pv.p, (int)nv, (int64_t)block, (const int64_t*)pr.p, (int)nr, (const int64_t*)pf.p, (const int64_t*)pt.p, (int)ng, h);
+    if (st == FMHIP_OK) { jlong o[48]; for (int k = 0; k < total; ++k) o[k] = (jlong)h[k]; env->SetLongArrayRegion(outs, 0, (jsize)total, o); }
+    return st;
+}
+FMJ(jint, blockOrderStatisticsHost)(JNIEnv* env, jclass, jfloatArray v, jlong block, jlongArray ranks, jlongArray rangeFrom, jlongArray rangeTo, jfloatArray outColumns) {
+    Pin<jfloat> pv(env, v, JNI_ABORT); Pin<jlong> pr(env, ranks, JNI_ABORT); Pin<jlong> pf(env, rangeFrom, JNI_ABORT); Pin<jlong> pt(env, rangeTo, JNI_ABORT); Pin<jfloat> po(env, outColumns);
+    const int64_t nr = pr.p ? pr.length() : 0, ng = pf.p ? pf.length() : 0;
+    if (!pv.p || !po.p || block < 1 || nr > 8 || ng > 4 || nr + ng < 1 || (int64_t)(pt.p ? pt.length() : 0) != ng) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int64_t n = pv.length();
+    if ((int64_t)po.length() < (nr + ng) * (n / (int64_t)block)) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_block_order_statistics_host(pv.p, n, (int64_t)block, (const int64_t*)pr.p, (int)nr, (const int64_t*)pf.p, (const int64_t*)pt.p, (int)ng, po.p);
+}
+FMJ(jint, blockSort)(JNIEnv* env, jclass, jlong v, jlong block, jlongArray out) {
+    if (!out || env->GetArrayLength(out) < 1) return FMHIP_ERR_INVALID_ARGUMENT;
+    fmhip_vec h = 0;
+    const int st = fmhip_block_sort(v, (int64_t)block, &h);
+    if (st == FMHIP_OK) set1(env, out, (jlong)h);
+    return st;
+}
+FMJ(jint, blockSortHost)(JNIEnv* env, jclass, jfloatArray v, jlong block, jfloatArray out) {
+    Pin<jfloat> pv(env, v, JNI_ABORT); Pin<jfloat> po(env, out);
+    if (!pv.p || !po.p || po.length() < pv.length()) return FMHIP_ERR_INVALID_ARGUMENT;
+    return fmhip_block_sort_host(pv.p, pv.length(), (int64_t)block, po.p);
+}
 // ---------------------------------------------------------------- named functions and option formulas per path
 FMJ(jint, functionApply)(JNIEnv* env, jclass, jlong x, jintArray kinds, jlongArray out) {
     Pin<jint> pk(env, kinds, JNI_ABORT);
