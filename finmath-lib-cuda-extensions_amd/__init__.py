@@ -31,6 +31,8 @@ from .analytic import NORMAL_CDF, NORMAL_DENSITY, NORMAL_QUANTILE, NamedFunction
 from .analytic import bachelier_option_value, black_scholes_option_value, option_formula, option_formula_double, option_formula_host
 from .nested import (block_max, block_means, block_min, block_moments, block_moments_host, block_order_statistics, block_order_statistics_host, block_quantile_expectations,
                      block_quantiles, block_sort, block_sort_host, device_nested, repeat_each, tile)
+from .cross_section import (argmax_across, argmin_across, cross_order_statistics_host, cross_select_host, device_cross_order, max_across, median_across, min_across,
+                            order_across, select_across, sort_across)
 from .kernel_regression import (MonteCarloConditionalExpectationKernelRegression, kernel_counts, kernel_density, kernel_local_fit, kernel_moments,
                                 kernel_moments_host, silverman_bandwidth)
 from .differentiable import RandomVariableDifferentiableAAD, RandomVariableDifferentiableAADFactory

@@ -33,6 +33,7 @@ SYMBOLS = [
     "fmhip_function_apply", "fmhip_function_apply_host", "fmhip_option_formula", "fmhip_option_formula_host",
     "fmhip_block_moments", "fmhip_block_moments_host", "fmhip_vec_repeat",
     "fmhip_block_order_statistics", "fmhip_block_order_statistics_host", "fmhip_block_sort", "fmhip_block_sort_host",
+    "fmhip_cross_order_statistics", "fmhip_cross_order_statistics_host", "fmhip_cross_select", "fmhip_cross_select_host",
     "fmhip_kernel_moments", "fmhip_kernel_moments_host",
     "fmhip_program_create", "fmhip_program_release", "fmhip_program_launch_count", "fmhip_program_shape",
     "fmhip_program_run", "fmhip_program_run_into",
@@ -198,6 +199,9 @@ def lib():
         "fmhip_block_order_statistics": [pv, i32, i64, C.POINTER(i64), i32, C.POINTER(i64), C.POINTER(i64), i32, pv],
         "fmhip_block_order_statistics_host": [vp, i64, i64, C.POINTER(i64), i32, C.POINTER(i64), C.POINTER(i64), i32, vp],
         "fmhip_block_sort": [vec, i64, pv], "fmhip_block_sort_host": [vp, i64, i64, vp],
+        "fmhip_cross_order_statistics": [pv, i32, C.POINTER(C.c_int32), i32, i32, pv],
+        "fmhip_cross_order_statistics_host": [C.POINTER(vp), i32, i64, C.POINTER(C.c_int32), i32, i32, C.POINTER(vp)],
+        "fmhip_cross_select": [vec, pv, i32, pv], "fmhip_cross_select_host": [vp, C.POINTER(vp), i32, i64, vp],
         "fmhip_kernel_moments": [vec, C.POINTER(dbl), C.POINTER(dbl), i32, i32, i32, pv, i32, C.POINTER(dbl)],
         "fmhip_kernel_moments_host": [vp, i64, C.POINTER(dbl), C.POINTER(dbl), i32, i32, i32, C.POINTER(vp), i32, C.POINTER(dbl)],
         "fmhip_program_create": [C.POINTER(ProgOp), i32, i32, C.POINTER(C.c_int32), i32, C.POINTER(C.c_int32), i32, pv],

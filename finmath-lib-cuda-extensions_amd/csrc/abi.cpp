@@ -951,6 +951,24 @@ int fmhip_block_sort(fmhip_vec v, int64_t block, fmhip_vec* out) {
     return guarded([&] { Engine::get().block_sort(v, block, out); });
 }
 
+// ---------------------------------------------------------------- order statistics across vectors and the selection behind their index (cross_order_engine.hpp)
+int fmhip_cross_order_statistics_host(const float* const* vs, int n_vs, int64_t n, const int* ranks, int n_ranks, int outputs, float* const* outs) {
+    return host_only([&] { fm::cross_order_statistics_host_checked(vs, n_vs, n, ranks, n_ranks, outputs, outs); });
+}
+int fmhip_cross_select_host(const float* index, const float* const* vs, int n_vs, int64_t n, float* out) {
+    return host_only([&] { fm::cross_select_host_checked(index, vs, n_vs, n, out); });
+}
+int fmhip_cross_order_statistics(const fmhip_vec* vs, int n_vs, const int* ranks, int n_ranks, int outputs, fmhip_vec* outs) {
+    FRONT(cross_order_statistics(vs, n_vs, ranks, n_ranks, outputs, outs));
+    TE_CHECKED_LOCAL(fm::cross_order_check_statistics(vs, n_vs, ranks, n_ranks, outputs, outs), te_operands(0, vs, n_vs, nullptr, 0), L, fmhip_cross_order_statistics(L, n_vs, ranks, n_ranks, outputs, outs));
+    return guarded([&] { Engine::get().cross_order_statistics(vs, n_vs, ranks, n_ranks, outputs, outs); });
+}
+int fmhip_cross_select(fmhip_vec index, const fmhip_vec* vs, int n_vs, fmhip_vec* out) {
+    FRONT(cross_select(index, vs, n_vs, out));
+    TE_CHECKED_LOCAL(fm::cross_order_check_select(index, vs, n_vs, out), te_operands(index, vs, n_vs, nullptr, 0), L, fmhip_cross_select(L[0], L + 1, n_vs, out));
+    return guarded([&] { Engine::get().cross_select(index, vs, n_vs, out); });
+}
+
 // The one call of a caller that values product after product: the engine lock is held for the bookkeeping (graph → launch → commit),
 // NOT while the device computes — other threads record and launch meanwhile.  The moments arrive in a slot of pinned memory of their
 // own; this thread polls its flag, then takes the lock again to copy them out and give the launch's buffers back.

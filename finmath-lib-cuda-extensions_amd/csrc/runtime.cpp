@@ -2782,3 +2782,4 @@ void Engine::profile_read(double* ms_total, int64_t* n) {
 #include "kreg_engine.hpp"             // Engine::kernel_moments_pass: kernel-weighted local moments at a grid of points of a key in one launch
 #include "nested_engine.hpp"           // Engine::block_moments, repeat: the moments of consecutive blocks as new vectors, k inner paths per outer state
 #include "block_order_engine.hpp"      // Engine::block_order_statistics, block_sort: ranks and range means of consecutive blocks as new vectors, the blocks sorted
+#include "cross_order_engine.hpp"      // Engine::cross_order_statistics, cross_select: ranks of the K values of every path as values and slots, the element an index names

@@ -441,6 +441,13 @@ public:
                                 int n_ranges, fmhip_vec* outs);
     void block_sort(fmhip_vec v, int64_t block, fmhip_vec* out);
 
+    // order statistics across vectors (cross_order_engine.hpp): the K = n_vs values of every path sorted by the key of
+    // host/block_order.hpp, ties by slot; of the selected ranks the values and / or the slots (a mask) as new, materialised vectors — values of
+    // all selectors first, then indices; and the element of vs[index[p]] per path, the quiet NaN where the index names no slot.  Arguments are
+    // checked before anything is flushed or launched; outs is written only when the call succeeds.  Elementwise.
+    void cross_order_statistics(const fmhip_vec* vs, int n_vs, const int* ranks, int n_ranks, int outputs, fmhip_vec* outs);
+    void cross_select(fmhip_vec index, const fmhip_vec* vs, int n_vs, fmhip_vec* out);
+
     // kernel regression (kreg_engine.hpp): the kernel-weighted local moments of n_y vectors at n_points points of `key`
     // (host/kernel_regression.hpp), sums_out[n_points][order 0: 1 + n_y, order 1: 3 + 2 n_y], from ONE launch.  Arguments are checked before
     // anything is flushed or launched.
@@ -866,6 +873,12 @@ void block_order_check_sort(fmhip_vec v, int64_t block, const fmhip_vec* out);
 void block_order_statistics_host_checked(const float* v, int64_t n, int64_t block, const int64_t* ranks, int n_ranks, const int64_t* range_from, const int64_t* range_to,
                                          int n_ranges, float* outs);
 void block_sort_host_checked(const float* v, int64_t n, int64_t block, float* out);
+// the same for fmhip_cross_order_statistics / fmhip_cross_select, and the definitions behind their _host twins (cross_order_engine.hpp; the rules
+// are host/cross_order.hpp's): all throw FMHIP_ERR_INVALID_ARGUMENT
+void cross_order_check_statistics(const fmhip_vec* vs, int n_vs, const int* ranks, int n_ranks, int outputs, const fmhip_vec* outs);
+void cross_order_check_select(fmhip_vec index, const fmhip_vec* vs, int n_vs, const fmhip_vec* out);
+void cross_order_statistics_host_checked(const float* const* vs, int n_vs, int64_t n, const int* ranks, int n_ranks, int outputs, float* const* outs);
+void cross_select_host_checked(const float* index, const float* const* vs, int n_vs, int64_t n, float* out);
 // what can be said about the arguments of fmhip_binned_cross_moments / fmhip_binned_evaluate without looking at a vector (binned_engine.hpp; the
 // rules are fmhost::binnedCheck*'s, host/binned_regression.hpp), and the host definitions: all throw FMHIP_ERR_INVALID_ARGUMENT
 void binned_check_moments(fmhip_vec key, const double* bounds, int n_bins, const fmhip_vec* x, int n_x, const fmhip_vec* y, int n_y, const int64_t* counts_out, const double* sums_out);

@@ -1061,6 +1061,31 @@ int block_sort(fmhip_vec v, int64_t block, fmhip_vec* out) {
         produce_per_shard(s, n, 1, out, [&](Worker& w, fmhip_vec* got) { return fmhip_block_sort(w.at(v), block, got); });
     });
 }
+// Order statistics across vectors and the selection behind their index (cross_order_engine.hpp).  Elementwise: every shard runs the call on
+// its block; the new vectors' blocks are the shards' results.
+int cross_order_statistics(const fmhip_vec* vs, int n_vs, const int* ranks, int n_ranks, int outputs, fmhip_vec* outs) {
+    return fronted([&](Shards& s) {
+        cross_order_check_statistics(vs, n_vs, ranks, n_ranks, outputs, outs);
+        const int64_t n = front_size(s, vs, n_vs, "cross order statistics", false);
+        const int n_out = n_ranks * ((outputs & 1) + ((outputs >> 1) & 1));
+        produce_per_shard(s, n, n_out, outs, [&](Worker& w, fmhip_vec* got) {
+            return fmhip_cross_order_statistics(localize(w, vs, n_vs).data(), n_vs, ranks, n_ranks, outputs, got);
+        });
+    });
+}
+int cross_select(fmhip_vec index, const fmhip_vec* vs, int n_vs, fmhip_vec* out) {
+    return fronted([&](Shards& s) {
+        cross_order_check_select(index, vs, n_vs, out);
+        std::vector<fmhip_vec> all; all.reserve((size_t)n_vs + 1);
+        all.push_back(index);
+        all.insert(all.end(), vs, vs + n_vs);
+        const int64_t n = front_size(s, all.data(), (int)all.size(), "cross select", false);
+        produce_per_shard(s, n, 1, out, [&](Worker& w, fmhip_vec* got) {
+            const std::vector<fmhip_vec> l = localize(w, all.data(), (int)all.size());
+            return fmhip_cross_select(l[0], l.data() + 1, n_vs, got);
+        });
+    });
+}
 
 int vec_give_up_values(const fmhip_vec* vectors, int count) {
     return fronted([&](Shards& s) {

@@ -88,6 +88,8 @@ int vec_repeat(fmhip_vec v, int64_t each, int64_t times, fmhip_vec* out);
 int block_order_statistics(const fmhip_vec* vs, int n_vs, int64_t block, const int64_t* ranks, int n_ranks, const int64_t* range_from, const int64_t* range_to,
                            int n_ranges, fmhip_vec* outs);                                             // one shard; more: FMHIP_ERR_UNSUPPORTED
 int block_sort(fmhip_vec v, int64_t block, fmhip_vec* out);
+int cross_order_statistics(const fmhip_vec* vs, int n_vs, const int* ranks, int n_ranks, int outputs, fmhip_vec* outs);      // per shard
+int cross_select(fmhip_vec index, const fmhip_vec* vs, int n_vs, fmhip_vec* out);                                            // per shard
 int kernel_moments(fmhip_vec key, const double* points, const double* bandwidths, int n_points, int kernel, int order, const fmhip_vec* y, int n_y, double* sums_out);      // sums add in shard order
 int polynomial_cross_moments(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const fmhip_vec* y, int n_y, double* sums_out);
 int polynomial_evaluate(const fmhip_vec* states, int n_states, const uint8_t* exponents, int n_terms, const fmhip_vec* extra_x, int n_extra, const double* coefficients, fmhip_vec* out);

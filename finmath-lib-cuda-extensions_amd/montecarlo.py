@@ -516,7 +516,8 @@ def monomial_exponents(n_assets, order):
     return out
 
 
-def bermudan_max_call_mc(brownian_motion, initial_values, risk_free_rate, dividend_yield, volatility, exercise_dates, strike, basis_order=2, one_pass_basis=False):
+def bermudan_max_call_mc(brownian_motion, initial_values, risk_free_rate, dividend_yield, volatility, exercise_dates, strike, basis_order=2, one_pass_basis=False,
+                         ordered_states=False):
     """Value of a Bermudan call on max_i S_i under Black–Scholes by Longstaff–Schwartz backward induction: independent assets, asset i driven
     by factor i of `brownian_motion` (log-Euler, exact for ln S), drift r − δ − σ²/2, all with one dividend yield and one volatility.  States
     are kept at the exercise dates (points of the time discretisation).  The value starts as the last date's discounted payoff; at each
@@ -526,8 +527,13 @@ def bermudan_max_call_mc(brownian_motion, initial_values, risk_free_rate, divide
     exercise date but the last.  Returns (value, standard error).  With one exercise date this is the European max-call on the same paths.
     one_pass_basis=True: the monomials are not built at all — MonteCarloConditionalExpectationPolynomialRegression forms them in registers
     from the scaled states.  The value is then the default's to the last bit wherever the default takes the wide pass
-    (more than 12 basis functions); with 12 or fewer the default's narrow pass adds in another order and the two agree to rounding only."""
+    (more than 12 basis functions); with 12 or fewer the default's narrow pass adds in another order and the two agree to rounding only.
+    ordered_states=True: the scaled states of each exercise date are replaced by their order statistics across the assets, largest first
+    (cross_section.sort_across, one launch per date: DESIGN.md §4.24), before the monomials are formed — the basis of ordered prices of
+    Longstaff–Schwartz, Broadie–Glasserman and Andersen–Broadie, in which the exercise region of a max option is far closer to polynomial —
+    on both routes, and the exercise value takes cross_section.max_across.  The default leaves the values as they were, bit for bit."""
     from .regression import MonteCarloConditionalExpectationPolynomialRegression, MonteCarloConditionalExpectationRegression
+    from .cross_section import max_across, sort_across
     dates = sorted(float(d) for d in exercise_dates)
     if not dates: raise ValueError("no exercise date")
     assets = len(initial_values)
@@ -546,8 +552,10 @@ def bermudan_max_call_mc(brownian_motion, initial_values, risk_free_rate, divide
         if abs(t - dates[len(states)]) <= 1e-12: states.append([x.exp() for x in xs])
 
     def exercise_value(s, date):
-        best = s[0]
-        for other in s[1:]: best = best.floor(other)             # max(best, other)
+        if ordered_states: best = max_across(s)
+        else:
+            best = s[0]
+            for other in s[1:]: best = best.floor(other)         # max(best, other)
         return best.sub(strike).floor(0.0).div(math.exp(risk_free_rate * date))
 
     value = exercise_value(states[-1], dates[-1])
@@ -555,6 +563,7 @@ def bermudan_max_call_mc(brownian_motion, initial_values, risk_free_rate, divide
     exponents = monomial_exponents(assets, basis_order)
     for k in range(len(dates) - 2, -1, -1):
         scaled = [s.div(strike) for s in states[k]]
+        if ordered_states: scaled = sort_across(scaled, descending=True)
         if one_pass_basis:
             continuation = MonteCarloConditionalExpectationPolynomialRegression(scaled, exponents=exponents, one=one).getConditionalExpectation(value)
             exercise = exercise_value(states[k], dates[k])
@@ -573,3 +582,30 @@ def bermudan_max_call_mc(brownian_motion, initial_values, risk_free_rate, divide
         exercise = exercise_value(states[k], dates[k])
         value = exercise.sub(continuation).choose(exercise, value)
     return value.getAverage(), value.getStandardError()
+
+
+def best_of_call_mc(brownian_motion, initial_values, risk_free_rate, dividend_yield, volatility, maturity, strike):
+    """Value of a European call on the best of A assets, max_i S_i(T) − K floored at 0, under Black–Scholes: independent assets, asset i driven
+    by factor i of `brownian_motion` (log-Euler, exact for ln S), all with one dividend yield and one volatility; `maturity` is a point of
+    the time discretisation.  The maximum per path is cross_section.max_across, ONE launch for any number of assets up to 32 (the composed
+    floor chain records A − 1 ops), and argmax_across says which asset it is.  Returns (value, standard error, [the fraction of paths on
+    which asset i is the best performer for i]).  bermudan_max_call_mc(ordered_states=True) with the one exercise date `maturity` gives
+    the same value to the last bit."""
+    from .cross_section import argmax_across, max_across
+    assets = len(initial_values)
+    if assets < 1 or assets > brownian_motion.getNumberOfFactors(): raise ValueError("one factor of the Brownian motion per asset")
+    td = brownian_motion.getTimeDiscretization()
+    xs = [brownian_motion.getRandomVariableForConstant(math.log(float(s0))) for s0 in initial_values]
+    drift = risk_free_rate - dividend_yield - 0.5 * volatility * volatility
+    t, i = td.getTime(0), 0
+    while t < maturity - 1e-12:
+        xs = [x.add(drift * td.getTimeStep(i)).addProduct(brownian_motion.getBrownianIncrement(i, a), volatility) for a, x in enumerate(xs)]
+        i += 1
+        t = td.getTime(i)
+    if abs(t - maturity) > 1e-12: raise ValueError("the maturity is not a point of the time discretisation")
+    s = [x.exp() for x in xs]
+    value = max_across(s).sub(strike).floor(0.0).div(math.exp(risk_free_rate * maturity))
+    best = argmax_across(s)
+    # asset i is the best where the index equals i: (best − i)² is 0 there and at least 1 elsewhere
+    shares = [best.sub(float(a)).squared().cap(1.0).mult(-1.0).add(1.0).getAverage() for a in range(assets)]
+    return value.getAverage(), value.getStandardError(), shares

@@ -610,6 +610,36 @@ int fmhip_block_order_statistics_host(const float* v, int64_t n, int64_t block, 
 int fmhip_block_sort(fmhip_vec v, int64_t block, fmhip_vec* out);
 int fmhip_block_sort_host(const float* v, int64_t n, int64_t block, float* out);                                        /* the DEFINITION; no device */
 
+/* Order statistics ACROSS vectors, per path: the largest, second largest, r-th largest of K assets on every path and WHICH
+ * asset it is — best-of, worst-of, rainbow and mountain-range payoffs, the r-th default of a basket, the ordered-price regression basis of a
+ * Bermudan max-call — from one launch, without the vectors leaving the device.  The definition is host/cross_order.hpp, one header for the
+ * host and the device.
+ * K = n_vs = 1 ... 32 vectors of one size n (1 ... 2^31 - 1); the same handle may stand in several slots.  For path p the K pairs
+ *   (key of vs[i][p], i) are sorted ascending by the 32-bit key of fmhip_select_ranks_batch — the order of java.util.Arrays.sort(float[]):
+ *   -0.0 before +0.0, every NaN equal and last — ties by slot i: a stable sort.
+ *   The device's outputs EQUAL the _host calls' bit for bit.
+ * Value of rank r (0 <= r < K): out[p] = the r-th smallest of the path's K values, one of them bit for bit; a position in the NaN tail gives
+ *   the quiet NaN 0x7fc00000.  Index of rank r: out[p] = the slot i of that pair as a float (exact: at most 31).
+ * fmhip_cross_order_statistics: n_ranks = 1 ... 32 selectors, duplicates allowed; outputs is a mask of FMHIP_CROSS_VALUES and
+ *   FMHIP_CROSS_INDICES.  outs receives new, materialised vectors of n elements: the values of all selectors (if asked for), then the indices.
+ *   An output depends on the path's K values and on r alone: not on n, the other selectors, the mask, the launch, or where the path sits.
+ * fmhip_cross_select: *out = a new, materialised vector, out[p] = vs[j][p] bit for bit where index[p] is an integer j in [0, K), and the quiet
+ *   NaN 0x7fc00000 for every other index[p] (a fraction, a negative, a value >= K, a NaN, an infinity): what carries a payload behind an index
+ *   output.  The index is range-checked before it picks a vector: no index faults.
+ * The _host calls are the DEFINITION over host float arrays (vs[i], outs[o]: n floats each); they need no device.
+ * Everything is checked on the host before anything is flushed or launched: a count outside its limits, a rank outside [0, K), a mask
+ * outside 1 ... 3, a NULL pointer, a handle of 0 -> FMHIP_ERR_INVALID_ARGUMENT; vectors of different sizes -> FMHIP_ERR_SIZE_MISMATCH;
+ * FMHIP_ERR_INVALID_HANDLE.  A refusal leaves outs untouched and no vector behind.  A build without the kernel answers
+ * FMHIP_ERR_UNSUPPORTED; it never falls back.  Elementwise: per shard with a device list, local to the rank under a communicator. */
+#define FMHIP_CROSS_VALUES 1
+#define FMHIP_CROSS_INDICES 2
+int fmhip_cross_order_statistics(const fmhip_vec* vs, int n_vs, const int* ranks, int n_ranks, int outputs, fmhip_vec* outs);
+    /* outs[j], then outs[n_ranks + j] with both bits: new vectors of size n */
+int fmhip_cross_order_statistics_host(const float* const* vs, int n_vs, int64_t n, const int* ranks, int n_ranks, int outputs,
+                                      float* const* outs);                                                /* the DEFINITION; no device */
+int fmhip_cross_select(fmhip_vec index, const fmhip_vec* vs, int n_vs, fmhip_vec* out);
+int fmhip_cross_select_host(const float* index, const float* const* vs, int n_vs, int64_t n, float* out);  /* the DEFINITION; no device */
+
 /* Kernel regression on the device: kernel-weighted LOCAL MOMENTS of up to four vectors at a grid of points of a key vector
  * in one pass — E[y | x = p_q] as a curve: the inner step of the particle method for local-stochastic-volatility calibration
  * (E[v_t | S_t = S] at every time step), kernel density estimates, smooth exercise boundaries, exposure profiles — without the vectors

@@ -142,6 +142,15 @@ final class Native {
 	static native int blockSort(long v, long block, long[] out);
 	/** The definition of blockSort over a host array. */
 	static native int blockSortHost(float[] v, long block, float[] out);
+	// ---- order statistics across vectors: the ranks of the K values of every path as values and as slots, and the element an index names
+	/** outs = new vectors of n elements: for every selector ranks[j] (0 ... K - 1, duplicates allowed) the ranks[j]-th smallest of vs[0][p] ... vs[K-1][p] (the order of Arrays.sort(float[]), ties by slot) if outputs has bit 1, then the slot it came from as a float if outputs has bit 2; K = vs.length = 1 ... 32, 1 ... 32 selectors; the bits are those of crossOrderStatisticsHost. */
+	static native int crossOrderStatistics(long[] vs, int[] ranks, int outputs, long[] outs);
+	/** The definition of crossOrderStatistics over host arrays: vsColumns holds nVs columns of n floats, outColumns one column of n floats per output. */
+	static native int crossOrderStatisticsHost(float[] vsColumns, int nVs, int[] ranks, int outputs, float[] outColumns);
+	/** out[0] = a new vector: out[p] = vs[j][p] bit for bit where index[p] is an integer j in [0, vs.length), the quiet NaN for every other index[p]. */
+	static native int crossSelect(long index, long[] vs, long[] out);
+	/** The definition of crossSelect over host arrays: vsColumns holds nVs columns of index.length floats. */
+	static native int crossSelectHost(float[] index, float[] vsColumns, int nVs, float[] out);
 	// ---- kernel regression: kernel-weighted local moments of up to 4 vectors at up to 256 points of a key from one launch
 	/** sumsOut[points.length][order 0: 1 + y.length; order 1: 3 + 2 y.length]: per point the fp64 sums [w, w*y...] or [w, w*d, w*d*d, w*y..., w*d*y...] over its members (lower &lt; key &lt; upper); kernel 0 uniform, 1 triangular, 2 Epanechnikov, 3 quartic, 4 triweight. */
 	static native int kernelMoments(long key, double[] points, double[] bandwidths, int kernel, int order, long[] y, double[] sumsOut);

@@ -412,6 +412,52 @@ FMJ(jint, blockSortHost)(JNIEnv* env, jclass, jfloatArray v, jlong block, jfloat
     if (!pv.p || !po.p || po.length() < pv.length()) return FMHIP_ERR_INVALID_ARGUMENT;
     return fmhip_block_sort_host(pv.p, pv.length(), (int64_t)block, po.p);
 }
+// ---------------------------------------------------------------- order statistics across vectors and the selection behind their index
+FMJ(jint, crossOrderStatistics)(JNIEnv* env, jclass, jlongArray vs, jintArray ranks, jint outputs, jlongArray outs) {
+    Pin<jlong> pv(env, vs, JNI_ABORT); Pin<jint> pr(env, ranks, JNI_ABORT);
+    const int64_t nv = pv.p ? pv.length() : 0, nr = pr.p ? pr.length() : 0;
+    if (nv < 1 || nv > 32 || nr < 1 || nr > 32 || outputs < 1 || outputs > 3 || !outs) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int total = (int)(nr * ((outputs & 1) + ((outputs >> 1) & 1)));
+    if (env->GetArrayLength(outs) < total) return FMHIP_ERR_INVALID_ARGUMENT;
+    int r[32];
+    for (int64_t j = 0; j < nr; ++j) r[j] = (int)pr.p[j];
+    fmhip_vec h[64] = { 0 };
+    const int st = fmhip_cross_order_statistics((const fmhip_vec*)pv.p, (int)nv, r, (int)nr, (int)outputs, h);
+    if (st == FMHIP_OK) { jlong o[64]; for (int k = 0; k < total; ++k) o[k] = (jlong)h[k]; env->SetLongArrayRegion(outs, 0, (jsize)total, o); }
+    return st;
+}
+FMJ(jint, crossOrderStatisticsHost)(JNIEnv* env, jclass, jfloatArray vsColumns, jint nVs, jintArray ranks, jint outputs, jfloatArray outColumns) {
+    Pin<jfloat> pv(env, vsColumns, JNI_ABORT); Pin<jint> pr(env, ranks, JNI_ABORT); Pin<jfloat> po(env, outColumns);
+    const int64_t nr = pr.p ? pr.length() : 0;
+    if (!pv.p || !po.p || nVs < 1 || nVs > 32 || nr < 1 || nr > 32 || outputs < 1 || outputs > 3 || pv.length() % nVs != 0) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int64_t n = pv.length() / nVs;
+    const int total = (int)(nr * ((outputs & 1) + ((outputs >> 1) & 1)));
+    if ((int64_t)po.length() < (int64_t)total * n) return FMHIP_ERR_INVALID_ARGUMENT;
+    int r[32];
+    for (int64_t j = 0; j < nr; ++j) r[j] = (int)pr.p[j];
+    const float* in[32]; float* columns[64];
+    for (int i = 0; i < nVs; ++i) in[i] = pv.p + (int64_t)i * n;
+    for (int k = 0; k < total; ++k) columns[k] = po.p + (int64_t)k * n;
+    return fmhip_cross_order_statistics_host(in, (int)nVs, n, r, (int)nr, (int)outputs, columns);
+}
+FMJ(jint, crossSelect)(JNIEnv* env, jclass, jlong index, jlongArray vs, jlongArray out) {
+    Pin<jlong> pv(env, vs, JNI_ABORT);
+    const int64_t nv = pv.p ? pv.length() : 0;
+    if (nv < 1 || nv > 32 || !out || env->GetArrayLength(out) < 1) return FMHIP_ERR_INVALID_ARGUMENT;
+    fmhip_vec h = 0;
+    const int st = fmhip_cross_select(index, (const fmhip_vec*)pv.p, (int)nv, &h);
+    if (st == FMHIP_OK) set1(env, out, (jlong)h);
+    return st;
+}
+FMJ(jint, crossSelectHost)(JNIEnv* env, jclass, jfloatArray index, jfloatArray vsColumns, jint nVs, jfloatArray out) {
+    Pin<jfloat> pi(env, index, JNI_ABORT); Pin<jfloat> pv(env, vsColumns, JNI_ABORT); Pin<jfloat> po(env, out);
+    if (!pi.p || !pv.p || !po.p || nVs < 1 || nVs > 32) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int64_t n = pi.length();
+    if ((int64_t)pv.length() != n * nVs || (int64_t)po.length() < n) return FMHIP_ERR_INVALID_ARGUMENT;
+    const float* in[32];
+    for (int i = 0; i < nVs; ++i) in[i] = pv.p + (int64_t)i * n;
+    return fmhip_cross_select_host(pi.p, in, (int)nVs, n, po.p);
+}
 // ---------------------------------------------------------------- named functions and option formulas per path
 FMJ(jint, functionApply)(JNIEnv* env, jclass, jlong x, jintArray kinds, jlongArray out) {
     Pin<jint> pk(env, kinds, JNI_ABORT);
