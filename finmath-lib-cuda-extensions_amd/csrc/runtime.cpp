@@ -1365,8 +1365,7 @@ void Engine::expand_replicas(ReplicaGroup* g) {
     clone_nodes_impl(graph, ep_graph, ep_leaf, g->n_copies,
                      [&](int j, size_t i) -> Node* { const Node* src = graph[i]; return src->rep_root >= 0 ? g->copy_roots[(size_t)j * g->n_roots + src->rep_root] : nullptr; },
                      [&](int j, size_t i) { return g->id_base + (int64_t)j * g->graph_size + graph[i]->rep_index; },
-                     [&](int j, size_t i, const Node* src) { const int32_t sl = g->scalar_slot[(size_t)src->rep_index];
-                                                             return (sl >= 0 && !g->scalars.empty()) ? g->scalars[(size_t)j * g->n_scalars + sl] : src->scalar; },
+                     [&](int j, size_t i, const Node* src) { return g->scalar_of(j, src->rep_index, src->scalar); },
                      [&](int j, int i) { return g->leaf_to[(size_t)j * n_map + i]; }, node_pool_, copies, [this](Node* nd) { pend_insert(nd); });
     for (Node* nd : graph) { nd->rep_id = 0; nd->rep_index = -1; }   // (rep_root is cleared with the roots below)
     std::vector<int> all;
@@ -1465,18 +1464,18 @@ struct Engine::Dag {
     bool rep_uniform = true, rep_any = false;
 };
 
-// Linearise the pending expressions below `roots` into ONE program (roots may share intermediates: they become
-// several outputs of the same launch).  Returns false when it cannot run as one launch.
-bool Engine::build_dag(const std::vector<Node*>& roots, Dag& dag) {
-    HostTimer timer(HostProfile::BUILD_DAG);
-    dag.roots = roots;
-    const uint64_t ep = ++epoch_;                   // nodes with mark == ep have been visited by THIS build
+// The walk build_dag and build_big share: the pending nodes below `roots` in post-order (operands before users) into d.order, every
+// node's scratch fields reset (tmp_id = -1; tmp_uses = its consumers inside the walk), the replica stamps of the pending nodes summed
+// up in d.rep_id / rep_uniform / rep_any.  on_leaf(c): a materialised operand met for the first time.  Gives up (false) as soon as the
+// order is longer than max_ops: too large for whoever asked, no point in walking the rest.
+template <class D, class Leaf> bool Engine::walk_pending(const std::vector<Node*>& roots, D& d, size_t max_ops, Leaf&& on_leaf) {
+    const uint64_t ep = ++epoch_;                   // nodes with mark == ep have been visited by THIS walk
     std::vector<std::pair<Node*, int>> stack;
     auto visit = [&](Node* nd) { nd->mark = ep; nd->tmp_id = -1; nd->tmp_uses = 0; };
     bool first_pending = true;
     auto note_rep = [&](const Node* nd) {
-        if (first_pending) { dag.rep_id = nd->rep_id; first_pending = false; } else if (nd->rep_id != dag.rep_id) dag.rep_uniform = false;
-        dag.rep_any |= nd->rep_id != 0;
+        if (first_pending) { d.rep_id = nd->rep_id; first_pending = false; } else if (nd->rep_id != d.rep_id) d.rep_uniform = false;
+        d.rep_any |= nd->rep_id != 0;
     };
     for (Node* root : roots) {
         if (root->mark == ep) continue;             // a root that is also an operand of an earlier root
@@ -1487,20 +1486,21 @@ bool Engine::build_dag(const std::vector<Node*>& roots, Dag& dag) {
             Node* nd = top.first;
             if (top.second < nd->n_in) {
                 Node* c = nd->in[top.second++];
-                if (c->buf) {
-                    if (c->mark != ep) { visit(c); dag.leaves.push_back(c); }
-                } else {
-                    if (c->mark != ep) { visit(c); note_rep(c); stack.push_back({ c, 0 }); }
-                    c->tmp_uses++;
-                }
-            } else {
-                dag.order.push_back(nd);
-                stack.pop_back();
-                if ((int)dag.order.size() > FM_MAX_OPS) return false;       // too large for one launch: no point in walking the rest
-            }
+                if (c->buf) { if (c->mark != ep) { visit(c); on_leaf(c); } }
+                else { if (c->mark != ep) { visit(c); note_rep(c); stack.push_back({ c, 0 }); } c->tmp_uses++; }
+            } else { d.order.push_back(nd); stack.pop_back(); if (d.order.size() > max_ops) return false; }
         }
     }
-    if ((int)dag.leaves.size() > FM_MAX_IN || (int)dag.order.size() > FM_MAX_OPS) return false;
+    return true;
+}
+
+// Linearise the pending expressions below `roots` into ONE program (roots may share intermediates: they become
+// several outputs of the same launch).  Returns false when it cannot run as one launch.
+bool Engine::build_dag(const std::vector<Node*>& roots, Dag& dag) {
+    HostTimer timer(HostProfile::BUILD_DAG);
+    dag.roots = roots;
+    if (!walk_pending(roots, dag, (size_t)FM_MAX_OPS, [&](Node* c) { dag.leaves.push_back(c); })) return false;
+    if ((int)dag.leaves.size() > FM_MAX_IN) return false;
     const int n_in = (int)dag.leaves.size();
     for (int k = 0; k < n_in; ++k) dag.leaves[k]->tmp_id = k;
     // structural signature: a short byte string (opcode + operand ids per op); scalars and vectors are NOT part of it
@@ -1673,81 +1673,89 @@ struct Engine::BigDag {
     bool described() const { return copy >= 0; }
     Buffer* value(size_t pos) const { return described() ? temp[pos] : order[pos]->buf; }        // nullptr: not computed (yet)
     float scalar_at(size_t pos) const {
-        if (!described()) return (float)order[pos]->scalar;
-        const ReplicaGroup* g = view->g;
-        const int32_t slot = g->scalar_slot[(size_t)view->rep_index[pos]];
-        return (float)((slot >= 0 && !g->scalars.empty()) ? g->scalars[(size_t)copy * g->n_scalars + slot] : view->scalar[pos]);
+        return (float)(described() ? view->g->scalar_of(copy, view->rep_index[pos], view->scalar[pos]) : order[pos]->scalar);
     }
 };
 
-bool Engine::build_big(const std::vector<Node*>& roots, BigDag& big) {
-    HostTimer timer(HostProfile::BUILD_BIG);
-    big.roots = roots;
-    const uint64_t ep = ++epoch_;
-    std::vector<std::pair<Node*, int>> stack;
-    int n_leaves = 0;
-    std::vector<Node*>& leaves = big.leaves;
-    leaves.clear();
-    auto visit = [&](Node* nd) { nd->mark = ep; nd->tmp_id = -1; nd->tmp_uses = 0; };
-    bool first_pending = true;
-    auto note_rep = [&](const Node* nd) {
-        if (first_pending) { big.rep_id = nd->rep_id; first_pending = false; } else if (nd->rep_id != big.rep_id) big.rep_uniform = false;
-        big.rep_any |= nd->rep_id != 0;
-    };
-    big.n = roots[0]->n;
-    big.discard_root = roots.size() == 1 && roots[0]->discard && roots[0]->refs_int == 0;
-    for (Node* root : roots) {
-        if (root->mark == ep) continue;
-        visit(root); note_rep(root);
-        stack.push_back({ root, 0 });
-        while (!stack.empty()) {
-            auto& top = stack.back();
-            Node* nd = top.first;
-            if (top.second < nd->n_in) {
-                Node* c = nd->in[top.second++];
-                if (c->buf) { if (c->mark != ep) { visit(c); c->tmp_id = --n_leaves; leaves.push_back(c); } }      // leaves: -1, -2, …
-                else { if (c->mark != ep) { visit(c); note_rep(c); stack.push_back({ c, 0 }); } c->tmp_uses++; }
-            } else { big.order.push_back(nd); stack.pop_back(); }
-        }
+// The STRUCTURAL signature of a list of nodes: per node its opcode and its operands (positions in the list; leaves by order of
+// discovery) as one 8-byte word whose top byte — the flag: is the value stored? — stays zero; and its hash, as it is written (until
+// round 4 the flag was part of it, so that a shape's identity depended on who held handles when the flush came).
+static uint64_t sign_structure(const std::vector<Node*>& order, int math_mode, std::string& sig) {
+    const size_t count = order.size();
+    sig.resize(1 + count * 8);
+    sig[0] = (char)('0' + math_mode);
+    char* p = &sig[1];
+    uint64_t h = 0x9e3779b97f4a7c15ull ^ (uint64_t)math_mode;
+    for (size_t i = 0; i < count; ++i, p += 8) {
+        const Node* nd = order[i];
+        uint64_t w = (uint64_t)(uint8_t)nd->opcode;
+        for (int k = 0; k < 3; ++k) w |= (uint64_t)(uint16_t)(k < nd->n_in ? nd->in[k]->tmp_id + 32768 : 0) << (8 + 16 * k);
+        std::memcpy(p, &w, 8);
+        h = (h ^ w) * 0xff51afd7ed558ccdull; h ^= h >> 32;
     }
-    if (big.order.size() > 60000) return false;
-    // The STRUCTURAL signature of a list of nodes: per node its opcode and its operands (positions in the list; leaves by order of
-    // discovery) as one 8-byte word whose top byte — the flag: is the value stored? — stays zero; and its hash, as it is written (until
-    // round 4 the flag was part of it, so that a shape's identity depended on who held handles when the flush came).
-    auto sign = [&](const std::vector<Node*>& order, std::string& sig) {
-        const size_t count = order.size();
-        sig.resize(1 + count * 8);
-        sig[0] = (char)('0' + math_mode);
-        char* p = &sig[1];
-        uint64_t h = 0x9e3779b97f4a7c15ull ^ (uint64_t)math_mode;
-        for (size_t i = 0; i < count; ++i, p += 8) {
-            const Node* nd = order[i];
-            uint64_t w = (uint64_t)(uint8_t)nd->opcode;
-            for (int k = 0; k < 3; ++k) w |= (uint64_t)(uint16_t)(k < nd->n_in ? nd->in[k]->tmp_id + 32768 : 0) << (8 + 16 * k);
-            std::memcpy(p, &w, 8);
-            h = (h ^ w) * 0xff51afd7ed558ccdull; h ^= h >> 32;
-        }
-        return h;
-    };
+    return h;
+}
+
+// the shape's full signature and hash: the structure with the flags in the top byte of every word
+static void sign_flags(const std::string& structural, uint64_t structural_hash, const std::vector<char>& fl, std::string& sig, uint64_t& hash) {
+    sig = structural;
+    uint64_t h = structural_hash;
+    for (size_t i = 0; i < fl.size(); ++i) { sig[1 + i * 8 + 7] = fl[i]; h = (h ^ ((uint64_t)(uint8_t)fl[i] + (i << 8))) * 0xff51afd7ed558ccdull; h ^= h >> 29; }
+    hash = h;
+}
+
+// Schedule: the DFS post-order of the walk is A topological order, but not a good one to cut into launches — it lists a whole
+// dependency chain (e.g. the running factor sum over all LIBOR components of an Euler step) before the values that merely
+// consume one link of it, so every link would have to be materialised for a later segment.  List scheduling, consumers
+// first: emit a ready node, then prefer the nodes it has just made ready (LIFO; ties by creation order).  A value is
+// consumed as soon as possible after it is produced: short live ranges, few values crossing a cut — two Euler steps
+// recorded back to back come out component by component, both steps of a component adjacent, and the intermediate state
+// never touches HBM.  Every op computes the same thing in any topological order: results are unchanged bit for bit.
+// PURE: reads the nodes of `order` (tmp_id = position in it), changes nothing; returns scheduled position → position in the walk.
+static std::vector<uint32_t> list_schedule(const std::vector<Node*>& order) {
+    const size_t m = order.size();
+    std::vector<uint32_t> perm;
+    perm.reserve(m);
+    std::vector<int> indeg(m, 0), head(m + 1, 0);
+    for (size_t i = 0; i < m; ++i)
+        for (int k = 0; k < order[i]->n_in; ++k) { const Node* c = order[i]->in[k]; if (!c->buf) { indeg[i]++; head[(size_t)c->tmp_id + 1]++; } }
+    for (size_t i = 0; i < m; ++i) head[i + 1] += head[i];
+    std::vector<int> consumers((size_t)head[m]), fill(head.begin(), head.end() - 1);
+    for (size_t i = 0; i < m; ++i)
+        for (int k = 0; k < order[i]->n_in; ++k) { const Node* c = order[i]->in[k]; if (!c->buf) consumers[(size_t)fill[(size_t)c->tmp_id]++] = (int)i; }
+    auto by_id_desc = [&](int a, int b) { return order[(size_t)a]->id > order[(size_t)b]->id; };
+    std::vector<int> stack_ready;
+    for (size_t i = 0; i < m; ++i) if (indeg[i] == 0) stack_ready.push_back((int)i);
+    std::sort(stack_ready.begin(), stack_ready.end(), by_id_desc);             // oldest node on top
+    std::vector<int> fresh;
+    while (!stack_ready.empty()) {
+        const int i = stack_ready.back(); stack_ready.pop_back();
+        perm.push_back((uint32_t)i);
+        fresh.clear();
+        for (int q = head[(size_t)i]; q < head[(size_t)i + 1]; ++q) if (--indeg[(size_t)consumers[(size_t)q]] == 0) fresh.push_back(consumers[(size_t)q]);
+        std::sort(fresh.begin(), fresh.end(), by_id_desc);
+        stack_ready.insert(stack_ready.end(), fresh.begin(), fresh.end());
+    }
+    if (perm.size() != m) { perm.resize(m); for (size_t i = 0; i < m; ++i) perm[i] = (uint32_t)i; }      // (never: the pending graph is acyclic)
+    return perm;
+}
+
+// build_big, step 2 — the order of the walk becomes the scheduled order (every node's tmp_id = its position in it).  A shape seen before
+// (same walk, same operands) is scheduled the way it was then: the schedule is a function of the structure up to ties, and any
+// topological order computes the same values — a caller that asks for one expectation after the other (144 products per objective
+// evaluation, each a graph of 50–250 nodes) pays for the walk and ONE signature, not for the scheduling pass and a second one (≈ 6 →
+// 3 µs per product, all of it time the device waits).  Returns the shape's memo — it also carries what the engine has learnt about the
+// shape's handles (escape policy) and the variants it has used —, nullptr for a component too large to remember.
+Engine::ScheduleMemo* Engine::schedule_big(BigDag& big) {
+    static const size_t MEMO_MAX_NODES = 16384;               // (a memo holds ≈ 30 bytes per node)
     const size_t m = big.order.size();
     for (size_t i = 0; i < m; ++i) big.order[i]->tmp_id = (int)i;
-    // A shape seen before (same walk, same operands) is scheduled the way it was then: the schedule below is a function of the structure
-    // up to ties, and any topological order computes the same values — a caller that asks for one expectation after the other (144
-    // products per objective evaluation, each a graph of 50–250 nodes) pays for the walk and ONE signature, not for the scheduling pass
-    // and a second one (≈ 6 → 3 µs per product, all of it time the device waits).  The memo also carries what the engine has learnt about
-    // the shape's handles (escape policy).
-    static const size_t MEMO_MAX_NODES = 16384;               // (a memo holds ≈ 30 bytes per node)
-    const bool memoise = m <= MEMO_MAX_NODES;
     ScheduleMemo* memo = nullptr;
-    if (memoise) {
-        const uint64_t walk_hash = sign(big.order, walk_sig_);
+    if (m <= MEMO_MAX_NODES) {
+        const uint64_t walk_hash = sign_structure(big.order, math_mode, walk_sig_);
         auto known = schedule_cache_.find(walk_hash);
-        if (known != schedule_cache_.end() && known->second.walk_sig == walk_sig_) {
-            memo = &known->second;
-            std::vector<Node*> scheduled(m);
-            for (size_t i = 0; i < m; ++i) { scheduled[i] = big.order[memo->perm[i]]; scheduled[i]->tmp_id = (int)i; }
-            big.order.swap(scheduled);
-        } else {
+        if (known != schedule_cache_.end() && known->second.walk_sig == walk_sig_) memo = &known->second;
+        else {
             if (schedule_cache_.size() >= 4096 || schedule_cache_bytes_ > (size_t(128) << 20)) { schedule_cache_.clear(); schedule_cache_bytes_ = 0; policy_reset(); }     // (shapes that never repeat: start again)
             memo = &schedule_cache_[walk_hash];
             schedule_cache_bytes_ -= std::min(schedule_cache_bytes_, memo->walk_sig.size() * 3 + memo->perm.size() * 6);       // (the same walk hash again: replaced)
@@ -1755,51 +1763,28 @@ bool Engine::build_big(const std::vector<Node*>& roots, BigDag& big) {
             memo->walk_sig = walk_sig_;
         }
     }
-    if (!memo || memo->perm.empty()) {
-        // Schedule: the DFS post-order above is A topological order, but not a good one to cut into launches — it lists a whole
-        // dependency chain (e.g. the running factor sum over all LIBOR components of an Euler step) before the values that merely
-        // consume one link of it, so every link would have to be materialised for a later segment.  List scheduling, consumers
-        // first: emit a ready node, then prefer the nodes it has just made ready (LIFO; ties by creation order).  A value is
-        // consumed as soon as possible after it is produced: short live ranges, few values crossing a cut — two Euler steps
-        // recorded back to back come out component by component, both steps of a component adjacent, and the intermediate state
-        // never touches HBM.  Every op computes the same thing in any topological order: results are unchanged bit for bit.
-        std::vector<uint32_t> perm(m);
-        {
-            std::vector<int> indeg(m, 0), head(m + 1, 0);
-            for (size_t i = 0; i < m; ++i)
-                for (int k = 0; k < big.order[i]->n_in; ++k) { Node* c = big.order[i]->in[k]; if (!c->buf) { indeg[i]++; head[(size_t)c->tmp_id + 1]++; } }
-            for (size_t i = 0; i < m; ++i) head[i + 1] += head[i];
-            std::vector<int> consumers((size_t)head[m]), fill(head.begin(), head.end() - 1);
-            for (size_t i = 0; i < m; ++i)
-                for (int k = 0; k < big.order[i]->n_in; ++k) { Node* c = big.order[i]->in[k]; if (!c->buf) consumers[(size_t)fill[(size_t)c->tmp_id]++] = (int)i; }
-            auto by_id_desc = [&](int a, int b) { return big.order[(size_t)a]->id > big.order[(size_t)b]->id; };
-            std::vector<int> stack_ready;
-            for (size_t i = 0; i < m; ++i) if (indeg[i] == 0) stack_ready.push_back((int)i);
-            std::sort(stack_ready.begin(), stack_ready.end(), by_id_desc);             // oldest node on top
-            std::vector<Node*> scheduled;
-            scheduled.reserve(m);
-            std::vector<int> fresh;
-            while (!stack_ready.empty()) {
-                const int i = stack_ready.back(); stack_ready.pop_back();
-                scheduled.push_back(big.order[(size_t)i]);
-                fresh.clear();
-                for (int q = head[(size_t)i]; q < head[(size_t)i + 1]; ++q) if (--indeg[(size_t)consumers[(size_t)q]] == 0) fresh.push_back(consumers[(size_t)q]);
-                std::sort(fresh.begin(), fresh.end(), by_id_desc);
-                stack_ready.insert(stack_ready.end(), fresh.begin(), fresh.end());
-            }
-            if (scheduled.size() == m) big.order.swap(scheduled);                      // (always: the pending graph is acyclic)
-            for (size_t i = 0; i < m; ++i) perm[i] = (uint32_t)big.order[i]->tmp_id;     // scheduled position → position in the walk
-        }
-        for (size_t i = 0; i < m; ++i) big.order[i]->tmp_id = (int)i;
-        if (memo) {
-            memo->perm.swap(perm);
-            memo->sched_hash = sign(big.order, memo->sched_sig);
-            schedule_cache_bytes_ += memo->walk_sig.size() * 3 + memo->perm.size() * 6;
-        }
+    const bool known = memo && !memo->perm.empty();
+    std::vector<uint32_t> fresh;
+    if (!known) fresh = list_schedule(big.order);
+    const std::vector<uint32_t>& perm = known ? memo->perm : fresh;
+    std::vector<Node*> scheduled(m);
+    for (size_t i = 0; i < m; ++i) { scheduled[i] = big.order[perm[i]]; scheduled[i]->tmp_id = (int)i; }
+    big.order.swap(scheduled);
+    if (memo && !known) {
+        memo->perm.swap(fresh);
+        memo->sched_hash = sign_structure(big.order, math_mode, memo->sched_sig);
+        schedule_cache_bytes_ += memo->walk_sig.size() * 3 + memo->perm.size() * 6;
     }
-    // Which values are stored.  A consumer outside the component, or being a root of this walk, is a fact; a value whose only claim is a
-    // live handle is the escape policy's decision ('?' → 'X' stored and watched / 'D' deferred); 'd': deferred earlier, stays so.
-    std::vector<char> flags(m);
+    return memo;
+}
+
+// build_big, step 3 — which values are stored.  A consumer outside the component, or being a root of this walk, is a fact; a value whose
+// only claim is a live handle is the escape policy's decision ('?' → 'x' stored and watched / '.' deferred); 'd': deferred earlier,
+// stays so.  facts: the flags before the policy spoke ('x' / 'm' there are facts; '?' and 'd' the policy's to decide, '.' nobody's).
+// Changes policy state only (policy_bind / policy_store), no node.
+void Engine::store_flags(const BigDag& big, ScheduleMemo* memo, std::vector<char>& flags, std::vector<char>& facts) {
+    const size_t m = big.order.size();
+    flags.resize(m);
     size_t n_cand = 0, interior = 0;
     for (size_t i = 0; i < m; ++i) {
         const Node* nd = big.order[i];
@@ -1816,88 +1801,110 @@ bool Engine::build_big(const std::vector<Node*>& roots, BigDag& big) {
         interior += nd->tmp_uses > 0 ? 1 : 0;
         flags[i] = f;
     }
-    const std::vector<char> facts = flags;                     // 'x' / 'm' here are facts; '?' and 'd' the policy's to decide, '.' nobody's
+    facts = flags;
     if (n_cand) {
         policy_bind(memo->policy, m);
         const bool optimistic = n_cand * 2 > interior;
         for (size_t i = 0; i < m; ++i) if (flags[i] == '?') flags[i] = policy_store(memo->policy, i, optimistic) ? 'x' : '.';
     }
     for (size_t i = 0; i < m; ++i) if (flags[i] == 'd') flags[i] = '.';
-    // the shape's full signature and hash: the structure with the flags in the top byte of every word
-    auto finish = [&](const std::string& structural, uint64_t structural_hash, const std::vector<char>& fl, std::string& sig, uint64_t& hash) {
-        sig = structural;
-        uint64_t h = structural_hash;
-        for (size_t i = 0; i < m; ++i) { sig[1 + i * 8 + 7] = fl[i]; h = (h ^ ((uint64_t)(uint8_t)fl[i] + (i << 8))) * 0xff51afd7ed558ccdull; h ^= h >> 29; }
-        hash = h;
+}
+
+// The hysteresis of choose_variant: the wanted variant `at` of the shape, or — while its kernel is still being compiled — the variant
+// used last whose kernel exists and which stores every value somebody outside the component needs (the facts).  A wanted variant that
+// was never planned is planned here (its loop is looked for, its kernels are asked for; nothing runs).
+size_t Engine::variant_with_kernel(BigDag& big, ScheduleMemo& memo, size_t at, const std::vector<char>& flags, const std::vector<char>& facts) {
+    std::vector<ScheduleMemo::Variant>& vs = memo.variants;
+    const size_t m = big.order.size();
+    auto plan_of = [&](const ScheduleMemo::Variant& v) -> BigPlan* { auto it = plan_cache_.find(v.hash); return it != plan_cache_.end() && it->second.sig == v.sig ? &it->second : nullptr; };
+    auto kernel_there = [&](const BigPlan& p) {
+        if (!p.rolled.present) return true;
+        const std::shared_ptr<JitSlot>& slot = p.rolled.peeled.present ? p.rolled.peeled.jit : p.rolled.jit;
+        return slot && slot->state.load(std::memory_order_acquire) != JitSlot::QUEUED;
     };
-    if (memo) {
-        // The variants of this shape — the same structure, other values stored — the engine has used: the escape policy moves a shape
-        // through a few of them while it learns (stored for observation → left unstored → stored after all), and each needs its own loop
-        // kernel.  A variant whose kernel is still being compiled does not run as segments on the interpreter meanwhile: the launch goes
-        // through the variant used last whose kernel exists, as long as that one stores every value somebody outside the component needs
-        // (the facts) — a value stored without need costs a write, one left unstored against the policy's wish is computed from its recipe
-        // if somebody asks (and watched all the same).  The wanted variant's kernel is asked for now, and used once it is there.
-        std::vector<ScheduleMemo::Variant>& vs = memo->variants;
-        size_t at = vs.size();
-        for (size_t v = 0; v < vs.size(); ++v) if (vs[v].flags == flags) { at = v; break; }
-        if (at == vs.size()) {
-            if (vs.size() >= 6) { vs.erase(vs.begin() + 1, vs.begin() + 2); at = vs.size(); }     // (the oldest but the first — the one that stores everything it was asked to at first sight)
-            vs.emplace_back();
-            vs[at].flags = flags;
-            finish(memo->sched_sig, memo->sched_hash, flags, vs[at].sig, vs[at].hash);
-            schedule_cache_bytes_ += vs[at].sig.size() + m;
-        }
-        size_t use = at;
-        static const bool HYSTERESIS = knob_on("FMHIP_VARIANT_HYSTERESIS");
-        if (HYSTERESIS && ESCAPE_POLICY && vs.size() > 1 && jit_mode == FMHIP_JIT_AUTO) {
-            auto plan_of = [&](const ScheduleMemo::Variant& v) -> BigPlan* { auto it = plan_cache_.find(v.hash); return it != plan_cache_.end() && it->second.sig == v.sig ? &it->second : nullptr; };
-            auto kernel_there = [&](const BigPlan& p) {
-                if (!p.rolled.present) return true;
-                const std::shared_ptr<JitSlot>& slot = p.rolled.peeled.present ? p.rolled.peeled.jit : p.rolled.jit;
-                return slot && slot->state.load(std::memory_order_acquire) != JitSlot::QUEUED;
-            };
-            BigPlan* wanted = plan_of(vs[at]);
-            if (!wanted && plan_cache_.count(vs[at].hash) == 0) {          // never planned: its loop is looked for and its kernels are asked for, nothing runs
-                big.escapes.resize(m);
-                for (size_t i = 0; i < m; ++i) big.escapes[i] = flags[i] == 'x' ? 1 : 0;
-                BigPlan np;
-                plan_loop(np, big);
-                np.sig = vs[at].sig; np.discards_root = big.discard_root; np.segs_missing = true;
-                wanted = &(plan_cache_[vs[at].hash] = std::move(np));
-            }
-            if (wanted && !kernel_there(*wanted)) {
-                for (size_t back = memo->last_variant < vs.size() ? memo->last_variant : 0, tried = 0; tried < vs.size(); ++tried, back = (back + 1) % vs.size()) {
-                    if (back == at) continue;
-                    const ScheduleMemo::Variant& v = vs[back];
-                    bool legal = true;
-                    for (size_t i = 0; i < m && legal; ++i) legal = (facts[i] != 'x' || v.flags[i] == 'x') && ((facts[i] == 'm') == (v.flags[i] == 'm'));
-                    if (!legal) continue;
-                    const BigPlan* p = plan_of(v);
-                    if (p && kernel_there(*p)) { use = back; break; }
-                }
-            }
-        }
-        memo->last_variant = use;
-        if (use != at) flags = vs[use].flags;
-        big.sig = vs[use].sig; big.hash = vs[use].hash;
-    } else {
-        std::string structural;
-        const uint64_t h = sign(big.order, structural);
-        finish(structural, h, flags, big.sig, big.hash);
+    BigPlan* wanted = plan_of(vs[at]);
+    if (!wanted && plan_cache_.count(vs[at].hash) == 0) {
+        big.escapes.resize(m);
+        for (size_t i = 0; i < m; ++i) big.escapes[i] = flags[i] == 'x' ? 1 : 0;
+        BigPlan np;
+        plan_loop(np, big);
+        np.sig = vs[at].sig; np.discards_root = big.discard_root; np.segs_missing = true;
+        wanted = &(plan_cache_[vs[at].hash] = std::move(np));
     }
-    // the nodes learn what has been decided: a handle whose value is stored is watched (a use makes its position a stored one for good), one
-    // whose value is not is deferred; whatever lives on as somebody's operand only leaves the pending list — no flush starts from it
+    if (!wanted || kernel_there(*wanted)) return at;
+    for (size_t back = memo.last_variant < vs.size() ? memo.last_variant : 0, tried = 0; tried < vs.size(); ++tried, back = (back + 1) % vs.size()) {
+        if (back == at) continue;
+        const ScheduleMemo::Variant& v = vs[back];
+        bool legal = true;
+        for (size_t i = 0; i < m && legal; ++i) legal = (facts[i] != 'x' || v.flags[i] == 'x') && ((facts[i] == 'm') == (v.flags[i] == 'm'));
+        if (!legal) continue;
+        const BigPlan* p = plan_of(v);
+        if (p && kernel_there(*p)) return back;
+    }
+    return at;
+}
+
+// build_big, step 4 — the shape's signature and hash (big.sig / big.hash) for the flags decided, through the VARIANTS of this shape —
+// the same structure, other values stored — the engine has used: the escape policy moves a shape through a few of them while it learns
+// (stored for observation → left unstored → stored after all), and each needs its own loop kernel.  A variant whose kernel is still
+// being compiled does not run as segments on the interpreter meanwhile: the launch goes through the variant used last whose kernel
+// exists (variant_with_kernel; `flags` become that variant's) — a value stored without need costs a write, one left unstored against the
+// policy's wish is computed from its recipe if somebody asks (and watched all the same).  The wanted variant's kernel is asked for now,
+// and used once it is there.  Changes the memo (variants, last_variant, the accounting of its bytes) and the plan cache, no node.
+void Engine::choose_variant(BigDag& big, ScheduleMemo* memo, std::vector<char>& flags, const std::vector<char>& facts) {
+    if (!memo) { std::string structural; const uint64_t h = sign_structure(big.order, math_mode, structural); sign_flags(structural, h, flags, big.sig, big.hash); return; }
+    std::vector<ScheduleMemo::Variant>& vs = memo->variants;
+    size_t at = vs.size();
+    for (size_t v = 0; v < vs.size(); ++v) if (vs[v].flags == flags) { at = v; break; }
+    if (at == vs.size()) {
+        if (vs.size() >= 6) { vs.erase(vs.begin() + 1, vs.begin() + 2); at = vs.size(); }     // (the oldest but the first — the one that stores everything it was asked to at first sight)
+        vs.emplace_back();
+        vs[at].flags = flags;
+        sign_flags(memo->sched_sig, memo->sched_hash, flags, vs[at].sig, vs[at].hash);
+        schedule_cache_bytes_ += vs[at].sig.size() + big.order.size();
+    }
+    size_t use = at;
+    static const bool HYSTERESIS = knob_on("FMHIP_VARIANT_HYSTERESIS");
+    if (HYSTERESIS && ESCAPE_POLICY && vs.size() > 1 && jit_mode == FMHIP_JIT_AUTO) use = variant_with_kernel(big, *memo, at, flags, facts);
+    memo->last_variant = use;
+    if (use != at) flags = vs[use].flags;
+    big.sig = vs[use].sig; big.hash = vs[use].hash;
+}
+
+// build_big, step 5 — the nodes learn what has been decided (and big.escapes says it per position): a handle whose value is stored is
+// watched (watch_node: a use makes its position a stored one for good), one whose value is not is deferred (defer_node); whatever lives
+// on as somebody's operand only leaves the pending list (pend_erase) — no flush starts from it.
+void Engine::teach_nodes(BigDag& big, ScheduleMemo* memo, const std::vector<char>& flags, const std::vector<char>& facts) {
+    const size_t m = big.order.size();
     big.escapes.resize(m);
     for (size_t i = 0; i < m; ++i) {
         Node* nd = big.order[i];
-        const bool policy_position = facts[i] == '?' || facts[i] == 'd';
-        if (flags[i] == 'x') { if (policy_position && facts[i] == '?') watch_node(nd, memo->policy, i); }
+        if (flags[i] == 'x') { if (facts[i] == '?') watch_node(nd, memo->policy, i); }
         else if (flags[i] == '.') {
             if (nd->refs_ext > 0 && nd->tmp_uses > 0 && nd->refs_int <= nd->tmp_uses) defer_node(nd, facts[i] == '?' ? &memo->policy : nullptr, i);
             else if (!nd->deferred) pend_erase(nd);
         }
         big.escapes[i] = flags[i] == 'x' ? 1 : 0;
     }
+}
+
+// A component that does not fit one launch, ready to be planned and run: walked (step 1: the walk of build_dag; leaves numbered -1,
+// -2, … in tmp_id), scheduled (schedule_big), its stored values decided (store_flags), signed (choose_variant), its nodes told
+// (teach_nodes).  Only the last step touches the pending list.  false: too large even for that.
+bool Engine::build_big(const std::vector<Node*>& roots, BigDag& big) {
+    HostTimer timer(HostProfile::BUILD_BIG);
+    big.roots = roots;
+    big.leaves.clear();
+    big.n = roots[0]->n;
+    big.discard_root = roots.size() == 1 && roots[0]->discard && roots[0]->refs_int == 0;
+    int n_leaves = 0;
+    walk_pending(roots, big, ~size_t(0), [&](Node* c) { c->tmp_id = --n_leaves; big.leaves.push_back(c); });
+    if (big.order.size() > 60000) return false;
+    ScheduleMemo* memo = schedule_big(big);
+    std::vector<char> flags, facts;
+    store_flags(big, memo, flags, facts);
+    choose_variant(big, memo, flags, facts);
+    teach_nodes(big, memo, flags, facts);
     return true;
 }
 
@@ -2121,7 +2128,10 @@ void Engine::run_plan(BigPlan& plan, std::vector<BigDag>& group, ReduceRequest* 
         std::vector<BigDag> described, with_nodes;
         for (BigDag& b : group) (b.described() ? described : with_nodes).push_back(std::move(b));
         if (with_nodes.empty()) throw Error(FMHIP_ERR_PROGRAM_LIMIT, "a group of copies without their original");
-        plan_segments(plan, with_nodes);
+        // (a launch that fails midway leaves no half-written cuts behind: the shape is cut afresh when it comes round again — until the flush
+        // was swept with a failing allocation the partial list stayed, was extended by the next attempt and run twice, and its programs
+        // were released at shutdown without ever having been held)
+        try { plan_segments(plan, with_nodes); } catch (...) { plan.segs.clear(); throw; }
         plan.segs_missing = false;
         for (BigPlan::Seg& seg : plan.segs) seg.prog->refs++;              // the plan holds its programs (pool_purge drops both caches together)
         if (!described.empty()) run_plan(plan, described);
@@ -2237,7 +2247,26 @@ void Engine::plan_segments(BigPlan& plan, std::vector<BigDag>& group) {
     }
 }
 
-struct Engine::SmallGroup { std::vector<Dag> members; Dag proto; const SmallMatch* match = nullptr; std::vector<std::pair<ReplicaGroup*, std::vector<int>>> done; };
+// A launch sequence that executes replicated roots with their copies that exist as a description: the scope guard of the flush, in the
+// spirit of PassOutputs::commit.  It owns the list of what is executed (per description, the roots by index) and ends in one of three
+// ways: finish() — everything ran, the roots are done; dismiss() — the group did not run as a group (its roots go on as leftovers or are
+// computed one by one), the descriptions stay as they are; fail() — also what the destructor does to a guard still open, i.e. on an
+// exception from anywhere in the flush: replicas_after_failure, which leaves a root whose original has NO buffer described — a no-op
+// for a group that has not run at all.
+struct Engine::ReplicaLaunch {
+    Engine* e;
+    std::vector<std::pair<ReplicaGroup*, std::vector<int>>> done;
+    bool open = true;
+    explicit ReplicaLaunch(Engine* engine) : e(engine) {}
+    ReplicaLaunch(ReplicaLaunch&& o) noexcept : e(o.e), done(std::move(o.done)), open(o.open) { o.open = false; }      // (move only)
+    void finish() { if (open) { open = false; for (auto& kv : done) e->replica_roots_done(kv.first, kv.second); } }
+    void dismiss() { open = false; }
+    void fail() { if (open) { open = false; e->replicas_after_failure(done); } }
+    ~ReplicaLaunch() { fail(); }
+};
+
+struct Engine::SmallGroup { std::vector<Dag> members; Dag proto; const SmallMatch* match = nullptr; ReplicaLaunch launch; explicit SmallGroup(Engine* e) : launch(e) {} };
+struct Engine::BigGroups { std::vector<std::vector<BigDag>> members; std::vector<ReplicaLaunch> launches; };       // per group of one shape: its members and its guard
 
 void Engine::run_big_group(std::vector<BigDag>& group, ReduceRequest* rr) {
     HostTimer timer(HostProfile::RUN_BIG);
@@ -2295,6 +2324,199 @@ void Engine::materialize(const std::vector<Node*>& targets) {
     }
 }
 
+// ---------------------------------------------------------------- the flush (flush_all, below, is a driver over these steps)
+
+// Step 1 — the live pending vectors nobody pending depends on, by id.  Reads the pending list, changes nothing.  false: there is none.
+bool Engine::pending_roots(std::vector<Node*>& roots) {
+    for (Node* nd = pending_head_.pend_next; nd != &pending_head_; nd = nd->pend_next) if (nd->refs_int == 0 && nd->refs_ext > 0 && !nd->discarded) roots.push_back(nd);
+    std::sort(roots.begin(), roots.end(), [](Node* a, Node* b) { return a->id < b->id; });
+    return !roots.empty();
+}
+// … and where there is none: a live pending node, if any (an operand of dead ones)
+Node* Engine::any_live_pending() {
+    for (Node* nd = pending_head_.pend_next; nd != &pending_head_; nd = nd->pend_next) if (nd->refs_ext > 0 && !nd->discarded) return nd;
+    return nullptr;
+}
+
+// Step 2 — the connected components of the pending graph below `roots` (union-find over root indices): per component its roots, the
+// components in the order of their first root.  Uses the nodes' scratch fields (mark, tmp_id), changes nothing else.
+void Engine::pending_components(const std::vector<Node*>& roots, OrderedGroups<int, Node*>& comps) {
+    std::vector<int> parent(roots.size());
+    for (size_t i = 0; i < roots.size(); ++i) parent[i] = (int)i;
+    auto find = [&](int x) { while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; } return x; };
+    const uint64_t ep = ++epoch_;
+    std::vector<Node*> stack;
+    for (size_t i = 0; i < roots.size(); ++i) {
+        stack.push_back(roots[i]);
+        roots[i]->mark = ep; roots[i]->tmp_id = (int)i;
+        while (!stack.empty()) {
+            Node* nd = stack.back(); stack.pop_back();
+            for (int k = 0; k < nd->n_in; ++k) {
+                Node* c = nd->in[k];
+                if (c->buf) continue;
+                if (c->mark == ep) { const int a = find((int)i), b = find(c->tmp_id); if (a != b) parent[b] = a; }
+                else { c->mark = ep; c->tmp_id = (int)i; stack.push_back(c); }
+            }
+        }
+    }
+    for (size_t i = 0; i < roots.size(); ++i) comps[find((int)i)].push_back(roots[i]);
+}
+
+// A component of a replicated graph runs with its copies as further rows — if it still is exactly what was replicated: all its
+// operations belong to ONE live description (rep_id, uniform) and nothing but the replicated roots escapes from it (escapes: per node,
+// nullptr = every node of `nodes` escapes).  Otherwise every description the pending graph below `roots` touches becomes ordinary nodes
+// (expand_replicas_below); true when that changed anything: the round starts again on the larger pending graph (an expansion may
+// release nodes other components were found through).
+bool Engine::expand_unless_whole(uint32_t rep_id, bool uniform, const std::vector<Node*>& nodes, const std::vector<char>* escapes, const std::vector<Node*>& roots) {
+    ReplicaGroup* g = clean_replica_group(rep_id, uniform);
+    for (size_t i = 0; g && i < nodes.size(); ++i) if ((!escapes || (*escapes)[i]) && (nodes[i]->rep_root < 0 || nodes[i]->rep_copy)) g = nullptr;
+    if (g) return false;
+    const size_t before = replicas_.size();
+    expand_replicas_below(roots);
+    return replicas_.size() != before;
+}
+
+// Step 3 — one Dag per component, grouped by structure and vector length (first-seen order); the roots of components that do not fit
+// one launch go to `leftovers`.  build_dag takes interior nodes off the pending list and defers what the escape policy leaves unstored.
+// false: a description was expanded (expand_unless_whole) — the pending graph has grown, the caller starts the round again.
+bool Engine::small_groups(OrderedGroups<int, Node*>& comps, OrderedGroups<std::string, Dag>& groups, std::vector<Node*>& leftovers) {
+    for (std::vector<Node*>& comp : comps.lists) {
+        Dag d;
+        if (!build_dag(comp, d)) { for (Node* r : comp) leftovers.push_back(r); continue; }
+        if (d.rep_any && expand_unless_whole(d.rep_id, d.rep_uniform, d.outs, nullptr, comp)) return false;
+        std::string key = d.sig; key.push_back('#'); key += std::to_string(d.roots[0]->n);
+        groups[key].push_back(std::move(d));
+    }
+    return true;
+}
+
+// What a launch group needs of a component that runs with its described copies: the replicated roots it executes (a BigDag also writes
+// down what its copies need to know once its nodes are gone: the ReplicaView all of them share) …
+std::vector<int> Engine::replicated_roots(Dag& d, ReplicaGroup*) {
+    std::vector<int> roots;
+    for (Node* o : d.outs) roots.push_back(o->rep_root);
+    return roots;
+}
+std::vector<int> Engine::replicated_roots(BigDag& b, ReplicaGroup* g) {
+    auto view = std::make_shared<ReplicaView>();
+    view->g = g;
+    const size_t m = b.order.size();
+    view->rep_index.resize(m); view->rep_root.resize(m); view->scalar.resize(m);
+    std::vector<int> roots;
+    for (size_t i = 0; i < m; ++i) {
+        const Node* nd = b.order[i];
+        view->rep_index[i] = nd->rep_index; view->rep_root[i] = nd->rep_root; view->scalar[i] = nd->scalar;
+        if (nd->rep_root >= 0) roots.push_back(nd->rep_root);
+    }
+    b.view = std::move(view);
+    return roots;
+}
+// … and copy `copy` as a member of its own: the vectors it reads, the root nodes that receive its results, its scalars.
+Engine::Dag Engine::replica_member(const Dag& d, ReplicaGroup* g, int copy) {
+    Dag r;
+    r.leaves.reserve(d.leaves.size());
+    for (Node* l : d.leaves) r.leaves.push_back(g->leaf_of(copy, l));
+    r.outs.reserve(d.outs.size());
+    for (Node* o : d.outs) r.outs.push_back(g->copy_roots[(size_t)copy * g->n_roots + (size_t)o->rep_root]);
+    for (const Node* nd : d.order) if (op_info(nd->opcode).scalar) r.scalars.push_back((float)g->scalar_of(copy, nd->rep_index, nd->scalar));
+    if (r.scalars.empty()) r.scalars.push_back(0.0f);
+    return r;
+}
+Engine::BigDag Engine::replica_member(const BigDag& b, ReplicaGroup* g, int copy) {
+    BigDag r;
+    r.n = b.n; r.view = b.view; r.copy = copy;
+    r.leaves.reserve(b.leaves.size());
+    for (Node* l : b.leaves) r.leaves.push_back(g->leaf_of(copy, l));
+    r.temp.assign(b.order.size(), nullptr);
+    return r;
+}
+
+// The members of a launch group: every component of `originals`, each followed by its copies that exist as a description; the roots
+// they execute are written into the group's guard.
+template <class D> void Engine::members_with_copies(std::vector<D>& originals, std::vector<D>& members, ReplicaLaunch& launch) {
+    for (D& d : originals) {
+        ReplicaGroup* g = d.rep_any ? clean_replica_group(d.rep_id, d.rep_uniform) : nullptr;
+        if (!g) { members.push_back(std::move(d)); continue; }
+        launch.done.push_back({ g, replicated_roots(d, g) });
+        const size_t at = members.size();
+        members.push_back(std::move(d));
+        for (int j = 0; j < g->n_copies; ++j) members.push_back(replica_member(members[at], g, j));
+    }
+}
+
+// The launches of a small group, ≤ 1024 members each.  A part that does not run as one launch after all gives its roots to `leftovers`
+// (they run as large components) or, late (leftovers == nullptr: behind the large components), computes them one by one; the group's
+// descriptions are then left alone (dismiss), otherwise its roots are done (finish).  An exception leaves the guard open.
+void Engine::run_small(SmallGroup& sg, std::vector<Node*>* leftovers) {
+    const size_t max_batch = 1024;
+    bool ran = true;
+    for (size_t off = 0; off < sg.members.size(); off += max_batch) {
+        std::vector<Dag> part(std::make_move_iterator(sg.members.begin() + off), std::make_move_iterator(sg.members.begin() + std::min(sg.members.size(), off + max_batch)));
+        if (run_dags(part, nullptr, nullptr, nullptr, &sg.proto)) continue;
+        ran = false;
+        for (Dag& d : part) for (Node* r : d.roots) { if (leftovers) leftovers->push_back(r); else if (!r->buf) materialize({ r }); }
+    }
+    if (ran) sg.launch.finish(); else sg.launch.dismiss();
+}
+
+// Step 4 — one group of structurally identical components (`g`, consumed) with their described copies: run now, or — a group whose
+// components may be chains of a merged launch (merge_families) — parked in `waiting`, behind the large components.  Commits buffers and
+// dismantles the expressions that ran; an exception closes the group here (its guard is a local), the parked ones are the driver's.
+void Engine::run_small_group(std::vector<Dag>& g, std::vector<SmallGroup>& waiting, std::vector<Node*>& leftovers) {
+    SmallGroup sg(this);
+    sg.proto = g[0];                                          // carries the structure for launches that start with another member
+    sg.match = (MERGE_CHAINS && want_root_moments_ && jit_mode != FMHIP_JIT_OFF) ? match_small(sg.proto) : nullptr;
+    members_with_copies(g, sg.members, sg.launch);
+    if (sg.match) waiting.push_back(std::move(sg)); else run_small(sg, &leftovers);
+}
+
+// The parked groups, late: what merge_families has left of them (nothing: their roots are done).
+void Engine::run_parked(std::vector<SmallGroup>& waiting) {
+    for (SmallGroup& sg : waiting) { if (!sg.members.empty()) run_small(sg, nullptr); else sg.launch.finish(); }
+    waiting.clear();
+}
+
+// Step 5 — the components `leftovers` belong to (they do not fit one launch) as BigDags, grouped by a 64-bit hash of (shape signature,
+// vector length) — the signatures are ~10 KB strings, hashed ONCE in build_big —, first-seen order; then per group its members with
+// their described copies and its guard.  build_big defers and un-pends nodes as build_dag does.  false: a description was expanded.
+bool Engine::big_groups(OrderedGroups<int, Node*>& comps, const std::vector<Node*>& leftovers, BigGroups& big) {
+    std::unordered_map<Node*, size_t> comp_of;                    // root -> component
+    for (size_t c = 0; c < comps.lists.size(); ++c) for (Node* r : comps.lists[c]) comp_of[r] = c;
+    std::unordered_set<size_t> big_comps;
+    std::vector<size_t> big_order;
+    for (Node* r : leftovers) { const size_t c = comp_of[r]; if (big_comps.insert(c).second) big_order.push_back(c); }
+    OrderedGroups<uint64_t, BigDag> shapes;
+    for (size_t c : big_order) {
+        std::vector<Node*> roots;
+        for (Node* r : comps.lists[c]) if (!r->buf) roots.push_back(r);
+        if (roots.empty()) continue;
+        BigDag b;
+        if (!build_big(roots, b)) throw Error(FMHIP_ERR_PROGRAM_LIMIT, "pending expression too large");
+        if (b.rep_any && expand_unless_whole(b.rep_id, b.rep_uniform, b.order, &b.escapes, roots)) return false;
+        uint64_t key = b.hash ^ ((uint64_t)roots[0]->n * 0x9E3779B97F4A7C15ull);
+        std::vector<BigDag>* members = &shapes[key];
+        if (!members->empty() && ((*members)[0].sig != b.sig || (*members)[0].roots[0]->n != roots[0]->n))      // hash collision (practically never): a group of its own
+            members = &shapes[key * 0xff51afd7ed558ccdull + shapes.lists.size() + 1];
+        members->push_back(std::move(b));
+    }
+    big.members.resize(shapes.lists.size());
+    big.launches.reserve(shapes.lists.size());
+    for (size_t k = 0; k < shapes.lists.size(); ++k) { big.launches.emplace_back(this); members_with_copies(shapes.lists[k], big.members[k], big.launches[k]); }
+    return true;
+}
+
+// Step 6 — components of one loop shape that read the same vectors, one a suffix of the other's, as one launch per family size
+// (merge_families: it takes chains out of the big groups and out of the parked small groups); then the parked groups, then the big
+// groups (run_big_group: planned, cut into segments; components of identical shape share the cuts and the launches).
+void Engine::run_big_groups(BigGroups& big, std::vector<SmallGroup>& waiting) {
+    merge_families(big.members, waiting);
+    run_parked(waiting);
+    for (size_t k = 0; k < big.members.size(); ++k) {
+        if (!big.members[k].empty()) run_big_group(big.members[k]);
+        big.launches[k].finish();
+    }
+}
+
 // Execute everything that is pending and still referenced.  Pending results that share intermediates form one
 // connected component and run as ONE multi-output launch; components with identical structure (same ops, different
 // vectors and scalars — e.g. all LIBOR components of an Euler step) are batched as rows of one launch.
@@ -2304,211 +2526,35 @@ void Engine::flush_all() {
     if (late_count() >= late_eager()) drain_late();
     ++flush_seq_;
     for (int round = 0; round < 1000000; ++round) {
-        std::unique_ptr<HostTimer> t_components(new HostTimer(HostProfile::FLUSH_COMPONENTS));
-        std::vector<Node*> roots;                   // live pending vectors nobody pending depends on
-        for (Node* nd = pending_head_.pend_next; nd != &pending_head_; nd = nd->pend_next) if (nd->refs_int == 0 && nd->refs_ext > 0 && !nd->discarded) roots.push_back(nd);
-        if (roots.empty()) {
-            Node* live = nullptr;
-            for (Node* nd = pending_head_.pend_next; nd != &pending_head_; nd = nd->pend_next) if (nd->refs_ext > 0 && !nd->discarded) { live = nd; break; }
-            if (!live) return;
-            materialize({ live });
-            continue;
-        }
-        std::sort(roots.begin(), roots.end(), [](Node* a, Node* b) { return a->id < b->id; });
-        // connected components of the pending graph (union-find over root indices)
-        std::vector<int> parent(roots.size());
-        for (size_t i = 0; i < roots.size(); ++i) parent[i] = (int)i;
-        auto find = [&](int x) { while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; } return x; };
-        const uint64_t ep = ++epoch_;
-        std::vector<Node*> stack;
-        for (size_t i = 0; i < roots.size(); ++i) {
-            stack.push_back(roots[i]);
-            roots[i]->mark = ep; roots[i]->tmp_id = (int)i;
-            while (!stack.empty()) {
-                Node* nd = stack.back(); stack.pop_back();
-                for (int k = 0; k < nd->n_in; ++k) {
-                    Node* c = nd->in[k];
-                    if (c->buf) continue;
-                    if (c->mark == ep) { const int a = find((int)i), b = find(c->tmp_id); if (a != b) parent[b] = a; }
-                    else { c->mark = ep; c->tmp_id = (int)i; stack.push_back(c); }
-                }
-            }
-        }
-        std::unordered_map<int, std::vector<Node*>> comps;
-        std::vector<int> comp_order;
-        for (size_t i = 0; i < roots.size(); ++i) {
-            const int c = find((int)i);
-            if (!comps.count(c)) comp_order.push_back(c);
-            comps[c].push_back(roots[i]);
-        }
-        t_components.reset();
-        // one DAG per component; group identical structures
-        std::unordered_map<std::string, std::vector<Dag>> groups;
-        std::vector<std::string> group_order;
-        std::vector<Node*> leftovers;
-        bool expanded = false;
-        for (int c : comp_order) {
-            Dag d;
-            if (!build_dag(comps[c], d)) { for (Node* r : comps[c]) leftovers.push_back(r); continue; }
-            // A component of a replicated graph runs with its copies as further rows — if it still is exactly what was replicated: all
-            // its operations belong to ONE live description and nothing but the replicated roots escapes from it.  Otherwise every
-            // description it touches becomes ordinary nodes first, and the round starts again on the larger pending graph.
-            if (d.rep_any) {
-                ReplicaGroup* g = clean_replica_group(d.rep_id, d.rep_uniform);
-                for (size_t k = 0; g && k < d.outs.size(); ++k) if (d.outs[k]->rep_root < 0 || d.outs[k]->rep_copy) g = nullptr;
-                if (!g) { const size_t before = replicas_.size(); expand_replicas_below(comps[c]); expanded |= replicas_.size() != before; }
-                if (expanded) break;                                 // (an expansion may release nodes other components were found through)
-            }
-            std::string key = d.sig; key.push_back('#'); key += std::to_string(d.roots[0]->n);
-            if (!groups.count(key)) group_order.push_back(key);
-            groups[key].push_back(std::move(d));
-        }
-        if (expanded) continue;
-        std::vector<SmallGroup> waiting;                                  // groups whose components may be chains of a merged launch (merge_families): run behind the large components
-        auto run_small = [&](std::vector<Dag>& members, const Dag& proto, std::vector<std::pair<ReplicaGroup*, std::vector<int>>>& done, bool late) {
-            const size_t max_batch = 1024;
-            bool ran = true;
-            try {
-                for (size_t off = 0; off < members.size(); off += max_batch) {
-                    std::vector<Dag> part(std::make_move_iterator(members.begin() + off), std::make_move_iterator(members.begin() + std::min(members.size(), off + max_batch)));
-                    if (!run_dags(part, nullptr, nullptr, nullptr, &proto)) {
-                        ran = false;
-                        for (Dag& d : part) for (Node* r : d.roots) { if (late) { if (!r->buf) materialize({ r }); } else leftovers.push_back(r); }
-                    }
-                }
-            } catch (...) { replicas_after_failure(done); throw; }
-            if (ran) for (auto& kv : done) replica_roots_done(kv.first, kv.second);
-        };
-        for (const std::string& key : group_order) {
-            std::vector<Dag>& g = groups[key];
-            // members: every component of this structure, each followed by its copies that exist as a description
-            std::vector<Dag> members;
-            std::vector<std::pair<ReplicaGroup*, std::vector<int>>> done;
-            const Dag proto = g[0];                                   // carries the structure for launches that start with another member
-            const SmallMatch* chain_of = (MERGE_CHAINS && want_root_moments_ && jit_mode != FMHIP_JIT_OFF) ? match_small(proto) : nullptr;
-            for (Dag& d : g) {
-                ReplicaGroup* rg = d.rep_any ? clean_replica_group(d.rep_id, d.rep_uniform) : nullptr;
-                if (rg) {
-                    std::vector<int> roots_done;
-                    for (Node* o : d.outs) roots_done.push_back(o->rep_root);
-                    done.push_back({ rg, std::move(roots_done) });
-                    const size_t at = members.size();
-                    members.push_back(std::move(d));
-                    for (int j = 0; j < rg->n_copies; ++j) members.push_back(replica_dag(members[at], rg, j));
-                } else members.push_back(std::move(d));
-            }
-            if (chain_of) {
-                waiting.emplace_back();
-                SmallGroup& sg = waiting.back();
-                sg.members = std::move(members); sg.proto = proto; sg.match = chain_of; sg.done = std::move(done);
+        std::vector<Node*> roots;
+        OrderedGroups<int, Node*> comps;
+        {
+            HostTimer t_components(HostProfile::FLUSH_COMPONENTS);
+            if (!pending_roots(roots)) {                          // only operands of dead nodes are left: one live one is computed on its own, then again
+                Node* live = any_live_pending();
+                if (!live) return;
+                materialize({ live });
                 continue;
             }
-            run_small(members, proto, done, false);
+            pending_components(roots, comps);
         }
-        // (nothing large in this flush: the waiting groups have no family to join)
-        if (leftovers.empty()) { for (SmallGroup& sg : waiting) run_small(sg.members, sg.proto, sg.done, true); waiting.clear(); }
-        // components that do not fit one launch: cut into segments; components of identical shape share the cuts and the launches
-        if (!leftovers.empty()) {
-            std::unordered_map<Node*, int> comp_of;                      // root -> component key
-            for (int c : comp_order) for (Node* r : comps[c]) comp_of[r] = c;
-            std::unordered_set<int> big_comps;
-            std::vector<int> big_order;
-            for (Node* r : leftovers) { const int c = comp_of[r]; if (big_comps.insert(c).second) big_order.push_back(c); }
-            // grouped by a 64-bit hash of (shape signature, vector length): the signatures are ~10 KB strings, hashed ONCE in build_big
-            std::unordered_map<uint64_t, std::vector<BigDag>> big_groups;
-            std::vector<uint64_t> big_group_order;
-            for (int c : big_order) {
-                std::vector<Node*> roots;
-                for (Node* r : comps[c]) if (!r->buf) roots.push_back(r);
-                if (roots.empty()) continue;
-                BigDag b;
-                if (!build_big(roots, b)) throw Error(FMHIP_ERR_PROGRAM_LIMIT, "pending expression too large");
-                if (b.rep_any) {                                         // as above
-                    ReplicaGroup* g = clean_replica_group(b.rep_id, b.rep_uniform);
-                    for (size_t i = 0; g && i < b.order.size(); ++i) if (b.escapes[i] && (b.order[i]->rep_root < 0 || b.order[i]->rep_copy)) g = nullptr;
-                    if (!g) { const size_t before = replicas_.size(); expand_replicas_below(roots); expanded |= replicas_.size() != before; }
-                    if (expanded) break;
-                }
-                uint64_t key = b.hash ^ ((uint64_t)roots[0]->n * 0x9E3779B97F4A7C15ull);
-                auto& members = big_groups[key];
-                if (members.empty()) big_group_order.push_back(key);
-                else if (members[0].sig != b.sig || members[0].roots[0]->n != roots[0]->n) {       // hash collision (practically never): a group of its own
-                    key = key * 0xff51afd7ed558ccdull + big_group_order.size() + 1;
-                    big_group_order.push_back(key);
-                    big_groups[key].push_back(std::move(b));
-                    continue;
-                }
-                members.push_back(std::move(b));
-            }
-            if (expanded) { for (SmallGroup& sg : waiting) run_small(sg.members, sg.proto, sg.done, true); continue; }
-            // members of every group: its components, each followed by its copies that exist as a description
-            std::vector<std::vector<BigDag>> all_members(big_group_order.size());
-            std::vector<std::vector<std::pair<ReplicaGroup*, std::vector<int>>>> all_done(big_group_order.size());
-            for (size_t ki = 0; ki < big_group_order.size(); ++ki) {
-                std::vector<BigDag>& originals = big_groups[big_group_order[ki]];
-                std::vector<BigDag>& members = all_members[ki];
-                std::vector<std::pair<ReplicaGroup*, std::vector<int>>>& done = all_done[ki];
-                for (BigDag& b : originals) {
-                    ReplicaGroup* rg = b.rep_any ? clean_replica_group(b.rep_id, b.rep_uniform) : nullptr;
-                    if (!rg) { members.push_back(std::move(b)); continue; }
-                    auto view = std::make_shared<ReplicaView>();
-                    view->g = rg;
-                    const size_t m = b.order.size();
-                    view->rep_index.resize(m); view->rep_root.resize(m); view->scalar.resize(m);
-                    std::vector<int> roots_done;
-                    for (size_t i = 0; i < m; ++i) {
-                        const Node* nd = b.order[i];
-                        view->rep_index[i] = nd->rep_index; view->rep_root[i] = nd->rep_root; view->scalar[i] = nd->scalar;
-                        if (nd->rep_root >= 0) roots_done.push_back(nd->rep_root);
-                    }
-                    done.push_back({ rg, std::move(roots_done) });
-                    const size_t n_map = rg->leaf_from.size();
-                    const size_t at = members.size();
-                    members.push_back(std::move(b));
-                    for (int j = 0; j < rg->n_copies; ++j) {
-                        BigDag r;
-                        r.n = members[at].n; r.view = view; r.copy = j;
-                        r.leaves.reserve(members[at].leaves.size());
-                        for (Node* l : members[at].leaves) r.leaves.push_back(l->leaf_rep_id == rg->id ? rg->leaf_to[(size_t)j * n_map + (size_t)l->leaf_rep_index] : l);
-                        r.temp.assign(m, nullptr);
-                        members.push_back(std::move(r));
-                    }
-                }
-            }
-            // components of one loop shape that read the same vectors, one a suffix of the other's: one launch per family size (merge_families)
-            try { merge_families(all_members, waiting); }
-            catch (...) { for (auto& done : all_done) replicas_after_failure(done); for (SmallGroup& sg : waiting) replicas_after_failure(sg.done); throw; }
-            for (SmallGroup& sg : waiting) {
-                if (!sg.members.empty()) run_small(sg.members, sg.proto, sg.done, true);
-                else for (auto& kv : sg.done) replica_roots_done(kv.first, kv.second);
-            }
-            waiting.clear();
-            for (size_t ki = 0; ki < big_group_order.size(); ++ki) {
-                if (!all_members[ki].empty()) {
-                    try { run_big_group(all_members[ki]); }
-                    catch (...) { for (size_t kj = ki; kj < big_group_order.size(); ++kj) replicas_after_failure(all_done[kj]); throw; }
-                }
-                for (auto& kv : all_done[ki]) replica_roots_done(kv.first, kv.second);
-            }
+        OrderedGroups<std::string, Dag> small;
+        std::vector<Node*> leftovers;
+        if (!small_groups(comps, small, leftovers)) continue;     // a description was expanded: again, on the larger pending graph
+        std::vector<SmallGroup> waiting;                           // groups parked behind the large components (run_small_group)
+        BigGroups big;
+        try {
+            for (std::vector<Dag>& g : small.lists) run_small_group(g, waiting, leftovers);
+            if (leftovers.empty()) { run_parked(waiting); continue; }                             // nothing large in this flush: the parked groups have no family to join
+            if (!big_groups(comps, leftovers, big)) { run_parked(waiting); continue; }            // expanded: again
+            run_big_groups(big, waiting);
+        } catch (...) {
+            // every group still in flight is closed, in this order: the big groups as they were to run, then the parked ones
+            for (ReplicaLaunch& l : big.launches) l.fail();
+            for (SmallGroup& sg : waiting) sg.launch.fail();
+            throw;
         }
     }
-}
-
-// A copy of the component `d` that exists as a description: the vectors it reads, the root nodes that receive its results, its scalars.
-Engine::Dag Engine::replica_dag(const Dag& d, ReplicaGroup* g, int copy) {
-    Dag r;
-    const size_t n_map = g->leaf_from.size();
-    r.leaves.reserve(d.leaves.size());
-    for (Node* l : d.leaves) r.leaves.push_back(l->leaf_rep_id == g->id ? g->leaf_to[(size_t)copy * n_map + (size_t)l->leaf_rep_index] : l);
-    r.outs.reserve(d.outs.size());
-    for (Node* o : d.outs) r.outs.push_back(g->copy_roots[(size_t)copy * g->n_roots + (size_t)o->rep_root]);
-    for (const Node* nd : d.order)
-        if (op_info(nd->opcode).scalar) {
-            const int32_t slot = g->scalar_slot[(size_t)nd->rep_index];
-            r.scalars.push_back((float)((slot >= 0 && !g->scalars.empty()) ? g->scalars[(size_t)copy * g->n_scalars + slot] : nd->scalar));
-        }
-    if (r.scalars.empty()) r.scalars.push_back(0.0f);
-    return r;
 }
 
 // ---------------------------------------------------------------- explicit programs

@@ -133,6 +133,13 @@ struct ReplicaGroup {
     std::vector<double> scalars;                // [copy][n_scalars]; empty = the original's
     std::vector<Node*> copy_roots;              // [copy][root]: pending nodes without an expression (each holds one refs_int), nullptr for a shared vector
     int remaining = 0;                          // roots not executed yet
+    // the copy arithmetic, in one place: the vector copy j reads where the original reads l, and copy j's scalar operand of the operation
+    // with recording index i (fallback = the original's: copies without a scalar list, operations without a slot)
+    Node* leaf_of(int copy, Node* l) const { return l->leaf_rep_id == id ? leaf_to[(size_t)copy * leaf_from.size() + (size_t)l->leaf_rep_index] : l; }
+    double scalar_of(int copy, int32_t i, double fallback) const {
+        const int32_t slot = scalar_slot[(size_t)i];
+        return slot >= 0 && !scalars.empty() ? scalars[(size_t)copy * n_scalars + slot] : fallback;
+    }
 };
 
 // ---------------------------------------------------------------- compiled programs
@@ -631,8 +638,11 @@ private:
             std::vector<uint32_t> final_pos;                            // positions whose value of the LAST iteration is stored behind the loop
         } rolled;
     };
+    // build_big: walk_pending (shared with build_dag) → schedule_big (list_schedule, or the shape's memo) → store_flags → choose_variant
+    // (variant_with_kernel: its hysteresis) → teach_nodes; only the last touches the pending list
     bool build_big(const std::vector<Node*>& roots, BigDag& big);
-    // build_big: how a shape (the signature of the walk) was scheduled when it was first seen
+    template <class D, class Leaf> bool walk_pending(const std::vector<Node*>& roots, D& d, size_t max_ops, Leaf&& on_leaf);
+    // how a shape (the signature of the walk) was scheduled when it was first seen
     // (signatures here are STRUCTURAL — opcodes and operands, never who holds a handle: the same memo serves a caller that frees its
     // temporaries at the end of the statement and one whose garbage collector frees them a hundred milliseconds later.)  The flags — which
     // values are stored — are decided per occurrence (escape policy); the signature and hash that go with the flags seen last are kept.
@@ -645,6 +655,11 @@ private:
     std::unordered_map<uint64_t, ScheduleMemo> schedule_cache_;
     size_t schedule_cache_bytes_ = 0;
     std::string walk_sig_;
+    ScheduleMemo* schedule_big(BigDag& big);
+    void store_flags(const BigDag& big, ScheduleMemo* memo, std::vector<char>& flags, std::vector<char>& facts);
+    void choose_variant(BigDag& big, ScheduleMemo* memo, std::vector<char>& flags, const std::vector<char>& facts);
+    size_t variant_with_kernel(BigDag& big, ScheduleMemo& memo, size_t at, const std::vector<char>& flags, const std::vector<char>& facts);
+    void teach_nodes(BigDag& big, ScheduleMemo* memo, const std::vector<char>& flags, const std::vector<char>& facts);
     // ---- escape policy: which values of a fused launch are STORED.
     // A value somebody outside the component needs (a pending consumer elsewhere, a root of the flush) is stored — that is a fact.  A value
     // whose only claim to storage is a live HANDLE is a guess about the caller's future: under a garbage-collected caller (the JVM the
@@ -801,7 +816,31 @@ private:
     // reduce_shift != nullptr (one DAG only): the root is ALSO reduced in the same launch — {Σ, Σ(x-shift)², min, max} into host_moments / dev_moments
     bool run_dags_plain(std::vector<Dag>& dags, const Dag* proto);
     bool run_dags(std::vector<Dag>& dags, const double* reduce_shift = nullptr, fmhip_moments* host_moments = nullptr, void* dev_moments = nullptr, const Dag* proto = nullptr);
-    Dag replica_dag(const Dag& d, ReplicaGroup* g, int copy);
+    // ---- the steps of flush_all (runtime.cpp: "the flush"), in the order a round takes them
+    // key → list of T, iterated in first-seen order of the keys (lists; a reference into it does not survive the next new key)
+    template <class K, class T> struct OrderedGroups {
+        std::unordered_map<K, size_t> index; std::vector<std::vector<T>> lists;
+        std::vector<T>& operator[](const K& key) { auto it = index.find(key); if (it == index.end()) { it = index.emplace(key, lists.size()).first; lists.emplace_back(); } return lists[it->second]; }
+    };
+    struct ReplicaLaunch;                                         // scope guard: the replicated roots a launch sequence executes are done, left alone, or closed after a failure
+    struct BigGroups;
+    bool pending_roots(std::vector<Node*>& roots);
+    Node* any_live_pending();
+    void pending_components(const std::vector<Node*>& roots, OrderedGroups<int, Node*>& comps);
+    bool small_groups(OrderedGroups<int, Node*>& comps, OrderedGroups<std::string, Dag>& groups, std::vector<Node*>& leftovers);
+    void run_small_group(std::vector<Dag>& g, std::vector<SmallGroup>& waiting, std::vector<Node*>& leftovers);
+    void run_small(SmallGroup& sg, std::vector<Node*>* leftovers);
+    void run_parked(std::vector<SmallGroup>& waiting);
+    bool big_groups(OrderedGroups<int, Node*>& comps, const std::vector<Node*>& leftovers, BigGroups& big);
+    void run_big_groups(BigGroups& big, std::vector<SmallGroup>& waiting);
+    // is a component still exactly what was replicated?  otherwise the descriptions it touches are expanded (true: the round starts again)
+    bool expand_unless_whole(uint32_t rep_id, bool uniform, const std::vector<Node*>& nodes, const std::vector<char>* escapes, const std::vector<Node*>& roots);
+    // a component followed by its described copies, as members of one launch group — for a Dag and for a BigDag
+    template <class D> void members_with_copies(std::vector<D>& originals, std::vector<D>& members, ReplicaLaunch& launch);
+    std::vector<int> replicated_roots(Dag& d, ReplicaGroup* g);
+    std::vector<int> replicated_roots(BigDag& b, ReplicaGroup* g);
+    Dag replica_member(const Dag& d, ReplicaGroup* g, int copy);
+    BigDag replica_member(const BigDag& b, ReplicaGroup* g, int copy);
     ReplicaGroup* clean_replica_group(uint32_t rep_id, bool uniform) const { if (!rep_id || !uniform) return nullptr; auto it = replicas_.find(rep_id); return it == replicas_.end() ? nullptr : it->second; }
 };
 

@@ -1,7 +1,8 @@
 // drive.cpp — drives the engine's host runtime through its C-ABI on the TEST-ONLY null device (null_hip.cpp) under the sanitizers:
 // the graph shapes of the GPU tests — record / flush / clone / expand / release in the orders of tests/test_gpu_replicas.py, long
 // chains through segments, rolled and peeled plans, expectations taken along, values given up, tickets begun and ended out of order,
-// the row-table ring and the moments arena wrapping at tiny sizes, a failing allocation in the middle of a replicated launch, eight
+// the row-table ring and the moments arena wrapping at tiny sizes, a failing allocation in the middle of a replicated launch and anywhere
+// in a flush of several replicated groups, eight
 // threads as tests/test_gpu_threads.py, shutdown and re-initialisation.  Nothing is computed: statuses are checked, the sanitizers do
 // the rest.   usage: drive [scenario …]   (none = all)
 #include <atomic>
@@ -323,6 +324,54 @@ static void scenario_failure() {
     OK(fmhip_flush());
 }
 
+// FMHIP_TEST_FAIL_ALLOC_AT is set by the caller (without it: the counting run that says where the flush's allocations are).  ONE flush
+// that holds, each with copies that exist as a description, two distinct shapes too long for one launch (segments: 150 and 200 methods,
+// 3 and 2 copies) and the two-root graph of `failure` (3 copies): an allocation that fails in any of its launches must leave every group
+// of copies closed — whichever group it belonged to, and whichever had run or was still to run.
+static void scenario_failure_big() {
+    OK(fmhip_set_fusion(1, nullptr));
+    OK(fmhip_set_jit(FMHIP_JIT_OFF, nullptr));
+    const int64_t n = 64;
+    // (an operand that is substituted belongs to ONE live description: each graph has its own)
+    std::vector<V> xa, xb, xs;
+    for (int j = 0; j < 4; ++j) { xa.push_back(filled(n, 1.0 + 0.01 * j)); xb.push_back(filled(n, 2.0 + 0.01 * j)); xs.push_back(filled(n, 3.0 + 0.01 * j)); }
+    V y = filled(n, 0.5), z = filled(n, 0.75);
+    OK(fmhip_fusion_hold(1, nullptr));
+    auto chain = [&](V x, int methods, int pattern) {
+        V cur = s1(FMHIP_OP_ADD_S, x, 1.0);
+        for (int k = 1; k < methods; ++k) {
+            V nx = 0;
+            if (pattern == 0) nx = k % 3 == 0 ? b2(FMHIP_OP_MULT, cur, y) : k % 3 == 1 ? s2(FMHIP_OP_ADDPRODUCT_VS, cur, z, 0.5) : u1(FMHIP_OP_ABS, cur);
+            else nx = k % 4 == 0 ? s2(FMHIP_OP_DISCOUNT, cur, y, 0.25) : k % 4 == 1 ? s1(FMHIP_OP_MULT_S, cur, 1.01) : k % 4 == 2 ? b2(FMHIP_OP_ADD, cur, z) : s1(FMHIP_OP_FLOOR_S, cur, 0.0);
+            rel(cur);
+            cur = nx;
+        }
+        return cur;
+    };
+    V a = chain(xa[0], 150, 0), b = chain(xb[0], 200, 1);
+    V t = s2(FMHIP_OP_ACCRUE, xs[0], y, 0.5), u = s1(FMHIP_OP_ADD_S, t, 1.0), w = b2(FMHIP_OP_MULT, u, y);
+    rel(u);
+    V small[2] = { t, w };
+    std::vector<V> out(3 + 2 + 3 * 2);
+    OK(fmhip_graph_clone(&a, 1, 3, &xa[0], &xa[1], 1, nullptr, 0, &out[0]));
+    OK(fmhip_graph_clone(&b, 1, 2, &xb[0], &xb[1], 1, nullptr, 0, &out[3]));
+    OK(fmhip_graph_clone(small, 2, 3, &xs[0], &xs[1], 1, nullptr, 0, &out[5]));
+    OK(fmhip_fusion_hold(0, nullptr));
+    fmhip_pool_stats_t before, after;
+    OK(fmhip_pool_stats(&before));
+    const int st = fmhip_flush();
+    OK(fmhip_pool_stats(&after));
+    if (st != FMHIP_OK && st != FMHIP_ERR_OUT_OF_MEMORY) std::abort();
+    int lost = 0;
+    std::vector<float> h((size_t)n);
+    for (V v : out) { const int r = fmhip_vec_read_float(v, h.data(), n); if (r != FMHIP_OK && r != FMHIP_ERR_INVALID_ARGUMENT && r != FMHIP_ERR_OUT_OF_MEMORY) std::abort(); lost += r == FMHIP_ERR_INVALID_ARGUMENT; }
+    for (V v : { a, b, t, w }) { const int r = fmhip_vec_read_float(v, h.data(), n); if (r != FMHIP_OK && r != FMHIP_ERR_OUT_OF_MEMORY) std::abort(); }
+    std::printf("failure_big: %lld allocations before the flush, %lld in it, flush status %d, %d copies lost\n", (long long)(before.n_alloc_hits + before.n_alloc_misses),
+                (long long)(after.n_alloc_hits + after.n_alloc_misses - before.n_alloc_hits - before.n_alloc_misses), st, lost);
+    rel(out); rel(a); rel(b); rel(t); rel(w); rel(xa); rel(xb); rel(xs); rel(y); rel(z);
+    OK(fmhip_flush());
+}
+
 // cost of a recorded method on the caller's side (and of its replay on the shards): not a sanitizer scenario — build with -O2, no sanitizer
 static void scenario_speed() {
     OK(fmhip_set_fusion(1, nullptr));
@@ -538,10 +587,10 @@ static void scenario_collective() {
 int main(int argc, char** argv) {
     struct Scenario { const char* name; void (*run)(); };
     const Scenario all[] = { { "basic", scenario_basic }, { "replicas", scenario_replicas }, { "expectations", scenario_expectations },
-                             { "programs", scenario_programs_and_steps }, { "threads", scenario_threads }, { "shared", scenario_shared }, { "failure", scenario_failure }, { "speed", scenario_speed }, { "lagging", scenario_lagging }, { "oom", scenario_oom }, { "collective", scenario_collective } };
+                             { "programs", scenario_programs_and_steps }, { "threads", scenario_threads }, { "shared", scenario_shared }, { "failure", scenario_failure }, { "failure_big", scenario_failure_big }, { "speed", scenario_speed }, { "lagging", scenario_lagging }, { "oom", scenario_oom }, { "collective", scenario_collective } };
     std::vector<std::string> wanted;
     for (int i = 1; i < argc; ++i) wanted.push_back(argv[i]);
-    const bool only_failure = wanted.size() == 1 && wanted[0] == "failure";      // (the hook counts the allocations of the whole process: one cycle)
+    const bool only_failure = wanted.size() == 1 && (wanted[0] == "failure" || wanted[0] == "failure_big");      // (the hook counts the allocations of the whole process: one cycle)
     for (int cycle = 0; cycle < (only_failure ? 1 : 2); ++cycle) {                  // twice: shutdown and re-initialisation in between
         // FMNULL_DEVICES=N: the same scenarios behind a device list of N shards (sharded.cpp: one engine and one worker thread per shard)
         const int n_devices = std::getenv("FMNULL_DEVICES") ? std::atoi(std::getenv("FMNULL_DEVICES")) : 1;
@@ -554,7 +603,7 @@ int main(int argc, char** argv) {
         // FMNULL_THREAD_ENGINES=1: an engine per caller thread (fmhip_set_thread_engines) — the scenarios' threads record side by side
         if (n_devices <= 1 && std::getenv("FMNULL_THREAD_ENGINES")) { int was = -1; OK(fmhip_set_thread_engines(1, &was)); if (was != 0) std::abort(); }
         for (const Scenario& s : all) {
-            bool run = wanted.empty() ? (std::strcmp(s.name, "failure") != 0 && std::strcmp(s.name, "speed") != 0 && std::strcmp(s.name, "oom") != 0) : false;
+            bool run = wanted.empty() ? (std::strcmp(s.name, "failure") != 0 && std::strcmp(s.name, "failure_big") != 0 && std::strcmp(s.name, "speed") != 0 && std::strcmp(s.name, "oom") != 0) : false;
             for (const std::string& w : wanted) run |= w == s.name;
             if (!run) continue;
             s.run();

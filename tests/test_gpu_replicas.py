@@ -288,3 +288,91 @@ def test_a_failure_between_the_parts_of_a_replicated_launch_never_yields_a_wrong
         else:
             assert out["lost"] == 0
     assert seen_failure >= 2, "the sweep must hit the flush at least twice"
+
+
+MIX_N = 300                                     # neither a multiple of 4 nor of a tile
+
+
+def mix_chain_a(x, y, z, methods=150):
+    cur = x.v1s1("ADD_S", 1.0)
+    for k in range(1, methods):
+        cur = cur.v2s0("MULT", y) if k % 3 == 0 else cur.v2s1("ADDPRODUCT_VS", z, 0.5) if k % 3 == 1 else cur.v1s0("ABS")
+    return [cur]
+
+
+def mix_chain_b(x, y, z, methods=200):
+    cur = x.v1s1("ADD_S", 1.0)
+    for k in range(1, methods):
+        cur = (cur.v2s1("DISCOUNT", y, 0.25) if k % 4 == 0 else cur.v1s1("MULT_S", 1.01) if k % 4 == 1 else
+               cur.v2s0("ADD", z) if k % 4 == 2 else cur.v1s1("FLOOR_S", 0.0))
+    return [cur]
+
+
+def mix_small(x, y, z):
+    t = x.v2s1("ACCRUE", y, 0.5)
+    return [t, t.v1s1("ADD_S", 1.0).v2s0("MULT", y)]
+
+
+MIX = ((mix_chain_a, 3), (mix_chain_b, 2), (mix_small, 3))
+
+
+def test_one_flush_of_two_long_shapes_and_a_small_graph_each_with_described_copies(gpu):
+    """ONE flush holds two distinct shapes too long for one launch (150 and 200 methods, 3 and 2 copies), a two-root graph that fits
+    one (3 copies) — every copy a description — and one unrelated expression, at n = 300.  With the specialised tier (compiled on the
+    caller's thread; the flush takes the moments of all roots along, so groups may be parked behind the large components) and on the
+    interpreter, every original and every copy has the bits of the same methods executed one by one with fusion off, and the pool is
+    back where it was once the handles are gone.  On the interpreter the flush straight from the plans is 11 launches (one per
+    segment of either long shape — 4 and 5 —, one for the small group, one for the unrelated expression): measured with this test
+    body on commit 6e398ab, before the flush was taken apart into named steps."""
+    rng = np.random.default_rng(23)
+    prev_fusion = gpu.set_fusion(True)
+    prev_jit = gpu.set_jit(gpu.JIT_SYNC)
+    try:
+        y = gpu.DeviceVector.from_host(rng.uniform(0.9, 1.1, MIX_N).astype(np.float32))
+        z = gpu.DeviceVector.from_host(rng.uniform(-0.05, 0.05, MIX_N).astype(np.float32))
+        q = gpu.DeviceVector.from_host(rng.uniform(-1.0, 1.0, MIX_N).astype(np.float32))
+        xs = [[gpu.DeviceVector.from_host(rng.uniform(0.5, 1.5, MIX_N).astype(np.float32)) for _ in range(copies + 1)] for _, copies in MIX]
+        gpu.set_fusion(False)
+        want = [[[bits(r) for r in chain(x, y, z)] for x in row] for (chain, _), row in zip(MIX, xs)]
+        want_single = bits(q.v1s0("EXP").v1s1("MULT_S", 2.0))
+        gpu.set_fusion(True)
+        gpu.flush()
+        st = gpu.pool_stats()
+        live0, bytes0 = st.n_live_vectors, st.bytes_in_use
+
+        def once(with_moments):
+            with gpu.holding():
+                originals = [chain(row[0], y, z) for (chain, _), row in zip(MIX, xs)]
+                clones = [gpu.graph_clone(roots, copies, leaf_from=[row[0]], leaf_to=[[v] for v in row[1:]]) for roots, (_, copies), row in zip(originals, MIX, xs)]
+                single = q.v1s0("EXP").v1s1("MULT_S", 2.0)
+            before = gpu.pool_stats().n_kernel_launches
+            if with_moments:
+                handles = [r for roots in originals for r in roots] + [r for group in clones for copy in group for r in copy] + [single]
+                gpu.reduce_moments_batch_end(gpu.reduce_moments_batch_begin(handles), len(handles))
+                del handles
+            gpu.flush()
+            launches = gpu.pool_stats().n_kernel_launches - before
+            for g in range(len(MIX)):
+                for k, r in enumerate(originals[g]):
+                    assert (bits(r) == want[g][0][k]).all(), ("original", g, k)
+                for j, copy in enumerate(clones[g]):
+                    for k, r in enumerate(copy):
+                        assert (bits(r) == want[g][j + 1][k]).all(), ("copy", g, j, k)
+            assert (bits(single) == want_single).all()
+            return launches
+
+        once(True)
+        gpu.flush()
+        st = gpu.pool_stats()
+        assert (st.n_live_vectors, st.bytes_in_use) == (live0, bytes0)
+        gpu.set_jit(gpu.JIT_OFF)
+        first = once(False)                                 # cuts the segments where the specialised tier never needed them
+        second = once(False)                                # straight from the plans
+        print(f"launches of the flush on the interpreter: {first} the first time, {second} from the plans")
+        gpu.flush()
+        st = gpu.pool_stats()
+        assert (st.n_live_vectors, st.bytes_in_use) == (live0, bytes0)
+        assert second == 11
+    finally:
+        gpu.set_jit(prev_jit)
+        gpu.set_fusion(prev_fusion)

@@ -4,7 +4,7 @@ csrc/expectations_engine.hpp: tickets, the pinned arena) under AddressSanitizer 
 pool.  tests/nulldev/drive.cpp replays the graph shapes of the GPU tests (replicas in the ten orders of test_gpu_replicas.py, long
 chains through segments / rolled / peeled plans, expectations taken along, values given up, tickets out of order, the row-table ring
 and the moments arena wrapping at tiny sizes, eight threads, shutdown and re-initialisation) and, in a sweep of its own, a failing
-allocation in the middle of a replicated launch of 1100 members; `lagging`: a caller whose handles are released late, in bursts, by a
+allocation in the middle of a replicated launch of 1100 members and at every allocation of a flush of several replicated groups; `lagging`: a caller whose handles are released late, in bursts, by a
 collector thread — the lifetime contract of a JVM (values left unstored, computed from their recipes on demand); `oom`: a device that is
 full.  The null device is not a back end and never ships."""
 import os
@@ -51,6 +51,25 @@ def test_a_failing_allocation_inside_a_replicated_launch_leaves_nothing_behind(b
         r = run(os.path.join(built, "drive_asan"), tmp_path, "failure", FMHIP_TEST_FAIL_ALLOC_AT=str(at))
         assert r.returncode == 0 and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, (at, r.stdout[-500:] + r.stderr[-6000:])
         assert "failure done" in r.stdout
+
+
+def test_a_failing_allocation_anywhere_in_a_flush_of_several_replicated_groups_leaves_nothing_behind(built, tmp_path):
+    """Scenario `failure_big`: ONE flush of two distinct shapes too long for one launch (segments; 3 and 2 described copies) and the
+    two-root graph of `failure` (3 copies).  A counting run says where the flush's pool allocations are; the hook is then put on EVERY
+    one of them — which includes the first and the last allocation of each of its launches — and on one beyond the end.  Every position
+    must leave a process that ends cleanly: no leak, no use after free, no status but OK / out of memory / a copy marked lost.
+    (Before the flush had a guard per group and run_plan dropped half-written cuts, the positions inside the first cutting of either
+    long shape — 9 of these 40 — ended in a leak or in a use after free at shutdown.)"""
+    import re
+    count = run(os.path.join(built, "drive_asan"), tmp_path, "failure_big")
+    assert count.returncode == 0 and "Sanitizer" not in count.stderr, count.stdout[-500:] + count.stderr[-6000:]
+    before, inside, status = map(int, re.search(r"failure_big: (\d+) allocations before the flush, (\d+) in it, flush status (-?\d+)", count.stdout).groups())
+    assert status == 0 and 0 < inside <= 39, "the sweep takes every allocation of the flush, 40 positions at the most"
+    for at in range(before + 1, before + inside + 2):
+        r = run(os.path.join(built, "drive_asan"), tmp_path, "failure_big", FMHIP_TEST_FAIL_ALLOC_AT=str(at))
+        assert r.returncode == 0 and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, (at, r.stdout[-500:] + r.stderr[-6000:])
+        assert "failure_big done" in r.stdout
+        assert ("flush status 0" in r.stdout) == (at == before + inside + 1), (at, r.stdout[-300:])
 
 
 def test_a_full_device(built, tmp_path):
