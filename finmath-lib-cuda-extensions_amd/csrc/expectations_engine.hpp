@@ -42,6 +42,19 @@ void Engine::arena_assign(Node* nd, double* slot)
     arena_outstanding_.push_back({ nd->id, nd->moments_slot });
 }
 
+// The moments a launch takes along for its roots (runtime.hpp): arena slots in a flush that does not wait, else a host array.
+bool Engine::RootMoments::open(Engine& engine, size_t count)
+{
+    e = &engine;
+    if (engine.async_moments_) slots = engine.arena_alloc(count); else all.resize(count);
+    return is_open();
+}
+
+void Engine::RootMoments::deliver(Node* root, size_t slot)
+{
+    if (slots) e->arena_assign(root, slots + slot * 4); else set_moments(root, all[slot]);
+}
+
 bool Engine::slot_arrived(const volatile uint64_t* slot)
 {
     return slot[0] != MOMENTS_SENTINEL && slot[1] != MOMENTS_SENTINEL && slot[2] != MOMENTS_SENTINEL && slot[3] != MOMENTS_SENTINEL;
@@ -258,7 +271,7 @@ void Engine::reduce_batch(const fmhip_vec* hs, int count, const double* shifts, 
     if (pending) flush_all();                                   // one batched flush instead of one launch per vector
     for (Node* nd : nds) if (!nd->buf) materialize({ nd });
     Program* prog = reduce_program();
-    const int max_rows = 1024;
+    const int max_rows = (int)MAX_LAUNCH_ROWS;
     for (int off = 0; off < count; off += max_rows) {
         const int m = std::min(max_rows, count - off);
         std::vector<RowSpec> rows((size_t)m);

@@ -4,7 +4,7 @@
 // that are computed once (CommonRows) and who else receives what they store (share_common_rows).  Part of runtime.cpp's translation unit
 // (included at its end, nowhere else): Engine member functions in a file of their own because runtime.cpp is long enough, and in that
 // translation unit so that every build that lists the engine's sources — the library's, the sanitizer builds against the null device —
-// has them without being told.  run_plan, plan_segments and run_big_group, which decide WHEN a loop kernel runs, stay in runtime.cpp.
+// has them without being told.  run_plan, plan_segments and run_big_group, which decide WHEN a loop kernel runs, are in plans_engine.hpp.
 //
 // The scheduled order of a large component is often PERIODIC: the same few operations over one vector after another, each
 // iteration feeding the next through a value or two — the running factor sum over the LIBOR components of an Euler step, a

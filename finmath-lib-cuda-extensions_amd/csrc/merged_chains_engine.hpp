@@ -377,7 +377,7 @@ bool Engine::merge_mark_whole_sets(MergeContext& mc) {
     return true;
 }
 
-// The families of one kernel, ≤ 1024 rows and what fits the pinned ring per launch.
+// The families of one kernel, rows_per_launch per launch.
 void Engine::merge_run_launch(MergeContext& mc, size_t launch) {
     const MergeContext::Launch& l = mc.launches[launch];
     if (!l.slot || l.slot->state.load(std::memory_order_acquire) != JitSlot::READY || l.rows.empty()) return;
@@ -391,7 +391,7 @@ void Engine::merge_run_launch(MergeContext& mc, size_t launch) {
         for (size_t q : mc.families[f].chain) w += mc.section_words(mc.chains[q], sh);
         rw = std::max(rw, w);
     }
-    const size_t max_rows = std::min((size_t)1024, ring_cap_ / (rw * 8 + 256));
+    const size_t max_rows = rows_per_launch(rw);
     if (max_rows == 0) return;
     // (rows of one launch have vectors of one length: families are looked for within a flush, whose components of a shape and length
     // share a group; a launch over rows of another length would be a different grid)
@@ -413,8 +413,7 @@ void Engine::merge_run_batch(MergeContext& mc, size_t launch, const std::vector<
     std::vector<uint64_t> table(count * rw, 0);
     std::vector<Stored> outs;
     size_t n_ops = 0, n_vec_in = 0;
-    std::vector<fmhip_moments> all;
-    void* dev_out = nullptr;
+    RootMoments along;
     RedLaunch red;
     std::vector<uint32_t> row_of(count);
     std::vector<size_t> family_of_row;                           // launch row → index into the batch
@@ -443,12 +442,11 @@ void Engine::merge_run_batch(MergeContext& mc, size_t launch, const std::vector<
         }
         const size_t launch_rows = family_of_row.size();
         table.resize(launch_rows * rw);
-        if (async_moments_) { dev_out = arena_alloc(launch_rows * K); if (!dev_out) { for (Stored& o : outs) buffer_unref(o.buf); return; } }
-        else all.resize(launch_rows * K);
+        if (!along.open(*this, launch_rows * K)) { for (Stored& o : outs) buffer_unref(o.buf); return; }
         RowLaunch l{ mc.launches[launch].slot.get(), "merged", n, (n + FM_UNIT_ELEMS - 1) / FM_UNIT_ELEMS, launch_rows, rw, 0, (uint32_t)K, false,
                      (int64_t)n_ops, (int64_t)(n_vec_in + outs.size()), (int64_t)outs.size(),
                      { (int)(n_ops / launch_rows), (int)(n_vec_in / launch_rows), (int)(K * sh.NXO), (int)K, (int)launch_rows, 4, n } };
-        l.red = &red; l.n_red = (int)K; l.host_moments = async_moments_ ? nullptr : all.data(); l.dev_moments = dev_out;
+        l.red = &red; l.n_red = (int)K; l.host_moments = along.host(); l.dev_moments = along.dev();
         launch_row_table(l, table);
         n_merged_launches_++; n_merged_chains_ += (int64_t)(count * K);
         red_wait(red, (int)launch_rows, (int)K, l.host_moments);
@@ -458,11 +456,7 @@ void Engine::merge_run_batch(MergeContext& mc, size_t launch, const std::vector<
         s = mc.stored(mc.chains[mc.families[batch[r]].chain[i / std::max<size_t>(1, sh.NXO)]], s.buf); });
     // the moments go to the chains' roots; stored values become vectors; expressions are dismantled
     for (size_t r = 0; r < count; ++r)
-        for (size_t k = 0; k < K; ++k) {
-            Node* root = mc.chains[mc.families[batch[r]].chain[k]].root;
-            if (dev_out) arena_assign(root, (double*)dev_out + ((size_t)row_of[r] * K + k) * 4);
-            else set_moments(root, all[(size_t)row_of[r] * K + k]);
-        }
+        for (size_t k = 0; k < K; ++k) along.deliver(mc.chains[mc.families[batch[r]].chain[k]].root, (size_t)row_of[r] * K + k);
     commit_stored(outs);
     for (size_t r = 0; r < count; ++r)
         for (size_t q : mc.families[batch[r]].chain) {

@@ -1326,9 +1326,23 @@ void Engine::replicas_after_failure(const std::vector<std::pair<ReplicaGroup*, s
         bool alive = false;
         for (const auto& r : replicas_) alive |= r.second == g;
         if (!alive) continue;
+        // (a root whose component has run IN PART — a segment committed, a later one failed — is closed too: what is left of the original
+        // reads a value the ORIGINAL's launches stored, an operation of the description with a buffer; its copies would read it as well)
+        auto ran_in_part = [&](Node* root) {
+            const uint64_t ep = ++epoch_;
+            for (std::vector<Node*> stack{ root }; !stack.empty();) {
+                Node* nd = stack.back(); stack.pop_back();
+                for (int k = 0; k < nd->n_in; ++k) {
+                    Node* c = nd->in[k];
+                    if (c->buf && c->rep_id == g->id && !c->rep_copy) return true;
+                    if (!c->buf && c->mark != ep) { c->mark = ep; stack.push_back(c); }
+                }
+            }
+            return false;
+        };
         std::vector<int> closed;
         for (int r : kv.second) {
-            if (r < 0 || r >= g->n_roots || g->root_done[(size_t)r] || !g->roots[(size_t)r] || !g->roots[(size_t)r]->buf) continue;
+            if (r < 0 || r >= g->n_roots || g->root_done[(size_t)r] || !g->roots[(size_t)r] || !(g->roots[(size_t)r]->buf || ran_in_part(g->roots[(size_t)r]))) continue;
             for (int j = 0; j < g->n_copies; ++j) { Node* c = g->copy_roots[(size_t)j * g->n_roots + (size_t)r]; if (c && !c->buf) c->discarded = true; }
             closed.push_back(r);
         }
@@ -1494,16 +1508,13 @@ template <class D, class Leaf> bool Engine::walk_pending(const std::vector<Node*
     return true;
 }
 
-// Linearise the pending expressions below `roots` into ONE program (roots may share intermediates: they become
-// several outputs of the same launch).  Returns false when it cannot run as one launch.
-bool Engine::build_dag(const std::vector<Node*>& roots, Dag& dag) {
-    HostTimer timer(HostProfile::BUILD_DAG);
-    dag.roots = roots;
-    if (!walk_pending(roots, dag, (size_t)FM_MAX_OPS, [&](Node* c) { dag.leaves.push_back(c); })) return false;
-    if ((int)dag.leaves.size() > FM_MAX_IN) return false;
+// The emitter build_dag and segment_dag share: dag.order — operands before users, what they read from outside in dag.leaves — becomes SSA
+// operations (ids: the leaves 0 … n_in-1, then the operations; left in the nodes' tmp_id), the scalars of the scalar-carrying ones, and
+// the head of the structural signature, a short byte string (math mode, number of inputs, opcode + operand ids per op; scalars and
+// vectors are NOT part of it; the caller appends the outputs).
+void Engine::emit_ssa(Dag& dag) {
     const int n_in = (int)dag.leaves.size();
-    for (int k = 0; k < n_in; ++k) dag.leaves[k]->tmp_id = k;
-    // structural signature: a short byte string (opcode + operand ids per op); scalars and vectors are NOT part of it
+    for (int k = 0; k < n_in; ++k) dag.leaves[(size_t)k]->tmp_id = k;
     dag.sig.clear();
     dag.sig.reserve(dag.order.size() * 4 + 16);
     dag.sig.push_back((char)('0' + math_mode)); dag.sig.push_back((char)n_in);
@@ -1518,6 +1529,16 @@ bool Engine::build_dag(const std::vector<Node*>& roots, Dag& dag) {
         dag.sig.push_back((char)nd->opcode); dag.sig.push_back((char)(op.a + 1)); dag.sig.push_back((char)(op.b + 1)); dag.sig.push_back((char)(op.c + 1));
     }
     if (dag.scalars.empty()) dag.scalars.push_back(0.0f);
+}
+
+// Linearise the pending expressions below `roots` into ONE program (roots may share intermediates: they become
+// several outputs of the same launch).  Returns false when it cannot run as one launch.
+bool Engine::build_dag(const std::vector<Node*>& roots, Dag& dag) {
+    HostTimer timer(HostProfile::BUILD_DAG);
+    dag.roots = roots;
+    if (!walk_pending(roots, dag, (size_t)FM_MAX_OPS, [&](Node* c) { dag.leaves.push_back(c); })) return false;
+    if ((int)dag.leaves.size() > FM_MAX_IN) return false;
+    emit_ssa(dag);
     // outputs: every root, plus every intermediate somebody else still needs (tmp_uses = consumers inside this DAG)
     for (Node* r : roots) if (r->tmp_uses >= 0) { dag.outs.push_back(r); dag.out_ids.push_back(r->tmp_id); r->tmp_uses = -1 - r->tmp_uses; }
     // … an intermediate with a consumer outside this DAG is a fact; one whose only claim is a live handle is the escape policy's decision
@@ -1574,18 +1595,14 @@ bool Engine::run_dags(std::vector<Dag>& dags, const double* reduce_shift, fmhip_
     if (reduce_shift && dags.size() != 1) throw Error(FMHIP_ERR_INVALID_ARGUMENT, "a fused expectation belongs to one expression");
     // a flush that collects the moments of all pending roots (Engine::reduce): expressions of one value each, all rows of this launch
     static const double no_shift = 0.0;
-    std::vector<fmhip_moments> all;
+    RootMoments along;                                              // (a host array or, from a flush that does not wait, slots of the pinned arena)
     bool moments_only = false;
-    double* async_slots = nullptr;                                  // … or, from a flush that does not wait, into slots of the pinned arena
-    { static const bool batch_trace = std::getenv("FMHIP_BATCH_TRACE") != nullptr;
-      if (batch_trace && want_root_moments_) std::fprintf(stderr, "[fmhip batch] launchable group of %zu, %zu ops, %zu outs, proto %d\n", dags.size(), d0.ops.size(), d0.out_ids.size(), proto ? 1 : 0); }
+    if (batch_trace_on()) std::fprintf(stderr, "[fmhip batch] launchable group of %zu, %zu ops, %zu outs, proto %d\n", dags.size(), d0.ops.size(), d0.out_ids.size(), proto ? 1 : 0);
     if (want_root_moments_ && !reduce_shift && !host_moments && !dev_moments && d0.out_ids.size() == 1) {
         bool roots_only = true;
         for (const Dag& d : dags) roots_only &= d.outs.size() == 1 && d.outs[0]->refs_ext > 0 && !d.outs[0]->moments_blocked;
         if (roots_only && (dags.size() >= 4 || n * (int64_t)d0.leaves.size() <= (int64_t(1) << 21) || unit_launch(n, (int64_t)dags.size()))) {
-            double* slots = async_moments_ ? arena_alloc(dags.size()) : nullptr;
-            if (slots) { async_slots = slots; reduce_shift = &no_shift; dev_moments = slots; }
-            else if (!async_moments_) { all.resize(dags.size()); reduce_shift = &no_shift; host_moments = all.data(); }
+            if (along.open(*this, dags.size())) { reduce_shift = &no_shift; host_moments = along.host(); dev_moments = along.dev(); }      // (no slots: without the moments)
             // … and where the caller has given the values up (fmhip_vec_give_up_values: every member's root, nobody else holds it) the
             // launch takes the moments and stores NOTHING: a program without outputs
             // (the root of a copy that exists as a description carries one internal reference, its group's hold, until the launch is done)
@@ -1602,9 +1619,8 @@ bool Engine::run_dags(std::vector<Dag>& dags, const double* reduce_shift, fmhip_
         try { prog = compile(d0.ops, (int)d0.leaves.size(), moments_only ? std::vector<int>{} : d0.out_ids, reduce_shift ? std::vector<int>{ d0.out_ids[0] } : std::vector<int>{}, nullptr, false); }
         catch (const Error& e) {
             if (e.code != FMHIP_ERR_PROGRAM_LIMIT) throw;
-            if (all.empty() && !async_slots) return false;
-            all.clear(); async_slots = nullptr; reduce_shift = nullptr; host_moments = nullptr; dev_moments = nullptr;       // without the moments, then
-            return run_dags_plain(dags, proto);
+            if (!along.is_open()) return false;
+            return run_dags_plain(dags, proto);                     // without the moments, then
         }
         program_cache_[key] = prog;
     }
@@ -1626,8 +1642,7 @@ bool Engine::run_dags(std::vector<Dag>& dags, const double* reduce_shift, fmhip_
         for (Stored& o : stored) buffer_unref(o.buf);
         throw;
     }
-    if (async_slots) for (size_t i = 0; i < dags.size(); ++i) arena_assign(dags[i].outs[0], async_slots + i * 4);
-    for (size_t i = 0; i < all.size(); ++i) set_moments(dags[i].outs[0], all[i]);
+    if (along.is_open()) for (size_t i = 0; i < dags.size(); ++i) along.deliver(dags[i].outs[0], i);
     if (moments_only) {         // nothing was stored: the roots keep their moments, give their expressions up and are no roots of later flushes
         for (size_t i = 0; i < dags.size(); ++i) give_up_value(dags[i].outs[0]);
         return true;
@@ -1636,14 +1651,8 @@ bool Engine::run_dags(std::vector<Dag>& dags, const double* reduce_shift, fmhip_
     return true;
 }
 
-// ---------------------------------------------------------------- components larger than one launch
-//
-// A connected component of pending work that does not fit one launch (12 inputs / 8 outputs / 15 live values / 128
-// micro-ops) is cut into consecutive SEGMENTS of its topological order.  Every prefix of a topological order is closed
-// under dependencies, so a segment only reads materialised vectors and outputs of earlier segments; its outputs are the
-// values somebody outside the segment still needs.  Each segment is the longest one that still fits (found once per
-// component SHAPE and cached); components of identical shape — e.g. the same Euler step of several parameter sets — are
-// cut identically and their segments run as rows of the same launches.
+// ---------------------------------------------------------------- components larger than one launch: what they are made of, and
+// build_big, which makes them (how they are planned, cut and run: plans_engine.hpp)
 
 // What a copy that exists as a description (ReplicaGroup) needs to know about the ORIGINAL's component, per position of its order —
 // taken from the nodes before anything runs (a segment's nodes are dismantled as soon as it has been committed).
@@ -1908,64 +1917,6 @@ bool Engine::build_big(const std::vector<Node*>& roots, BigDag& big) {
     return true;
 }
 
-// uses: per position of the component's order, the consumers INSIDE the component (structural: equal for all members of a group)
-bool Engine::segment_dag(const BigDag& big, size_t s, size_t e, Dag& dag, const std::vector<int32_t>& uses) {
-    const uint64_t ep = ++epoch_, ep_leaf = ++epoch_;          // mark == ep: produced inside the segment; == ep_leaf: registered input
-    dag = Dag();
-    for (size_t i = s; i < e; ++i) { Node* nd = big.order[i]; nd->mark = ep; nd->tmp_uses = 0; }
-    for (size_t i = s; i < e; ++i) {
-        Node* nd = big.order[i];
-        for (int k = 0; k < nd->n_in; ++k) {
-            Node* c = nd->in[k];
-            if (c->mark == ep) { c->tmp_uses++; continue; }
-            if (c->mark == ep_leaf) continue;
-            if (!c->buf) return false;                          // reads a value that is neither materialised nor produced here: not a valid cut
-            c->mark = ep_leaf;
-            dag.leaves.push_back(c);
-            if ((int)dag.leaves.size() > FM_MAX_IN) return false;
-        }
-    }
-    if (e - s > (size_t)FM_MAX_OPS) return false;
-    const int n_in = (int)dag.leaves.size();
-    for (int k = 0; k < n_in; ++k) dag.leaves[(size_t)k]->tmp_id = k;
-    dag.sig.push_back((char)('0' + math_mode)); dag.sig.push_back((char)n_in);
-    for (size_t i = s; i < e; ++i) {
-        Node* nd = big.order[i];
-        nd->tmp_id = n_in + (int)(i - s);
-        SsaOp op{ nd->opcode, -1, -1, -1, nd->scalar };
-        int* slots[3] = { &op.a, &op.b, &op.c };
-        for (int k = 0; k < nd->n_in; ++k) *slots[k] = nd->in[k]->tmp_id;
-        dag.order.push_back(nd);
-        dag.ops.push_back(op);
-        if (op_info(nd->opcode).scalar) dag.scalars.push_back((float)nd->scalar);
-        dag.sig.push_back((char)nd->opcode); dag.sig.push_back((char)(op.a + 1)); dag.sig.push_back((char)(op.b + 1)); dag.sig.push_back((char)(op.c + 1));
-    }
-    if (dag.scalars.empty()) dag.scalars.push_back(0.0f);
-    for (size_t i = s; i < e; ++i) {
-        Node* nd = big.order[i];
-        // an output of the component (build_big's decision — a handle alone does not make one), a consumer in a later segment, or the
-        // component's root (also where its value has been given up: a segment cannot take the moments along, it stores it all the same)
-        if (big.escapes[i] || uses[i] > nd->tmp_uses || (uses[i] == 0 && nd->refs_ext > 0)) { dag.outs.push_back(nd); dag.out_ids.push_back(nd->tmp_id); }
-    }
-    if (dag.outs.empty() || (int)dag.outs.size() > FM_MAX_OUT) return false;
-    dag.roots = dag.outs;
-    dag.sig.push_back((char)0xff);
-    for (int v : dag.out_ids) dag.sig.push_back((char)(v + 1));
-    return true;
-}
-
-// A value of a member without nodes has been computed: it is kept for the launches that read it, and handed to the copy's root node
-// if it is one of the replicated roots.
-void Engine::commit_described(BigDag& big, size_t pos, Buffer* b) {
-    big.temp[pos] = b;                                  // owns the buffer's first reference
-    const int32_t root = big.view->rep_root[pos];
-    if (root < 0) return;
-    const ReplicaGroup* g = big.view->g;
-    Node* c = g->copy_roots[(size_t)big.copy * g->n_roots + root];
-    b->refs++;
-    commit_node(c, b);
-}
-
 // Commit: what a launch has stored becomes materialised vectors; their expressions (and unreferenced intermediates) go away.  All
 // outputs are kept alive until every expression has been dismantled: one that nobody holds — stored for the sake of a launch shape whose
 // kernel exists (build_big), a position a loop stores in every iteration for the sake of one — goes away with its last consumer.
@@ -1985,267 +1936,7 @@ void Engine::commit_stored(const std::vector<Stored>& outs) {
 
 void Engine::give_up_value(Node* r) { r->discarded = true; r->refs_int++; drop_expression(r); r->refs_int--; }
 
-// One segment of a planned component for every member of a group: gather the row blocks by index, launch, commit.
-void Engine::run_planned_segment(const BigPlan::Seg& seg, std::vector<BigDag>& group, size_t first, size_t count, ReduceRequest* rr, Program* prog_red) {
-    const int64_t n = group[first].n;
-    const size_t n_scal = seg.scal.empty() ? 1 : seg.scal.size();
-    std::vector<RowSpec> rows(count);
-    std::vector<float> scalars(count * n_scal, 0.0f);
-    std::vector<Stored> stored;
-    stored.reserve(count * seg.out.size());
-    try {
-        for (size_t c = 0; c < count; ++c) {
-            BigDag& big = group[first + c];
-            RowSpec& r = rows[c];
-            r.in.reserve(seg.in.size()); r.out.reserve(seg.out.size());
-            for (int32_t i : seg.in) {
-                Buffer* b = i >= 0 ? big.value((size_t)i) : big.leaves[(size_t)(-1 - i)]->buf;
-                if (!b) throw Error(FMHIP_ERR_PROGRAM_LIMIT, "planned segment reads a value that has not been computed");
-                r.in.push_back(b->ptr);
-            }
-            for (size_t k = 0; k < seg.out.size(); ++k) { Buffer* b = new_buffer(n); stored.push_back({ &big, (size_t)seg.out[k], nullptr, b }); r.out.push_back(b->ptr); }
-            float* sc = scalars.data() + c * n_scal;
-            for (size_t k = 0; k < seg.scal.size(); ++k) sc[k] = big.scalar_at((size_t)seg.scal[k]);
-            r.scalars = sc; r.shifts = rr ? &rr->shift : nullptr;
-        }
-        if (rr) { launch(prog_red, n, rows, rr->host_out, rr->dev_out); rr->done = true; }
-        else launch(seg.prog, n, rows, nullptr, nullptr);
-    } catch (...) { for (Stored& o : stored) buffer_unref(o.buf); throw; }
-    commit_stored(stored);
-}
-
 static const bool MERGE_CHAINS = knob_on("FMHIP_MERGE_CHAINS");          // =0: off (merged_chains_engine.hpp)
-
-// A kernel of the specialised tier on demand: asked for when its slot is empty — with FMHIP_JIT=sync also while it still waits for the
-// worker: the caller compiles it now —; true when it is there.
-template <class Source> bool Engine::kernel_ready(std::shared_ptr<JitSlot>& slot, Source&& source, int elems) {
-    const bool sync = jit_mode == FMHIP_JIT_SYNC;
-    if (!slot || (sync && slot->state.load(std::memory_order_acquire) == JitSlot::QUEUED)) {
-        std::string text = source();
-        if (text.empty()) return false;
-        slot = jit().request_source(std::move(text), elems, sync);
-    }
-    return slot && slot->state.load(std::memory_order_acquire) == JitSlot::READY;
-}
-
-struct Engine::TempGuard {
-    Engine* e; std::vector<BigDag>& g;
-    static void drop(Engine* e, BigDag& b) { if (b.described()) for (Buffer*& t : b.temp) if (t) { e->buffer_unref(t); t = nullptr; } }
-    ~TempGuard() { for (BigDag& b : g) drop(e, b); }
-};
-
-struct Engine::OperandTable {
-    std::unordered_map<const Node*, int32_t> index_of;          // position in the order; a leaf: -1 - its number
-    std::vector<std::array<int32_t, 3>> operand;                 // per operation
-    explicit OperandTable(const BigDag& g) : operand(g.order.size()) {
-        index_of.reserve(g.order.size() + g.leaves.size());
-        for (size_t i = 0; i < g.order.size(); ++i) index_of[g.order[i]] = (int32_t)i;
-        for (size_t i = 0; i < g.leaves.size(); ++i) index_of[g.leaves[i]] = -1 - (int32_t)i;
-        for (size_t i = 0; i < g.order.size(); ++i)
-            for (int k = 0; k < g.order[i]->n_in; ++k) operand[i][(size_t)k] = index_of.at(g.order[i]->in[k]);
-    }
-};
-
-// The root of a component that has exactly one, as its LAST operation — its node (for a copy that exists as a description: the copy's
-// root node) or nullptr.  g0 = the member that carries the order.
-Node* Engine::single_root(const BigDag& b, const BigDag& g0)
-{
-    if (!b.described()) return (b.roots.size() == 1 && !b.order.empty() && b.order.back() == b.roots[0]) ? b.roots[0] : nullptr;
-    const std::vector<int32_t>& rep_root = b.view->rep_root;
-    const size_t n = g0.order.size();
-    if (rep_root.size() != n || n == 0 || rep_root[n - 1] < 0) return nullptr;
-    for (size_t i = 0; i + 1 < n; ++i) if (rep_root[i] >= 0) return nullptr;
-    const ReplicaGroup* g = b.view->g;
-    return g->copy_roots[(size_t)b.copy * g->n_roots + (size_t)rep_root[n - 1]];
-}
-
-// A component shape with a plan, for every member of a group: segment by segment (the rolled stretch as one launch once its kernel
-// exists), ≤ 1024 members per launch.
-void Engine::run_plan(BigPlan& plan, std::vector<BigDag>& group, ReduceRequest* rr) {
-    const size_t max_batch = 1024;
-    { static const bool batch_trace = std::getenv("FMHIP_BATCH_TRACE") != nullptr;
-      if (batch_trace && want_root_moments_) std::fprintf(stderr, "[fmhip batch] plan for a group of %zu, %zu nodes, %zu roots: rolled %d peeled %d segs %zu\n", group.size(), group[0].order.size(), group[0].roots.size(), plan.rolled.present ? 1 : 0, plan.rolled.peeled.present ? 1 : 0, plan.segs.size()); }
-    bool rolled = plan.rolled.present && jit_mode != FMHIP_JIT_OFF && kernel_ready(plan.rolled.jit, [&] { return plan.rolled.source; }, plan.rolled.elems);
-    // The rolled launch carries one row table for all its members through the pinned ring (≈ 5 KB per row for the LMM step, but
-    // iterations x (inputs + outputs) words in general): as many members per launch as fit; a single row that does not fit leaves the
-    // stretch to its segments.
-    size_t rolled_batch = max_batch;
-    if (rolled) {
-        const size_t rows_fit = ring_cap_ / ((size_t)plan.rolled.row_words * 8 + 256);
-        if (rows_fit == 0) rolled = false; else rolled_batch = std::min(max_batch, rows_fit);
-    }
-    // The peeled form — head, loop and tail of the component in one launch.  A caller that values one product after the other (1 row x
-    // 489 tiles) turns three launches of ≈ 9 + 20 + 8 µs into one; the lock-step batches of the native driver save the stores and loads
-    // of the values between the parts (measured on the 1 M-path calibration, same box: 12 671 → 4 639 launches, 2.65 → 2.50 s of
-    // kernel time with the head and the tail limited to 128 operations each).  FMHIP_PEEL_MAX_WORKGROUPS limits it to small launches.
-    {
-        BigPlan::Rolled::Peeled& pe = plan.rolled.peeled;
-        auto red_ready = [&] { return kernel_ready(pe.jit_red, [&] { return pe.source_red; }, pe.elems); };
-        if (pe.present && jit_mode != FMHIP_JIT_OFF && kernel_ready(pe.jit, [&] { return pe.source; }, pe.elems) && group[0].n > 0) {
-            static const size_t PEEL_MAX_WORKGROUPS = knob_size("FMHIP_PEEL_MAX_WORKGROUPS", ~(size_t)0);
-            const size_t tiles = (size_t)((group[0].n + (int64_t)FM_BLOCK * pe.jit->elems - 1) / ((int64_t)FM_BLOCK * pe.jit->elems));
-            const size_t rows_fit = ring_cap_ / ((size_t)pe.row_words * 8 + 256);
-            if (group.size() * tiles <= PEEL_MAX_WORKGROUPS && rows_fit >= group.size()) {
-                TempGuard guard{ this, group };
-                // `chain.getAverage()` on the component's root: the same launch takes the moments (a workgroup's tile is one unit of the
-                // reduction tree) — a product of a caller that values one after the other is ONE launch, and its value is not read again
-                ReduceRequest* fused = nullptr;
-                if (rr && group.size() == 1 && !group[0].described() && !pe.source_red.empty() && group[0].order.back() == group[0].roots[0] &&
-                    tiles <= (size_t)FM_SPAN_UNITS * 65536 && red_ready()) fused = rr;
-                // … and with a flush that collects the moments of all pending roots (Engine::reduce): of every member, as rows of this launch
-                std::vector<fmhip_moments> all;
-                ReduceRequest every{ 0.0, nullptr, nullptr, false };
-                static const bool batch_trace = std::getenv("FMHIP_BATCH_TRACE") != nullptr;
-                if (batch_trace && want_root_moments_) std::fprintf(stderr, "[fmhip batch] peeled group of %zu, %zu nodes: rr %d source_red %d roots %zu root_last %d\n", group.size(), group[0].order.size(), rr ? 1 : 0, pe.source_red.empty() ? 0 : 1, group[0].roots.size(), (int)(!group[0].order.empty() && !group[0].roots.empty() && group[0].order.back() == group[0].roots[0]));
-                if (!fused && want_root_moments_ && !rr && !pe.source_red.empty() && tiles <= (size_t)FM_SPAN_UNITS * 65536) {
-                    bool roots_only = true;
-                    for (const BigDag& b : group) { Node* r = single_root(b, group[0]); roots_only &= r != nullptr && !r->moments_blocked && (!plan.discards_root || r->discard); }
-                    if (roots_only && red_ready()) {
-                        if (async_moments_) { every.dev_out = arena_alloc(group.size()); if (every.dev_out) fused = &every; }
-                        else { all.resize(group.size()); every.host_out = all.data(); fused = &every; }
-                    }
-                }
-                // A plan whose root is wanted for its moments only has peeled kernels that do not store it: usable only when this launch
-                // takes the moments of every member's root; otherwise the segments below run (they go by the nodes' references and store it)
-                if (!plan.discards_root || fused == &every) {
-                std::vector<Node*> root_nodes;
-                if (fused == &every) for (const BigDag& b : group) root_nodes.push_back(single_root(b, group[0]));
-                std::vector<uint32_t> row_of;
-                run_peeled(plan.rolled, group, 0, group.size(), fused, &row_of);
-                if (fused == &every && every.done && every.dev_out)
-                    for (size_t i = 0; i < root_nodes.size(); ++i) arena_assign(root_nodes[i], (double*)every.dev_out + (size_t)row_of[i] * 4);      // (members of a common row: the same slot)
-                else if (fused == &every && every.done)
-                    for (size_t i = 0; i < root_nodes.size(); ++i) set_moments(root_nodes[i], all[i]);
-                if (plan.discards_root && every.done)       // moments taken, value not stored: not a root of later flushes; what it was computed from is let go
-                    for (Node* r : root_nodes) if (!r->buf) give_up_value(r);
-                return;
-                }
-            }
-        }
-    }
-    if (plan.segs_missing) {
-        // this shape has never run as segments: the members with nodes take the general path now, which writes the cuts into the plan
-        std::vector<BigDag> described, with_nodes;
-        for (BigDag& b : group) (b.described() ? described : with_nodes).push_back(std::move(b));
-        if (with_nodes.empty()) throw Error(FMHIP_ERR_PROGRAM_LIMIT, "a group of copies without their original");
-        // (a launch that fails midway leaves no half-written cuts behind: the shape is cut afresh when it comes round again — until the flush
-        // was swept with a failing allocation the partial list stayed, was extended by the next attempt and run twice, and its programs
-        // were released at shutdown without ever having been held)
-        try { plan_segments(plan, with_nodes); } catch (...) { plan.segs.clear(); throw; }
-        plan.segs_missing = false;
-        for (BigPlan::Seg& seg : plan.segs) seg.prog->refs++;              // the plan holds its programs (pool_purge drops both caches together)
-        if (!described.empty()) run_plan(plan, described);
-        return;
-    }
-    bool any_described = false;
-    for (const BigDag& b : group) any_described |= b.described();
-    auto release_temps = [&](const std::vector<int32_t>& positions) {
-        if (!any_described) return;
-        for (BigDag& b : group) {
-            if (!b.described()) continue;
-            for (int32_t pos : positions) if (Buffer* t = b.temp[(size_t)pos]) { b.temp[(size_t)pos] = nullptr; buffer_unref(t); }
-        }
-    };
-    TempGuard guard{ this, group };
-    // The variant of the last segment that also reduces the component's root, for `chain.getAverage()` on a single large expression: one
-    // launch and one read of the root less than a stand-alone reduction behind the segment.  Only when that variant accumulates like
-    // the stand-alone reduction program does (8 elements per lane: the sums are then the same to the last bit).
-    Program* prog_red = nullptr;
-    if (rr && group.size() == 1 && !group[0].described() && !plan.segs.empty()) {
-        BigPlan::Seg& last = plan.segs.back();
-        const int32_t root_pos = (int32_t)group[0].order.size() - 1;
-        size_t k_root = last.out.size();
-        for (size_t k = 0; k < last.out.size(); ++k) if (last.out[k] == root_pos) k_root = k;
-        // (the size gate of reduce(): a launch with a fused reduction has one workgroup per 8192 elements of a row — fine for a segment
-        // over two input vectors, a starved launch for one over eleven)
-        if (!(rolled && last.zone == 1) && !last.no_red && !last.ssa.empty() && k_root < last.out.size() && group[0].order[(size_t)root_pos] == group[0].roots[0] &&
-            (group[0].n * (int64_t)last.n_in <= (int64_t(1) << 21) || unit_launch(group[0].n, 1))) {
-            if (!last.prog_red) {
-                try { last.prog_red = compile(last.ssa, last.n_in, last.out_ids, { last.out_ids[k_root] }, nullptr, false); }
-                catch (const Error& e) { if (e.code != FMHIP_ERR_PROGRAM_LIMIT) throw; last.no_red = true; }
-                if (last.prog_red && last.prog_red->proto.variant != 1u) { delete last.prog_red; last.prog_red = nullptr; last.no_red = true; }
-            }
-            prog_red = last.prog_red;
-        }
-    }
-    bool rolled_done = false;
-    for (size_t si = 0; si < plan.segs.size(); ++si) {
-        const BigPlan::Seg& seg = plan.segs[si];
-        if (rolled && seg.zone == 1) {              // the loop's stretch: one launch of the rolled kernel instead of its segments
-            if (!rolled_done) for (size_t off = 0; off < group.size(); off += rolled_batch) run_rolled(plan.rolled, group, off, std::min(rolled_batch, group.size() - off));
-            rolled_done = true;
-        } else if (prog_red && si + 1 == plan.segs.size())
-            run_planned_segment(seg, group, 0, 1, rr, prog_red);
-        else
-            for (size_t off = 0; off < group.size(); off += max_batch) run_planned_segment(seg, group, off, std::min(max_batch, group.size() - off));
-        release_temps(seg.free_after);
-    }
-}
-
-// The general path: the members WITH nodes of a group whose shape has no segments yet are cut into launches (longest segment that fits
-// one launch, again and again; cuts forced at the ends of the loop plan.rolled describes, so that either form can run between them), run
-// segment by segment, and the cuts are written into the plan.
-void Engine::plan_segments(BigPlan& plan, std::vector<BigDag>& group) {
-    const size_t n_ops = group[0].order.size();
-    const size_t max_batch = 1024;
-    // Node -> index in group[0] for the plan (segment_dag reuses the nodes' scratch fields)
-    const OperandTable table(group[0]);
-    const std::unordered_map<const Node*, int32_t>& index_of = table.index_of;
-    std::vector<int32_t> uses(n_ops, 0);                    // consumers inside the component, per position (before anything runs)
-    for (size_t i = 0; i < n_ops; ++i)
-        for (int k = 0; k < group[0].order[i]->n_in; ++k) { const int32_t o = table.operand[i][(size_t)k]; if (o >= 0) uses[(size_t)o]++; }
-    size_t zone_begin = n_ops, zone_end = n_ops;
-    if (plan.rolled.present) { zone_begin = plan.rolled.begin; zone_end = zone_begin + (size_t)plan.rolled.period * plan.rolled.iterations; }
-    size_t s = 0;
-    while (s < n_ops) {
-        size_t e = 0;
-        const size_t limit = s < zone_begin ? zone_begin : (s < zone_end ? zone_end : n_ops);      // a segment never crosses an end of the loop
-        {
-            // longest segment starting at s that fits one launch.  Inputs grow monotonically with the end; outputs and live
-            // values do not: collect every end that passes the cheap checks, then take the largest one that also compiles.
-            std::vector<size_t> cheap;
-            for (size_t cand = s + 1; cand <= limit && cand - s <= (size_t)FM_MAX_OPS; ++cand) {
-                Dag d;
-                if (segment_dag(group[0], s, cand, d, uses)) cheap.push_back(cand);
-                else if ((int)d.leaves.size() > FM_MAX_IN) break;
-            }
-            for (size_t k = cheap.size(); k-- > 0 && e == 0;) {
-                Dag d;
-                segment_dag(group[0], s, cheap[k], d, uses);
-                if (!program_cache_.count(d.sig)) {
-                    try { program_cache_[d.sig] = compile(d.ops, (int)d.leaves.size(), d.out_ids, {}, nullptr, false); }
-                    catch (const Error& err) { if (err.code == FMHIP_ERR_PROGRAM_LIMIT) continue; throw; }
-                }
-                e = cheap[k];
-            }
-            if (e == 0) throw Error(FMHIP_ERR_PROGRAM_LIMIT, "an operation does not fit one launch");
-        }
-        std::vector<Dag> dags(group.size());
-        for (size_t c = 0; c < group.size(); ++c)
-            if (!segment_dag(group[c], s, e, dags[c], uses)) throw Error(FMHIP_ERR_PROGRAM_LIMIT, "inconsistent segment of a split component");
-        {
-            BigPlan::Seg seg;
-            seg.prog = program_cache_.at(dags[0].sig);
-            for (Node* l : dags[0].leaves) seg.in.push_back(index_of.at(l));
-            for (Node* o : dags[0].outs) seg.out.push_back(index_of.at(o));
-            for (size_t i = s; i < e; ++i) if (op_info(group[0].order[i]->opcode).scalar) seg.scal.push_back((int32_t)i);
-            seg.zone = s < zone_begin ? 0 : (s < zone_end ? 1 : 2);
-            if (e == n_ops) { seg.ssa = dags[0].ops; seg.out_ids = dags[0].out_ids; seg.n_in = (int)dags[0].leaves.size(); }
-            plan.segs.push_back(std::move(seg));
-        }
-        for (size_t off = 0; off < dags.size(); off += max_batch) {
-            std::vector<Dag> part(std::make_move_iterator(dags.begin() + off), std::make_move_iterator(dags.begin() + std::min(dags.size(), off + max_batch)));
-            if (!run_dags(part)) throw Error(FMHIP_ERR_PROGRAM_LIMIT, "segment of a split component does not fit one launch");
-        }
-        s = e;
-    }
-    // values no later segment reads: members without nodes give them back to the pool there
-    {
-        std::unordered_map<int32_t, size_t> last_reader;
-        for (size_t k = 0; k < plan.segs.size(); ++k) for (int32_t i : plan.segs[k].in) if (i >= 0) last_reader[i] = k;
-        for (const auto& kv : last_reader) plan.segs[kv.second].free_after.push_back(kv.first);
-    }
-}
 
 // A launch sequence that executes replicated roots with their copies that exist as a description: the scope guard of the flush, in the
 // spirit of PassOutputs::commit.  It owns the list of what is executed (per description, the roots by index) and ends in one of three
@@ -2267,41 +1958,6 @@ struct Engine::ReplicaLaunch {
 
 struct Engine::SmallGroup { std::vector<Dag> members; Dag proto; const SmallMatch* match = nullptr; ReplicaLaunch launch; explicit SmallGroup(Engine* e) : launch(e) {} };
 struct Engine::BigGroups { std::vector<std::vector<BigDag>> members; std::vector<ReplicaLaunch> launches; };       // per group of one shape: its members and its guard
-
-void Engine::run_big_group(std::vector<BigDag>& group, ReduceRequest* rr) {
-    HostTimer timer(HostProfile::RUN_BIG);
-    BigDag& g0 = group[0];
-    auto planned = plan_cache_.find(g0.hash);
-    if (planned != plan_cache_.end() && planned->second.sig != g0.sig) planned = plan_cache_.end();       // hash collision: general path, nothing cached
-    const bool collision = planned == plan_cache_.end() && plan_cache_.count(g0.hash) != 0;
-    if (planned != plan_cache_.end()) { run_plan(planned->second, group, rr); return; }
-    // First component of this shape.  Its loop, if it has one, is found first: a periodic stretch of the order becomes a rolled loop (one
-    // launch) as soon as its kernel exists; segments remain its fallback.
-    BigPlan plan;
-    size_t first_with_nodes = 0;
-    while (first_with_nodes < group.size() && group[first_with_nodes].described()) ++first_with_nodes;
-    if (first_with_nodes == group.size()) throw Error(FMHIP_ERR_PROGRAM_LIMIT, "a group of copies without their original");
-    plan_loop(plan, group[first_with_nodes]);
-    plan.sig = g0.sig;
-    plan.discards_root = g0.discard_root;
-    plan.segs_missing = true;
-    if (collision) {                                        // (practically never) nothing is cached: segments for the members with nodes, the plan they leave for the copies
-        std::vector<BigDag> described, with_nodes;
-        for (BigDag& b : group) (b.described() ? described : with_nodes).push_back(std::move(b));
-        plan_segments(plan, with_nodes);
-        plan.segs_missing = false;
-        if (!described.empty()) run_plan(plan, described);
-        return;
-    }
-    // The plan is written down WITHOUT its segments: where the whole component is one launch of a kernel that exists already (the peeled
-    // form, from the code-object caches or the build-time pack) nothing else is ever needed; run_plan cuts the segments — by running the
-    // component through the general path — the first time that launch is not available (until round 5 every shape's first occurrence ran as
-    // segments on the interpreter, whatever kernels existed: a tenth of a second per calibration, and again for every variant of a shape
-    // the escape policy moves through).
-    BigPlan& cached = plan_cache_[g0.hash];
-    cached = std::move(plan);
-    run_plan(cached, group, rr);
-}
 
 bool Engine::try_fused(const std::vector<Node*>& roots) {
     std::vector<Dag> dags(1);
@@ -2444,14 +2100,13 @@ template <class D> void Engine::members_with_copies(std::vector<D>& originals, s
     }
 }
 
-// The launches of a small group, ≤ 1024 members each.  A part that does not run as one launch after all gives its roots to `leftovers`
+// The launches of a small group, MAX_LAUNCH_ROWS members each.  A part that does not run as one launch after all gives its roots to `leftovers`
 // (they run as large components) or, late (leftovers == nullptr: behind the large components), computes them one by one; the group's
 // descriptions are then left alone (dismiss), otherwise its roots are done (finish).  An exception leaves the guard open.
 void Engine::run_small(SmallGroup& sg, std::vector<Node*>* leftovers) {
-    const size_t max_batch = 1024;
     bool ran = true;
-    for (size_t off = 0; off < sg.members.size(); off += max_batch) {
-        std::vector<Dag> part(std::make_move_iterator(sg.members.begin() + off), std::make_move_iterator(sg.members.begin() + std::min(sg.members.size(), off + max_batch)));
+    for (size_t off = 0; off < sg.members.size(); off += MAX_LAUNCH_ROWS) {
+        std::vector<Dag> part(std::make_move_iterator(sg.members.begin() + off), std::make_move_iterator(sg.members.begin() + std::min(sg.members.size(), off + MAX_LAUNCH_ROWS)));
         if (run_dags(part, nullptr, nullptr, nullptr, &sg.proto)) continue;
         ran = false;
         for (Dag& d : part) for (Node* r : d.roots) { if (leftovers) leftovers->push_back(r); else if (!r->buf) materialize({ r }); }
@@ -2810,6 +2465,7 @@ void Engine::profile_read(double* ms_total, int64_t* n) {
 
 } // namespace fm
 
+#include "plans_engine.hpp"            // Engine::segment_dag, run_plan and its steps, plan_segments, run_big_group: components larger than one launch, from a group of one shape to launches
 #include "loop_engine.hpp"             // Engine::detect_loop, plan_peel, plan_loop, run_rolled, run_peeled: the periodic stretch of a component as one launch
 #include "merged_chains_engine.hpp"    // Engine::match_small, merge_shape_index, merge_families: components of one loop shape over the same vectors as one launch
 #include "expectations_engine.hpp"     // Engine::red_*, arena_*, slot_wait, reduce, reduce_batch*, give_up_values, ticket_*: from a vector to its expectation

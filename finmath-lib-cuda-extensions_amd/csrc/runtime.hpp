@@ -587,6 +587,10 @@ private:
     // rows: per batch row, n_in input buffers + n_out output buffers (+ per-row scalars, shifts)
     struct RowSpec { std::vector<const float*> in; std::vector<float*> out; const float* scalars; const double* shifts; };
     void launch(Program* p, int64_t n, const std::vector<RowSpec>& rows, fmhip_moments* host_moments, void* dev_moments);
+    static constexpr size_t MAX_LAUNCH_ROWS = 1024;             // rows (members of a group, families, vectors of a batched reduction) per launch
+    // … and of a launch whose rows go through the pinned ring as a table of row_words words each: what fits the ring (ring_rows), and both.  0: not even one row.
+    size_t ring_rows(size_t row_words) const { return ring_cap_ / (row_words * 8 + 256); }
+    size_t rows_per_launch(size_t row_words) const { return std::min(MAX_LAUNCH_ROWS, ring_rows(row_words)); }
     Program* reduce_program();
     bool try_fused(const std::vector<Node*>& roots);
     struct Dag;
@@ -698,6 +702,17 @@ private:
     bool segment_dag(const BigDag& big, size_t s, size_t e, Dag& dag, const std::vector<int32_t>& uses);
     // An expectation asked of a large pending expression: taken by the launch that computes its root (the last segment of its plan)
     struct ReduceRequest { double shift; fmhip_moments* host_out; void* dev_out; bool done; };
+    // The moments a launch takes along for its roots (want_root_moments_, below), one slot each: slots of the pinned arena in a flush that
+    // does not wait (async_moments_), else a host array.  open: false when the arena has none — what happens then is the launch site's
+    // affair; host() / dev(): what the launch is given, exactly one of them non-null; deliver: slot `slot` is that root's.
+    struct RootMoments {
+        Engine* e = nullptr; std::vector<fmhip_moments> all; double* slots = nullptr;
+        bool open(Engine& engine, size_t count);
+        bool is_open() const { return slots || !all.empty(); }
+        fmhip_moments* host() { return all.empty() ? nullptr : all.data(); }
+        void* dev() const { return slots; }
+        void deliver(Node* root, size_t slot);
+    };
     // reduce() of a pending expression: the launch that takes the moments leaves its wait to reduce() — the bookkeeping behind the launch
     // (outputs become vectors, expressions are dismantled) happens while the device works, not after it
     RedLaunch* defer_red_ = nullptr;
@@ -735,7 +750,23 @@ private:
     void red_wait(RedLaunch& red, int batch, int n_red, fmhip_moments* host_moments);
     void red_release(RedLaunch& red);
     void run_big_group(std::vector<BigDag>& group, ReduceRequest* rr = nullptr);
+    struct TempGuard;                                             // whatever happens, the values held for members without nodes go back to the pool
+    struct OperandTable;                                          // of a component: node → position, and every operation's operands by position
+    // run_plan (plans_engine.hpp): peeled_applies → run_peeled_group, else cut_on_first_use (plan_segments: longest_segment, describe_segment,
+    // run_cut_segment, commit_cuts) or last_segment_reducer → run_segments
     void plan_segments(BigPlan& plan, std::vector<BigDag>& group);
+    size_t longest_segment(const BigDag& g0, size_t s, size_t limit, const std::vector<int32_t>& uses);
+    BigPlan::Seg describe_segment(const Dag& d, const BigDag& g0, const OperandTable& table, size_t s, size_t e, int zone);
+    void run_cut_segment(std::vector<Dag>& dags);
+    static void commit_cuts(BigPlan& plan, std::vector<BigPlan::Seg>& cuts);
+    bool batch_trace_on() const { static const bool on = std::getenv("FMHIP_BATCH_TRACE") != nullptr; return on && want_root_moments_; }
+    void trace_batch(const BigPlan& plan, const std::vector<BigDag>& group, const ReduceRequest* rr, bool peeled) const;      // the FMHIP_BATCH_TRACE lines of a plan
+    bool peeled_applies(BigPlan& plan, const std::vector<BigDag>& group);
+    bool run_peeled_group(BigPlan& plan, std::vector<BigDag>& group, ReduceRequest* rr);
+    void cut_on_first_use(BigPlan& plan, std::vector<BigDag>& group);
+    Program* last_segment_reducer(BigPlan& plan, const std::vector<BigDag>& group, bool rolled, const ReduceRequest* rr);
+    void run_segments(BigPlan& plan, std::vector<BigDag>& group, size_t rolled_batch, ReduceRequest* rr, Program* prog_red);
+    void emit_ssa(Dag& dag);                                      // dag.order → SSA operations, scalars, the signature's bytes up to the outputs (build_dag, segment_dag)
     void plan_loop(BigPlan& plan, const BigDag& g);
     void run_planned_segment(const BigPlan::Seg& seg, std::vector<BigDag>& group, size_t first, size_t count, ReduceRequest* rr = nullptr, Program* prog_red = nullptr);
     void run_plan(BigPlan& plan, std::vector<BigDag>& group, ReduceRequest* rr = nullptr);
@@ -747,8 +778,6 @@ private:
     struct Stored { BigDag* big; size_t pos; Node* node; Buffer* buf; };
     void commit_stored(const std::vector<Stored>& outs);
     void give_up_value(Node* r);                                  // moments taken, value not stored: no root of later flushes, its expression is let go
-    struct TempGuard;                                             // whatever happens, the values held for members without nodes go back to the pool
-    struct OperandTable;                                          // of a component: node → position, and every operation's operands by position
     // a kernel of the specialised tier on demand (source(): its text, made only when it is asked for; empty: there is none): is it there?
     template <class Source> bool kernel_ready(std::shared_ptr<JitSlot>& slot, Source&& source, int elems);
     // the launches of the loop kernels (loop_engine.hpp): one row-table launch, the rows that are computed once, who else receives what they store

@@ -372,6 +372,56 @@ static void scenario_failure_big() {
     OK(fmhip_flush());
 }
 
+// FMHIP_TEST_FAIL_ALLOC_AT is set by the caller (without it: the counting run).  What `failure_big` never walks, because it runs with the
+// JIT off: ONE loop-shaped component too long for one launch, with copies that exist as a description, with the kernels of its plan
+// there at once (FMHIP_JIT_SYNC on the null device) — the peeled launch of the whole group or, with FMHIP_PEEL_MAX_WORKGROUPS=0 in the
+// caller's environment, the cutting on first use with the rolled kernel inside the cuts.  The shape is long_chain of 76 periods, the fewest
+// whose loop is found (its operands repeat every 15 periods, a loop has five iterations at least).  Flush A: the expectation of the
+// original's root while the copies are pending — and four further members of the same shape with nodes of their own: the flush takes the
+// moments of every pending root along only when four times the asked root's weight is pending (Engine::reduce).  Flush B, whatever became
+// of A: everything released, the same shape recorded again, flushed plainly, every root read — twice, since a shape whose cutting A did
+// not finish is rightly cut by the first of them; the launches of the second, counted alone, say whether the shape's plan is what a plan
+// should be (cuts written twice would run twice).
+static void scenario_failure_plan() {
+    OK(fmhip_set_fusion(1, nullptr));
+    OK(fmhip_set_jit(FMHIP_JIT_SYNC, nullptr));
+    const int64_t n = 64; const int copies = 2, further = 4, periods = 76;
+    Inputs in = make_inputs(n, copies + further);
+    std::vector<V> roots, out;
+    auto record_shape = [&] {
+        OK(fmhip_fusion_hold(1, nullptr));
+        roots = long_chain(in.dev[0].data(), in.shared, in.scal[0].data(), periods);
+        for (int j = copies + 1; j <= copies + further; ++j) roots.push_back(long_chain(in.dev[(size_t)j].data(), in.shared, in.scal[(size_t)j].data(), periods)[0]);
+        std::vector<V> to;
+        for (int j = 1; j <= copies; ++j) for (V v : in.dev[(size_t)j]) to.push_back(v);
+        out.assign((size_t)copies, 0);
+        OK(fmhip_graph_clone(roots.data(), 1, copies, in.dev[0].data(), to.data(), 3, nullptr, 0, out.data()));
+        OK(fmhip_fusion_hold(0, nullptr));
+    };
+    fmhip_pool_stats_t before, after;
+    record_shape();
+    OK(fmhip_pool_stats(&before));
+    fmhip_moments m;
+    const int st_a = fmhip_reduce_moments(roots[0], 0.0, &m);
+    OK(fmhip_pool_stats(&after));
+    const long long allocs_before = (long long)(before.n_alloc_hits + before.n_alloc_misses), allocs_a = (long long)(after.n_alloc_hits + after.n_alloc_misses) - allocs_before;
+    int st_b = FMHIP_OK;
+    for (int pass = 0; pass < 2 && st_b == FMHIP_OK; ++pass) {      // (the first pass cuts the shape where A did not get that far; the second is counted)
+        rel(roots); rel(out);
+        OK(fmhip_flush());
+        record_shape();
+        OK(fmhip_pool_stats(&before));
+        st_b = fmhip_flush();
+        OK(fmhip_pool_stats(&after));
+        if (st_b == FMHIP_OK) { read_all(roots, n); read_all(out, n); }
+    }
+    std::printf("failure_plan: %lld allocations before flush A, %lld in it, flush A status %d; flush B status %d, %lld launches\n", allocs_before, allocs_a, st_a, st_b,
+                (long long)(after.n_kernel_launches - before.n_kernel_launches));
+    rel(roots); rel(out);
+    free_inputs(in);
+    OK(fmhip_flush());
+}
+
 // cost of a recorded method on the caller's side (and of its replay on the shards): not a sanitizer scenario — build with -O2, no sanitizer
 static void scenario_speed() {
     OK(fmhip_set_fusion(1, nullptr));
@@ -587,10 +637,10 @@ static void scenario_collective() {
 int main(int argc, char** argv) {
     struct Scenario { const char* name; void (*run)(); };
     const Scenario all[] = { { "basic", scenario_basic }, { "replicas", scenario_replicas }, { "expectations", scenario_expectations },
-                             { "programs", scenario_programs_and_steps }, { "threads", scenario_threads }, { "shared", scenario_shared }, { "failure", scenario_failure }, { "failure_big", scenario_failure_big }, { "speed", scenario_speed }, { "lagging", scenario_lagging }, { "oom", scenario_oom }, { "collective", scenario_collective } };
+                             { "programs", scenario_programs_and_steps }, { "threads", scenario_threads }, { "shared", scenario_shared }, { "failure", scenario_failure }, { "failure_big", scenario_failure_big }, { "failure_plan", scenario_failure_plan }, { "speed", scenario_speed }, { "lagging", scenario_lagging }, { "oom", scenario_oom }, { "collective", scenario_collective } };
     std::vector<std::string> wanted;
     for (int i = 1; i < argc; ++i) wanted.push_back(argv[i]);
-    const bool only_failure = wanted.size() == 1 && (wanted[0] == "failure" || wanted[0] == "failure_big");      // (the hook counts the allocations of the whole process: one cycle)
+    const bool only_failure = wanted.size() == 1 && (wanted[0] == "failure" || wanted[0] == "failure_big" || wanted[0] == "failure_plan");      // (the hook counts the allocations of the whole process: one cycle)
     for (int cycle = 0; cycle < (only_failure ? 1 : 2); ++cycle) {                  // twice: shutdown and re-initialisation in between
         // FMNULL_DEVICES=N: the same scenarios behind a device list of N shards (sharded.cpp: one engine and one worker thread per shard)
         const int n_devices = std::getenv("FMNULL_DEVICES") ? std::atoi(std::getenv("FMNULL_DEVICES")) : 1;
@@ -603,7 +653,7 @@ int main(int argc, char** argv) {
         // FMNULL_THREAD_ENGINES=1: an engine per caller thread (fmhip_set_thread_engines) — the scenarios' threads record side by side
         if (n_devices <= 1 && std::getenv("FMNULL_THREAD_ENGINES")) { int was = -1; OK(fmhip_set_thread_engines(1, &was)); if (was != 0) std::abort(); }
         for (const Scenario& s : all) {
-            bool run = wanted.empty() ? (std::strcmp(s.name, "failure") != 0 && std::strcmp(s.name, "failure_big") != 0 && std::strcmp(s.name, "speed") != 0 && std::strcmp(s.name, "oom") != 0) : false;
+            bool run = wanted.empty() ? (std::strcmp(s.name, "failure") != 0 && std::strcmp(s.name, "failure_big") != 0 && std::strcmp(s.name, "failure_plan") != 0 && std::strcmp(s.name, "speed") != 0 && std::strcmp(s.name, "oom") != 0) : false;
             for (const std::string& w : wanted) run |= w == s.name;
             if (!run) continue;
             s.run();

@@ -472,3 +472,72 @@ def test_moments_into_a_device_buffer_past_one_gather_launch(gpu):
     finally:
         gpu.set_jit(prev_jit)
         gpu.set_fusion(prev_fusion)
+
+
+@pytest.mark.parametrize("mode", ["host_array", "arena_slots"])
+@pytest.mark.parametrize("site", ["small_group", "peeled_group", "merged_family"])
+def test_moments_taken_along_are_those_of_the_stand_alone_reduction(gpu, oracle, site, mode):
+    """The three launch sites that take the moments of their roots along hand them over through ONE receiver (runtime.hpp: RootMoments): a
+    group of four small independent expressions (run_dags), a peeled group of three members of which two are identical — a common row:
+    two roots receive the same slot — (run_plan: run_peeled_group), a merged family of two chain lengths (merge_run_batch).  Each once
+    with the flush triggered by an expectation (Engine::reduce with much pending: a host array the launch is waited for) and once while the
+    caller is still recording under the engine's step-group hold (slots of the pinned arena).  n = 2049 is one full pass of 256 lanes x 8
+    elements plus one element.  The moments every root received are, bit for bit, those of a stand-alone reduction of the stored vector,
+    and asking for them costs no launch.  (test_one_expectation_asked_many_pending and test_gpu_merged_chains.py compare such moments,
+    at other sizes, with those of other fused launches; none of the six cells is asserted there against the stand-alone reduction.)"""
+    n = 2049
+    rng = np.random.default_rng(2049)
+    L_h = [oracle.f_from_double(rng.uniform(0.005, 0.04, n)) for _ in range(24)]
+    num_h = oracle.f_from_double(rng.uniform(1.0, 1.3, n))
+    prev_fusion, prev_jit = gpu.set_fusion(True), gpu.set_jit(gpu.JIT_SYNC)
+    launches = lambda: gpu.pool_stats().n_kernel_launches
+    try:
+        L = [gpu.DeviceVector.from_host(x) for x in L_h]
+        num = gpu.DeviceVector.from_host(num_h)
+        bm = gpu.BrownianMotionHip(gpu.TimeDiscretization(0.0, 8, 0.25), 1, n, 99)
+
+        def build():
+            if site == "small_group":
+                return [L[k].v1s1("ADD_S", 1.0 + k).v1s0("EXP").v2s0("MULT", L[k + 4]) for k in range(4)]
+            if site == "peeled_group":
+                return [swaption_like_chain(lambda p: L[p], 24, num, strike, 0.5) for strike in (0.02, 0.02, 0.03)]
+            return [swaption_like_chain(lambda p: L[p], periods, num, 0.02, 0.5) for periods in (24, 16)]
+
+        for round_ in range(3):                              # (round 0 meets the shapes for the first time; families are found from round 1 on)
+            before = gpu.engine_stats()
+            if mode == "host_array":
+                soft = gpu.fusion_hold(2)
+                roots = build()
+                pad = [L[k % 24].v1s1("MULT_S", 1.0 + 1e-3 * k).v1s1("ADD_S", 0.5).v1s0("ABS") for k in range(100)]      # much pending: 300 methods
+                gpu.fusion_hold(soft)
+                pad[0].moments()                             # everything pending runs, the launches take the moments of their roots along
+            else:
+                state = L[0]
+                for step in range(3):                        # "the simulation": the engine's hold is on afterwards
+                    state = state.v2s1("ADDPRODUCT_VS", bm.getBrownianIncrement(step, 0).realizations, 0.1)
+                roots = build()
+                launches_before = launches()
+                for _ in range(2200):                        # the caller goes on recording: after 2000 methods the engine runs what is pending, without waiting
+                    L[0].v1s1("MULT_S", 1.0)
+                    if launches() != launches_before:
+                        break
+                else:
+                    raise AssertionError("the engine did not run the pending work on its own")
+            after = gpu.engine_stats()
+            launches_before = launches()
+            got = [r.moments() for r in roots]
+            assert launches() == launches_before, (round_, "the moments came with the launches that computed the values")
+            for i, (r, g) in enumerate(zip(roots, got)):
+                w = gpu.DeviceVector.from_host(r.to_float32()).moments()
+                for f in ("sum", "sumsq", "min", "max"):
+                    assert np.float64(getattr(g, f)).tobytes() == np.float64(getattr(w, f)).tobytes(), (round_, i, f, getattr(g, f), getattr(w, f))
+            if round_ == 2 and site == "peeled_group":
+                assert after["common_rows"] > before["common_rows"], "the two identical members were not recognised as a common row"
+            if round_ == 2 and site == "merged_family":
+                assert after["merged_launches"] > before["merged_launches"], "the two chain lengths did not run as a merged family"
+            del roots, got
+    finally:
+        gpu.fusion_hold(0)
+        gpu.flush()
+        gpu.set_jit(prev_jit)
+        gpu.set_fusion(prev_fusion)

@@ -72,6 +72,35 @@ def test_a_failing_allocation_anywhere_in_a_flush_of_several_replicated_groups_l
         assert ("flush status 0" in r.stdout) == (at == before + inside + 1), (at, r.stdout[-300:])
 
 
+@pytest.mark.parametrize("peel_env", [{}, {"FMHIP_PEEL_MAX_WORKGROUPS": "0"}], ids=["peeled", "cut_on_first_use"])
+def test_a_failing_allocation_anywhere_in_a_planned_flush_leaves_the_plan_whole(built, tmp_path, peel_env):
+    """Scenario `failure_plan`: what `failure_big` (JIT off: segments only) never walks.  One loop-shaped shape too long for one launch —
+    the original, two copies that exist as a description, four further members — with its kernels there at once (FMHIP_JIT_SYNC).
+    Flush A, the expectation of the original's root, takes the moments of every pending root along: by default as ONE peeled launch of the
+    whole group; with FMHIP_PEEL_MAX_WORKGROUPS=0 the plan has no segments yet, run_plan cuts them with the members that have nodes and
+    runs the copies from the cuts, the rolled kernel inside.  The hook is put on every allocation of flush A and on one beyond the end of
+    the process's (the position right behind flush A is an allocation of flush B).  Flush B — everything released, the same shape recorded
+    again, flushed plainly, every root read; done twice, the first pass cuts the shape where A did not get that far — must then be OK
+    both times, the second with exactly the launches of the counting run's: a plan that was cut twice, or left half-cut, would run other
+    launches.  On the engine before the cuts were committed whole and before a partly run replicated component was closed
+    (replicas_after_failure), the second configuration ended in a use after free at every position behind the first segment's launch:
+    the copies, still described, ran with what was left of the original and read a value of the ORIGINAL's first segment."""
+    import re
+    line = re.compile(r"failure_plan: (\d+) allocations before flush A, (\d+) in it, flush A status (-?\d+); flush B status (-?\d+), (\d+) launches")
+    count = run(os.path.join(built, "drive_asan"), tmp_path, "failure_plan", **peel_env)
+    assert count.returncode == 0 and "Sanitizer" not in count.stderr, count.stdout[-500:] + count.stderr[-6000:]
+    before, inside, status_a, status_b, launches_b = map(int, line.search(count.stdout).groups())
+    assert status_a == 0 and status_b == 0 and launches_b > 0
+    assert 0 < inside <= 80, "the sweep takes every allocation of flush A, 80 positions at the most, and one beyond"
+    for at in [*range(before + 1, before + inside + 1), 10**9]:
+        r = run(os.path.join(built, "drive_asan"), tmp_path, "failure_plan", FMHIP_TEST_FAIL_ALLOC_AT=str(at), **peel_env)
+        assert r.returncode == 0 and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, (at, r.stdout[-500:] + r.stderr[-6000:])
+        assert "failure_plan done" in r.stdout
+        _, _, a, b, launches = map(int, line.search(r.stdout).groups())
+        assert a in (0, -3), (at, a)                 # FMHIP_OK or FMHIP_ERR_OUT_OF_MEMORY
+        assert b == 0 and launches == launches_b, (at, b, launches, launches_b)
+
+
 def test_a_full_device(built, tmp_path):
     """The pool's last resort (drop every cached slab, try once more) on the first allocation of a new size class, the out-of-memory
     status, and a fused launch that cannot get its output — on a null device of 800 MB.  Round 5: heap corruption on the real device
