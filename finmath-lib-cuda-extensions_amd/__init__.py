@@ -29,6 +29,8 @@ from .prefix import weighted_expected_shortfall, weighted_quantiles
 from .tabulated import TabulatedFunction, table_apply, table_apply_host
 from .analytic import NORMAL_CDF, NORMAL_DENSITY, NORMAL_QUANTILE, NamedFunction, function_apply, function_apply_host, normal_scores
 from .analytic import bachelier_option_value, black_scholes_option_value, option_formula, option_formula_double, option_formula_host
+from .analytic import (bachelier_implied_volatility, black_scholes_implied_volatility, convert_volatility, implied_volatility,
+                       implied_volatility_double, implied_volatility_host)
 from .nested import (block_max, block_means, block_min, block_moments, block_moments_host, block_order_statistics, block_order_statistics_host, block_quantile_expectations,
                      block_quantiles, block_sort, block_sort_host, device_nested, repeat_each, tile)
 from .cross_section import (argmax_across, argmin_across, cross_order_statistics_host, cross_select_host, device_cross_order, max_across, median_across, min_across,

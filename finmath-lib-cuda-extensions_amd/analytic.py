@@ -9,6 +9,10 @@ of host/gamma_icdf.hpp, every operation rounded on its own.  The device's bits a
 fmhip_option_formula_host.  The formulas are finmath-lib's AnalyticFormulas.blackScholesGeneralizedOptionValue / bachelierOptionValue as
 remembered, not as read: that class is not part of the reference tree.
 
+The inverse of the formulas' value in the volatility (fmhip_implied_volatility and its _host twin; host/implied_volatility.hpp; DESIGN.md
+§4.25) is below them: implied_volatility with its partials in the price and the forward, a put by parity, a strike per path, the conversion
+between a lognormal and a normal volatility, and adjoint differentiation through a quoted volatility.
+
 FMHIP_DEVICE_ANALYTIC=0, read per call: the A/B switch and the fallback — the vectors are downloaded, the definition runs on one core, and
 the results are uploaded.  The device path never falls back on its own: a missing kernel is an error.
 """
@@ -258,3 +262,210 @@ def black_scholes_option_value(forward, volatility, maturity, strike, payoff_uni
 def bachelier_option_value(forward, volatility, maturity, strike, payoff_unit=1.0):
     """payoff_unit · ((F − K)·Φ(d) + σ√T·φ(d)), d = (F − K)/(σ√T): AnalyticFormulas.bachelierOptionValue per path."""
     return option_formula("bachelier", forward, volatility, maturity, strike, payoff_unit, ("value",))[0]
+
+
+# ---------------------------------------------------------------- the implied volatility (DESIGN.md §4.25)
+IMPLIED_OUTPUTS = {"volatility": 1, "d_price": 2, "d_forward": 4}
+
+
+def _implied_mask(outputs):
+    if isinstance(outputs, str): outputs = (outputs,)
+    outputs = tuple(outputs)
+    if not outputs or any(o not in IMPLIED_OUTPUTS for o in outputs) or len(set(outputs)) != len(outputs):
+        raise ValueError(f"implied_volatility: outputs {outputs!r} (distinct names out of {sorted(IMPLIED_OUTPUTS)})")
+    return outputs, sum(IMPLIED_OUTPUTS[o] for o in outputs), [o for o in ("volatility", "d_price", "d_forward") if o in outputs]
+
+
+def _time_value_double(m, F, s, K):
+    """The time value of total volatility s from the out-of-the-money side, in double."""
+    if m == 0:
+        A, B = min(F, K), max(F, K)
+        d = (math.log(A / B) + 0.5 * s * s) / s
+        return A * _cdf(d) - B * _cdf(d - s)
+    gap = abs(F - K)
+    return s * _density(gap / s) - gap * _cdf(-gap / s)
+
+
+def implied_volatility_double(model, price, forward, maturity, strike, payoff_unit=1.0) -> dict:
+    """The implied volatility at doubles, in double: {"volatility", "d_price", "d_forward"} with the semantics of include/fmhip.h.  What a
+    call with deterministic operands returns: a bisection on the time value in ln s, then Newton steps on the value."""
+    m = _model(model)
+    T, K = _check_scalars(maturity, strike)
+    P, F, unit = float(price), float(forward), float(payoff_unit)
+    nan = {"volatility": math.nan, "d_price": math.nan, "d_forward": math.nan}
+    if any(v != v for v in (P, F, unit)) or not unit > 0.0: return nan
+    c = P / unit
+    if c != c: return nan
+    intrinsic = max(F - K, 0.0)
+    if c == intrinsic: return dict(nan, volatility=0.0)
+    if not T > 0.0 or math.isinf(F) or c < intrinsic: return nan
+    if m == 0:
+        if not (F > 0.0 and K > 0.0) or c > F: return nan
+        if c == F: return dict(nan, volatility=math.inf)
+    elif math.isinf(c): return dict(nan, volatility=math.inf)
+    tv = c - intrinsic
+    lo, hi = -80.0, 80.0                                                      # ln s
+    scale = 0.0 if m == 0 else math.log(max(abs(F - K), tv, 5e-324))
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if _time_value_double(m, F, math.exp(mid + scale), K) < tv: lo = mid
+        else: hi = mid
+    s = math.exp(0.5 * (lo + hi) + scale)
+    for _ in range(3):
+        slope = _density((math.log(min(F, K) / max(F, K)) + 0.5 * s * s) / s) * min(F, K) if m == 0 else _density(abs(F - K) / s)
+        if not slope > 0.0: break
+        step = (_time_value_double(m, F, s, K) - tv) / slope
+        if not abs(step) < 0.5 * s: break
+        s -= step
+    sigma = s / math.sqrt(T)
+    at = option_formula_double(model, F, sigma, T, K, 1.0)
+    if sigma == 0.0 or math.isinf(sigma) or not at["vega"] > 0.0: return dict(nan, volatility=sigma)
+    return {"volatility": sigma, "d_price": 1.0 / (unit * at["vega"]), "d_forward": -at["delta"] / at["vega"]}
+
+
+def _implied_call(m, host, scalars, n, T, K, mask, n_out):
+    out = [np.empty(n, dtype=np.float32) for _ in range(n_out)]
+    cols = (C.c_void_p * n_out)(*[o.ctypes.data for o in out])
+    ptr = [a.ctypes.data_as(C.c_void_p) if a is not None else None for a in host]
+    N.check(N.lib().fmhip_implied_volatility_host(m, ptr[0], scalars[0], ptr[1], scalars[1], ptr[2], scalars[2], n, T, K, mask, cols))
+    return out
+
+
+def implied_volatility_host(model, price, forward, maturity, strike, payoff_unit=1.0, outputs=("volatility",)) -> list:
+    """The DEFINITION (fmhip_implied_volatility_host) over host arrays: price, forward and payoff_unit are float32 arrays of one size or
+    numbers (fp64 scalars), at least one an array; one float32 array per name of `outputs`, in the order given."""
+    m = _model(model)
+    T, K = _check_scalars(maturity, strike)
+    names, mask, in_bit_order = _implied_mask(outputs)
+    arrays, scalars, n = [], [], None
+    for o in (price, forward, payoff_unit):
+        if np.isscalar(o):
+            arrays.append(None); scalars.append(float(o))
+        else:
+            a = np.ascontiguousarray(o, dtype=np.float32).ravel()
+            if n is not None and a.size != n: raise ValueError("implied_volatility: arrays of different size")
+            n = a.size
+            arrays.append(a); scalars.append(0.0)
+    if n is None: raise ValueError("implied_volatility_host: at least one operand is an array (implied_volatility_double takes numbers)")
+    by_name = dict(zip(in_bit_order, _implied_call(m, arrays, scalars, n, T, K, mask, len(in_bit_order))))
+    return [by_name[o] for o in names]
+
+
+def _implied_vectors(m, operands, T, K, mask, n_out):
+    """fmhip_implied_volatility on DeviceVectors and floats: n_out new DeviceVectors, in bit order."""
+    handles = [o.handle if isinstance(o, DeviceVector) else 0 for o in operands]
+    scalars = [0.0 if isinstance(o, DeviceVector) else float(o) for o in operands]
+    n = next(o.n for o in operands if isinstance(o, DeviceVector))
+    if not device_analytic():
+        host = [o.to_float32() if isinstance(o, DeviceVector) else None for o in operands]
+        return [DeviceVector.from_host(o) for o in _implied_call(m, host, scalars, n, T, K, mask, n_out)]
+    out = (C.c_int64 * n_out)()
+    N.check(N.lib().fmhip_implied_volatility(m, handles[0], scalars[0], handles[1], scalars[1], handles[2], scalars[2], T, K, mask, out))
+    return [DeviceVector(int(h), n) for h in out]
+
+
+def _inner_implied(model, operands, T, K, names, inner_factory=None):
+    """The inverse on plain (not differentiable) operands — RandomVariableHip, numbers, or with inner_factory any RandomVariable with
+    getRealizations: {name: RandomVariable} with the maximum filtration time."""
+    m = _model(model)
+    _, mask, in_bit_order = _implied_mask(names)
+    times = [o.getFiltrationTime() for o in operands if not np.isscalar(o)]
+    time = max(times) if times else -math.inf
+    make = (lambda value: RandomVariableHip(time, value)) if inner_factory is None else (lambda value: inner_factory.createRandomVariable(time, value))
+    if all(np.isscalar(o) or o.isDeterministic() for o in operands):
+        P, F, unit = (float(o) if np.isscalar(o) else o.doubleValue() for o in operands)
+        values = implied_volatility_double(model, P, F, T, K, unit)
+        return {o: make(values[o]) for o in in_bit_order}
+    if inner_factory is None:
+        for o in operands:
+            if not np.isscalar(o) and not isinstance(o, RandomVariableHip): raise TypeError(f"implied_volatility: {type(o).__name__} operands need the factory that made them (an AAD wrapper carries it)")
+        plain = [float(o) if np.isscalar(o) else o.doubleValue() if o.isDeterministic() else o.realizations for o in operands]
+        return {o: make(v) for o, v in zip(in_bit_order, _implied_vectors(m, plain, T, K, mask, len(in_bit_order)))}
+    plain = [float(o) if np.isscalar(o) else o.doubleValue() if o.isDeterministic() else np.asarray(o.getRealizations(), dtype=np.float32) for o in operands]
+    return {o: make(v) for o, v in zip(in_bit_order, implied_volatility_host(model, plain[0], plain[1], T, K, plain[2], in_bit_order))}
+
+
+def _scaled(x, y, op):
+    """x op y for numbers and RandomVariables on either side (op: "mult", "div", "add", "sub")."""
+    if np.isscalar(x) and np.isscalar(y):
+        return {"mult": x * y, "div": x / y, "add": x + y, "sub": x - y}[op]
+    if np.isscalar(x):
+        return {"mult": lambda: y.mult(x), "div": lambda: y.vid(x), "add": lambda: y.add(x), "sub": lambda: y.bus(x)}[op]()
+    return getattr(x, op)(y)
+
+
+def implied_volatility(model, price, forward, maturity, strike, payoff_unit=1.0, outputs=("volatility",), put=False):
+    """The volatility per path at which fm.option_formula(model, forward, ·, maturity, strike, payoff_unit) has the value `price`, with —
+    by name in `outputs` — "d_price" = ∂σ/∂price = 1/vega and "d_forward" = ∂σ/∂forward = −delta/vega at the root: price, forward and
+    payoff_unit are RandomVariableHip or numbers, maturity >= 0 is a number, strike a number or a RandomVariable.  One launch whatever the
+    outputs; operands stay where they are.  Returns one RandomVariable per name, as a tuple in the order given; the filtration time is
+    the operands' maximum.  Deterministic operands give a deterministic result computed in double.  A price at the intrinsic value gives
+    volatility 0, a Black–Scholes price equal to the forward +∞ (partials NaN); a price outside the no-arbitrage bounds, a payoff unit
+    <= 0, maturity 0 with a time value, and a NaN give NaN (include/fmhip.h has the list).
+
+    put=True: `price` is a put's; it is converted by parity, price + payoff_unit·(forward − strike), before the call, and "d_forward"
+    is the put's.  A strike that is a RandomVariable is normalised away — Black–Scholes: price/K, forward/K, strike 1; Bachelier:
+    forward − K, strike 0 — the entry point keeps a scalar strike; the partials are those in the operands given.
+
+    RandomVariableDifferentiableAAD operands: ONE launch with payoff unit 1 and all three outputs on c = price/payoff_unit; the partials in
+    c and the forward are recorded, and ∂σ/∂payoff_unit = −(price/payoff_unit)·∂σ/∂price follows from the recorded division.  A "d_price" or
+    "d_forward" asked for by name is, as without AAD, the partial in the operand given (a put's, with a strike per path), itself not
+    differentiable further."""
+    from .differentiable import RandomVariableDifferentiableAAD, _Node
+    names, _, _ = _implied_mask(outputs)
+    T, _ = _check_scalars(maturity, 0.0)
+    m = _model(model)
+    given_forward, K_vector = forward, None
+    if put: price = _scaled(price, _scaled(payoff_unit, _scaled(forward, strike, "sub"), "mult"), "add")
+    if not np.isscalar(strike):
+        if strike.isDeterministic(): strike = strike.doubleValue()
+        elif m == 0: K_vector, price, forward, strike = strike, _scaled(price, strike, "div"), _scaled(forward, strike, "div"), 1.0
+        else: forward, strike = _scaled(forward, strike, "sub"), 0.0
+    _, K = _check_scalars(maturity, strike)
+    operands = (price, forward, payoff_unit)
+    if not any(isinstance(o, RandomVariableDifferentiableAAD) for o in operands):
+        wanted = set(names) | ({"d_price"} if put and "d_forward" in names else set())
+        results = _inner_implied(model, operands, T, K, tuple(o for o in ("volatility", "d_price", "d_forward") if o in wanted))
+        if K_vector is not None:                                                   # ∂/∂(price/K) and ∂/∂(forward/K) to ∂/∂price and ∂/∂forward
+            for name in ("d_price", "d_forward"):
+                if name in results: results[name] = results[name].div(K_vector)
+        if put and "d_forward" in results: results["d_forward"] = results["d_forward"].add(_scaled(results["d_price"], payoff_unit, "mult"))
+        return tuple(results[o] for o in names)
+    factory = next(o.factory for o in operands if isinstance(o, RandomVariableDifferentiableAAD))
+    c = price if np.isscalar(payoff_unit) and float(payoff_unit) == 1.0 else _scaled(price, payoff_unit, "div")
+    ops = (c, forward)
+    inner = [o.values if isinstance(o, RandomVariableDifferentiableAAD) else o for o in ops]
+    hip = all(np.isscalar(o) or isinstance(o, RandomVariableHip) for o in inner)
+    if not hip and factory is None: raise NotImplementedError("implied_volatility on this inner implementation needs the factory that made the variables")
+    unit = _inner_implied(model, (inner[0], inner[1], 1.0), T, K, ("volatility", "d_price", "d_forward"), None if hip else factory.inner)
+    nodes = tuple(o.node if isinstance(o, RandomVariableDifferentiableAAD) else None for o in ops)
+    sigma = RandomVariableDifferentiableAAD(unit["volatility"], _Node("IMPLIED_VOLATILITY", nodes, (unit["d_price"], unit["d_forward"]), 0.0), factory)
+    results = {"volatility": sigma}
+    if "d_price" in names or "d_forward" in names:
+        # the partials asked for by name: those of the plain branch, in the operands GIVEN — from ∂/∂c and ∂/∂(the forward handed to the entry
+        # point) by the chain rule on the inner values; not differentiable further
+        plain = lambda o: o.values if isinstance(o, RandomVariableDifferentiableAAD) else o
+        d_price, d_forward = unit["d_price"], unit["d_forward"]
+        if not (np.isscalar(payoff_unit) and float(payoff_unit) == 1.0): d_price = _scaled(d_price, plain(payoff_unit), "div")      # c = price/N
+        if K_vector is not None: d_price, d_forward = _scaled(d_price, plain(K_vector), "div"), _scaled(d_forward, plain(K_vector), "div")
+        if put: d_forward = _scaled(d_forward, _scaled(d_price, plain(payoff_unit), "mult"), "add")
+        for name, value in (("d_price", d_price), ("d_forward", d_forward)):
+            if name in names: results[name] = RandomVariableDifferentiableAAD(value, None, factory)
+    return tuple(results[o] for o in names)
+
+
+def black_scholes_implied_volatility(price, forward, maturity, strike, payoff_unit=1.0, put=False):
+    """The σ with payoff_unit · (F·Φ(d₊) − K·Φ(d₋)) = price, per path: AnalyticFormulas.blackScholesOptionImpliedVolatility."""
+    return implied_volatility("black_scholes", price, forward, maturity, strike, payoff_unit, ("volatility",), put)[0]
+
+
+def bachelier_implied_volatility(price, forward, maturity, strike, payoff_unit=1.0, put=False):
+    """The σ with payoff_unit · ((F − K)·Φ(d) + σ√T·φ(d)) = price, per path: AnalyticFormulas.bachelierOptionImpliedVolatility."""
+    return implied_volatility("bachelier", price, forward, maturity, strike, payoff_unit, ("volatility",), put)[0]
+
+
+def convert_volatility(from_model, to_model, forward, volatility, maturity, strike):
+    """The volatility of `to_model` that gives the price `from_model` gives with `volatility` (lognormal to normal, or back), per path:
+    one option_formula followed by one implied_volatility — two launches."""
+    value, = option_formula(from_model, forward, volatility, maturity, strike, 1.0, ("value",))
+    return implied_volatility(to_model, value, forward, maturity, strike, 1.0, ("volatility",))[0]

@@ -915,6 +915,21 @@ int fmhip_option_formula(int model, fmhip_vec forward, double forward_scalar, fm
     return guarded([&] { Engine::get().option_formula(model, forward, forward_scalar, volatility, volatility_scalar, payoff_unit, payoff_unit_scalar, maturity, strike, outputs, out); });
 }
 
+// ---------------------------------------------------------------- implied volatility per path (implied_volatility_engine.hpp)
+int fmhip_implied_volatility_host(int model, const float* price, double price_scalar, const float* forward, double forward_scalar, const float* payoff_unit,
+                                  double payoff_unit_scalar, int64_t n, double maturity, double strike, int outputs, float* const* out) {
+    return host_only([&] { fm::implied_volatility_host_checked(model, price, price_scalar, forward, forward_scalar, payoff_unit, payoff_unit_scalar, n, maturity, strike, outputs, out); });
+}
+int fmhip_implied_volatility(int model, fmhip_vec price, double price_scalar, fmhip_vec forward, double forward_scalar, fmhip_vec payoff_unit,
+                             double payoff_unit_scalar, double maturity, double strike, int outputs, fmhip_vec* out) {
+    FRONT(implied_volatility(model, price, price_scalar, forward, forward_scalar, payoff_unit, payoff_unit_scalar, maturity, strike, outputs, out));
+    // (all three in the list: a handle of 0 stays 0, the scalar beside it)
+    const fmhip_vec operands[3] = { price, forward, payoff_unit };
+    TE_CHECKED_LOCAL(fm::implied_check(model, price, forward, payoff_unit, maturity, strike, outputs, out), te_operands(0, operands, 3, nullptr, 0), L,
+                     fmhip_implied_volatility(model, L[0], price_scalar, L[1], forward_scalar, L[2], payoff_unit_scalar, maturity, strike, outputs, out));
+    return guarded([&] { Engine::get().implied_volatility(model, price, price_scalar, forward, forward_scalar, payoff_unit, payoff_unit_scalar, maturity, strike, outputs, out); });
+}
+
 // ---------------------------------------------------------------- nested simulation: block moments and the repeat (nested_engine.hpp)
 int fmhip_block_moments_host(const float* v, int64_t n, int64_t block, uint32_t mask, float* outs) {
     return host_only([&] { fm::block_moments_host_checked(v, n, block, mask, outs); });

@@ -432,6 +432,12 @@ public:
     void option_formula(int model, fmhip_vec forward, double forward_scalar, fmhip_vec volatility, double volatility_scalar, fmhip_vec payoff_unit,
                         double payoff_unit_scalar, double maturity, double strike, int outputs, fmhip_vec* out);
 
+    // implied volatility per path (implied_volatility_engine.hpp): the inverse of option_formula's value in the volatility —
+    // sigma / ∂sigma/∂price / ∂sigma/∂forward (a mask) of a call whose price, forward and payoff unit are a vector or — handle 0 — the
+    // scalar beside it; out: new, materialised vectors from one launch.  Checked before anything is flushed; out written only on success.
+    void implied_volatility(int model, fmhip_vec price, double price_scalar, fmhip_vec forward, double forward_scalar, fmhip_vec payoff_unit,
+                            double payoff_unit_scalar, double maturity, double strike, int outputs, fmhip_vec* out);
+
     // nested simulation (nested_engine.hpp): the moments of the n / block consecutive blocks of up to four vectors — sum, mean,
     // population variance by a mask, fp64 sums in an association that is a function of `block` alone (host/block_moments.hpp) — as new,
     // materialised vectors of n / block elements, outs[i·popcount(mask) + j]; and the repeat out[(t·n + p)·each + e] = v[p], bit for bit.
@@ -928,6 +934,11 @@ void analytic_check_formula(int model, fmhip_vec forward, fmhip_vec volatility, 
 void function_apply_host_checked(const float* x, int64_t n, const int* kinds, int n_functions, float* const* out);
 void option_formula_host_checked(int model, const float* forward, double forward_scalar, const float* volatility, double volatility_scalar, const float* payoff_unit,
                                  double payoff_unit_scalar, int64_t n, double maturity, double strike, int outputs, float* const* out);
+// the same for fmhip_implied_volatility, and the definition behind its _host twin (implied_volatility_engine.hpp; the rules are
+// host/implied_volatility.hpp's): both throw FMHIP_ERR_INVALID_ARGUMENT
+void implied_check(int model, fmhip_vec price, fmhip_vec forward, fmhip_vec payoff_unit, double maturity, double strike, int outputs, const fmhip_vec* out);
+void implied_volatility_host_checked(int model, const float* price, double price_scalar, const float* forward, double forward_scalar, const float* payoff_unit,
+                                     double payoff_unit_scalar, int64_t n, double maturity, double strike, int outputs, float* const* out);
 // the same for fmhip_block_moments / fmhip_vec_repeat, and the definition behind fmhip_block_moments_host (nested_engine.hpp; the rules are
 // host/block_moments.hpp's): all throw FMHIP_ERR_INVALID_ARGUMENT
 void nested_check_moments(const fmhip_vec* vs, int n_vs, int64_t block, uint32_t mask, const fmhip_vec* outs);

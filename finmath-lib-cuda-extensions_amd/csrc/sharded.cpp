@@ -1018,6 +1018,21 @@ int option_formula(int model, fmhip_vec forward, double forward_scalar, fmhip_ve
     });
 }
 
+// Implied volatility per path (implied_volatility_engine.hpp).  Elementwise, as the option formulas are.
+int implied_volatility(int model, fmhip_vec price, double price_scalar, fmhip_vec forward, double forward_scalar, fmhip_vec payoff_unit,
+                       double payoff_unit_scalar, double maturity, double strike, int outputs, fmhip_vec* out) {
+    return fronted([&](Shards& s) {
+        implied_check(model, price, forward, payoff_unit, maturity, strike, outputs, out);
+        std::vector<fmhip_vec> vectors;
+        for (fmhip_vec h : { price, forward, payoff_unit }) if (h) vectors.push_back(h);
+        const int64_t n = front_size(s, vectors.data(), (int)vectors.size(), "implied volatility", false);
+        const int n_out = (outputs & 1) + ((outputs >> 1) & 1) + ((outputs >> 2) & 1);      // one new vector per set bit of the mask
+        produce_per_shard(s, n, n_out, out, [&](Worker& w, fmhip_vec* got) {            // (a handle of 0 stays 0 on every shard: the scalar)
+            return fmhip_implied_volatility(model, w.at(price), price_scalar, w.at(forward), forward_scalar, w.at(payoff_unit), payoff_unit_scalar, maturity, strike, outputs, got);
+        });
+    });
+}
+
 // Nested simulation (nested_engine.hpp).  The blocks of a sample that is spread over several shards would straddle them, and a repeat's
 // output is laid out over the whole sample (one_shard).
 int block_moments(const fmhip_vec* vs, int n_vs, int64_t block, uint32_t mask, fmhip_vec* outs) {

@@ -82,6 +82,8 @@ int table_apply(fmhip_vec x, const double* knots, int count, const double* coeff
 int function_apply(fmhip_vec x, const int* kinds, int n_functions, fmhip_vec* out);                                         // per shard
 int option_formula(int model, fmhip_vec forward, double forward_scalar, fmhip_vec volatility, double volatility_scalar, fmhip_vec payoff_unit,
                    double payoff_unit_scalar, double maturity, double strike, int outputs, fmhip_vec* out);                 // per shard
+int implied_volatility(int model, fmhip_vec price, double price_scalar, fmhip_vec forward, double forward_scalar, fmhip_vec payoff_unit,
+                       double payoff_unit_scalar, double maturity, double strike, int outputs, fmhip_vec* out);             // per shard
 int prefix_search(fmhip_vec v, const double* thresholds, int count, int relative, int64_t* positions_out, double* sums_out, double* total_out);
 int block_moments(const fmhip_vec* vs, int n_vs, int64_t block, uint32_t mask, fmhip_vec* outs);      // one shard; more: FMHIP_ERR_UNSUPPORTED
 int vec_repeat(fmhip_vec v, int64_t each, int64_t times, fmhip_vec* out);

@@ -305,6 +305,7 @@ def _partial_times(nd, k, d, const):
     if op == "AVERAGE": return d.average()
     if op == "APPLY_TABLE": return d.mult(X)                                # X holds f'(x): x.apply(f.derivative())
     if op == "OPTION_FORMULA": return d.mult(nd.arg_values[k])               # (delta, vega) of the unit value: analytic.option_formula
+    if op == "IMPLIED_VOLATILITY": return d.mult(nd.arg_values[k])           # (∂σ/∂c, ∂σ/∂F) at the root: analytic.implied_volatility
     raise NotImplementedError(op)
 
 

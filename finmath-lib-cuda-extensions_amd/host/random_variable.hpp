@@ -84,7 +84,7 @@ public:
     virtual RV cos() const = 0;
     // apply maps on the host, as the reference does (a std::function has no name the device could know: a caller who wants Φ, φ, Φ⁻¹ or a
     // Black–Scholes / Bachelier value per path on the device calls fmhip_function_apply / fmhip_option_formula on the handles, DESIGN.md
-    // §4.21; block means per outer path and the repeat of nested simulation are fmhip_block_moments / fmhip_vec_repeat on the handles, §4.22,
+    // §4.21, and the volatility implied by a price per path fmhip_implied_volatility, §4.25; block means per outer path and the repeat of nested simulation are fmhip_block_moments / fmhip_vec_repeat on the handles, §4.22,
     // a quantile or a tail mean per outer path fmhip_block_order_statistics, §4.23; the r-th largest of several variables per path and the
     // variable that holds it are fmhip_cross_order_statistics / fmhip_cross_select on the handles, §4.24);
     // the order statistics below are selected and counted on the DEVICE when the object

@@ -27,6 +27,8 @@ a RandomVariableFactory by injection (LIBORMarketModelCalibrationATMTest.java:35
                             martingale from inner simulations at every exercise date of every outer path (nested.py)
     nested_initial_margin_mc  the dynamic initial margin of a forward contract at a future date: the quantile, per outer state, of the inner
                             P&L over the margin period of risk — a block order statistic (nested.py)
+    forward_implied_volatility_mc  the forward smile: the distribution, at a future date, of the volatility implied by a call's price under
+                            heston_call_mc's scheme — inner means per outer state, inverted per path (analytic.py)
     bermudan_max_call_mc    the same induction for a call on the maximum of several assets, regressed on all monomials of the assets up
                             to a total degree: 10 … 56 basis functions, the wide one-pass normal equations
 """
@@ -276,6 +278,74 @@ def heston_call_conditional_mc(brownian_motion, initial_value, risk_free_rate, v
     volatility = integral.mult((1.0 - rho * rho) / maturity).sqrt()
     value = black_scholes_option_value(forward, volatility, maturity, strike, math.exp(-risk_free_rate * maturity))
     return value.getAverage(), value
+
+
+def forward_implied_volatility_mc(brownian_motion_outer, brownian_motion_inner, inner_paths, initial_value, risk_free_rate, v0, kappa, theta, xi, rho, time, maturity,
+                                  moneyness=(1.0,), quantiles=(0.05, 0.5, 0.95)):
+    """The distribution, at `time`, of the Black–Scholes volatility implied by the price of a call expiring at `maturity` under
+    heston_call_mc's scheme — the FORWARD SMILE — by nested simulation.  Returns one dict per moneyness m: {"moneyness", "mean",
+    "standard_error", "quantiles" (getQuantile at each of `quantiles`, in its convention: the value that this fraction of the paths exceeds),
+    "not_invertible"}.
+    OUTER: the paths of brownian_motion_outer carry (S, v) from the first point of its time discretisation to `time` (a point of it).
+    INNER: inner_paths paths per outer state (nested.repeat_each) carry both on over the steps of brownian_motion_inner until
+    maturity − time has passed (a point of its discretisation, counted from its first).  Per outer path the inner payoffs at the strike
+    m·S_t·exp(r(T − t)) — moneyness m of the forward at t — are reduced by nested.block_means to the undiscounted forward price of the call,
+    and analytic.implied_volatility inverts it with that per-path strike and the maturity T − t.
+    "not_invertible" is the share of outer paths whose implied volatility is NaN or 0 (an inner mean at or outside the bounds); mean,
+    standard error and quantiles are those of the other paths.  Nothing leaves the device but these numbers.  FMHIP_DEVICE_NESTED=0 and
+    FMHIP_DEVICE_ANALYTIC=0 give the same numbers to the last bit: the host definitions are the device's."""
+    from .analytic import implied_volatility
+    from .nested import block_means, repeat_each
+    inner_paths = int(inner_paths)
+    if inner_paths < 1: raise ValueError("at least one inner path per outer path")
+    if brownian_motion_inner.getNumberOfPaths() != brownian_motion_outer.getNumberOfPaths() * inner_paths:
+        raise ValueError("the inner Brownian motion has not inner_paths paths per outer path")
+    if not maturity > time: raise ValueError("the option expires after the time at which its volatility is implied")
+    rho_c = math.sqrt(1.0 - rho * rho)
+
+    def advance(bm, x, v, span):                                                # heston_call_mc's step
+        td = bm.getTimeDiscretization()
+        start, i = td.getTime(0), 0
+        while td.getTime(i) - start < span - 1e-12:
+            dt = td.getTimeStep(i)
+            dw1 = bm.getBrownianIncrement(i, 0)
+            vp = v.floor(0.0)
+            sq = vp.sqrt()
+            x = x.add(risk_free_rate * dt).addProduct(vp, -0.5 * dt).addProduct(sq, dw1)
+            if xi != 0.0:
+                dz = dw1.mult(rho).addProduct(bm.getBrownianIncrement(i, 1), rho_c)
+                v = v.addProduct(vp.bus(theta), kappa * dt).addProduct(sq.mult(xi), dz)
+            else:
+                v = v.addProduct(vp.bus(theta), kappa * dt)
+            i += 1
+        if abs(td.getTime(i) - start - span) > 1e-12: raise ValueError("the horizon is not a point of the time discretisation")
+        return x, v
+
+    t0 = brownian_motion_outer.getTimeDiscretization().getTime(0)
+    x, v = advance(brownian_motion_outer, brownian_motion_outer.getRandomVariableForConstant(math.log(initial_value)),
+                   brownian_motion_outer.getRandomVariableForConstant(v0), time - t0)
+    x_inner, _ = advance(brownian_motion_inner, repeat_each(x, inner_paths), repeat_each(v, inner_paths), maturity - time)
+    forward = x.exp().mult(math.exp(risk_free_rate * (maturity - time)))
+    terminal = x_inner.exp()
+    one, zero = forward.mult(0.0).add(1.0), forward.mult(0.0)
+    n_outer = brownian_motion_outer.getNumberOfPaths()
+    results = []
+    for m in moneyness:
+        strike = forward.mult(float(m))
+        price = block_means(terminal.sub(repeat_each(strike, inner_paths)).floor(0.0), inner_paths)
+        sigma, = implied_volatility("black_scholes", price, forward, maturity - time, strike)
+        valid = sigma.choose(one, zero).mult(sigma.mult(-1.0).choose(zero, one))       # 1 where sigma > 0, 0 where it is 0 or a NaN
+        clean = valid.sub(0.5).choose(sigma, zero)
+        share = valid.getAverage()
+        if share > 0.0:
+            mean = clean.getAverage() / share
+            variance = max(clean.squared().getAverage() / share - mean * mean, 0.0)
+            error = math.sqrt(variance / (n_outer * share))
+            levels = [clean.getQuantile(q * share) for q in quantiles]     # getQuantile(q): the value that the fraction q of the sample exceeds; the invalid paths are the zeros at the bottom
+        else:
+            mean, error, levels = math.nan, math.nan, [math.nan for _ in quantiles]
+        results.append({"moneyness": float(m), "mean": mean, "standard_error": error, "quantiles": levels, "not_invertible": 1.0 - share})
+    return results
 
 
 def stochastic_local_volatility_call_mc(brownian_motion, initial_value, risk_free_rate, times, spots, dupire_vols, v0, kappa, theta, xi, rho, maturity, strike,

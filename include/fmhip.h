@@ -542,6 +542,43 @@ int fmhip_option_formula_host(int model, const float* forward, double forward_sc
                               const float* payoff_unit, double payoff_unit_scalar, int64_t n, double maturity, double strike,
                               int outputs, float* const* out);
 
+/* Implied volatility per path on the device: the inverse of fmhip_option_formula's value in sigma, without the vectors
+ * leaving the device.  The definition is host/implied_volatility.hpp, one header for the host and the device under the rules of
+ * host/normal_functions.hpp; the device's bits EQUAL the host entry point's.  A CALL in forward form; the models are FMHIP_FORMULA_*.
+ * Operands: price P, forward F, payoff unit N — each a vector, (double) of its fp32 elements, or with a handle of 0 the fp64 scalar beside
+ * it — and the fp64 scalars maturity T >= 0 and strike K.  Per element, in fp64: c = P/N, intrinsic = max(F - K, 0), tv = c - intrinsic,
+ * decided in this order:
+ *   a NaN among P, F, N; N <= 0                                        the quiet NaN 0x7fc00000 in every output
+ *   c == intrinsic                                                     sigma = +0, both partials NaN
+ *   T == 0; F or K infinite; c < intrinsic                             NaN in every output
+ *   Black-Scholes: F <= 0 or K <= 0; c > F                             NaN in every output
+ *   Black-Scholes: c == F;  Bachelier: c == +inf                       sigma = +inf, both partials NaN
+ *   live: Black-Scholes intrinsic < c < F, Bachelier intrinsic < c < inf
+ *                                                                      sigma the root; d_price = 1/(N*vega1), d_forward = -delta1/vega1,
+ *                                                                      where vega1 and delta1 are fmhip_option_formula's with payoff unit 1
+ *                                                                      at the fp64 root.  Results are narrowed to fp32 once.
+ *   The fp64 root is within 1*2^-50*(|F| + |K|)/vega1 (Black-Scholes) resp. 4*2^-50*(|F| + |K|)/vega1 (Bachelier) of the exact one over
+ *   the grid of DESIGN.md 4.25 (four times what was measured), and every iteration of the solver is bounded by FM_IMPLIED_MAX_ITERATIONS
+ *   (64) whatever the data: an element that has not met the stopping rule by then returns its last iterate.
+ * fmhip_implied_volatility: outputs is a mask of FMHIP_IMPLIED_VOLATILITY, _D_PRICE, _D_FORWARD; out receives one new, materialised vector
+ *   per set bit, in bit order, from ONE launch.  At least one operand is a vector, and all vectors have one size.
+ * fmhip_implied_volatility_host (host only): the DEFINITION over host float arrays of n (1 ... 2^31) elements; out[f][p]; an operand array
+ *   that is NULL is the scalar beside it; it needs no device.
+ * The pass is elementwise: with a device list every shard runs the call on its block.  Everything is checked on the host before anything is
+ * flushed or launched: an unknown model, a mask outside 1 ... 7, a NULL pointer, no vector operand, a maturity that is negative or not
+ * finite, a strike that is not finite -> FMHIP_ERR_INVALID_ARGUMENT; vectors of different sizes -> FMHIP_ERR_SIZE_MISMATCH;
+ * FMHIP_ERR_INVALID_HANDLE.  A refusal leaves out untouched and no vector behind.  A vector whose values were given up is the error a read
+ * of it is.  A build without the kernel answers FMHIP_ERR_UNSUPPORTED; it never falls back. */
+#define FMHIP_IMPLIED_VOLATILITY 1
+#define FMHIP_IMPLIED_D_PRICE    2
+#define FMHIP_IMPLIED_D_FORWARD  4
+int fmhip_implied_volatility(int model, fmhip_vec price, double price_scalar, fmhip_vec forward, double forward_scalar,
+                             fmhip_vec payoff_unit, double payoff_unit_scalar, double maturity, double strike,
+                             int outputs /* mask 1 ... 7 */, fmhip_vec* out /* one new vector per set bit, in bit order */);
+int fmhip_implied_volatility_host(int model, const float* price, double price_scalar, const float* forward, double forward_scalar,
+                                  const float* payoff_unit, double payoff_unit_scalar, int64_t n, double maturity, double strike,
+                                  int outputs, float* const* out);
+
 /* Nested simulation on the device: the two operations that change the SHAPE of a sample — k inner paths started from each
  * of m outer states (fmhip_vec_repeat), and the m*k inner payoffs reduced to m conditional means with their inner variances
  * (fmhip_block_moments) — without the vectors leaving the device.  The definition is host/block_moments.hpp, one header for the host and

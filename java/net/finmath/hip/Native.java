@@ -126,6 +126,11 @@ final class Native {
 	static native int optionFormula(int model, long forward, double forwardScalar, long volatility, double volatilityScalar, long payoffUnit, double payoffUnitScalar, double maturity, double strike, int outputs, long[] out);
 	/** The definition of optionFormula over host arrays of n floats; an operand array that is null is the scalar beside it; outColumns holds one column of n floats per set bit. */
 	static native int optionFormulaHost(int model, float[] forwardOrNull, double forwardScalar, float[] volatilityOrNull, double volatilityScalar, float[] payoffUnitOrNull, double payoffUnitScalar, int n, double maturity, double strike, int outputs, float[] outColumns);
+	// ---- implied volatility per path: the inverse of optionFormula's value in the volatility
+	/** out = one new vector per set bit of outputs (1 volatility, 2 its partial in the price, 4 its partial in the forward), in bit order: the volatility at which the call of model 0 (Black-Scholes) or 1 (Bachelier) has the given price; an operand handle of 0 is the scalar beside it, at least one is a vector. */
+	static native int impliedVolatility(int model, long price, double priceScalar, long forward, double forwardScalar, long payoffUnit, double payoffUnitScalar, double maturity, double strike, int outputs, long[] out);
+	/** The definition of impliedVolatility over host arrays of n floats; an operand array that is null is the scalar beside it; outColumns holds one column of n floats per set bit. */
+	static native int impliedVolatilityHost(int model, float[] priceOrNull, double priceScalar, float[] forwardOrNull, double forwardScalar, float[] payoffUnitOrNull, double payoffUnitScalar, int n, double maturity, double strike, int outputs, float[] outColumns);
 	// ---- nested simulation: the moments of consecutive blocks as new vectors, and the repeat that starts k inner paths per outer state
 	/** outs[i * popcount(mask) + j] = a new vector of n / block elements: output j (mask bits in ascending order: 1 sum, 2 mean, 4 population variance) of the consecutive blocks of vs[i]; 1 ... 4 vectors of one size, each read once; the bits are those of blockMomentsHost. */
 	static native int blockMoments(long[] vs, long block, int mask, long[] outs);

@@ -79,4 +79,36 @@ public final class NormalDistributionHip implements DoubleUnaryOperator {
 		for(int f = 0; f < out.length; f++) result[f] = new RandomVariableHip(time, new DeviceVector(out[f], size));
 		return result;
 	}
+
+	public static final int IMPLIED_VOLATILITY = 1, IMPLIED_D_PRICE = 2, IMPLIED_D_FORWARD = 4;			// FMHIP_IMPLIED_*
+
+	/** The Black-Scholes volatility per path at which the call has optionValue (AnalyticFormulas.blackScholesOptionImpliedVolatility, as remembered); one launch of {@code fmhip_implied_volatility} (DESIGN.md 4.25). */
+	public static RandomVariableHip blackScholesOptionImpliedVolatility(final RandomVariableHip forward, final double optionMaturity, final double optionStrike, final RandomVariableHip payoffUnit, final RandomVariableHip optionValue) {
+		return impliedVolatility(BLACK_SCHOLES, optionValue, forward, optionMaturity, optionStrike, payoffUnit, IMPLIED_VOLATILITY)[0];
+	}
+
+	/** The Bachelier (normal) volatility per path at which the call has optionValue (AnalyticFormulas.bachelierOptionImpliedVolatility, as remembered). */
+	public static RandomVariableHip bachelierOptionImpliedVolatility(final RandomVariableHip forward, final double optionMaturity, final double optionStrike, final RandomVariableHip payoffUnit, final RandomVariableHip optionValue) {
+		return impliedVolatility(BACHELIER, optionValue, forward, optionMaturity, optionStrike, payoffUnit, IMPLIED_VOLATILITY)[0];
+	}
+
+	/** One new vector per set bit of outputs (IMPLIED_VOLATILITY, IMPLIED_D_PRICE, IMPLIED_D_FORWARD), in bit order, from ONE launch; the filtration time is the operands' maximum. */
+	public static RandomVariableHip[] impliedVolatility(final int model, final RandomVariableHip optionValue, final RandomVariableHip forward, final double optionMaturity, final double optionStrike, final RandomVariableHip payoffUnit, final int outputs) {
+		final RandomVariableHip[] operands = { optionValue, forward, payoffUnit };
+		final long[] handles = new long[3];
+		final double[] scalars = new double[3];
+		double time = Double.NEGATIVE_INFINITY;
+		int size = 0;
+		for(int k = 0; k < 3; k++) {
+			time = Math.max(time, operands[k].getFiltrationTime());
+			if(operands[k].isDeterministic()) scalars[k] = operands[k].doubleValue();
+			else { handles[k] = operands[k].deviceHandle(); size = operands[k].size(); }
+		}
+		if(size == 0) throw new IllegalArgumentException("at least one of optionValue, forward and payoffUnit is stochastic");
+		final long[] out = new long[Integer.bitCount(outputs)];
+		Native.check(Native.impliedVolatility(model, handles[0], scalars[0], handles[1], scalars[1], handles[2], scalars[2], optionMaturity, optionStrike, outputs, out));
+		final RandomVariableHip[] result = new RandomVariableHip[out.length];
+		for(int f = 0; f < out.length; f++) result[f] = new RandomVariableHip(time, new DeviceVector(out[f], size));
+		return result;
+	}
 }

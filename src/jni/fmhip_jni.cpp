@@ -502,6 +502,28 @@ FMJ(jint, optionFormulaHost)(JNIEnv* env, jclass, jint model, jfloatArray forwar
     for (int f = 0; f < count; ++f) columns[f] = po.p + (int64_t)f * n;
     return fmhip_option_formula_host((int)model, pf.p, forwardScalar, pv.p, volatilityScalar, pn.p, payoffUnitScalar, (int64_t)n, maturity, strike, (int)outputs, columns);
 }
+// ---------------------------------------------------------------- implied volatility per path: the inverse of optionFormula's value in the volatility
+FMJ(jint, impliedVolatility)(JNIEnv* env, jclass, jint model, jlong price, jdouble priceScalar, jlong forward, jdouble forwardScalar, jlong payoffUnit, jdouble payoffUnitScalar,
+                             jdouble maturity, jdouble strike, jint outputs, jlongArray out) {
+    if (!out || outputs < 1 || outputs > 7) return FMHIP_ERR_INVALID_ARGUMENT;
+    const jsize count = (jsize)((outputs & 1) + ((outputs >> 1) & 1) + ((outputs >> 2) & 1));
+    if (env->GetArrayLength(out) < count) return FMHIP_ERR_INVALID_ARGUMENT;
+    fmhip_vec h[3] = { 0, 0, 0 };
+    const int st = fmhip_implied_volatility((int)model, price, priceScalar, forward, forwardScalar, payoffUnit, payoffUnitScalar, maturity, strike, (int)outputs, h);
+    if (st == FMHIP_OK) { jlong o[3]; for (jsize f = 0; f < count; ++f) o[f] = (jlong)h[f]; env->SetLongArrayRegion(out, 0, count, o); }
+    return st;
+}
+FMJ(jint, impliedVolatilityHost)(JNIEnv* env, jclass, jint model, jfloatArray priceOrNull, jdouble priceScalar, jfloatArray forwardOrNull, jdouble forwardScalar,
+                                 jfloatArray payoffUnitOrNull, jdouble payoffUnitScalar, jint n, jdouble maturity, jdouble strike, jint outputs, jfloatArray outColumns) {
+    Pin<jfloat> pc(env, priceOrNull, JNI_ABORT); Pin<jfloat> pf(env, forwardOrNull, JNI_ABORT); Pin<jfloat> pn(env, payoffUnitOrNull, JNI_ABORT); Pin<jfloat> po(env, outColumns);
+    if (!po.p || n < 1 || outputs < 1 || outputs > 7) return FMHIP_ERR_INVALID_ARGUMENT;
+    if ((priceOrNull && (!pc.p || pc.length() < n)) || (forwardOrNull && (!pf.p || pf.length() < n)) || (payoffUnitOrNull && (!pn.p || pn.length() < n))) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int count = (outputs & 1) + ((outputs >> 1) & 1) + ((outputs >> 2) & 1);
+    if ((int64_t)po.length() < (int64_t)count * n) return FMHIP_ERR_INVALID_ARGUMENT;
+    float* columns[3] = { nullptr, nullptr, nullptr };
+    for (int f = 0; f < count; ++f) columns[f] = po.p + (int64_t)f * n;
+    return fmhip_implied_volatility_host((int)model, pc.p, priceScalar, pf.p, forwardScalar, pn.p, payoffUnitScalar, (int64_t)n, maturity, strike, (int)outputs, columns);
+}
 // ---------------------------------------------------------------- polynomial regression in one pass: the monomials of the states are formed in registers
 // exponents: states.length (nStates) entries per term, each 0 … 6, as ints; anything outside a byte is refused here, the rest by the library
 static bool poly_exponents(const jint* e, int64_t count, std::vector<uint8_t>& out) {
