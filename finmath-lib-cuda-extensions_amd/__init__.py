@@ -26,6 +26,8 @@ from .regression import MonteCarloConditionalExpectationPolynomialRegression, po
 from .sorting import argsort, rank_scores, read_elements, sort_by_key, sorted_quantiles, spearman_matrix
 from .prefix import cumulative_sums, expected_shortfall_curve, prefix_search, prefix_sums_at, prefix_sums_host, running_average
 from .prefix import weighted_expected_shortfall, weighted_quantiles
+from .resample import (bootstrap_resample, device_resample, effective_sample_size, multinomial_resample, resample, resample_host, stratified_resample,
+                       systematic_resample)
 from .tabulated import TabulatedFunction, table_apply, table_apply_host
 from .analytic import NORMAL_CDF, NORMAL_DENSITY, NORMAL_QUANTILE, NamedFunction, function_apply, function_apply_host, normal_scores
 from .analytic import bachelier_option_value, black_scholes_option_value, option_formula, option_formula_double, option_formula_host

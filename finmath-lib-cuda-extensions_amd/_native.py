@@ -29,6 +29,7 @@ SYMBOLS = [
     "fmhip_polynomial_cross_moments", "fmhip_polynomial_evaluate", "fmhip_polynomial_cross_moments_host", "fmhip_polynomial_evaluate_host",
     "fmhip_sort_by_key", "fmhip_argsort", "fmhip_argsort_host", "fmhip_rank_scores", "fmhip_vec_read_elements",
     "fmhip_prefix_sums", "fmhip_prefix_sums_at", "fmhip_prefix_search", "fmhip_prefix_sums_host",
+    "fmhip_resample", "fmhip_resample_host",
     "fmhip_table_build", "fmhip_table_apply", "fmhip_table_apply_host",
     "fmhip_function_apply", "fmhip_function_apply_host", "fmhip_option_formula", "fmhip_option_formula_host",
     "fmhip_implied_volatility", "fmhip_implied_volatility_host",
@@ -189,6 +190,8 @@ def lib():
         "fmhip_prefix_sums": [vec, i32, pv, C.POINTER(dbl)], "fmhip_prefix_sums_at": [vec, C.POINTER(i64), i32, C.POINTER(dbl)],
         "fmhip_prefix_search": [vec, C.POINTER(dbl), i32, i32, C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)],
         "fmhip_prefix_sums_host": [vp, i64, C.POINTER(dbl)],
+        "fmhip_resample": [vec, i32, i64, dbl, vec, pv, i32, pv, pv, C.POINTER(dbl)],
+        "fmhip_resample_host": [vp, i64, i32, i64, dbl, vp, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(dbl)],
         "fmhip_table_build": [C.POINTER(dbl), C.POINTER(dbl), i32, i32, i32, i32, C.POINTER(dbl)],
         "fmhip_table_apply": [vec, C.POINTER(dbl), i32, C.POINTER(dbl), i32, pv],
         "fmhip_table_apply_host": [vp, i64, C.POINTER(dbl), i32, C.POINTER(dbl), i32, C.POINTER(vp)],

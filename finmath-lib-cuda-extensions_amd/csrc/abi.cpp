@@ -857,6 +857,28 @@ int fmhip_prefix_search(fmhip_vec v, const double* thresholds, int count, int re
     return guarded([&] { Engine::get().prefix_search(v, thresholds, count, relative, positions_out, sums_out, total_out); });
 }
 
+// ---------------------------------------------------------------- resampling (resample_engine.hpp)
+int fmhip_resample_host(const float* weights, int64_t n, int scheme, int64_t m, double offset, const float* uniforms, const float* const* values, int n_values,
+                        float* const* values_out, int64_t* ancestors_out, double* total_out) {
+    return host_only([&] { fm::resample_host_checked(weights, n, scheme, m, offset, uniforms, values, n_values, values_out, ancestors_out, total_out); });
+}
+// the operands of a resample as ONE list for TE_LOCAL: the weights and the uniforms where there are any, then the companions
+static std::vector<fmhip_vec> te_resample_operands(fmhip_vec weights, fmhip_vec uniforms, const fmhip_vec* values, int n_values) {
+    std::vector<fmhip_vec> all;
+    if (weights) all.push_back(weights);
+    if (uniforms) all.push_back(uniforms);
+    all.insert(all.end(), values, values + n_values);
+    return all;
+}
+int fmhip_resample(fmhip_vec weights, int scheme, int64_t m, double offset, fmhip_vec uniforms, const fmhip_vec* values, int n_values, fmhip_vec* values_out,
+                   fmhip_vec* ancestors_out, double* total_out) {
+    FRONT(resample(weights, scheme, m, offset, uniforms, values, n_values, values_out, ancestors_out, total_out));
+    const int at_uniforms = weights ? 1 : 0, at_values = at_uniforms + (uniforms ? 1 : 0);
+    TE_CHECKED_LOCAL(fm::resample_check(weights, scheme, m, offset, uniforms, values, n_values, values_out, ancestors_out), te_resample_operands(weights, uniforms, values, n_values), L,
+                     fmhip_resample(weights ? L[0] : 0, scheme, m, offset, uniforms ? L[at_uniforms] : 0, L + at_values, n_values, values_out, ancestors_out, total_out));
+    return guarded([&] { Engine::get().resample(weights, scheme, m, offset, uniforms, values, n_values, values_out, ancestors_out, total_out); });
+}
+
 // ---------------------------------------------------------------- tabulated functions (table_engine.hpp)
 int fmhip_table_build(const double* knots, const double* values, int count, int interpolation, int extrapolation, int derivative, double* coefficients_out) {
     return host_only([&] { fm::table_build_checked(knots, values, count, interpolation, extrapolation, derivative, coefficients_out); });

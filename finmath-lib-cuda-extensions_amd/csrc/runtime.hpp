@@ -419,6 +419,13 @@ public:
     void prefix_sums_at(fmhip_vec v, const int64_t* positions, int count, double* sums_out);
     void prefix_search(fmhip_vec v, const double* thresholds, int count, int relative, int64_t* positions_out, double* sums_out, double* total_out);
 
+    // resampling (resample_engine.hpp): m ancestors drawn from the weights (0: equal weights) by the scheme of resample_host.hpp,
+    // up to 8 companion vectors gathered along, values_out[i][j] = values[i][a_j] bit for bit, and the ancestors as floats (n <= 2^24) — new,
+    // materialised vectors of m elements; the inputs are unchanged.  Arguments are checked before anything is flushed or launched; the outputs
+    // are written only when the call succeeds; one engine's sample only (UNSUPPORTED with a communicator).
+    void resample(fmhip_vec weights, int scheme, int64_t m, double offset, fmhip_vec uniforms, const fmhip_vec* values, int n_values, fmhip_vec* values_out,
+                  fmhip_vec* ancestors_out, double* total_out);
+
     // tabulated functions (table_engine.hpp): n_tables functions on the same knots (host/tabulated_function.hpp) applied to
     // every element of x, out[0 … n_tables) new, materialised vectors from one launch that reads x once.  Arguments are checked before
     // anything is flushed or launched; out is written only when the call succeeds.
@@ -922,6 +929,13 @@ void sort_argsort_host_checked(const float* key, int64_t n, int64_t* permutation
 void prefix_check_sums(fmhip_vec v, int mode, const fmhip_vec* out);
 void prefix_check_queries(fmhip_vec v, const void* queries, int count, const void* sums_out, const char* what);
 void prefix_sums_host_checked(const float* v, int64_t n, double* prefix_out);
+// the same for fmhip_resample, and the definition behind its _host twin (resample_engine.hpp; the rules are resample_host.hpp's): both throw
+// FMHIP_ERR_INVALID_ARGUMENT
+void resample_check(fmhip_vec weights, int scheme, int64_t m, double offset, fmhip_vec uniforms, const fmhip_vec* values, int n_values, const fmhip_vec* values_out,
+                    const fmhip_vec* ancestors_out);
+void resample_check_sizes(int64_t n, int64_t m, int64_t n_uniforms, bool want_ancestors);      // FMHIP_ERR_INVALID_ARGUMENT, FMHIP_ERR_SIZE_MISMATCH
+void resample_host_checked(const float* weights, int64_t n, int scheme, int64_t m, double offset, const float* uniforms, const float* const* values, int n_values,
+                           float* const* values_out, int64_t* ancestors_out, double* total_out);
 // the same for fmhip_table_apply, and the definitions behind fmhip_table_build / fmhip_table_apply_host (table_engine.hpp; the rules are
 // host/tabulated_function.hpp's): all throw FMHIP_ERR_INVALID_ARGUMENT
 void table_check_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, const fmhip_vec* out);

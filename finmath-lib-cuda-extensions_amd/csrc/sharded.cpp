@@ -985,6 +985,31 @@ int prefix_search(fmhip_vec v, const double* thresholds, int count, int relative
     });
 }
 
+// Resampling (resample_engine.hpp).  The ancestors of a sample that is spread over several shards need the carry of the prefix sums and an
+// exchange of elements between the shards: neither is built (one_shard).
+int resample(fmhip_vec weights, int scheme, int64_t m, double offset, fmhip_vec uniforms, const fmhip_vec* values, int n_values, fmhip_vec* values_out,
+             fmhip_vec* ancestors_out, double* total_out) {
+    return fronted([&](Shards& s) {
+        resample_check(weights, scheme, m, offset, uniforms, values, n_values, values_out, ancestors_out);
+        std::vector<fmhip_vec> sample;
+        if (weights) sample.push_back(weights);
+        sample.insert(sample.end(), values, values + n_values);
+        const int64_t n = front_size(s, sample.data(), (int)sample.size(), "resample", false);
+        const bool with_uniforms = scheme != 0;                                          // (FMHIP_RESAMPLE_SYSTEMATIC does not look at the uniforms)
+        resample_check_sizes(n, m, with_uniforms ? s.vec(uniforms).n : m, ancestors_out != nullptr);
+        one_shard(s, "resample", PREFIX_WHY);
+        const int want_ancestors = ancestors_out ? 1 : 0;
+        std::vector<fmhip_vec> ids((size_t)(n_values + want_ancestors), 0);              // the companions, then the ancestors if they are asked for
+        produce_per_shard(s, m, n_values + want_ancestors, ids.data(), [&](Worker& w, fmhip_vec* got) {
+            const std::vector<fmhip_vec> l = localize(w, sample.data(), (int)sample.size());
+            return fmhip_resample(weights ? l[0] : 0, scheme, m, offset, with_uniforms ? w.at(uniforms) : 0, l.data() + (weights ? 1 : 0), n_values, got,
+                                  want_ancestors ? got + n_values : nullptr, total_out);
+        });
+        for (int i = 0; i < n_values; ++i) values_out[i] = ids[(size_t)i];
+        if (want_ancestors) *ancestors_out = ids[(size_t)n_values];
+    });
+}
+
 // Tabulated functions (table_engine.hpp).  Elementwise: every shard runs the call on its block; the new vectors' blocks are the shards' results.
 int table_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, fmhip_vec* out) {
     return fronted([&](Shards& s) {

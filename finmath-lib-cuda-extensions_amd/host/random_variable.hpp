@@ -86,7 +86,7 @@ public:
     // Black–Scholes / Bachelier value per path on the device calls fmhip_function_apply / fmhip_option_formula on the handles, DESIGN.md
     // §4.21, and the volatility implied by a price per path fmhip_implied_volatility, §4.25; block means per outer path and the repeat of nested simulation are fmhip_block_moments / fmhip_vec_repeat on the handles, §4.22,
     // a quantile or a tail mean per outer path fmhip_block_order_statistics, §4.23; the r-th largest of several variables per path and the
-    // variable that holds it are fmhip_cross_order_statistics / fmhip_cross_select on the handles, §4.24);
+    // variable that holds it are fmhip_cross_order_statistics / fmhip_cross_select on the handles, §4.24; ancestors drawn from weights and the state carried along are fmhip_resample, §4.26);
     // the order statistics below are selected and counted on the DEVICE when the object
     // has a device vector (orderStatisticsHandle) — fmhip_select_ranks_batch, fmhip_rank_sums_batch, fmhip_count_not_above — and sort
     // on the host as the reference does (:970-1091; twin :473-602, :667-748) otherwise, or with FMHIP_DEVICE_ORDER_STATS=0

@@ -29,6 +29,10 @@ a RandomVariableFactory by injection (LIBORMarketModelCalibrationATMTest.java:35
                             P&L over the margin period of risk — a block order statistic (nested.py)
     forward_implied_volatility_mc  the forward smile: the distribution, at a future date, of the volatility implied by a call's price under
                             heston_call_mc's scheme — inner means per outer state, inverted per path (analytic.py)
+    particle_filter_log_likelihood  the bootstrap particle filter of a linear-Gaussian state-space model — propagate, weight by the
+                            observation density, resample on the device (resample.py) — with kalman_log_likelihood, the
+                            exact answer, as its check; stochastic_volatility_log_likelihood is the same filter on the discrete
+                            stochastic-volatility model, which has no closed form
     bermudan_max_call_mc    the same induction for a call on the maximum of several assets, regressed on all monomials of the assets up
                             to a total degree: 10 … 56 basis functions, the wide one-pass normal equations
 """
@@ -679,3 +683,75 @@ def best_of_call_mc(brownian_motion, initial_values, risk_free_rate, dividend_yi
     # asset i is the best where the index equals i: (best − i)² is 0 there and at least 1 elsewhere
     shares = [best.sub(float(a)).squared().cap(1.0).mult(-1.0).add(1.0).getAverage() for a in range(assets)]
     return value.getAverage(), value.getStandardError(), shares
+
+
+def _filter_resample(weights, state, generator, scheme):
+    """One resampling step of the filters below: (the resampled state, the total weight).  The systematic offset, or the m uniforms of the
+    other schemes, come from `generator` on the host; nothing but the total leaves the device."""
+    from .resample import resample
+    if scheme == "systematic":
+        (state,), total = resample(weights, [state], scheme=scheme, offset=generator.random())
+    else:
+        import numpy as np
+        (state,), total = resample(weights, [state], scheme=scheme, uniforms=type(state)(state.getFiltrationTime(), generator.random(state.size()).astype(np.float32)))
+    return state, total
+
+
+def particle_filter_log_likelihood(observations, a, q, r, p0, brownian_motion, offsets_seed, scheme="systematic"):
+    """log p(y_1 … y_T) of the linear-Gaussian model x_t = a·x_{t-1} + √q·ε_t, y_t = x_t + √r·η_t, x_0 ~ N(0, p0) by the BOOTSTRAP particle
+    filter, one particle per path of `brownian_motion`: factor 0 of increment 0 (scaled to unit variance) draws x_0, increment t propagates
+    to x_t, so the time discretisation has at least T + 1 steps.  Per observation: propagate; weight with the observation density,
+    w = φ((x_t − y_t)/√r) (analytic.function_apply, NORMAL_DENSITY); add log(total/n) − log(r)/2 to the log-likelihood, total being the
+    sum of the weights that the resample call returns; resample the state (resample.resample).  Nothing but `total` leaves
+    the device.  The systematic offsets (one per observation; the m uniforms of the other schemes) come from a seeded HOST generator,
+    numpy.random.Generator(numpy.random.PCG64(offsets_seed)).  exp of the result is an unbiased estimate of the likelihood; its logarithm is
+    biased low.  A weight total of zero gives -inf.  FMHIP_DEVICE_RESAMPLE=0 gives the same number to the last bit."""
+    import numpy as np
+    from .analytic import NORMAL_DENSITY, function_apply
+    generator = np.random.Generator(np.random.PCG64(int(offsets_seed)))
+    td = brownian_motion.getTimeDiscretization()
+    n = brownian_motion.getNumberOfPaths()
+    x = brownian_motion.getBrownianIncrement(0, 0).mult(math.sqrt(p0 / td.getTimeStep(0)))
+    log_likelihood = 0.0
+    for t, y in enumerate(observations, start=1):
+        x = x.mult(a).addProduct(brownian_motion.getBrownianIncrement(t, 0), math.sqrt(q / td.getTimeStep(t)))
+        weights, = function_apply(x.sub(float(y)).div(math.sqrt(r)), [NORMAL_DENSITY])
+        x, total = _filter_resample(weights, x, generator, scheme)
+        if not total > 0.0: return -math.inf
+        log_likelihood += math.log(total / n) - 0.5 * math.log(r)
+    return log_likelihood
+
+
+def kalman_log_likelihood(observations, a, q, r, p0):
+    """The exact log p(y_1 … y_T) of particle_filter_log_likelihood's model: the Kalman filter's prediction-error decomposition, on the host."""
+    mean, variance, log_likelihood = 0.0, float(p0), 0.0
+    for y in observations:
+        mean, variance = a * mean, a * a * variance + q
+        s = variance + r
+        log_likelihood += -0.5 * (math.log(2.0 * math.pi * s) + (y - mean) ** 2 / s)
+        gain = variance / s
+        mean, variance = mean + gain * (y - mean), (1.0 - gain) * variance
+    return log_likelihood
+
+
+def stochastic_volatility_log_likelihood(returns, mu, phi, sigma_eta, brownian_motion, offsets_seed, scheme="systematic"):
+    """log p(y_1 … y_T) of the standard discrete stochastic-volatility model h_t = μ + φ(h_{t-1} − μ) + σ_η·η_t, y_t = exp(h_t/2)·ε_t,
+    h_0 ~ N(μ, σ_η²/(1 − φ²)) (|φ| < 1), by particle_filter_log_likelihood's filter: the weight of a particle is the density of the return
+    given its log-variance, φ(y_t·e^{−h_t/2})·e^{−h_t/2}.  Nothing closed-form checks it — it is the workload the resampling is for;
+    FMHIP_DEVICE_RESAMPLE=0 gives the same number to the last bit.  Increments, offsets and schemes as in particle_filter_log_likelihood."""
+    import numpy as np
+    from .analytic import NORMAL_DENSITY, function_apply
+    if not abs(phi) < 1.0: raise ValueError("the log-variance is stationary: |phi| < 1")
+    generator = np.random.Generator(np.random.PCG64(int(offsets_seed)))
+    td = brownian_motion.getTimeDiscretization()
+    n = brownian_motion.getNumberOfPaths()
+    h = brownian_motion.getBrownianIncrement(0, 0).mult(sigma_eta / math.sqrt((1.0 - phi * phi) * td.getTimeStep(0))).add(mu)
+    log_likelihood = 0.0
+    for t, y in enumerate(returns, start=1):
+        h = h.sub(mu).mult(phi).add(mu).addProduct(brownian_motion.getBrownianIncrement(t, 0), sigma_eta / math.sqrt(td.getTimeStep(t)))
+        scale = h.mult(-0.5).exp()
+        density, = function_apply(scale.mult(float(y)), [NORMAL_DENSITY])
+        h, total = _filter_resample(scale.mult(type(scale)(scale.getFiltrationTime(), density)), h, generator, scheme)
+        if not total > 0.0: return -math.inf
+        log_likelihood += math.log(total / n)
+    return log_likelihood

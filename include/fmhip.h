@@ -459,6 +459,45 @@ int fmhip_prefix_search(fmhip_vec v, const double* thresholds, int count, int re
                         int64_t* positions_out, double* sums_out, double* total_out);
 int fmhip_prefix_sums_host(const float* v, int64_t n, double* prefix_out);   /* the DEFINITION */
 
+/* Resampling on the device: the step that follows the weighted sample of the prefix sums — the weighted sample becomes an
+ * equally weighted one without a vector leaving the device: m ancestors a_j are drawn from the weights and up to 8 state vectors are
+ * carried along, values_out[i][j] = values[i][a_j].  A particle filter's resampling step, importance sampling with weight degeneracy, the
+ * bootstrap (weights == 0: equal weights), one draw of ancestors for several state vectors.  The definition is csrc/resample_host.hpp, one
+ * header for the host and the device; fp64, every operation rounded on its own, no libm.
+ *   cleaned weights  cw[r] = w[r] if w[r] > 0, otherwise +0.0: a NaN, a negative weight and -0.0 count as zero.
+ *   P, total         P = fmhip_prefix_sums_host's P of cw (the same association, non-decreasing), total = P[n-1].  With weights == 0
+ *                    P[r] = (double)(r + 1) and total = (double)n exactly: nothing is summed and nothing is searched.
+ *   degenerate total !(total > 0) or total == +inf: every element of every output is the quiet NaN 0x7fc00000, the ancestors are NaN on the
+ *                    device and -1 in the host twin, and the status is still FMHIP_OK (no data-dependent status); total_out tells.
+ *   fraction f_j     FMHIP_RESAMPLE_SYSTEMATIC ((double)j + offset) / (double)m with ONE offset in [0, 1); _STRATIFIED ((double)j + U_j) /
+ *                    (double)m; _MULTINOMIAL U_j (in the order of the uniforms: no sort is needed or done).  U_j = (double)uniforms[j]; below 0
+ *                    it is taken as 0, at or above 1 as the largest double below 1; a NaN makes element j dead (NaN in every output).
+ *   target, ancestor t_j = fl(f_j * total); a_j = the smallest r with P[r] > t_j, and if there is none (only rounding at the top can cause
+ *                    that) the smallest r with P[r] == total.  Hence cw[a_j] > 0 ALWAYS — a path of zero weight is never an ancestor, at
+ *                    t = 0 as little as anywhere — and 0 <= a_j <= n - 1 ALWAYS.  With equal weights a_j = min((int64)t_j, n - 1).
+ *   outputs          values_out[i] = a new, materialised vector of m elements, copied bit for bit (a NaN keeps its payload, a zero its sign);
+ *                    *ancestors_out (optional, n <= 2^24, where the float is exact) = (float)a_j.  The inputs are unchanged.
+ * n is the size of weights, or of values[0] when weights is 0.  The device's bits are fmhip_resample_host's.
+ * Checked on the host before anything is flushed or launched: an unknown scheme, m or n outside 1 ... 2^31 - 1, n_values outside 0 ... 8,
+ * nothing asked for (n_values == 0 and no ancestors_out), neither weights nor a value vector, an offset outside [0, 1) or not finite
+ * (whatever the scheme: pass 0 where it is not read), uniforms == 0 with a scheme that needs them (with _SYSTEMATIC they are not looked at),
+ * ancestors_out with n > 2^24, a NULL pointer -> FMHIP_ERR_INVALID_ARGUMENT; a value vector whose size is not n, uniforms whose size is not
+ * m -> FMHIP_ERR_SIZE_MISMATCH; FMHIP_ERR_INVALID_HANDLE.  A refusal leaves the outputs untouched and no vector behind.  A vector whose
+ * values were given up is the error a read of it is.  If the pool cannot give the temporary of P (8n bytes): FMHIP_ERR_OUT_OF_MEMORY.  A
+ * build without the kernel answers FMHIP_ERR_UNSUPPORTED; it never falls back.
+ * ONE sample on ONE device, as the prefix sums: a device list of more than one shard or an expectation communicator of more than one rank
+ * -> FMHIP_ERR_UNSUPPORTED. */
+#define FMHIP_RESAMPLE_SYSTEMATIC  0
+#define FMHIP_RESAMPLE_STRATIFIED  1
+#define FMHIP_RESAMPLE_MULTINOMIAL 2
+int fmhip_resample(fmhip_vec weights /* 0: equal weights */, int scheme, int64_t m, double offset,
+                   fmhip_vec uniforms /* m elements; 0 with SYSTEMATIC */,
+                   const fmhip_vec* values, int n_values /* 0 ... 8 */, fmhip_vec* values_out,
+                   fmhip_vec* ancestors_out /* may be NULL */, double* total_out /* may be NULL */);
+int fmhip_resample_host(const float* weights, int64_t n, int scheme, int64_t m, double offset, const float* uniforms,
+                        const float* const* values, int n_values, float* const* values_out,
+                        int64_t* ancestors_out, double* total_out);          /* the DEFINITION; needs no device */
+
 /* Tabulated functions on the device: RandomVariable.apply for a CURVE — a function tabulated on knots and interpolated: a
  * local-volatility slice, a Markov-functional numeraire, a payoff profile, an exercise boundary, an inverse empirical CDF — without the
  * vector leaving the device.  The definition is host/tabulated_function.hpp, one header for the host and the device.

@@ -110,6 +110,11 @@ final class Native {
 	static native int prefixSearch(long v, double[] thresholds, boolean relative, long[] positionsOut, double[] sumsOut, double[] totalOutOrNull);
 	/** The definition of the prefix sums over a host array. */
 	static native int prefixSumsHost(float[] v, double[] prefixOut);
+	// ---- resampling on the device: ancestors drawn from the cumulative weights (systematic, stratified, multinomial; equal weights: the bootstrap), state vectors gathered along
+	/** valuesOut[i] = a new vector of m elements, values[i][a_j] bit for bit (values.length <= 8); ancestorsOutOrNull[0] = the ancestors as floats (n <= 2^24); totalOutOrNull[0] = the total weight (not positive or infinite: every output is NaN).  weights == 0: equal weights; scheme 0 systematic (offset in [0, 1), uniforms not read), 1 stratified, 2 multinomial (uniforms: m elements).  The bits are those of resampleHost. */
+	static native int resample(long weights, int scheme, long m, double offset, long uniforms, long[] values, long[] valuesOut, long[] ancestorsOutOrNull, double[] totalOutOrNull);
+	/** The definition of resample over host arrays: valueColumns holds nValues columns of n floats, outColumns nValues columns of m floats; ancestorsOutOrNull[j] = a_j, -1 for a dead element. */
+	static native int resampleHost(float[] weightsOrNull, long n, int scheme, long m, double offset, float[] uniformsOrNull, float[] valueColumns, int nValues, float[] outColumns, long[] ancestorsOutOrNull, double[] totalOutOrNull);
 	// ---- tabulated functions on the device: RandomVariable.apply for a curve; the device's bits are those of tableApplyHost
 	/** coefficientsOut[(knots.length + 1) * 4]: the segments of one function from its values at the knots; interpolation 0 piecewise constant, 1 linear, 2 natural cubic spline, 3 monotone cubic; extrapolation 0 constant, 1 linear; derivative 0 or 1. */
 	static native int tableBuild(double[] knots, double[] values, int interpolation, int extrapolation, int derivative, double[] coefficientsOut);

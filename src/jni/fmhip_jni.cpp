@@ -312,6 +312,41 @@ FMJ(jint, prefixSumsHost)(JNIEnv* env, jclass, jfloatArray v, jdoubleArray prefi
     if (!pv.p || !po.p || po.length() < pv.length()) return FMHIP_ERR_INVALID_ARGUMENT;
     return fmhip_prefix_sums_host(pv.p, pv.length(), po.p);
 }
+// ---------------------------------------------------------------- resampling on the device
+FMJ(jint, resample)(JNIEnv* env, jclass, jlong weights, jint scheme, jlong m, jdouble offset, jlong uniforms, jlongArray values, jlongArray valuesOut, jlongArray ancestorsOutOrNull,
+                    jdoubleArray totalOutOrNull) {
+    Pin<jlong> pv(env, values, JNI_ABORT);
+    const int64_t nv = pv.p ? pv.length() : 0;
+    if (nv > 8 || (nv > 0 && (!valuesOut || env->GetArrayLength(valuesOut) < nv)) || (ancestorsOutOrNull && env->GetArrayLength(ancestorsOutOrNull) < 1)
+        || (totalOutOrNull && env->GetArrayLength(totalOutOrNull) < 1)) return FMHIP_ERR_INVALID_ARGUMENT;
+    fmhip_vec a = 0, out[8] = { 0 };
+    double total = 0.0;
+    const int st = fmhip_resample((fmhip_vec)weights, (int)scheme, (int64_t)m, (double)offset, (fmhip_vec)uniforms, (const fmhip_vec*)pv.p, (int)nv, out, ancestorsOutOrNull ? &a : nullptr, &total);
+    if (st == FMHIP_OK) {
+        if (nv > 0) { jlong o[8]; for (int i = 0; i < nv; ++i) o[i] = (jlong)out[i]; env->SetLongArrayRegion(valuesOut, 0, (jsize)nv, o); }
+        set1(env, ancestorsOutOrNull, (jlong)a);
+        if (totalOutOrNull) env->SetDoubleArrayRegion(totalOutOrNull, 0, 1, &total);
+    }
+    return st;
+}
+FMJ(jint, resampleHost)(JNIEnv* env, jclass, jfloatArray weightsOrNull, jlong n, jint scheme, jlong m, jdouble offset, jfloatArray uniformsOrNull, jfloatArray valueColumns, jint nValues,
+                        jfloatArray outColumns, jlongArray ancestorsOutOrNull, jdoubleArray totalOutOrNull) {
+    if (totalOutOrNull && env->GetArrayLength(totalOutOrNull) < 1) return FMHIP_ERR_INVALID_ARGUMENT;
+    double total = 0.0;
+    int st;
+    {
+        Pin<jfloat> pw(env, weightsOrNull, JNI_ABORT); Pin<jfloat> pu(env, uniformsOrNull, JNI_ABORT); Pin<jfloat> pv(env, valueColumns, JNI_ABORT); Pin<jfloat> po(env, outColumns);
+        Pin<jlong> pa(env, ancestorsOutOrNull);
+        if (n < 1 || m < 1 || nValues < 0 || nValues > 8 || (pw.p && (int64_t)pw.length() < (int64_t)n) || (pu.p && (int64_t)pu.length() < (int64_t)m)
+            || (pa.p && (int64_t)pa.length() < (int64_t)m)) return FMHIP_ERR_INVALID_ARGUMENT;
+        if (nValues > 0 && (!pv.p || !po.p || (int64_t)pv.length() < (int64_t)nValues * n || (int64_t)po.length() < (int64_t)nValues * m)) return FMHIP_ERR_INVALID_ARGUMENT;
+        const float* in[8] = { nullptr }; float* columns[8] = { nullptr };
+        for (int i = 0; i < nValues; ++i) { in[i] = pv.p + (int64_t)i * n; columns[i] = po.p + (int64_t)i * m; }
+        st = fmhip_resample_host(pw.p, (int64_t)n, (int)scheme, (int64_t)m, (double)offset, pu.p, in, (int)nValues, columns, (int64_t*)pa.p, &total);
+    }
+    if (st == FMHIP_OK && totalOutOrNull) env->SetDoubleArrayRegion(totalOutOrNull, 0, 1, &total);
+    return st;
+}
 // ---------------------------------------------------------------- tabulated functions on the device
 FMJ(jint, tableBuild)(JNIEnv* env, jclass, jdoubleArray knots, jdoubleArray values, jint interpolation, jint extrapolation, jint derivative, jdoubleArray coefficientsOut) {
     Pin<jdouble> pk(env, knots, JNI_ABORT); Pin<jdouble> pv(env, values, JNI_ABORT); Pin<jdouble> po(env, coefficientsOut);
