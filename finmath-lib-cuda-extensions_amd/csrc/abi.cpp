@@ -879,6 +879,35 @@ int fmhip_resample(fmhip_vec weights, int scheme, int64_t m, double offset, fmhi
     return guarded([&] { Engine::get().resample(weights, scheme, m, offset, uniforms, values, n_values, values_out, ancestors_out, total_out); });
 }
 
+// ---------------------------------------------------------------- selection (select_engine.hpp)
+int fmhip_compress_host(const float* mask, int64_t n, const float* const* values, int n_values, float* const* values_out, int64_t* positions_out, int64_t* count_out) {
+    return host_only([&] { fm::compress_host_checked(mask, n, values, n_values, values_out, positions_out, count_out); });
+}
+int fmhip_expand_host(const float* mask, int64_t n, const float* const* values, int n_values, int64_t n_value_elements, double fill, float* const* values_out) {
+    return host_only([&] { fm::expand_host_checked(mask, n, values, n_values, n_value_elements, fill, values_out); });
+}
+int fmhip_gather_host(const float* index, int64_t m, const float* const* values, int n_values, int64_t n, float* const* values_out) {
+    return host_only([&] { fm::gather_host_checked(index, m, values, n_values, n, values_out); });
+}
+int fmhip_compress(fmhip_vec mask, const fmhip_vec* values, int n_values, fmhip_vec* values_out, fmhip_vec* positions_out, int64_t* count_out) {
+    FRONT(compress(mask, values, n_values, values_out, positions_out, count_out));
+    TE_CHECKED_LOCAL(fm::select_check_compress(mask, values, n_values, values_out, positions_out, count_out), te_operands(mask, values, n_values, nullptr, 0), L,
+                     fmhip_compress(L[0], L + 1, n_values, values_out, positions_out, count_out));
+    return guarded([&] { Engine::get().compress(mask, values, n_values, values_out, positions_out, count_out); });
+}
+int fmhip_expand(fmhip_vec mask, const fmhip_vec* values, int n_values, double fill, fmhip_vec* values_out) {
+    FRONT(expand(mask, values, n_values, fill, values_out));
+    TE_CHECKED_LOCAL(fm::select_check_expand(mask, values, n_values, values_out), te_operands(mask, values, n_values, nullptr, 0), L,
+                     fmhip_expand(L[0], L + 1, n_values, fill, values_out));
+    return guarded([&] { Engine::get().expand(mask, values, n_values, fill, values_out); });
+}
+int fmhip_gather(fmhip_vec index, const fmhip_vec* values, int n_values, fmhip_vec* values_out) {
+    FRONT(gather(index, values, n_values, values_out));
+    TE_CHECKED_LOCAL(fm::select_check_gather(index, values, n_values, values_out), te_operands(index, values, n_values, nullptr, 0), L,
+                     fmhip_gather(L[0], L + 1, n_values, values_out));
+    return guarded([&] { Engine::get().gather(index, values, n_values, values_out); });
+}
+
 // ---------------------------------------------------------------- tabulated functions (table_engine.hpp)
 int fmhip_table_build(const double* knots, const double* values, int count, int interpolation, int extrapolation, int derivative, double* coefficients_out) {
     return host_only([&] { fm::table_build_checked(knots, values, count, interpolation, extrapolation, derivative, coefficients_out); });

@@ -247,6 +247,7 @@ public:
 };
 
 struct DevMtBmArgs;             // mt_bm_kernel.h
+struct DevCompressArgs;         // select_kernel.h
 
 class Engine {
 public:
@@ -426,6 +427,15 @@ public:
     void resample(fmhip_vec weights, int scheme, int64_t m, double offset, fmhip_vec uniforms, const fmhip_vec* values, int n_values, fmhip_vec* values_out,
                   fmhip_vec* ancestors_out, double* total_out);
 
+    // selection (select_engine.hpp; selected(x) is x >= 0.0f): compress — the selected paths of up to 8 vectors and their
+    // positions (n <= 2^24) as new vectors of exactly `count` elements, count == 0: every handle 0; expand — the inverse, the paths that are
+    // not selected filled with (float)fill, SIZE_MISMATCH (behind the count) where the values are not `count` long; gather — values_out[i][j]
+    // = values[i][index[j]], the quiet NaN where the index is no integer in [0, n - 1].  compress and expand wait twice: the count decides the
+    // size of what is allocated.  The outputs are written only when the call succeeds; one engine's sample only (UNSUPPORTED with a communicator).
+    void compress(fmhip_vec mask, const fmhip_vec* values, int n_values, fmhip_vec* values_out, fmhip_vec* positions_out, int64_t* count_out);
+    void expand(fmhip_vec mask, const fmhip_vec* values, int n_values, double fill, fmhip_vec* values_out);
+    void gather(fmhip_vec index, const fmhip_vec* values, int n_values, fmhip_vec* values_out);
+
     // tabulated functions (table_engine.hpp): n_tables functions on the same knots (host/tabulated_function.hpp) applied to
     // every element of x, out[0 … n_tables) new, materialised vectors from one launch that reads x once.  Arguments are checked before
     // anything is flushed or launched; out is written only when the call succeeds.
@@ -575,6 +585,8 @@ private:
     template <class Launch> void pass_launch(volatile uint64_t* flag, uint64_t*& done_flag, uint64_t& done_value, const char* what, Launch launch);
     template <class Enqueue> void pass_launch_raising(volatile uint64_t* flag, const char* what, Enqueue enqueue);
     void pass_wait(volatile uint64_t* flag, uint64_t value, const char* what);
+    int64_t select_count_phase(DevCompressArgs& a, int64_t n, const char* what);                  // select_engine.hpp: the two phases of a compress or an expand
+    template <class Launch> void select_second_phase(const char* what, Launch launch);
     void pass_release();
     void* pass_zero_ = nullptr; size_t pass_zero_cap_ = 0; void* pass_other_ = nullptr; size_t pass_other_cap_ = 0;
     uint64_t pass_seq_ = 0; bool pass_dirty_ = false;
@@ -936,6 +948,15 @@ void resample_check(fmhip_vec weights, int scheme, int64_t m, double offset, fmh
 void resample_check_sizes(int64_t n, int64_t m, int64_t n_uniforms, bool want_ancestors);      // FMHIP_ERR_INVALID_ARGUMENT, FMHIP_ERR_SIZE_MISMATCH
 void resample_host_checked(const float* weights, int64_t n, int scheme, int64_t m, double offset, const float* uniforms, const float* const* values, int n_values,
                            float* const* values_out, int64_t* ancestors_out, double* total_out);
+// the same for fmhip_compress / fmhip_expand / fmhip_gather, and the definitions behind their _host twins (select_engine.hpp; the rules are
+// select_host.hpp's): FMHIP_ERR_INVALID_ARGUMENT; expand_host_checked also FMHIP_ERR_SIZE_MISMATCH
+void select_check_compress(fmhip_vec mask, const fmhip_vec* values, int n_values, const fmhip_vec* values_out, const fmhip_vec* positions_out, const int64_t* count_out);
+void select_check_expand(fmhip_vec mask, const fmhip_vec* values, int n_values, const fmhip_vec* values_out);
+void select_check_gather(fmhip_vec index, const fmhip_vec* values, int n_values, const fmhip_vec* values_out);
+void select_check_mask_size(const char* what, int64_t n, bool want_positions);
+void compress_host_checked(const float* mask, int64_t n, const float* const* values, int n_values, float* const* values_out, int64_t* positions_out, int64_t* count_out);
+void expand_host_checked(const float* mask, int64_t n, const float* const* values, int n_values, int64_t n_value_elements, double fill, float* const* values_out);
+void gather_host_checked(const float* index, int64_t m, const float* const* values, int n_values, int64_t n, float* const* values_out);
 // the same for fmhip_table_apply, and the definitions behind fmhip_table_build / fmhip_table_apply_host (table_engine.hpp; the rules are
 // host/tabulated_function.hpp's): all throw FMHIP_ERR_INVALID_ARGUMENT
 void table_check_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, const fmhip_vec* out);

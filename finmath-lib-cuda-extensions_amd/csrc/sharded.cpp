@@ -1010,6 +1010,61 @@ int resample(fmhip_vec weights, int scheme, int64_t m, double offset, fmhip_vec 
     });
 }
 
+// Selection (select_engine.hpp).  The shards' counts differ, and a compressed vector would have to be laid out over the shards again: an
+// exchange of elements between the shards, which is not built (one_shard).  A list of one shard is that shard's call; a compress learns the
+// size of its vectors from the shard before the front can name them.
+static const char* const SELECT_WHY = "the shards' counts differ and an exchange of elements between the shards is not built";
+int compress(fmhip_vec mask, const fmhip_vec* values, int n_values, fmhip_vec* values_out, fmhip_vec* positions_out, int64_t* count_out) {
+    return fronted([&](Shards& s) {
+        select_check_compress(mask, values, n_values, values_out, positions_out, count_out);
+        std::vector<fmhip_vec> sample{ mask };
+        sample.insert(sample.end(), values, values + n_values);
+        const int64_t n = front_size(s, sample.data(), (int)sample.size(), "compress", false);
+        select_check_mask_size("compress", n, positions_out != nullptr);
+        one_shard(s, "compress", SELECT_WHY);
+        const int want_positions = positions_out ? 1 : 0, n_out = n_values + want_positions;
+        std::vector<fmhip_vec> got((size_t)n_out + 1, 0), ids((size_t)n_out + 1, 0);
+        int64_t count = 0;
+        on_the_shard(s, [&](Worker& w) {
+            const std::vector<fmhip_vec> l = localize(w, sample.data(), (int)sample.size());
+            return fmhip_compress(l[0], l.data() + 1, n_values, got.data(), want_positions ? &got[(size_t)n_values] : nullptr, &count);
+        });
+        if (count > 0 && n_out > 0) {
+            for (int f = 0; f < n_out; ++f) ids[(size_t)f] = s.fresh(count);
+            s.post([&](Worker& w) { for (int f = 0; f < n_out; ++f) w.bind(ids[(size_t)f], got[(size_t)f]); });
+            s.wait();
+        }
+        for (int i = 0; i < n_values; ++i) values_out[i] = ids[(size_t)i];
+        if (want_positions) *positions_out = ids[(size_t)n_values];
+        if (count_out) *count_out = count;
+    });
+}
+int expand(fmhip_vec mask, const fmhip_vec* values, int n_values, double fill, fmhip_vec* values_out) {
+    return fronted([&](Shards& s) {
+        select_check_expand(mask, values, n_values, values_out);
+        const int64_t n = front_size(s, &mask, 1, "expand", false);
+        (void)front_size(s, values, n_values, "expand", false);
+        select_check_mask_size("expand", n, false);
+        one_shard(s, "expand", SELECT_WHY);
+        produce_per_shard(s, n, n_values, values_out, [&](Worker& w, fmhip_vec* got) {
+            return fmhip_expand(w.at(mask), localize(w, values, n_values).data(), n_values, fill, got);
+        });
+    });
+}
+int gather(fmhip_vec index, const fmhip_vec* values, int n_values, fmhip_vec* values_out) {
+    return fronted([&](Shards& s) {
+        select_check_gather(index, values, n_values, values_out);
+        const int64_t m = front_size(s, &index, 1, "gather", false);
+        const int64_t n = front_size(s, values, n_values, "gather", false);
+        select_check_mask_size("gather", m, false);
+        select_check_mask_size("gather from a vector", n, false);
+        one_shard(s, "gather", SELECT_WHY);
+        produce_per_shard(s, m, n_values, values_out, [&](Worker& w, fmhip_vec* got) {
+            return fmhip_gather(w.at(index), localize(w, values, n_values).data(), n_values, got);
+        });
+    });
+}
+
 // Tabulated functions (table_engine.hpp).  Elementwise: every shard runs the call on its block; the new vectors' blocks are the shards' results.
 int table_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, fmhip_vec* out) {
     return fronted([&](Shards& s) {

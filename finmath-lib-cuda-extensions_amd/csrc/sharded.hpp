@@ -80,6 +80,9 @@ int prefix_sums(fmhip_vec v, int mode, fmhip_vec* out, double* total_out);      
 int prefix_sums_at(fmhip_vec v, const int64_t* positions, int count, double* sums_out);
 int resample(fmhip_vec weights, int scheme, int64_t m, double offset, fmhip_vec uniforms, const fmhip_vec* values, int n_values, fmhip_vec* values_out,
              fmhip_vec* ancestors_out, double* total_out);                                   // one shard; more: FMHIP_ERR_UNSUPPORTED
+int compress(fmhip_vec mask, const fmhip_vec* values, int n_values, fmhip_vec* values_out, fmhip_vec* positions_out, int64_t* count_out);      // one shard; more: FMHIP_ERR_UNSUPPORTED
+int expand(fmhip_vec mask, const fmhip_vec* values, int n_values, double fill, fmhip_vec* values_out);
+int gather(fmhip_vec index, const fmhip_vec* values, int n_values, fmhip_vec* values_out);
 int table_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, fmhip_vec* out);      // per shard
 int function_apply(fmhip_vec x, const int* kinds, int n_functions, fmhip_vec* out);                                         // per shard
 int option_formula(int model, fmhip_vec forward, double forward_scalar, fmhip_vec volatility, double volatility_scalar, fmhip_vec payoff_unit,

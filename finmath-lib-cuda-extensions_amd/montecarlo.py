@@ -399,15 +399,21 @@ def stochastic_local_volatility_call_mc(brownian_motion, initial_value, risk_fre
     return value.getAverage(), value.getStandardError()
 
 
-def bermudan_option_mc(brownian_motion, initial_value, risk_free_rate, volatility, exercise_dates, strike, call=False, basis_order=3, bins=0):
+def bermudan_option_mc(brownian_motion, initial_value, risk_free_rate, volatility, exercise_dates, strike, call=False, basis_order=3, bins=0, in_the_money_only=False):
     """Value of a Bermudan option under Black–Scholes by Longstaff–Schwartz backward induction.  States from the log-Euler scheme of
     black_scholes_call_mc, kept at the exercise dates (points of the time discretisation).  The value starts as the last date's discounted
     payoff; at each earlier date the current value is regressed on 1, S, …, S^basis_order over ALL paths (the constant is a deterministic
     random variable: a host scalar to the estimator), and paths on which exercise − continuation estimate >= 0 take the discounted exercise
     value.  Returns (value.getAverage(), value).  With one exercise date this is the European option on the same paths.
     bins > 0: the regression is LOCALIZED — per quantile bin of S (bins of equal count, at most 64) on 1, S, …, S^basis_order with
-    basis_order <= 2 (MonteCarloConditionalExpectationLocalizedRegression); bins = 0: the global fit."""
+    basis_order <= 2 (MonteCarloConditionalExpectationLocalizedRegression); bins = 0: the global fit.
+    in_the_money_only=True: Longstaff & Schwartz's regression over the paths on which exercise is worth something.  At
+    each date the mask is strike − S (put) or S − strike (call); the state and the current value are compressed by it
+    (selection.compress), the estimator fits and evaluates on the short vectors, and the estimate is expanded back with fill = +inf, so
+    that exercise − continuation is −inf on the other paths and choose keeps the value there.  A date on which no path is selected
+    leaves the value as it is.  A cubic then suffices where the all-paths fit needs degree 5."""
     from .regression import MonteCarloConditionalExpectationLocalizedRegression, MonteCarloConditionalExpectationRegression
+    from .selection import compress, expand
     if bins and basis_order + 1 > 3: raise ValueError("a localized regression takes at most 3 basis functions per bin: basis_order <= 2")
     dates = sorted(float(d) for d in exercise_dates)
     if not dates: raise ValueError("no exercise date")
@@ -432,6 +438,19 @@ def bermudan_option_mc(brownian_motion, initial_value, risk_free_rate, volatilit
     one = brownian_motion.getRandomVariableForConstant(1.0)
     for k in range(len(dates) - 2, -1, -1):
         s = states[k]
+        if in_the_money_only:
+            mask = s.sub(strike) if call else s.bus(strike)
+            (short_s, short_value), count = compress(mask, [s, value])
+            if count == 0: continue
+            basis = [one, short_s]
+            for _ in range(2, basis_order + 1): basis.append(basis[-1].mult(short_s))
+            basis = basis[:basis_order + 1]
+            if bins: estimate = MonteCarloConditionalExpectationLocalizedRegression(short_s, bins, basis).getConditionalExpectation(short_value)
+            else: estimate = MonteCarloConditionalExpectationRegression(basis).getConditionalExpectation(short_value)
+            (continuation,) = expand(mask, [estimate], fill=math.inf)
+            exercise = exercise_value(s, dates[k])
+            value = exercise.sub(continuation).choose(exercise, value)
+            continue
         basis = [one, s]
         for _ in range(2, basis_order + 1): basis.append(basis[-1].mult(s))
         basis = basis[:basis_order + 1]

@@ -498,6 +498,48 @@ int fmhip_resample_host(const float* weights, int64_t n, int scheme, int64_t m, 
                         const float* const* values, int n_values, float* const* values_out,
                         int64_t* ancestors_out, double* total_out);          /* the DEFINITION; needs no device */
 
+/* Selection on the device: keep the paths on which a condition holds — copy_if —, put them back, and read by a caller's
+ * index.  Longstaff-Schwartz on the in-the-money paths, a quantile or a tail mean given a barrier hit or a default, rare events whose
+ * downstream work should run on 1 % of the paths, particles that are killed, one index list carried to any number of vectors.  The
+ * definition is csrc/select_host.hpp, one header for the host and the device; counts are integers, nothing is summed in floating point:
+ * the device's bits are the _host twins' for every input.
+ *   selected(x)      x >= 0.0f in fp32, the trigger of FMHIP_OP_CHOOSE: a NaN is not selected, -0.0 is, +inf is.
+ *   q(r), count      q(r) = the number of selected elements of mask before r; count = the number of all of them.
+ *   fmhip_compress   for the selected r in ascending order: values_out[i][q(r)] = values[i][r] bit for bit (a NaN keeps its payload) and
+ *                    positions_out[q(r)] = (float)r — new, materialised vectors of exactly `count` elements.  n_values is 0 ... 8;
+ *                    values_out (with n_values == 0) and positions_out may be NULL; a call that only wants count_out is valid.  Positions
+ *                    are offered up to n = 2^24, where the float is exact.  count == 0: FMHIP_OK, *count_out = 0, every output handle is
+ *                    written as 0 and nothing is allocated — an empty vector is not a vector here.
+ *   fmhip_expand     the inverse: values_out[i][r] = values[i][q(r)] where selected(mask[r]), otherwise (float)fill (which may be +-inf or
+ *                    NaN) — new vectors of n elements.  n_values is 1 ... 8.  Every values[i] has exactly count(mask) elements, otherwise
+ *                    FMHIP_ERR_SIZE_MISMATCH: found after the count, with no vector and no byte left behind.
+ *   fmhip_gather     index has m elements, the values n each: values_out[i][j] = values[i][k] bit for bit where index[j] is an integer k
+ *                    with 0 <= k <= n - 1 (-0.0 counts as 0; the comparison is made in double, so it is right for every n); anywhere else
+ *                    — not an integer, out of range, NaN — the quiet NaN 0x7fc00000.  The status is FMHIP_OK whatever the index holds.
+ *                    n_values is 1 ... 8.  gather(positions_out of a compress, v) is that compress of v.
+ * compress and expand run in TWO phases with one host wait between them: the count is on the device, and the outputs are allocated at
+ * exactly the size it says (a 1 % selection holds 1 % of the memory).  A refusal or a failed allocation at either stage leaves the outputs
+ * untouched and no vector behind.
+ * Checked on the host before anything is flushed or launched: n_values outside its range, nothing asked for, a handle of 0, a NULL pointer,
+ * n or m outside 1 ... 2^31 - 1, positions_out with n > 2^24 -> FMHIP_ERR_INVALID_ARGUMENT; values whose size is not the mask's (compress)
+ * or that differ among themselves -> FMHIP_ERR_SIZE_MISMATCH; FMHIP_ERR_INVALID_HANDLE.  A build without the kernels answers
+ * FMHIP_ERR_UNSUPPORTED; it never falls back.
+ * ONE sample on ONE device: a device list of more than one shard or an expectation communicator of more than one rank ->
+ * FMHIP_ERR_UNSUPPORTED for all three (the shards' counts differ and an exchange between shards is not built).
+ * The _host twins are the definitions on plain arrays and need no device.  fmhip_compress_host: values_out[i] and positions_out have
+ * capacity n, the first *count_out elements are written; fmhip_expand_host: values[i] has n_value_elements elements, which must be the
+ * mask's count (FMHIP_ERR_SIZE_MISMATCH, nothing written); fmhip_gather_host: index and values_out[i] have m elements, values[i] n. */
+int fmhip_compress(fmhip_vec mask, const fmhip_vec* values, int n_values /* 0 ... 8 */, fmhip_vec* values_out,
+                   fmhip_vec* positions_out /* may be NULL */, int64_t* count_out /* may be NULL */);
+int fmhip_expand(fmhip_vec mask, const fmhip_vec* values, int n_values /* 1 ... 8 */, double fill, fmhip_vec* values_out);
+int fmhip_gather(fmhip_vec index, const fmhip_vec* values, int n_values /* 1 ... 8 */, fmhip_vec* values_out);
+int fmhip_compress_host(const float* mask, int64_t n, const float* const* values, int n_values, float* const* values_out,
+                        int64_t* positions_out, int64_t* count_out);         /* the DEFINITION; needs no device */
+int fmhip_expand_host(const float* mask, int64_t n, const float* const* values, int n_values, int64_t n_value_elements, double fill,
+                      float* const* values_out);                             /* the DEFINITION */
+int fmhip_gather_host(const float* index, int64_t m, const float* const* values, int n_values, int64_t n,
+                      float* const* values_out);                             /* the DEFINITION */
+
 /* Tabulated functions on the device: RandomVariable.apply for a CURVE — a function tabulated on knots and interpolated: a
  * local-volatility slice, a Markov-functional numeraire, a payoff profile, an exercise boundary, an inverse empirical CDF — without the
  * vector leaving the device.  The definition is host/tabulated_function.hpp, one header for the host and the device.

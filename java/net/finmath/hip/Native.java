@@ -115,6 +115,19 @@ final class Native {
 	static native int resample(long weights, int scheme, long m, double offset, long uniforms, long[] values, long[] valuesOut, long[] ancestorsOutOrNull, double[] totalOutOrNull);
 	/** The definition of resample over host arrays: valueColumns holds nValues columns of n floats, outColumns nValues columns of m floats; ancestorsOutOrNull[j] = a_j, -1 for a dead element. */
 	static native int resampleHost(float[] weightsOrNull, long n, int scheme, long m, double offset, float[] uniformsOrNull, float[] valueColumns, int nValues, float[] outColumns, long[] ancestorsOutOrNull, double[] totalOutOrNull);
+	// ---- selection on the device: the paths on which mask >= 0 as shorter vectors (copy_if), back again, and a gather by an index; the device's bits are those of the Host twins
+	/** valuesOutOrNull[i] = a new vector of count elements, the selected paths of values[i] in path order, bit for bit (at most 8 vectors; none: null); positionsOutOrNull[0] = their positions as floats (n <= 2^24); countOutOrNull[0] = count.  count == 0: every handle is 0, nothing is allocated. */
+	static native int compress(long mask, long[] valuesOrNull, long[] valuesOutOrNull, long[] positionsOutOrNull, long[] countOutOrNull);
+	/** The inverse of compress: valuesOut[i] = a new vector of the mask's size, values[i][q(r)] on the selected paths and (float) fill elsewhere; values of another size than the mask's count: FMHIP_ERR_SIZE_MISMATCH. */
+	static native int expand(long mask, long[] values, double fill, long[] valuesOut);
+	/** valuesOut[i][j] = values[i][index[j]] bit for bit where index[j] is an integer in [0, n - 1], the quiet NaN elsewhere; the status does not depend on the index. */
+	static native int gather(long index, long[] values, long[] valuesOut);
+	/** The definition of compress over host arrays: valueColumns and outColumns hold nValues columns of mask.length floats; the first countOutOrNull[0] elements of each output column and of positionsOutOrNull are written. */
+	static native int compressHost(float[] mask, float[] valueColumns, int nValues, float[] outColumns, long[] positionsOutOrNull, long[] countOutOrNull);
+	/** The definition of expand over host arrays: valueColumns holds nValues columns of nValueElements floats, outColumns nValues columns of mask.length floats. */
+	static native int expandHost(float[] mask, float[] valueColumns, int nValues, long nValueElements, double fill, float[] outColumns);
+	/** The definition of gather over host arrays: valueColumns holds nValues columns of n floats, outColumns nValues columns of index.length floats. */
+	static native int gatherHost(float[] index, float[] valueColumns, int nValues, long n, float[] outColumns);
 	// ---- tabulated functions on the device: RandomVariable.apply for a curve; the device's bits are those of tableApplyHost
 	/** coefficientsOut[(knots.length + 1) * 4]: the segments of one function from its values at the knots; interpolation 0 piecewise constant, 1 linear, 2 natural cubic spline, 3 monotone cubic; extrapolation 0 constant, 1 linear; derivative 0 or 1. */
 	static native int tableBuild(double[] knots, double[] values, int interpolation, int extrapolation, int derivative, double[] coefficientsOut);

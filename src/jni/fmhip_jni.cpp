@@ -347,6 +347,72 @@ FMJ(jint, resampleHost)(JNIEnv* env, jclass, jfloatArray weightsOrNull, jlong n,
     if (st == FMHIP_OK && totalOutOrNull) env->SetDoubleArrayRegion(totalOutOrNull, 0, 1, &total);
     return st;
 }
+// ---------------------------------------------------------------- selection on the device
+FMJ(jint, compress)(JNIEnv* env, jclass, jlong mask, jlongArray valuesOrNull, jlongArray valuesOutOrNull, jlongArray positionsOutOrNull, jlongArray countOutOrNull) {
+    Pin<jlong> pv(env, valuesOrNull, JNI_ABORT);
+    const int64_t nv = pv.p ? pv.length() : 0;
+    if (nv > 8 || (nv > 0 && (!valuesOutOrNull || env->GetArrayLength(valuesOutOrNull) < nv)) || (positionsOutOrNull && env->GetArrayLength(positionsOutOrNull) < 1)
+        || (countOutOrNull && env->GetArrayLength(countOutOrNull) < 1)) return FMHIP_ERR_INVALID_ARGUMENT;
+    fmhip_vec positions = 0, out[8] = { 0 };
+    int64_t count = 0;
+    const int st = fmhip_compress((fmhip_vec)mask, (const fmhip_vec*)pv.p, (int)nv, out, positionsOutOrNull ? &positions : nullptr, &count);
+    if (st == FMHIP_OK) {
+        if (nv > 0) { jlong o[8]; for (int i = 0; i < nv; ++i) o[i] = (jlong)out[i]; env->SetLongArrayRegion(valuesOutOrNull, 0, (jsize)nv, o); }
+        set1(env, positionsOutOrNull, (jlong)positions);
+        set1(env, countOutOrNull, (jlong)count);
+    }
+    return st;
+}
+FMJ(jint, expand)(JNIEnv* env, jclass, jlong mask, jlongArray values, jdouble fill, jlongArray valuesOut) {
+    Pin<jlong> pv(env, values, JNI_ABORT);
+    const int64_t nv = pv.p ? pv.length() : 0;
+    if (nv < 1 || nv > 8 || !valuesOut || env->GetArrayLength(valuesOut) < nv) return FMHIP_ERR_INVALID_ARGUMENT;
+    fmhip_vec out[8] = { 0 };
+    const int st = fmhip_expand((fmhip_vec)mask, (const fmhip_vec*)pv.p, (int)nv, (double)fill, out);
+    if (st == FMHIP_OK) { jlong o[8]; for (int i = 0; i < nv; ++i) o[i] = (jlong)out[i]; env->SetLongArrayRegion(valuesOut, 0, (jsize)nv, o); }
+    return st;
+}
+FMJ(jint, gather)(JNIEnv* env, jclass, jlong index, jlongArray values, jlongArray valuesOut) {
+    Pin<jlong> pv(env, values, JNI_ABORT);
+    const int64_t nv = pv.p ? pv.length() : 0;
+    if (nv < 1 || nv > 8 || !valuesOut || env->GetArrayLength(valuesOut) < nv) return FMHIP_ERR_INVALID_ARGUMENT;
+    fmhip_vec out[8] = { 0 };
+    const int st = fmhip_gather((fmhip_vec)index, (const fmhip_vec*)pv.p, (int)nv, out);
+    if (st == FMHIP_OK) { jlong o[8]; for (int i = 0; i < nv; ++i) o[i] = (jlong)out[i]; env->SetLongArrayRegion(valuesOut, 0, (jsize)nv, o); }
+    return st;
+}
+FMJ(jint, compressHost)(JNIEnv* env, jclass, jfloatArray mask, jfloatArray valueColumns, jint nValues, jfloatArray outColumns, jlongArray positionsOutOrNull, jlongArray countOutOrNull) {
+    if (countOutOrNull && env->GetArrayLength(countOutOrNull) < 1) return FMHIP_ERR_INVALID_ARGUMENT;
+    int64_t count = 0;
+    int st;
+    {
+        Pin<jfloat> pm(env, mask, JNI_ABORT); Pin<jfloat> pv(env, valueColumns, JNI_ABORT); Pin<jfloat> po(env, outColumns); Pin<jlong> pp(env, positionsOutOrNull);
+        const int64_t n = pm.p ? (int64_t)pm.length() : 0;
+        if (n < 1 || nValues < 0 || nValues > 8 || (pp.p && (int64_t)pp.length() < n)) return FMHIP_ERR_INVALID_ARGUMENT;
+        if (nValues > 0 && (!pv.p || !po.p || (int64_t)pv.length() < (int64_t)nValues * n || (int64_t)po.length() < (int64_t)nValues * n)) return FMHIP_ERR_INVALID_ARGUMENT;
+        const float* in[8] = { nullptr }; float* columns[8] = { nullptr };
+        for (int i = 0; i < nValues; ++i) { in[i] = pv.p + (int64_t)i * n; columns[i] = po.p + (int64_t)i * n; }
+        st = fmhip_compress_host(pm.p, n, in, (int)nValues, columns, (int64_t*)pp.p, &count);
+    }
+    if (st == FMHIP_OK) set1(env, countOutOrNull, (jlong)count);
+    return st;
+}
+FMJ(jint, expandHost)(JNIEnv* env, jclass, jfloatArray mask, jfloatArray valueColumns, jint nValues, jlong nValueElements, jdouble fill, jfloatArray outColumns) {
+    Pin<jfloat> pm(env, mask, JNI_ABORT); Pin<jfloat> pv(env, valueColumns, JNI_ABORT); Pin<jfloat> po(env, outColumns);
+    const int64_t n = pm.p ? (int64_t)pm.length() : 0, c = (int64_t)nValueElements;
+    if (n < 1 || c < 0 || nValues < 1 || nValues > 8 || !pv.p || !po.p || (int64_t)pv.length() < (int64_t)nValues * c || (int64_t)po.length() < (int64_t)nValues * n) return FMHIP_ERR_INVALID_ARGUMENT;
+    const float* in[8] = { nullptr }; float* columns[8] = { nullptr };
+    for (int i = 0; i < nValues; ++i) { in[i] = pv.p + (int64_t)i * c; columns[i] = po.p + (int64_t)i * n; }
+    return fmhip_expand_host(pm.p, n, in, (int)nValues, c, (double)fill, columns);
+}
+FMJ(jint, gatherHost)(JNIEnv* env, jclass, jfloatArray index, jfloatArray valueColumns, jint nValues, jlong n, jfloatArray outColumns) {
+    Pin<jfloat> pi(env, index, JNI_ABORT); Pin<jfloat> pv(env, valueColumns, JNI_ABORT); Pin<jfloat> po(env, outColumns);
+    const int64_t m = pi.p ? (int64_t)pi.length() : 0;
+    if (m < 1 || n < 1 || nValues < 1 || nValues > 8 || !pv.p || !po.p || (int64_t)pv.length() < (int64_t)nValues * (int64_t)n || (int64_t)po.length() < (int64_t)nValues * m) return FMHIP_ERR_INVALID_ARGUMENT;
+    const float* in[8] = { nullptr }; float* columns[8] = { nullptr };
+    for (int i = 0; i < nValues; ++i) { in[i] = pv.p + (int64_t)i * (int64_t)n; columns[i] = po.p + (int64_t)i * m; }
+    return fmhip_gather_host(pi.p, m, in, (int)nValues, (int64_t)n, columns);
+}
 // ---------------------------------------------------------------- tabulated functions on the device
 FMJ(jint, tableBuild)(JNIEnv* env, jclass, jdoubleArray knots, jdoubleArray values, jint interpolation, jint extrapolation, jint derivative, jdoubleArray coefficientsOut) {
     Pin<jdouble> pk(env, knots, JNI_ABORT); Pin<jdouble> pv(env, values, JNI_ABORT); Pin<jdouble> po(env, coefficientsOut);
