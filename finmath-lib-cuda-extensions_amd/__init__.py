@@ -34,6 +34,8 @@ from .analytic import NORMAL_CDF, NORMAL_DENSITY, NORMAL_QUANTILE, NamedFunction
 from .analytic import bachelier_option_value, black_scholes_option_value, option_formula, option_formula_double, option_formula_host
 from .analytic import (bachelier_implied_volatility, black_scholes_implied_volatility, convert_volatility, implied_volatility,
                        implied_volatility_double, implied_volatility_host)
+from .transform import (TransformNodes, bates_option_value, bates_transform_nodes, black_scholes_transform_nodes, heston_call_analytic, heston_option_value,
+                        heston_transform_nodes, merton_transform_nodes, transform_option_host, transform_option_value)
 from .nested import (block_max, block_means, block_min, block_moments, block_moments_host, block_order_statistics, block_order_statistics_host, block_quantile_expectations,
                      block_quantiles, block_sort, block_sort_host, device_nested, repeat_each, tile)
 from .cross_section import (argmax_across, argmin_across, cross_order_statistics_host, cross_select_host, device_cross_order, max_across, median_across, min_across,

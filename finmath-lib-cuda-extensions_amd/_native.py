@@ -34,6 +34,7 @@ SYMBOLS = [
     "fmhip_table_build", "fmhip_table_apply", "fmhip_table_apply_host",
     "fmhip_function_apply", "fmhip_function_apply_host", "fmhip_option_formula", "fmhip_option_formula_host",
     "fmhip_implied_volatility", "fmhip_implied_volatility_host",
+    "fmhip_transform_option", "fmhip_transform_option_host",
     "fmhip_block_moments", "fmhip_block_moments_host", "fmhip_vec_repeat",
     "fmhip_block_order_statistics", "fmhip_block_order_statistics_host", "fmhip_block_sort", "fmhip_block_sort_host",
     "fmhip_cross_order_statistics", "fmhip_cross_order_statistics_host", "fmhip_cross_select", "fmhip_cross_select_host",
@@ -205,6 +206,8 @@ def lib():
         "fmhip_option_formula_host": [i32, vp, dbl, vp, dbl, vp, dbl, i64, dbl, dbl, i32, C.POINTER(vp)],
         "fmhip_implied_volatility": [i32, vec, dbl, vec, dbl, vec, dbl, dbl, dbl, i32, pv],
         "fmhip_implied_volatility_host": [i32, vp, dbl, vp, dbl, vp, dbl, i64, dbl, dbl, i32, C.POINTER(vp)],
+        "fmhip_transform_option": [C.POINTER(dbl), i32, i32, vec, dbl, pv, C.POINTER(dbl), vec, dbl, dbl, i32, pv],
+        "fmhip_transform_option_host": [C.POINTER(dbl), i32, i32, vp, dbl, C.POINTER(vp), C.POINTER(dbl), vp, dbl, i64, dbl, i32, C.POINTER(vp)],
         "fmhip_block_moments": [pv, i32, i64, C.c_uint32, pv], "fmhip_block_moments_host": [vp, i64, i64, C.c_uint32, vp],
         "fmhip_vec_repeat": [vec, i64, i64, pv],
         "fmhip_block_order_statistics": [pv, i32, i64, C.POINTER(i64), i32, C.POINTER(i64), C.POINTER(i64), i32, pv],

@@ -981,6 +981,22 @@ int fmhip_implied_volatility(int model, fmhip_vec price, double price_scalar, fm
     return guarded([&] { Engine::get().implied_volatility(model, price, price_scalar, forward, forward_scalar, payoff_unit, payoff_unit_scalar, maturity, strike, outputs, out); });
 }
 
+// ---------------------------------------------------------------- transform option value per path (transform_engine.hpp)
+int fmhip_transform_option_host(const double* nodes, int n_nodes, int n_states, const float* forward, double forward_scalar, const float* const* states,
+                                const double* state_scalars, const float* payoff_unit, double payoff_unit_scalar, int64_t n, double strike, int outputs, float* const* out) {
+    return host_only([&] { fm::transform_option_host_checked(nodes, n_nodes, n_states, forward, forward_scalar, states, state_scalars, payoff_unit, payoff_unit_scalar, n, strike, outputs, out); });
+}
+int fmhip_transform_option(const double* nodes, int n_nodes, int n_states, fmhip_vec forward, double forward_scalar, const fmhip_vec* states, const double* state_scalars,
+                           fmhip_vec payoff_unit, double payoff_unit_scalar, double strike, int outputs, fmhip_vec* out) {
+    FRONT(transform_option(nodes, n_nodes, n_states, forward, forward_scalar, states, state_scalars, payoff_unit, payoff_unit_scalar, strike, outputs, out));
+    // (all four in the list: a handle of 0 stays 0, the scalar beside it; the check below refuses a count the list could not hold)
+    fmhip_vec operands[4] = { forward, payoff_unit, 0, 0 };
+    if (states && n_states >= 1 && n_states <= 2) for (int s = 0; s < n_states; ++s) operands[2 + s] = states[s];
+    TE_CHECKED_LOCAL(fm::transform_check(nodes, n_nodes, n_states, forward, states, state_scalars, payoff_unit, strike, outputs, out), te_operands(0, operands, 4, nullptr, 0), L,
+                     fmhip_transform_option(nodes, n_nodes, n_states, L[0], forward_scalar, L + 2, state_scalars, L[1], payoff_unit_scalar, strike, outputs, out));
+    return guarded([&] { Engine::get().transform_option(nodes, n_nodes, n_states, forward, forward_scalar, states, state_scalars, payoff_unit, payoff_unit_scalar, strike, outputs, out); });
+}
+
 // ---------------------------------------------------------------- nested simulation: block moments and the repeat (nested_engine.hpp)
 int fmhip_block_moments_host(const float* v, int64_t n, int64_t block, uint32_t mask, float* outs) {
     return host_only([&] { fm::block_moments_host_checked(v, n, block, mask, outs); });

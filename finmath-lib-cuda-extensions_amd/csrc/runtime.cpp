@@ -2484,6 +2484,7 @@ void Engine::profile_read(double* ms_total, int64_t* n) {
 #include "table_engine.hpp"            // Engine::table_apply: tabulated functions of a vector's elements, a new vector each from one launch
 #include "analytic_engine.hpp"         // Engine::function_apply, option_formula: Φ, φ, Φ⁻¹ and the Black–Scholes / Bachelier formulas per path
 #include "implied_volatility_engine.hpp"      // Engine::implied_volatility: the inverse of the option formulas' value in the volatility, per path
+#include "transform_engine.hpp"               // Engine::transform_option: a call under an exponential-affine transform as a sum over a node table, per path
 #include "kreg_engine.hpp"             // Engine::kernel_moments_pass: kernel-weighted local moments at a grid of points of a key in one launch
 #include "nested_engine.hpp"           // Engine::block_moments, repeat: the moments of consecutive blocks as new vectors, k inner paths per outer state
 #include "block_order_engine.hpp"      // Engine::block_order_statistics, block_sort: ranks and range means of consecutive blocks as new vectors, the blocks sorted

@@ -455,6 +455,13 @@ public:
     void implied_volatility(int model, fmhip_vec price, double price_scalar, fmhip_vec forward, double forward_scalar, fmhip_vec payoff_unit,
                             double payoff_unit_scalar, double maturity, double strike, int outputs, fmhip_vec* out);
 
+    // transform option value per path (transform_engine.hpp): value / ∂/∂forward / ∂/∂V_0 (a mask) of a call under a model whose
+    // transform is exponential-affine in n_states states, as the finite sum over n_nodes rows of `nodes` (host/transform_formula.hpp); forward,
+    // payoff unit and the states are a vector or — handle 0 — the scalar beside it; out: new, materialised vectors from one launch.  Checked
+    // before anything is flushed; out written only on success.
+    void transform_option(const double* nodes, int n_nodes, int n_states, fmhip_vec forward, double forward_scalar, const fmhip_vec* states,
+                          const double* state_scalars, fmhip_vec payoff_unit, double payoff_unit_scalar, double strike, int outputs, fmhip_vec* out);
+
     // nested simulation (nested_engine.hpp): the moments of the n / block consecutive blocks of up to four vectors — sum, mean,
     // population variance by a mask, fp64 sums in an association that is a function of `block` alone (host/block_moments.hpp) — as new,
     // materialised vectors of n / block elements, outs[i·popcount(mask) + j]; and the repeat out[(t·n + p)·each + e] = v[p], bit for bit.
@@ -974,6 +981,12 @@ void option_formula_host_checked(int model, const float* forward, double forward
 void implied_check(int model, fmhip_vec price, fmhip_vec forward, fmhip_vec payoff_unit, double maturity, double strike, int outputs, const fmhip_vec* out);
 void implied_volatility_host_checked(int model, const float* price, double price_scalar, const float* forward, double forward_scalar, const float* payoff_unit,
                                      double payoff_unit_scalar, int64_t n, double maturity, double strike, int outputs, float* const* out);
+// the same for fmhip_transform_option, and the definition behind its _host twin (transform_engine.hpp; the rules are
+// host/transform_formula.hpp's): both throw FMHIP_ERR_INVALID_ARGUMENT
+void transform_check(const double* nodes, int n_nodes, int n_states, fmhip_vec forward, const fmhip_vec* states, const double* state_scalars, fmhip_vec payoff_unit,
+                     double strike, int outputs, const fmhip_vec* out);
+void transform_option_host_checked(const double* nodes, int n_nodes, int n_states, const float* forward, double forward_scalar, const float* const* states,
+                                   const double* state_scalars, const float* payoff_unit, double payoff_unit_scalar, int64_t n, double strike, int outputs, float* const* out);
 // the same for fmhip_block_moments / fmhip_vec_repeat, and the definition behind fmhip_block_moments_host (nested_engine.hpp; the rules are
 // host/block_moments.hpp's): all throw FMHIP_ERR_INVALID_ARGUMENT
 void nested_check_moments(const fmhip_vec* vs, int n_vs, int64_t block, uint32_t mask, const fmhip_vec* outs);

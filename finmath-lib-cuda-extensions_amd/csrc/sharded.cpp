@@ -1113,6 +1113,24 @@ int implied_volatility(int model, fmhip_vec price, double price_scalar, fmhip_ve
     });
 }
 
+// Transform option value per path (transform_engine.hpp).  Elementwise, as the option formulas are.
+int transform_option(const double* nodes, int n_nodes, int n_states, fmhip_vec forward, double forward_scalar, const fmhip_vec* states, const double* state_scalars,
+                     fmhip_vec payoff_unit, double payoff_unit_scalar, double strike, int outputs, fmhip_vec* out) {
+    return fronted([&](Shards& s) {
+        transform_check(nodes, n_nodes, n_states, forward, states, state_scalars, payoff_unit, strike, outputs, out);
+        std::vector<fmhip_vec> vectors;
+        for (fmhip_vec h : { forward, payoff_unit }) if (h) vectors.push_back(h);
+        for (int k = 0; k < n_states; ++k) if (states[k]) vectors.push_back(states[k]);
+        const int64_t n = front_size(s, vectors.data(), (int)vectors.size(), "transform option", false);
+        const int n_out = (outputs & 1) + ((outputs >> 1) & 1) + ((outputs >> 2) & 1);      // one new vector per set bit of the mask
+        produce_per_shard(s, n, n_out, out, [&](Worker& w, fmhip_vec* got) {            // (a handle of 0 stays 0 on every shard: the scalar)
+            fmhip_vec local[2] = { 0, 0 };
+            for (int k = 0; k < n_states; ++k) local[k] = w.at(states[k]);
+            return fmhip_transform_option(nodes, n_nodes, n_states, w.at(forward), forward_scalar, local, state_scalars, w.at(payoff_unit), payoff_unit_scalar, strike, outputs, got);
+        });
+    });
+}
+
 // Nested simulation (nested_engine.hpp).  The blocks of a sample that is spread over several shards would straddle them, and a repeat's
 // output is laid out over the whole sample (one_shard).
 int block_moments(const fmhip_vec* vs, int n_vs, int64_t block, uint32_t mask, fmhip_vec* outs) {

@@ -89,6 +89,8 @@ int option_formula(int model, fmhip_vec forward, double forward_scalar, fmhip_ve
                    double payoff_unit_scalar, double maturity, double strike, int outputs, fmhip_vec* out);                 // per shard
 int implied_volatility(int model, fmhip_vec price, double price_scalar, fmhip_vec forward, double forward_scalar, fmhip_vec payoff_unit,
                        double payoff_unit_scalar, double maturity, double strike, int outputs, fmhip_vec* out);             // per shard
+int transform_option(const double* nodes, int n_nodes, int n_states, fmhip_vec forward, double forward_scalar, const fmhip_vec* states, const double* state_scalars,
+                     fmhip_vec payoff_unit, double payoff_unit_scalar, double strike, int outputs, fmhip_vec* out);                  // per shard
 int prefix_search(fmhip_vec v, const double* thresholds, int count, int relative, int64_t* positions_out, double* sums_out, double* total_out);
 int block_moments(const fmhip_vec* vs, int n_vs, int64_t block, uint32_t mask, fmhip_vec* outs);      // one shard; more: FMHIP_ERR_UNSUPPORTED
 int vec_repeat(fmhip_vec v, int64_t each, int64_t times, fmhip_vec* out);

@@ -306,6 +306,7 @@ def _partial_times(nd, k, d, const):
     if op == "APPLY_TABLE": return d.mult(X)                                # X holds f'(x): x.apply(f.derivative())
     if op == "OPTION_FORMULA": return d.mult(nd.arg_values[k])               # (delta, vega) of the unit value: analytic.option_formula
     if op == "IMPLIED_VOLATILITY": return d.mult(nd.arg_values[k])           # (∂σ/∂c, ∂σ/∂F) at the root: analytic.implied_volatility
+    if op == "TRANSFORM_OPTION": return d.mult(nd.arg_values[k])             # (delta, state delta) of the unit value: transform.transform_option_value
     raise NotImplementedError(op)
 
 

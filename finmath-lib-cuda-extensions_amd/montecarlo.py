@@ -169,6 +169,13 @@ def merton_call_analytic(initial_value, risk_free_rate, volatility, jump_intensi
             return total
 
 
+def heston_call_analytic(initial_value, risk_free_rate, v0, kappa, theta, xi, rho, maturity, strike, **node_arguments):
+    """Heston (1993) by Lewis' single integral: transform.heston_call_analytic, the host definition of the device's transform pass at a
+    number.  What heston_call_mc and heston_call_conditional_mc estimate, but for their Euler bias."""
+    from .transform import heston_call_analytic as at_a_number
+    return at_a_number(initial_value, risk_free_rate, v0, kappa, theta, xi, rho, maturity, strike, **node_arguments)
+
+
 def variance_gamma_martingale_correction(sigma, theta, nu):
     """ω = ln(1 − θν − σ²ν/2)/ν:  E exp(X_t) = exp(−ω t) for the variance-gamma process X, so S = S₀ exp((r + ω) t + X_t) is a martingale
     after discounting."""
@@ -346,6 +353,57 @@ def forward_implied_volatility_mc(brownian_motion_outer, brownian_motion_inner, 
             variance = max(clean.squared().getAverage() / share - mean * mean, 0.0)
             error = math.sqrt(variance / (n_outer * share))
             levels = [clean.getQuantile(q * share) for q in quantiles]     # getQuantile(q): the value that the fraction q of the sample exceeds; the invalid paths are the zeros at the bottom
+        else:
+            mean, error, levels = math.nan, math.nan, [math.nan for _ in quantiles]
+        results.append({"moneyness": float(m), "mean": mean, "standard_error": error, "quantiles": levels, "not_invertible": 1.0 - share})
+    return results
+
+
+def forward_implied_volatility_transform_mc(brownian_motion_outer, initial_value, risk_free_rate, v0, kappa, theta, xi, rho, time, maturity,
+                                            moneyness=(1.0,), quantiles=(0.05, 0.5, 0.95), **node_arguments):
+    """forward_implied_volatility_mc without the inner simulation: the OUTER paths are its own (heston_call_mc's scheme carries (S, v) from the
+    first point of brownian_motion_outer's time discretisation to `time`, a point of it), and the price of the call expiring at `maturity`
+    at the strike m·S_t·exp(r(T − t)) is the model's — transform.heston_option_value on the forward S_t·exp(r(T − t)) and the variance
+    v_t⁺ = max(v_t, 0) of every path for the maturity T − t (one node table, one launch per moneyness) — which analytic.implied_volatility
+    inverts with that per-path strike.  The same dicts: {"moneyness", "mean", "standard_error", "quantiles", "not_invertible"}.  No inner paths,
+    no inner noise, no inner Euler bias; what is left in "not_invertible" is a time value below the fp32 rounding of the price.  ξ > 0 (the
+    transform of Heston's model has no ξ = 0 form).  node_arguments go to transform.heston_transform_nodes."""
+    from .analytic import implied_volatility
+    from .transform import heston_transform_nodes, transform_option_value
+    if not maturity > time: raise ValueError("the option expires after the time at which its volatility is implied")
+    rho_c = math.sqrt(1.0 - rho * rho)
+    td = brownian_motion_outer.getTimeDiscretization()
+    x = brownian_motion_outer.getRandomVariableForConstant(math.log(initial_value))
+    v = brownian_motion_outer.getRandomVariableForConstant(v0)
+    start, i = td.getTime(0), 0
+    while td.getTime(i) - start < time - start - 1e-12:                        # heston_call_mc's step
+        dt = td.getTimeStep(i)
+        dw1 = brownian_motion_outer.getBrownianIncrement(i, 0)
+        vp = v.floor(0.0)
+        sq = vp.sqrt()
+        x = x.add(risk_free_rate * dt).addProduct(vp, -0.5 * dt).addProduct(sq, dw1)
+        dz = dw1.mult(rho).addProduct(brownian_motion_outer.getBrownianIncrement(i, 1), rho_c)
+        v = v.addProduct(vp.bus(theta), kappa * dt).addProduct(sq.mult(xi), dz)
+        i += 1
+    if abs(td.getTime(i) - time) > 1e-12: raise ValueError("the horizon is not a point of the time discretisation")
+    nodes = heston_transform_nodes(kappa, theta, xi, rho, maturity - time, **node_arguments)
+    forward = x.exp().mult(math.exp(risk_free_rate * (maturity - time)))
+    variance = v.floor(0.0)
+    one, zero = forward.mult(0.0).add(1.0), forward.mult(0.0)
+    n_outer = brownian_motion_outer.getNumberOfPaths()
+    results = []
+    for m in moneyness:
+        strike = forward.mult(float(m))
+        price, = transform_option_value(nodes, forward, (variance,), strike)
+        sigma, = implied_volatility("black_scholes", price, forward, maturity - time, strike)
+        valid = sigma.choose(one, zero).mult(sigma.mult(-1.0).choose(zero, one))       # 1 where sigma > 0, 0 where it is 0 or a NaN
+        clean = valid.sub(0.5).choose(sigma, zero)
+        share = valid.getAverage()
+        if share > 0.0:
+            mean = clean.getAverage() / share
+            variance_of = max(clean.squared().getAverage() / share - mean * mean, 0.0)
+            error = math.sqrt(variance_of / (n_outer * share))
+            levels = [clean.getQuantile(q * share) for q in quantiles]
         else:
             mean, error, levels = math.nan, math.nan, [math.nan for _ in quantiles]
         results.append({"moneyness": float(m), "mean": mean, "standard_error": error, "quantiles": levels, "not_invertible": 1.0 - share})

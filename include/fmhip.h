@@ -660,6 +660,45 @@ int fmhip_implied_volatility_host(int model, const float* price, double price_sc
                                   const float* payoff_unit, double payoff_unit_scalar, int64_t n, double maturity, double strike,
                                   int outputs, float* const* out);
 
+/* Transform option values per path on the device: the value of a CALL in forward form under a model whose characteristic
+ * function is exponential-affine in at most two state variables (Black-Scholes, Merton: none; Heston, Bates: the variance; double Heston:
+ * two), given the state of every path, without the vectors leaving the device.  In Lewis' single-integral form with a fixed quadrature the
+ * price is a finite sum over NODES; the node table is computed by the caller once (transform.py does it for the four named models) and is
+ * data to this pass.  The definition is host/transform_formula.hpp, one header for the host and the device under the rules of
+ * host/normal_functions.hpp, with the sine and cosine of host/trig64.hpp; the device's bits EQUAL the host entry point's.
+ * nodes: n_nodes (1 ... FMHIP_TRANSFORM_MAX_NODES) rows of 3 + 2*n_states doubles (n_states 0 ... FMHIP_TRANSFORM_MAX_STATES):
+ *   u_j, a_re, a_im, b_re[0..S), b_im[0..S), every entry finite.
+ * Operands: forward F, payoff unit N and the states V_0 ... V_{S-1} - each a vector, (double) of its fp32 elements, or with a handle of 0
+ * the fp64 scalar beside it (states[s], state_scalars[s]) - and the fp64 scalar strike K.  Per element, in fp64, every operation on its own:
+ *   a NaN among F, N, V_s, K                   the quiet NaN 0x7fc00000 in every output
+ *   not (F > 0 and K > 0)                      the limit of fmhip_option_formula: value N*max(F - K, 0), delta N*[F > K], state delta 0
+ *   otherwise  k = log(F/K), and for j = 0 ... J-1 in this order
+ *       e = a_re + sum_s b_re[s]*V_s,  theta = a_im + sum_s b_im[s]*V_s + u_j*k,  E = exp(e),  (s, c) = sincos(theta)
+ *       G += E*c,  H -= (E*u_j)*s,  GV += E*(b_re[0]*c - b_im[0]*s)
+ *     root = sqrt(F*K);  value N*(F - root*G);  delta (d/dF) N*(1 - (root/F)*(0.5*G + H));  state delta (d/dV_0, S >= 1) N*(0 - root*GV)
+ *   Results are narrowed to fp32 once.  NOTHING IS CLAMPED: the value is not forced into the arbitrage bounds, and an e that overflows or a
+ *   theta beyond 2^20 in size gives what IEEE 754 and the definition's sine give, a NaN (back as the quiet NaN) or an infinity.
+ * fmhip_transform_option: outputs is a mask of FMHIP_TRANSFORM_VALUE, _DELTA, _STATE_DELTA; out receives one new, materialised vector per
+ *   set bit, in bit order, from ONE launch.  At least one operand is a vector, and all vectors have one size.
+ * fmhip_transform_option_host (host only): the DEFINITION over host float arrays of n (1 ... 2^31) elements; out[f][p]; an operand array
+ *   that is NULL is the scalar beside it; it needs no device.
+ * The pass is elementwise: with a device list every shard runs the call on its block.  Everything is checked on the host before anything is
+ * flushed or launched: n_nodes or n_states out of range, a mask outside 1 ... 7, the state delta without a state, a NULL pointer, a table
+ * entry that is not finite, no vector operand, a strike that is a NaN -> FMHIP_ERR_INVALID_ARGUMENT; vectors of different sizes ->
+ * FMHIP_ERR_SIZE_MISMATCH; FMHIP_ERR_INVALID_HANDLE.  A refusal leaves out untouched and no vector behind.  A vector whose values were
+ * given up is the error a read of it is.  A build without the kernel answers FMHIP_ERR_UNSUPPORTED; it never falls back. */
+#define FMHIP_TRANSFORM_VALUE       1
+#define FMHIP_TRANSFORM_DELTA       2
+#define FMHIP_TRANSFORM_STATE_DELTA 4
+#define FMHIP_TRANSFORM_MAX_NODES   256
+#define FMHIP_TRANSFORM_MAX_STATES  2
+int fmhip_transform_option(const double* nodes, int n_nodes, int n_states, fmhip_vec forward, double forward_scalar,
+                           const fmhip_vec* states, const double* state_scalars, fmhip_vec payoff_unit, double payoff_unit_scalar,
+                           double strike, int outputs /* mask 1 ... 7 */, fmhip_vec* out /* one new vector per set bit, in bit order */);
+int fmhip_transform_option_host(const double* nodes, int n_nodes, int n_states, const float* forward, double forward_scalar,
+                                const float* const* states, const double* state_scalars, const float* payoff_unit,
+                                double payoff_unit_scalar, int64_t n, double strike, int outputs, float* const* out);
+
 /* Nested simulation on the device: the two operations that change the SHAPE of a sample — k inner paths started from each
  * of m outer states (fmhip_vec_repeat), and the m*k inner payoffs reduced to m conditional means with their inner variances
  * (fmhip_block_moments) — without the vectors leaving the device.  The definition is host/block_moments.hpp, one header for the host and

@@ -149,6 +149,11 @@ final class Native {
 	static native int impliedVolatility(int model, long price, double priceScalar, long forward, double forwardScalar, long payoffUnit, double payoffUnitScalar, double maturity, double strike, int outputs, long[] out);
 	/** The definition of impliedVolatility over host arrays of n floats; an operand array that is null is the scalar beside it; outColumns holds one column of n floats per set bit. */
 	static native int impliedVolatilityHost(int model, float[] priceOrNull, double priceScalar, float[] forwardOrNull, double forwardScalar, float[] payoffUnitOrNull, double payoffUnitScalar, int n, double maturity, double strike, int outputs, float[] outColumns);
+	// ---- transform option value per path: a call under a model with an exponential-affine transform (Black-Scholes, Merton, Heston, Bates, double Heston) as a finite sum over a node table
+	/** out = one new vector per set bit of outputs (1 value, 2 its partial in the forward, 4 its partial in the first state), in bit order; nodes holds nNodes rows of 3 + 2 nStates doubles (u, a_re, a_im, b_re[], b_im[]); states and stateScalars hold nStates entries (null for none); an operand handle of 0 is the scalar beside it, at least one is a vector. */
+	static native int transformOption(double[] nodes, int nNodes, int nStates, long forward, double forwardScalar, long[] statesOrNull, double[] stateScalarsOrNull, long payoffUnit, double payoffUnitScalar, double strike, int outputs, long[] out);
+	/** The definition of transformOption over host arrays of n floats; an operand array that is null is the scalar beside it; outColumns holds one column of n floats per set bit. */
+	static native int transformOptionHost(double[] nodes, int nNodes, int nStates, float[] forwardOrNull, double forwardScalar, float[] state0OrNull, float[] state1OrNull, double[] stateScalarsOrNull, float[] payoffUnitOrNull, double payoffUnitScalar, int n, double strike, int outputs, float[] outColumns);
 	// ---- nested simulation: the moments of consecutive blocks as new vectors, and the repeat that starts k inner paths per outer state
 	/** outs[i * popcount(mask) + j] = a new vector of n / block elements: output j (mask bits in ascending order: 1 sum, 2 mean, 4 population variance) of the consecutive blocks of vs[i]; 1 ... 4 vectors of one size, each read once; the bits are those of blockMomentsHost. */
 	static native int blockMoments(long[] vs, long block, int mask, long[] outs);

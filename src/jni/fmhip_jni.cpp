@@ -625,6 +625,43 @@ FMJ(jint, impliedVolatilityHost)(JNIEnv* env, jclass, jint model, jfloatArray pr
     for (int f = 0; f < count; ++f) columns[f] = po.p + (int64_t)f * n;
     return fmhip_implied_volatility_host((int)model, pc.p, priceScalar, pf.p, forwardScalar, pn.p, payoffUnitScalar, (int64_t)n, maturity, strike, (int)outputs, columns);
 }
+// ---------------------------------------------------------------- transform option value per path: a call under an exponential-affine transform as a sum over a node table
+// nodes: nNodes rows of 3 + 2·nStates doubles; states, stateScalars: nStates entries each (null where nStates is 0)
+FMJ(jint, transformOption)(JNIEnv* env, jclass, jdoubleArray nodes, jint nNodes, jint nStates, jlong forward, jdouble forwardScalar, jlongArray statesOrNull, jdoubleArray stateScalarsOrNull,
+                           jlong payoffUnit, jdouble payoffUnitScalar, jdouble strike, jint outputs, jlongArray out) {
+    if (!out || outputs < 1 || outputs > 7 || nNodes < 1 || nNodes > FMHIP_TRANSFORM_MAX_NODES || nStates < 0 || nStates > FMHIP_TRANSFORM_MAX_STATES) return FMHIP_ERR_INVALID_ARGUMENT;
+    const jsize count = (jsize)((outputs & 1) + ((outputs >> 1) & 1) + ((outputs >> 2) & 1));
+    if (env->GetArrayLength(out) < count) return FMHIP_ERR_INVALID_ARGUMENT;
+    Pin<jdouble> pt(env, nodes, JNI_ABORT); Pin<jlong> ps(env, statesOrNull, JNI_ABORT); Pin<jdouble> pc(env, stateScalarsOrNull, JNI_ABORT);
+    if (!pt.p || (int64_t)pt.length() < (int64_t)nNodes * (3 + 2 * nStates)) return FMHIP_ERR_INVALID_ARGUMENT;
+    if (nStates > 0 && (!ps.p || !pc.p || ps.length() < nStates || pc.length() < nStates)) return FMHIP_ERR_INVALID_ARGUMENT;
+    fmhip_vec states[FMHIP_TRANSFORM_MAX_STATES] = { 0, 0 };
+    double scalars[FMHIP_TRANSFORM_MAX_STATES] = { 0.0, 0.0 };
+    for (jint k = 0; k < nStates; ++k) { states[k] = (fmhip_vec)ps.p[k]; scalars[k] = pc.p[k]; }
+    fmhip_vec h[3] = { 0, 0, 0 };
+    const int st = fmhip_transform_option(pt.p, (int)nNodes, (int)nStates, forward, forwardScalar, states, scalars, payoffUnit, payoffUnitScalar, strike, (int)outputs, h);
+    if (st == FMHIP_OK) { jlong o[3]; for (jsize f = 0; f < count; ++f) o[f] = (jlong)h[f]; env->SetLongArrayRegion(out, 0, count, o); }
+    return st;
+}
+FMJ(jint, transformOptionHost)(JNIEnv* env, jclass, jdoubleArray nodes, jint nNodes, jint nStates, jfloatArray forwardOrNull, jdouble forwardScalar, jfloatArray state0OrNull,
+                               jfloatArray state1OrNull, jdoubleArray stateScalarsOrNull, jfloatArray payoffUnitOrNull, jdouble payoffUnitScalar, jint n, jdouble strike, jint outputs,
+                               jfloatArray outColumns) {
+    Pin<jdouble> pt(env, nodes, JNI_ABORT); Pin<jdouble> pc(env, stateScalarsOrNull, JNI_ABORT);
+    Pin<jfloat> pf(env, forwardOrNull, JNI_ABORT); Pin<jfloat> p0(env, state0OrNull, JNI_ABORT); Pin<jfloat> p1(env, state1OrNull, JNI_ABORT); Pin<jfloat> pn(env, payoffUnitOrNull, JNI_ABORT);
+    Pin<jfloat> po(env, outColumns);
+    if (!po.p || n < 1 || outputs < 1 || outputs > 7 || nNodes < 1 || nNodes > FMHIP_TRANSFORM_MAX_NODES || nStates < 0 || nStates > FMHIP_TRANSFORM_MAX_STATES) return FMHIP_ERR_INVALID_ARGUMENT;
+    if (!pt.p || (int64_t)pt.length() < (int64_t)nNodes * (3 + 2 * nStates) || (nStates > 0 && (!pc.p || pc.length() < nStates))) return FMHIP_ERR_INVALID_ARGUMENT;
+    if ((forwardOrNull && (!pf.p || pf.length() < n)) || (state0OrNull && (!p0.p || p0.length() < n)) || (state1OrNull && (!p1.p || p1.length() < n))
+        || (payoffUnitOrNull && (!pn.p || pn.length() < n))) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int count = (outputs & 1) + ((outputs >> 1) & 1) + ((outputs >> 2) & 1);
+    if ((int64_t)po.length() < (int64_t)count * n) return FMHIP_ERR_INVALID_ARGUMENT;
+    const float* states[FMHIP_TRANSFORM_MAX_STATES] = { nStates > 0 ? p0.p : nullptr, nStates > 1 ? p1.p : nullptr };
+    double scalars[FMHIP_TRANSFORM_MAX_STATES] = { 0.0, 0.0 };
+    for (jint k = 0; k < nStates; ++k) scalars[k] = pc.p[k];
+    float* columns[3] = { nullptr, nullptr, nullptr };
+    for (int f = 0; f < count; ++f) columns[f] = po.p + (int64_t)f * n;
+    return fmhip_transform_option_host(pt.p, (int)nNodes, (int)nStates, pf.p, forwardScalar, states, scalars, pn.p, payoffUnitScalar, (int64_t)n, strike, (int)outputs, columns);
+}
 // ---------------------------------------------------------------- polynomial regression in one pass: the monomials of the states are formed in registers
 // exponents: states.length (nStates) entries per term, each 0 … 6, as ints; anything outside a byte is refused here, the rest by the library
 static bool poly_exponents(const jint* e, int64_t count, std::vector<uint8_t>& out) {
