@@ -29,6 +29,8 @@ from .prefix import weighted_expected_shortfall, weighted_quantiles
 from .resample import (bootstrap_resample, device_resample, effective_sample_size, multinomial_resample, resample, resample_host, stratified_resample,
                        systematic_resample)
 from .selection import compress, compress_host, count_selected, device_select, expand, expand_host, gather, gather_host
+from .group import (conditional_expectation_by_state, device_group, group_counts, group_means, group_moments, group_sums, group_sums_host,
+                    offspring_counts)
 from .tabulated import TabulatedFunction, table_apply, table_apply_host
 from .analytic import NORMAL_CDF, NORMAL_DENSITY, NORMAL_QUANTILE, NamedFunction, function_apply, function_apply_host, normal_scores
 from .analytic import bachelier_option_value, black_scholes_option_value, option_formula, option_formula_double, option_formula_host

@@ -31,6 +31,7 @@ SYMBOLS = [
     "fmhip_prefix_sums", "fmhip_prefix_sums_at", "fmhip_prefix_search", "fmhip_prefix_sums_host",
     "fmhip_resample", "fmhip_resample_host",
     "fmhip_compress", "fmhip_expand", "fmhip_gather", "fmhip_compress_host", "fmhip_expand_host", "fmhip_gather_host",
+    "fmhip_group_sums", "fmhip_group_sums_host",
     "fmhip_table_build", "fmhip_table_apply", "fmhip_table_apply_host",
     "fmhip_function_apply", "fmhip_function_apply_host", "fmhip_option_formula", "fmhip_option_formula_host",
     "fmhip_implied_volatility", "fmhip_implied_volatility_host",
@@ -198,6 +199,8 @@ def lib():
         "fmhip_compress_host": [vp, i64, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)],
         "fmhip_expand_host": [vp, i64, C.POINTER(vp), i32, i64, dbl, C.POINTER(vp)],
         "fmhip_gather_host": [vp, i64, C.POINTER(vp), i32, i64, C.POINTER(vp)],
+        "fmhip_group_sums": [vec, i64, pv, i32, C.c_uint32, pv, pv, C.POINTER(i64)],
+        "fmhip_group_sums_host": [vp, i64, i64, C.POINTER(vp), i32, C.c_uint32, vp, C.POINTER(vp), C.POINTER(i64)],
         "fmhip_table_build": [C.POINTER(dbl), C.POINTER(dbl), i32, i32, i32, i32, C.POINTER(dbl)],
         "fmhip_table_apply": [vec, C.POINTER(dbl), i32, C.POINTER(dbl), i32, pv],
         "fmhip_table_apply_host": [vp, i64, C.POINTER(dbl), i32, C.POINTER(dbl), i32, C.POINTER(vp)],

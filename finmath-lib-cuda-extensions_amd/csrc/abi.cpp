@@ -908,6 +908,18 @@ int fmhip_gather(fmhip_vec index, const fmhip_vec* values, int n_values, fmhip_v
     return guarded([&] { Engine::get().gather(index, values, n_values, values_out); });
 }
 
+// ---------------------------------------------------------------- reduce by key (group_engine.hpp)
+int fmhip_group_sums_host(const float* index, int64_t n, int64_t m, const float* const* values, int n_values, uint32_t mask, float* counts_out, float* const* outs,
+                          int64_t* ungrouped_out) {
+    return host_only([&] { fm::group_sums_host_checked(index, n, m, values, n_values, mask, counts_out, outs, ungrouped_out); });
+}
+int fmhip_group_sums(fmhip_vec index, int64_t m, const fmhip_vec* values, int n_values, uint32_t mask, fmhip_vec* counts_out, fmhip_vec* outs, int64_t* ungrouped_out) {
+    FRONT(group_sums(index, m, values, n_values, mask, counts_out, outs, ungrouped_out));
+    TE_CHECKED_LOCAL(fm::group_check(index, m, values, n_values, mask, counts_out, outs, ungrouped_out), te_operands(index, values, n_values, nullptr, 0), L,
+                     fmhip_group_sums(L[0], m, L + 1, n_values, mask, counts_out, outs, ungrouped_out));
+    return guarded([&] { Engine::get().group_sums(index, m, values, n_values, mask, counts_out, outs, ungrouped_out); });
+}
+
 // ---------------------------------------------------------------- tabulated functions (table_engine.hpp)
 int fmhip_table_build(const double* knots, const double* values, int count, int interpolation, int extrapolation, int derivative, double* coefficients_out) {
     return host_only([&] { fm::table_build_checked(knots, values, count, interpolation, extrapolation, derivative, coefficients_out); });

@@ -2481,6 +2481,7 @@ void Engine::profile_read(double* ms_total, int64_t* n) {
 #include "prefix_engine.hpp"           // Engine::prefix_sums, prefix_sums_at, prefix_search: fp64 prefix sums in a tree that is a function of n alone
 #include "resample_engine.hpp"         // Engine::resample: ancestors drawn from the cumulative weights, the state vectors gathered along
 #include "select_engine.hpp"           // Engine::compress, expand, gather: the paths on which a mask is selected as shorter vectors, back again, and a gather by an index
+#include "group_engine.hpp"            // Engine::group_sums: reduce by key — count, sum, mean and variance per group of an index vector
 #include "table_engine.hpp"            // Engine::table_apply: tabulated functions of a vector's elements, a new vector each from one launch
 #include "analytic_engine.hpp"         // Engine::function_apply, option_formula: Φ, φ, Φ⁻¹ and the Black–Scholes / Bachelier formulas per path
 #include "implied_volatility_engine.hpp"      // Engine::implied_volatility: the inverse of the option formulas' value in the volatility, per path

@@ -436,6 +436,12 @@ public:
     void expand(fmhip_vec mask, const fmhip_vec* values, int n_values, double fill, fmhip_vec* values_out);
     void gather(fmhip_vec index, const fmhip_vec* values, int n_values, fmhip_vec* values_out);
 
+    // reduce by key (group_engine.hpp): per group k of m — the elements whose index is the integer k — the count and, of up
+    // to 4 value vectors, the masked outputs sum, mean, variance (the bits of FMHIP_BLOCK_*) as new, materialised vectors of m elements, in
+    // the association of group_host.hpp; an element whose index is no integer in [0, m - 1] belongs to no group and is counted in
+    // ungrouped_out.  The outputs are written only when the call succeeds; one engine's sample only (UNSUPPORTED with a communicator).
+    void group_sums(fmhip_vec index, int64_t m, const fmhip_vec* values, int n_values, uint32_t mask, fmhip_vec* counts_out, fmhip_vec* outs, int64_t* ungrouped_out);
+
     // tabulated functions (table_engine.hpp): n_tables functions on the same knots (host/tabulated_function.hpp) applied to
     // every element of x, out[0 … n_tables) new, materialised vectors from one launch that reads x once.  Arguments are checked before
     // anything is flushed or launched; out is written only when the call succeeds.
@@ -964,6 +970,11 @@ void select_check_mask_size(const char* what, int64_t n, bool want_positions);
 void compress_host_checked(const float* mask, int64_t n, const float* const* values, int n_values, float* const* values_out, int64_t* positions_out, int64_t* count_out);
 void expand_host_checked(const float* mask, int64_t n, const float* const* values, int n_values, int64_t n_value_elements, double fill, float* const* values_out);
 void gather_host_checked(const float* index, int64_t m, const float* const* values, int n_values, int64_t n, float* const* values_out);
+// the same for fmhip_group_sums, and the definition behind fmhip_group_sums_host (group_engine.hpp; the rules are group_host.hpp's):
+// FMHIP_ERR_INVALID_ARGUMENT
+void group_check(fmhip_vec index, int64_t m, const fmhip_vec* values, int n_values, uint32_t mask, const fmhip_vec* counts_out, const fmhip_vec* outs, const int64_t* ungrouped_out);
+void group_check_index_size(int64_t n);
+void group_sums_host_checked(const float* index, int64_t n, int64_t m, const float* const* values, int n_values, uint32_t mask, float* counts_out, float* const* outs, int64_t* ungrouped_out);
 // the same for fmhip_table_apply, and the definitions behind fmhip_table_build / fmhip_table_apply_host (table_engine.hpp; the rules are
 // host/tabulated_function.hpp's): all throw FMHIP_ERR_INVALID_ARGUMENT
 void table_check_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, const fmhip_vec* out);

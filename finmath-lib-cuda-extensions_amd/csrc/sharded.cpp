@@ -1065,6 +1065,31 @@ int gather(fmhip_vec index, const fmhip_vec* values, int n_values, fmhip_vec* va
     });
 }
 
+// Reduce by key (group_engine.hpp).  A group's members lie on every shard and the association of group_host.hpp is over the whole sample:
+// a combine over the shards is not built (one_shard).  A list of one shard is that shard's call; the outputs have m elements.
+int group_sums(fmhip_vec index, int64_t m, const fmhip_vec* values, int n_values, uint32_t mask, fmhip_vec* counts_out, fmhip_vec* outs, int64_t* ungrouped_out) {
+    return fronted([&](Shards& s) {
+        group_check(index, m, values, n_values, mask, counts_out, outs, ungrouped_out);
+        std::vector<fmhip_vec> sample{ index };
+        sample.insert(sample.end(), values, values + n_values);
+        const int64_t n = front_size(s, sample.data(), (int)sample.size(), "group sums", false);
+        group_check_index_size(n);
+        one_shard(s, "group sums", "a group's members lie on every shard and a combine over the shards is not built");
+        const int want_counts = counts_out ? 1 : 0, n_out = want_counts + n_values * (int)((mask & 1u) + ((mask >> 1) & 1u) + ((mask >> 2) & 1u));
+        if (n_out == 0) {
+            on_the_shard(s, [&](Worker& w) { return fmhip_group_sums(w.at(index), m, nullptr, 0, mask, nullptr, nullptr, ungrouped_out); });
+            return;
+        }
+        std::vector<fmhip_vec> ids((size_t)n_out, 0);                                    // the counts if they are asked for, then the outputs
+        produce_per_shard(s, m, n_out, ids.data(), [&](Worker& w, fmhip_vec* got) {
+            const std::vector<fmhip_vec> l = localize(w, sample.data(), (int)sample.size());
+            return fmhip_group_sums(l[0], m, l.data() + 1, n_values, mask, want_counts ? got : nullptr, got + want_counts, ungrouped_out);
+        });
+        if (want_counts) *counts_out = ids[0];
+        for (int i = want_counts; i < n_out; ++i) outs[i - want_counts] = ids[(size_t)i];
+    });
+}
+
 // Tabulated functions (table_engine.hpp).  Elementwise: every shard runs the call on its block; the new vectors' blocks are the shards' results.
 int table_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, fmhip_vec* out) {
     return fronted([&](Shards& s) {

@@ -83,6 +83,7 @@ int resample(fmhip_vec weights, int scheme, int64_t m, double offset, fmhip_vec 
 int compress(fmhip_vec mask, const fmhip_vec* values, int n_values, fmhip_vec* values_out, fmhip_vec* positions_out, int64_t* count_out);      // one shard; more: FMHIP_ERR_UNSUPPORTED
 int expand(fmhip_vec mask, const fmhip_vec* values, int n_values, double fill, fmhip_vec* values_out);
 int gather(fmhip_vec index, const fmhip_vec* values, int n_values, fmhip_vec* values_out);
+int group_sums(fmhip_vec index, int64_t m, const fmhip_vec* values, int n_values, uint32_t mask, fmhip_vec* counts_out, fmhip_vec* outs, int64_t* ungrouped_out);      // one shard; more: FMHIP_ERR_UNSUPPORTED
 int table_apply(fmhip_vec x, const double* knots, int count, const double* coefficients, int n_tables, fmhip_vec* out);      // per shard
 int function_apply(fmhip_vec x, const int* kinds, int n_functions, fmhip_vec* out);                                         // per shard
 int option_formula(int model, fmhip_vec forward, double forward_scalar, fmhip_vec volatility, double volatility_scalar, fmhip_vec payoff_unit,

@@ -18,6 +18,8 @@ a RandomVariableFactory by injection (LIBORMarketModelCalibrationATMTest.java:35
                             something to show
     merton_call_mc          Merton's jump-diffusion driven by IndependentIncrementsFromICDF (increments.py: Brownian increment, normal
                             jump size, Poisson jump count), with merton_call_analytic, Merton's series, as its closed-form check
+    merton_call_by_jump_count_mc  the same simulation with the payoff grouped by the number of jumps on the device (group.py, DESIGN.md
+                            §4.29): Merton's series term by term
     variance_gamma_call_mc  the variance-gamma model (Madan, Carr, Chang 1998) driven by VarianceGammaProcess (increments.py: a gamma clock
                             and a standard normal per step), with variance_gamma_call_analytic — Black–Scholes conditional on the gamma
                             time, integrated against its density — as its check
@@ -149,6 +151,37 @@ def merton_call_mc(increments, initial_value, risk_free_rate, volatility, jump_i
     payoff = x.exp().sub(strike).floor(0.0)
     value = payoff.div(math.exp(risk_free_rate * maturity))
     return value.getAverage(), value
+
+
+def merton_call_by_jump_count_mc(increments, initial_value, risk_free_rate, volatility, jump_intensity, jump_size_mean, jump_size_stddev, maturity, strike,
+                                 max_jumps=15):
+    """Merton's series, term by term, by Monte-Carlo: merton_call_mc's simulation, the Poisson factor summed over the time steps to the
+    number of jumps N_T per path (exact small integers), and the discounted payoff grouped by it on the device (group.py, DESIGN.md
+    §4.29).  Returns a dict of lists over k = 0 … max_jumps — "share" (the fraction of paths with N_T = k: the Poisson probability),
+    "mean" (E[discounted payoff | N_T = k]: e^{-rT}·Black(F_k, K, σ²T + kδ²), NaN for a count of 0), "standard_error" (of that mean),
+    "count" — and "ungrouped", the number of paths with more than max_jumps jumps."""
+    from .group import group_moments
+    td = increments.getTimeDiscretization()
+    x = increments.getRandomVariableForConstant(math.log(initial_value))
+    compensator = jump_intensity * (math.exp(jump_size_mean + 0.5 * jump_size_stddev * jump_size_stddev) - 1.0)
+    drift = risk_free_rate - 0.5 * volatility * volatility - compensator
+    jumps = None
+    t, i = td.getTime(0), 0
+    while t < maturity - 1e-12:
+        dt = td.getTimeStep(i)
+        dw, z, dn = increments.getIncrement(i, 0), increments.getIncrement(i, 1), increments.getIncrement(i, 2)
+        x = x.add(drift * dt).addProduct(dw, volatility).addProduct(dn, jump_size_mean).addProduct(dn.sqrt().mult(z), jump_size_stddev)
+        jumps = dn if jumps is None else jumps.add(dn)
+        i += 1
+        t = td.getTime(i)
+    value = x.exp().sub(strike).floor(0.0).div(math.exp(risk_free_rate * maturity))
+    ((mean, variance),), counts, ungrouped = group_moments(jumps, [value], max_jumps + 1, what=("mean", "variance"), counts=True)
+    count = [float(c) for c in counts.realizations.to_float32()]
+    mean = [float(v) for v in mean.realizations.to_float32()]
+    variance = [float(v) for v in variance.realizations.to_float32()]
+    paths = sum(count) + ungrouped
+    return {"share": [c / paths for c in count], "mean": mean, "count": count, "ungrouped": ungrouped,
+            "standard_error": [math.sqrt(v / c) if c > 0 else math.nan for v, c in zip(variance, count)]}
 
 
 def merton_call_analytic(initial_value, risk_free_rate, volatility, jump_intensity, jump_size_mean, jump_size_stddev, maturity, strike):

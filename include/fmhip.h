@@ -540,6 +540,37 @@ int fmhip_expand_host(const float* mask, int64_t n, const float* const* values, 
 int fmhip_gather_host(const float* index, int64_t m, const float* const* values, int n_values, int64_t n,
                       float* const* values_out);                             /* the DEFINITION */
 
+/* Reduce by key on the device: out[k] = the sum of { v[j] : index[j] == k } — reduce_by_key, index_add, bincount with
+ * weights — for an index vector that another pass left on the device: the ancestors of a resample (offspring counts), the slot of an
+ * argmax, a bin number, a Poisson count (E[y | discrete state]), inner paths of unequal number, histograms of any number of bins.  The
+ * definition is csrc/group_host.hpp, one header for the host and the device: the device's bits are the _host twin's for every input.
+ *   membership       index[j] belongs to group k where it is the integer k with 0 <= k <= m - 1 (-0.0 counts as 0); anywhere else — NaN,
+ *                    +-inf, a fraction, negative, >= m — the element belongs to NO group and is counted in *ungrouped_out.  The status is
+ *                    FMHIP_OK whatever the index holds.  m is 1 ... 2^24, where the float index is exact.
+ *   the sums         the members of a group are summed in ascending path order, in fp64, as the run-prefixes of the prefix sums' tree over
+ *                    the elements ordered by (group, path): S1 of (double)v, S2 of the exact squares.  With one group S1 is P[n - 1] of
+ *                    fmhip_prefix_sums_host bit for bit; a group of one member is that member; the bits of a group do not depend on the
+ *                    values of other groups, on n_values, on a vector's slot or on the mask; |S - exact| <= (chain(n) + 1) 2^-53 times the
+ *                    sum of the |terms| of that group alone.  A NaN or +-inf stays inside its own group.
+ *   outputs          new, materialised vectors of m elements, rounded to fp32 once: *counts_out the count as a float (may be NULL); outs,
+ *                    n_values x popcount(mask) handles, vector-major, the mask's bits ascending: FMHIP_BLOCK_SUM (float)S1, FMHIP_BLOCK_MEAN
+ *                    (float)(S1 / count), FMHIP_BLOCK_VARIANCE (float)max(0, S2/count - (S1/count)^2), the population variance from raw
+ *                    moments with the caveat of fmhip_block_moments.  An EMPTY group has count 0, sum +0.0, mean and variance NaN
+ *                    (0x7fc00000, as every NaN that comes back).
+ * n_values is 0 ... 4: a call with none asks for counts_out or ungrouped_out (or both).
+ * Checked on the host before anything is flushed or launched: m or n_values outside their range, a mask of 0 with n_values > 0, a mask
+ * with unknown bits, nothing asked for, a handle of 0, a NULL pointer -> FMHIP_ERR_INVALID_ARGUMENT; values whose size is not the index's
+ * -> FMHIP_ERR_SIZE_MISMATCH; FMHIP_ERR_INVALID_HANDLE.  A refusal or a failed allocation at any stage leaves the outputs untouched and no
+ * vector behind.  A build without the kernels answers FMHIP_ERR_UNSUPPORTED; it never falls back.
+ * ONE sample on ONE device: a device list of more than one shard or an expectation communicator of more than one rank ->
+ * FMHIP_ERR_UNSUPPORTED.
+ * fmhip_group_sums_host is the definition on plain arrays (counts_out and every outs[i]: m floats) and needs no device. */
+int fmhip_group_sums(fmhip_vec index, int64_t m, const fmhip_vec* values, int n_values /* 0 ... 4 */, uint32_t mask,
+                     fmhip_vec* counts_out /* may be NULL */, fmhip_vec* outs /* n_values x popcount(mask), vector-major */,
+                     int64_t* ungrouped_out /* may be NULL */);
+int fmhip_group_sums_host(const float* index, int64_t n, int64_t m, const float* const* values, int n_values, uint32_t mask,
+                          float* counts_out, float* const* outs, int64_t* ungrouped_out);   /* the DEFINITION; no device */
+
 /* Tabulated functions on the device: RandomVariable.apply for a CURVE — a function tabulated on knots and interpolated: a
  * local-volatility slice, a Markov-functional numeraire, a payoff profile, an exercise boundary, an inverse empirical CDF — without the
  * vector leaving the device.  The definition is host/tabulated_function.hpp, one header for the host and the device.

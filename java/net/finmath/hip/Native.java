@@ -128,6 +128,11 @@ final class Native {
 	static native int expandHost(float[] mask, float[] valueColumns, int nValues, long nValueElements, double fill, float[] outColumns);
 	/** The definition of gather over host arrays: valueColumns holds nValues columns of n floats, outColumns nValues columns of index.length floats. */
 	static native int gatherHost(float[] index, float[] valueColumns, int nValues, long n, float[] outColumns);
+	// ---- reduce by key on the device: count, sum, mean and variance per group of an index vector; the device's bits are those of the Host twin
+	/** Per group k of m (index[j] == k; anything that is no integer in [0, m - 1] belongs to no group): countsOutOrNull[0] = a new vector of m counts, outs[i * popcount(mask) + j] = a new vector of m elements, output j (the set bits of mask ascending: 1 sum, 2 mean, 4 variance) of values[i] (at most 4 vectors; none: null); ungroupedOutOrNull[0] = the elements of no group. */
+	static native int groupSums(long index, long m, long[] valuesOrNull, int mask, long[] countsOutOrNull, long[] outsOrNull, long[] ungroupedOutOrNull);
+	/** The definition of groupSums over host arrays: valueColumns holds nValues columns of index.length floats, outColumns nValues * popcount(mask) columns of m floats, countsOutOrNull m floats. */
+	static native int groupSumsHost(float[] index, long m, float[] valueColumns, int nValues, int mask, float[] countsOutOrNull, float[] outColumns, long[] ungroupedOutOrNull);
 	// ---- tabulated functions on the device: RandomVariable.apply for a curve; the device's bits are those of tableApplyHost
 	/** coefficientsOut[(knots.length + 1) * 4]: the segments of one function from its values at the knots; interpolation 0 piecewise constant, 1 linear, 2 natural cubic spline, 3 monotone cubic; extrapolation 0 constant, 1 linear; derivative 0 or 1. */
 	static native int tableBuild(double[] knots, double[] values, int interpolation, int extrapolation, int derivative, double[] coefficientsOut);

@@ -413,6 +413,43 @@ FMJ(jint, gatherHost)(JNIEnv* env, jclass, jfloatArray index, jfloatArray valueC
     for (int i = 0; i < nValues; ++i) { in[i] = pv.p + (int64_t)i * (int64_t)n; columns[i] = po.p + (int64_t)i * m; }
     return fmhip_gather_host(pi.p, m, in, (int)nValues, (int64_t)n, columns);
 }
+// ---------------------------------------------------------------- reduce by key on the device
+static int groupOutputs(jint mask) { return (mask & 1) + ((mask >> 1) & 1) + ((mask >> 2) & 1); }
+FMJ(jint, groupSums)(JNIEnv* env, jclass, jlong index, jlong m, jlongArray valuesOrNull, jint mask, jlongArray countsOutOrNull, jlongArray outsOrNull, jlongArray ungroupedOutOrNull) {
+    Pin<jlong> pv(env, valuesOrNull, JNI_ABORT);
+    const int64_t nv = pv.p ? pv.length() : 0;
+    if (mask < 0 || mask > 7 || nv > 4) return FMHIP_ERR_INVALID_ARGUMENT;
+    const int64_t n_out = nv * groupOutputs(mask);
+    if ((n_out > 0 && (!outsOrNull || env->GetArrayLength(outsOrNull) < n_out)) || (countsOutOrNull && env->GetArrayLength(countsOutOrNull) < 1)
+        || (ungroupedOutOrNull && env->GetArrayLength(ungroupedOutOrNull) < 1)) return FMHIP_ERR_INVALID_ARGUMENT;
+    fmhip_vec counts = 0, out[12] = { 0 };
+    int64_t ungrouped = 0;
+    const int st = fmhip_group_sums((fmhip_vec)index, (int64_t)m, (const fmhip_vec*)pv.p, (int)nv, (uint32_t)mask, countsOutOrNull ? &counts : nullptr, out, ungroupedOutOrNull ? &ungrouped : nullptr);
+    if (st == FMHIP_OK) {
+        if (n_out > 0) { jlong o[12]; for (int i = 0; i < n_out; ++i) o[i] = (jlong)out[i]; env->SetLongArrayRegion(outsOrNull, 0, (jsize)n_out, o); }
+        set1(env, countsOutOrNull, (jlong)counts);
+        set1(env, ungroupedOutOrNull, (jlong)ungrouped);
+    }
+    return st;
+}
+FMJ(jint, groupSumsHost)(JNIEnv* env, jclass, jfloatArray index, jlong m, jfloatArray valueColumns, jint nValues, jint mask, jfloatArray countsOutOrNull, jfloatArray outColumns, jlongArray ungroupedOutOrNull) {
+    if (ungroupedOutOrNull && env->GetArrayLength(ungroupedOutOrNull) < 1) return FMHIP_ERR_INVALID_ARGUMENT;
+    int64_t ungrouped = 0;
+    int st;
+    {
+        Pin<jfloat> pi(env, index, JNI_ABORT); Pin<jfloat> pv(env, valueColumns, JNI_ABORT); Pin<jfloat> pc(env, countsOutOrNull); Pin<jfloat> po(env, outColumns);
+        const int64_t n = pi.p ? (int64_t)pi.length() : 0;
+        if (n < 1 || m < 1 || m > (int64_t(1) << 24) || nValues < 0 || nValues > 4 || mask < 0 || mask > 7 || (pc.p && (int64_t)pc.length() < (int64_t)m)) return FMHIP_ERR_INVALID_ARGUMENT;
+        const int per = groupOutputs(mask);
+        if (nValues > 0 && (!pv.p || !po.p || (int64_t)pv.length() < (int64_t)nValues * n || (int64_t)po.length() < (int64_t)nValues * per * (int64_t)m)) return FMHIP_ERR_INVALID_ARGUMENT;
+        const float* in[4] = { nullptr }; float* columns[12] = { nullptr };
+        for (int i = 0; i < nValues; ++i) in[i] = pv.p + (int64_t)i * n;
+        for (int i = 0; i < nValues * per; ++i) columns[i] = po.p + (int64_t)i * (int64_t)m;
+        st = fmhip_group_sums_host(pi.p, n, (int64_t)m, in, (int)nValues, (uint32_t)mask, pc.p, columns, ungroupedOutOrNull ? &ungrouped : nullptr);
+    }
+    if (st == FMHIP_OK) set1(env, ungroupedOutOrNull, (jlong)ungrouped);
+    return st;
+}
 // ---------------------------------------------------------------- tabulated functions on the device
 FMJ(jint, tableBuild)(JNIEnv* env, jclass, jdoubleArray knots, jdoubleArray values, jint interpolation, jint extrapolation, jint derivative, jdoubleArray coefficientsOut) {
     Pin<jdouble> pk(env, knots, JNI_ABORT); Pin<jdouble> pv(env, values, JNI_ABORT); Pin<jdouble> po(env, coefficientsOut);
